@@ -29,6 +29,9 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` 
 timed, algorithmic bytes), `cpu_baseline` (the C oracle on the host cores), `oracle_gate`, the reference-
 precision leg `f64`, the `cfg2` leg, and `prelude` (plan build / radix sort / voxelizer with their own
 algorithmic-bytes fractions).
+
+`--dump-outputs DIR` writes what the last timed step computed (quantized integers and reconstruction; a fixed, seeded
+sample of rows when larger than 64 MB) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -89,7 +92,34 @@ def parse():
                     help="frames with xyz columns (14 / 59 channels): time the all-float32 fused kernels instead of the mixed-precision ones "
                          "(raht_fwd_quant_mixed: xyz columns in float64, the reference's integers there)")
     ap.add_argument("--ablate", type=int, default=0, help="kernel-timing experiment for the roofline probe only (0 = real kernel; needs a make ABLATE=1 library)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; "
+                         "larger outputs as the same seeded sample of rows in every run, at most 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: payload of all the files of one process (npy headers and all stay under 64 MB)
+
+
+def dump_outputs(d, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: `arrays` maps name -> the (rows, ...) device tensor a caller of the timed path receives from its last
+    step. Each is written as d/<name>.npy: float32 stays float32, float64 and integers become float64 (exact below 2^53).
+    An array larger than its share of `budget` is cut to a sorted sample of rows drawn from a fixed seed, so that two runs
+    with the same arguments write the same rows."""
+    os.makedirs(d, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.reshape(t.shape[0], -1)
+        dt = torch.float32 if t.dtype == torch.float32 else torch.float64
+        row_bytes = max(1, t.shape[1] * (4 if dt == torch.float32 else 8))
+        k = min(t.shape[0], max(1, share // row_bytes))
+        if k < t.shape[0]:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], k, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.to(dt).cpu().numpy())
 
 
 def kernel_source_hash():
@@ -401,6 +431,10 @@ class SoloScene:
             return
         self._lib.check(self.L.raht_dequant_inv(self.plan._h, vp(self.Q.data_ptr()), self.D, self.D, self.steps32, 1, vp(self.Crec.data_ptr()), self.D, self.s_()))
 
+    def outputs(self, no_quant):
+        """What the step hands its caller: the quantized integers (or the coefficients) and the reconstruction."""
+        return {"T": self.T, "C_rec": self.Crec} if no_quant else {"Q": self.Q, "C_rec": self.Crec}
+
     def step_fn(self, no_quant, unfused):
         if no_quant:
             return lambda: (self.fwd(), self.inv(self.T))
@@ -552,6 +586,11 @@ def cfg4_batch_main(a, R, synth, dev, real_stdout):
     rt = max(float(((r - c).abs().max() / c.abs().max()).item()) for r, c in zip(Rb, Cs))
     assert rt <= 1e-5, f"round trip error {rt}"
     del Qb, Rb
+    if a.dump_outputs:                              # keep the reconstructions of the last timed step
+        last, _batched = [None], batched
+
+        def batched():
+            last[0] = _batched()
     settle = a.settle_steps if a.settle_steps >= 0 else max(0, 64 - a.warmup)
     for _ in range(settle + a.warmup):
         batched()
@@ -561,6 +600,9 @@ def cfg4_batch_main(a, R, synth, dev, real_stdout):
         batched()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {f"C_rec_scene{i}": r for i, r in enumerate(last[0])})
+        last[0] = None
     t_loop = timed(looped, min(a.steps, 20))
     alg = 2 * (8.0 * rows * D + 8.0 * rows)
     out = {"metric": "M-Gaussians/s fwd+inv RAHT, 59-ch SH3 3DGS", "value": round(rows / (dt / a.steps) / 1e6, 2), "unit": "M-Gaussians/s", "n_gpus": 1,
@@ -692,8 +734,13 @@ def main():
         sh = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9, force_collectives=True, direct=a.direct)
         qs = None if a.no_quant else a.quant_step
 
+        last = [None]
+
         def step():
-            sh.step(Cd, qs)
+            if a.dump_outputs:                          # keep this rank's reconstruction of the last timed step
+                last[0] = sh.step(Cd, qs)
+            else:
+                sh.step(Cd, qs)
         total_rows = N
         rt_err = sh.roundtrip_error(Cd)
         assert rt_err <= 1e-5, f"round trip error {rt_err}"
@@ -721,6 +768,13 @@ def main():
     dt = time.perf_counter() - t0
     if not solo and a.direct:
         sh.check_exchange()                                # a direct gather that timed out: no number for stale buffers
+    if a.dump_outputs:
+        got = sc.outputs(a.no_quant) if solo else {"C_rec": last[0]}
+        if world > 1:
+            got = {f"{k}_rank{rank}": v for k, v in got.items()}
+        dump_outputs(a.dump_outputs, got, DUMP_BYTES // world)
+        if not solo:
+            last[0] = None
     if world > 1:
         tt = torch.tensor([dt, float(N)], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         tmax = tt.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -498,3 +498,33 @@ def mixed_cases():
 
 if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "mixed"):
     mixed_cases()
+
+
+def rlgr_random_cases():
+    """The reference coder's streams for the inputs of tests/test_rlgr.py's two randomised cross-checks
+    (tests/rlgr_inputs.py), so that they compare against the reference everywhere, not only where its build (oracle/_ref)
+    exists. Stored as lengths and SHA-256 digests of the streams and of the inputs: byte-exact at a few kilobytes."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref"))
+    import rlgr
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests.rlgr_inputs import digest, laplace_stream, random_sequences
+
+    def enc(x, flag):
+        m = rlgr.membuf()
+        m.rlgrWrite([int(v) for v in x], flag)
+        m.close()
+        return np.array(m.get_buffer(), dtype=np.uint8)
+
+    lap = laplace_stream()
+    lb = enc(lap, 1)
+    xs = random_sequences()
+    bs = [enc(x, 1) for x in xs]
+    np.savez_compressed(os.path.join(HERE, "rlgr_random.npz"),
+                        lap_x_sha256=digest(lap), lap_len=np.int64(len(lb)), lap_sha256=digest(lb),
+                        x_sha256=np.stack([digest(x) for x in xs]), x_len=np.array([len(x) for x in xs], np.int64),
+                        sha256=np.stack([digest(b) for b in bs]), bytes_len=np.array([len(b) for b in bs], np.int64))
+    print("rlgr_random:", len(xs), "sequences,", sum(len(b) for b in bs), "bytes")
+
+
+if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "rlgr_random"):
+    rlgr_random_cases()

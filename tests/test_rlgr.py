@@ -87,74 +87,69 @@ def test_truncated_stream_does_not_crash(rl):
     assert len(back) == len(x)
 
 
-def test_reference_build_agrees_when_present(rl):
-    """If oracle/_ref/rlgr*.so was built here (container with /root/reference), cross-check live."""
+def _reference_build():
+    """The reference's own coder if oracle/_ref/rlgr*.so was built here (`make -C oracle ref`, where its sources are), else None."""
+    import importlib
     ref_dir = os.path.join(ROOT, "oracle", "_ref")
     if not any(f.startswith("rlgr") for f in (os.listdir(ref_dir) if os.path.isdir(ref_dir) else [])):
-        pytest.skip("reference rlgr build not present")
+        return None
     sys.path.insert(0, ref_dir)
-    import rlgr as ref
-    rng = np.random.default_rng(77)
-    x = (rng.laplace(0, 40, 30000)).astype(np.int64)
-    x[rng.random(30000) < 0.5] = 0
-    a = ref.membuf(); a.rlgrWrite(x.tolist(), 1); a.close()
+    try:
+        ref = importlib.import_module("rlgr")
+    except Exception:
+        return None
+    finally:
+        sys.path.remove(ref_dir)
+    return ref if hasattr(ref, "membuf") else None
+
+
+# the reference coder's streams for the inputs of tests/rlgr_inputs.py, as lengths and SHA-256 digests
+# (tests/golden/gen_golden.py::rlgr_random_cases)
+RANDOM = load_golden("rlgr_random")
+
+
+def test_reference_build_agrees_when_present(rl):
+    """A 30 000-symbol Laplacian stream: byte-identical to what the reference's coder wrote for it (stored digest), and live
+    against its build when that is present."""
+    from .rlgr_inputs import digest, laplace_stream
+    x = laplace_stream()
+    assert np.array_equal(digest(x), RANDOM["lap_x_sha256"]), "seeded input differs from the one the digests were made for"
     b = rl.membuf(); b.rlgrWrite(x, 1)
-    assert a.get_buffer() == b.get_buffer()
+    got = np.frombuffer(bytes(b.get_buffer()), dtype=np.uint8)
+    assert len(got) == int(RANDOM["lap_len"]) and np.array_equal(digest(got), RANDOM["lap_sha256"])
+    ref = _reference_build()
+    if ref is not None:
+        a = ref.membuf(); a.rlgrWrite(x.tolist(), 1); a.close()
+        assert a.get_buffer() == b.get_buffer()
 
 
 def test_random_streams_round_trip_and_match_the_reference_build_when_present():
-    """300 random sequences (all-zero, sparse, dense, full int32 range, one very long run): exact round
-    trip; byte-identical to the reference's own coder when its build is available (oracle/_ref, built
-    by `make -C oracle ref` in the build container)."""
-    import importlib
-    import os
-    import sys
+    """300 random sequences (all-zero, sparse, dense, full int32 range, rare large values, wide normals) and one very long
+    run: exact round trip; the 300 byte-identical to what the reference's own coder wrote for them (stored digests), and live
+    against its build when that is present (oracle/_ref, built by `make -C oracle ref` where its sources are)."""
     from raht_3dgs_codec_amd import rlgr
-    ref = None
-    refdir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
-    if os.path.isdir(refdir):
-        sys.path.insert(0, refdir)
-        try:
-            ref = importlib.import_module("rlgr")
-            if not hasattr(ref, "membuf") or ref is rlgr:
-                ref = None
-        except Exception:
-            ref = None
-        finally:
-            sys.path.remove(refdir)
-    rng = np.random.default_rng(7)
-    cases = []
-    for t in range(300):
-        n = int(rng.integers(0, 3000))
-        kind = t % 6
-        if kind == 0:
-            x = np.zeros(n, dtype=np.int32)
-        elif kind == 1:
-            x = np.round(rng.laplace(0, 0.05, n)).astype(np.int32)
-        elif kind == 2:
-            x = np.round(rng.laplace(0, 30, n)).astype(np.int32)
-        elif kind == 3:
-            x = rng.integers(-2 ** 31 + 1, 2 ** 31 - 1, n).astype(np.int32)
-        elif kind == 4:
-            x = np.zeros(n, dtype=np.int32)
-            if n:
-                x[rng.integers(0, n, max(1, n // 500))] = rng.integers(-2 ** 30, 2 ** 30, max(1, n // 500))
-        else:
-            x = np.round(rng.normal(0, 10 ** rng.uniform(-1, 6), n)).astype(np.int32)
-        cases.append(x)
-    cases.append(np.zeros(300_000, dtype=np.int32))                 # one very long run: the run parameter keeps growing
+    from .rlgr_inputs import digest, random_sequences
+    ref = _reference_build()
+    xs = random_sequences()
+    assert len(xs) == 300 and np.array_equal(RANDOM["x_len"], [len(x) for x in xs])
+    assert np.array_equal(np.stack([digest(x) for x in xs]), RANDOM["x_sha256"]), "seeded inputs differ from the digested ones"
+    cases = list(zip(xs, RANDOM["bytes_len"], RANDOM["sha256"]))
+    cases.append((np.zeros(300_000, dtype=np.int32), None, None))   # one very long run: the run parameter keeps growing
     checked = 0
-    for x in cases:
+    for x, n_bytes, sha in cases:
         streams, _ = rlgr.encode_channels(x.reshape(1, -1), 1, nthreads=1, channel_major=True)
         back, _ = rlgr.decode_channels(streams, x.shape[0], 1, nthreads=1, channel_major=True)
         assert np.array_equal(back.reshape(-1), x)
+        if sha is not None:
+            s = np.frombuffer(streams[0].tobytes(), dtype=np.uint8)
+            assert len(s) == int(n_bytes) and np.array_equal(digest(s), sha)
+            checked += 1
         if ref is not None and x.shape[0] <= 3000:
             m = ref.membuf()
             m.rlgrWrite(x.tolist(), 1)
             m.close()
             assert bytes(bytearray(m.get_buffer())) == streams[0].tobytes()
-            checked += 1
-    assert ref is None or checked == 300
+    assert checked == 300
 
 
 def test_channel_coder_keeps_one_arena_and_checks_round_trips():

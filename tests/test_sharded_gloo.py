@@ -28,6 +28,13 @@ def _free_port():
     return p
 
 
+def _cpu_barrier():
+    """dist.barrier() asks torch for an accelerator at run time (torch._C._get_accelerator), which initialises HIP and
+    opens the GPU in every rank on a machine that has one. These ranks are CPU-only: an all-reduce of a CPU tensor over
+    gloo synchronises them the same way without touching the device."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, J, n, D, q, balanced=False, prefix_range=None):
     try:
         sys.path.insert(0, ROOT)
@@ -85,7 +92,7 @@ def _worker(rank, world, port, J, n, D, q, balanced=False, prefix_range=None):
         e_loc = torch.tensor([float(((Rq - C_loc) ** 2).sum()), float(((Tq - T) ** 2).sum())], dtype=torch.float64)
         dist.all_reduce(e_loc)
         assert abs(e_loc[0].item() - e_loc[1].item()) <= 1e-6 * max(e_loc[1].item(), 1e-30)
-        dist.barrier()
+        _cpu_barrier()
         dist.destroy_process_group()
         q.put((rank, "ok"))
     except Exception:
@@ -178,7 +185,7 @@ def _worker_frontend(rank, world, port, J, n, d, q, empty_rank=-1):
         np.testing.assert_allclose(T.numpy(), To[lo:lo + PCvox.shape[0]], rtol=1e-11, atol=1e-11 * np.abs(To).max())
         chk = sh.check_against_unsharded(C_loc, 0.05)
         assert chk["ok"], chk
-        dist.barrier()
+        _cpu_barrier()
         dist.destroy_process_group()
         q.put((rank, "ok"))
     except Exception:

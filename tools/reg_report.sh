@@ -2,8 +2,11 @@
 # VGPRs / spills / occupancy of every tile and top kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
 # Any spill is a regression: a kernel that touches scratch at all lost 30 %.
 cd "$(dirname "$0")/../raht-3dgs-codec_amd/csrc" || exit 1
+# a private object file: a fixed name under /tmp can belong to another user of the machine
+obj=$(mktemp "${TMPDIR:-/tmp}/reg_report.XXXXXX.o") || exit 1
+trap 'rm -f "$obj"' EXIT
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -fno-fast-math -ffp-contract=on ${EXTRA} \
-  -Rpass-analysis=kernel-resource-usage -c ${1:-transform.hip} -o /tmp/reg_report.o 2>&1 | python3 -c "
+  -Rpass-analysis=kernel-resource-usage -c ${1:-transform.hip} -o "$obj" 2>&1 | python3 -c "
 import re,sys
 cur=None; rows=[]
 for line in sys.stdin:
