@@ -231,7 +231,9 @@ def rlgr_decode(buf, N, flag_signed=1):
 
 
 def merge_clusters(cluster_indices, cluster_offsets, means, quats, scales, opacities, colors, weight_by_opacity=True):
-    """merge_weighted_mean_kernel restated from cuda/merge_cluster.cu:2-111 (PARITY UNPINNED)."""
+    """merge_weighted_mean_kernel restated from cuda/merge_cluster.cu:2-111, in the HIP kernels' float32 operation order (they
+    must match it bit for bit). Its own bit parity with a CUDA build stays UNPINNED; it is checked against the independent
+    float64 model tests/numpy_merge.py within that model's error bars (tests/test_merge_model.py)."""
     ci = np.ascontiguousarray(cluster_indices, dtype=np.int32)
     co = np.ascontiguousarray(cluster_offsets, dtype=np.int32)
     f = lambda a: np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731

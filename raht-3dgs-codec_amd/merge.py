@@ -1,5 +1,10 @@
 """Per-voxel Gaussian merge: drop-in for the reference's ``merge_cluster_cuda`` Python API
-(reference cuda/merge_cluster_cuda/__init__.py:30-204), backed by the HIP kernel in csrc/merge.hip."""
+(reference cuda/merge_cluster_cuda/__init__.py:30-204), backed by the HIP kernel in csrc/merge.hip.
+
+What is pinned: ``prepare_cluster_data`` against the reference's own function (fixture tests/golden/merge/merge_prepare.npz:
+offsets exactly, members per cluster as a set); the kernel's arithmetic against an independent float64 model of
+cuda/merge_cluster.cu within derived float32 error bars (tests/numpy_merge.py). What is not: bit parity with a CUDA build
+of the reference, which cannot run here (its setup.py also builds with --use_fast_math)."""
 import ctypes as C
 
 import torch

@@ -10,7 +10,8 @@ fixture holds inputs and the reference's outputs (data only -- no reference sour
 Reference entry points exercised (the ``raht_fn`` table of python/encode_3dgs.py:23-27 plus the
 voxelizer):  RAHT_param_reorder_fast (RAHT_param.py:190), RAHT2_optimized (RAHT.py:252),
 inverse_RAHT_optimized (iRAHT.py:40), get_morton_code / voxelize_pc_batched (voxelize_pc.py:25,62),
-and the driver-inline quantize/reorder arithmetic (encode_3dgs.py:204-217, 261-268).
+and the driver-inline quantize/reorder arithmetic (encode_3dgs.py:204-217, 261-268); the Gaussian merge's
+prepare_cluster_data (cuda/merge_cluster_cuda/__init__.py:30-75) for merge/merge_prepare.npz.
 """
 import os
 import sys
@@ -528,3 +529,45 @@ def rlgr_random_cases():
 
 if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "rlgr_random"):
     rlgr_random_cases()
+
+
+def merge_cases():
+    """The reference's ``prepare_cluster_data`` (cuda/merge_cluster_cuda/__init__.py:30-75, pure torch, runs on the CPU; only
+    its ``_C`` import is CUDA-only and merely warns) on seeded label sets: labels -> (cluster_indices, cluster_offsets).
+    The reference's argsort is unstable, so the order INSIDE a cluster is not part of the answer; the tests compare the
+    offsets exactly and the indices as a set per cluster. Stored flat: set k is labels[lab_off[k]:lab_off[k + 1]],
+    its indices are at the same positions, its offsets are offsets[off_off[k]:off_off[k + 1]]."""
+    import warnings
+    sys.path.insert(0, os.path.join(os.path.dirname(REF), "cuda"))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        import merge_cluster_cuda
+    rng = np.random.default_rng(20261015)
+    sets = [("docstring", np.array([2, 0, 2, 1, 0, 2], np.int64)),
+            ("n1", np.array([7], np.int64)),
+            ("all_equal", np.full(1000, 3, np.int64)),
+            ("all_distinct", rng.permutation(2000).astype(np.int64)),
+            ("negative", rng.integers(-50, 50, size=3000).astype(np.int64)),
+            ("sparse_1e12", rng.choice(rng.integers(0, 10 ** 12, size=400), size=4000))]
+    # a few clusters of thousands of members among many singletons, shuffled
+    big = np.concatenate([np.full(n, -(k + 1), np.int64) for k, n in enumerate((5000, 3000, 1500))])
+    skew = np.concatenate([big, np.arange(6000, dtype=np.int64) * 17 + 5])
+    sets.append(("skewed", skew[rng.permutation(skew.size)]))
+    labels, indices, offsets, lab_off, off_off = [], [], [], [0], [0]
+    for _, lab in sets:
+        ci, co = merge_cluster_cuda.prepare_cluster_data(torch.from_numpy(lab))
+        labels.append(lab)
+        indices.append(ci.numpy().astype(np.int32))
+        offsets.append(co.numpy().astype(np.int32))
+        lab_off.append(lab_off[-1] + lab.size)
+        off_off.append(off_off[-1] + co.numel())
+    # (in a directory of its own: every tests/golden/*.npz outside the rlgr_ / pipeline_ / voxres_ families is a transform case)
+    os.makedirs(os.path.join(HERE, "merge"), exist_ok=True)
+    np.savez_compressed(os.path.join(HERE, "merge", "merge_prepare.npz"), names=np.array([n for n, _ in sets]),
+                        labels=np.concatenate(labels), indices=np.concatenate(indices), offsets=np.concatenate(offsets),
+                        lab_off=np.array(lab_off, np.int64), off_off=np.array(off_off, np.int64))
+    print("merge_prepare:", len(sets), "label sets,", lab_off[-1], "labels")
+
+
+if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "merge_prepare"):
+    merge_cases()
