@@ -110,10 +110,18 @@ int raht_plan_create_from_keys_borrowed(const uint64_t *keys_sorted, int64_t N, 
  *                               (row stride D), or NULL. When set, forward transforms write the roots'
  *                               low-pass rows there (and, in the fused-quantization entry, leave
  *                               their Q rows untouched), inverse transforms read the roots from
- *                               there instead of from T / Q. */
+ *                               there instead of from T / Q.
+ *   raht_plan_set_root_buffer_wide : the second root buffer of the MIXED-precision entries (raht_fwd_quant_mixed,
+ *                               raht_dequant_inv_mixed): DEVICE n_roots x n_wide doubles (row stride n_wide), or NULL.
+ *                               With both buffers set, the mixed forward writes the roots' columns [n_wide, D) to the
+ *                               float buffer and their columns [0, n_wide) to this one, in float64, unrounded (their Q
+ *                               rows untouched); the mixed inverse reads them from the two. What the float buffer's
+ *                               columns [0, n_wide) hold is unspecified: nothing may read them. Truncated plans run the
+ *                               mixed entries only with both buffers set; the other entries ignore this one. */
 int raht_plan_set_top_level(raht_plan *plan, int top_level, raht_stream_t stream);
 int raht_plan_roots(const raht_plan *plan, int64_t *n_roots, int64_t *rows_dev, raht_stream_t stream);
 int raht_plan_set_root_buffer(raht_plan *plan, void *buf_dev);
+int raht_plan_set_root_buffer_wide(raht_plan *plan, double *buf_dev);
 
 /* Row map (small plans only: N <= 8192, they run as ONE launch): plan row i lives in row map[i] of the
  * matrices handed to raht_fwd* / raht_inv* (which then have n_matrix_rows rows; rows outside the map are not
@@ -246,7 +254,9 @@ int raht_dequant_inv_f64(const raht_plan *plan, const int32_t *Q, int64_t ldq, i
  *   channels [n_wide, D)  : float32 arithmetic with (float) steps[c]: bit-identical to raht_fwd_quant / raht_dequant_inv.
  * steps: HOST float64[n_steps], n_steps == 1 or D. D - n_wide >= 4 and D <= 68 run the mixed tile kernels (one pass, ~5 % slower
  * than the float32 kernels); other shapes, and plans switched to the level engine, run the float32 path followed by a float64
- * pass over the n_wide columns (same results up to rounding ties). Not available for row-mapped or truncated plans. */
+ * pass over the n_wide columns (same results up to rounding ties). Not available for row-mapped plans. Root buffers: both
+ * (raht_plan_set_root_buffer + raht_plan_set_root_buffer_wide) or neither; truncated plans need both -- the shard-local
+ * half of a Morton-prefix sharded step (the roots' Q rows are left to the caller's top stage). */
 int raht_fwd_quant_mixed(const raht_plan *plan, const float *C, int64_t ldc, int D, const double *steps, int n_steps,
                          int n_wide, int32_t *Q, int64_t ldq, raht_stream_t stream);
 int raht_dequant_inv_mixed(const raht_plan *plan, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps,
@@ -433,6 +443,12 @@ int raht_quant_rows(const float *X, int64_t ldx, int64_t n, int D, const float *
                     const int64_t *pos, int32_t *Q, int64_t ldq, raht_stream_t stream);
 int raht_dequant_rows(const int32_t *Q, int64_t ldq, const int64_t *pos, int64_t n, int D, const float *steps,
                       int n_steps, float *X, int64_t ldx, raht_stream_t stream);
+/* The same at the reference's precision (float64 X, float64 steps, IEEE double division as raht_quant_reorder_f64): the
+ * sharded driver quantizes the top tree's wide columns of a mixed-precision step with these. */
+int raht_quant_rows_f64(const double *X, int64_t ldx, int64_t n, int D, const double *steps, int n_steps,
+                        const int64_t *pos, int32_t *Q, int64_t ldq, raht_stream_t stream);
+int raht_dequant_rows_f64(const int32_t *Q, int64_t ldq, const int64_t *pos, int64_t n, int D, const double *steps,
+                          int n_steps, double *X, int64_t ldx, raht_stream_t stream);
 
 /* Rows at explicit positions, no arithmetic (elem_size 4 or 8 bytes per element; pos: DEVICE int64[n]):
  *   raht_rows_gather :  dst[i, :] = src[pos[i], :]        raht_rows_scatter :  dst[pos[i], :] = src[i, :]

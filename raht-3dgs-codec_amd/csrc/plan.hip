@@ -2043,6 +2043,13 @@ int raht_plan_set_root_buffer(raht_plan *p, void *buf_dev)
     return RAHT_OK;
 }
 
+int raht_plan_set_root_buffer_wide(raht_plan *p, double *buf_dev)
+{
+    if (!p) return RAHT_ERR_INVALID;
+    p->root_buf_w = buf_dev;
+    return RAHT_OK;
+}
+
 int raht_plan_copy_array(const raht_plan *p, int which, void *dst, raht_stream_t stream)
 {
     if (!p || !dst || which < 0 || which > 3) { set_error("raht_plan_copy_array: bad argument"); return RAHT_ERR_INVALID; }

@@ -160,6 +160,26 @@ __global__ __launch_bounds__(256) void reorder_f64_kernel(const void *__restrict
     }
 }
 
+// A few rows at explicit positions, float64 (raht_quant_rows_f64 / raht_dequant_rows_f64): QUANT: Q[pos[i], :] = quantize(X[i, :]);
+// else X[i, :] = Q[pos[i], :] * step
+template <bool QUANT>
+__global__ __launch_bounds__(256) void rows_f64_kernel(const void *__restrict__ src_, int64_t lds, int64_t n, int D,
+                                                       const int64_t *__restrict__ pos, const StepTable64 steps,
+                                                       void *__restrict__ dst_, int64_t ldd)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t i = wave; i < n; i += nwaves) {
+        const int64_t r = pos ? pos[i] : i;
+        for (int c = lane; c < D; c += 64) {
+            const double st = steps.v[steps.n == 1 ? 0 : c];
+            if constexpr (QUANT) ((int32_t *)dst_)[r * ldd + c] = quantize_one_f64(((const double *)src_)[i * lds + c], st);   // :204, :215
+            else ((double *)dst_)[i * ldd + c] = (double)((const int32_t *)src_)[r * lds + c] * st;                         // :261
+        }
+    }
+}
+
 static int fill_steps64(StepTable64 &t, const double *steps, int n_steps, int D)
 {
     if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("quant: n_steps must be 1 or D"); return RAHT_ERR_INVALID; }
@@ -390,6 +410,34 @@ int raht_dequant_rows(const int32_t *Q, int64_t ldq, const int64_t *pos, int64_t
     if (!X || !Q || ldx < D || ldq < D) { set_error("raht_dequant_rows: bad argument"); return RAHT_ERR_INVALID; }
     const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
     hipLaunchKernelGGL(dequant_rows_kernel, dim3(gb), dim3(256), 0, (hipStream_t)stream, Q, ldq, pos, n, D, st, X, ldx);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+int raht_quant_rows_f64(const double *X, int64_t ldx, int64_t n, int D, const double *steps, int n_steps,
+                        const int64_t *pos, int32_t *Q, int64_t ldq, raht_stream_t stream)
+{
+    if (n < 0 || D < 1) { set_error("raht_quant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
+    StepTable64 st;
+    RAHT_RET(fill_steps64(st, steps, n_steps, D));
+    if (n == 0) return RAHT_OK;
+    if (!X || !Q || ldx < D || ldq < D) { set_error("raht_quant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
+    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
+    hipLaunchKernelGGL(rows_f64_kernel<true>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)X, ldx, n, D, pos, st, (void *)Q, ldq);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+int raht_dequant_rows_f64(const int32_t *Q, int64_t ldq, const int64_t *pos, int64_t n, int D, const double *steps,
+                          int n_steps, double *X, int64_t ldx, raht_stream_t stream)
+{
+    if (n < 0 || D < 1) { set_error("raht_dequant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
+    StepTable64 st;
+    RAHT_RET(fill_steps64(st, steps, n_steps, D));
+    if (n == 0) return RAHT_OK;
+    if (!X || !Q || ldx < D || ldq < D) { set_error("raht_dequant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
+    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
+    hipLaunchKernelGGL(rows_f64_kernel<false>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)Q, ldq, n, D, pos, st, (void *)X, ldx);
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }

@@ -67,9 +67,14 @@ struct MxPtrs {
     const double *in_w;      // fwd, stages >= 1: wide part of ws_k (n_wide doubles per entry)
     double *out_w;           // inv, stages >= 1: wide part of ws_k
     double *wsn_w;           // wide part of ws_{k+1}
+    double *root_w;          // last stage of a plan with root buffers: the roots' wide channels (n_wide doubles per root); their
+                             // float channels go through TileArgs::root_buf (D floats per root, the wide columns' floats unspecified)
 };
 
-template <bool INV, bool IDENT, int SLOTS>
+// ROOTS: last stage of a plan with root buffers (TileArgs::root_buf, MxPtrs::root_w): the roots' low-pass rows go to / come from
+// the caller's buffers instead of Q. A kernel of its own (tile_kernel_mx_roots), so that every other launch runs the code it ran
+// without them.
+template <bool INV, bool IDENT, int SLOTS, bool ROOTS>
 __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &ST, const int64_t tile_id)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -238,7 +243,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             m_merged[s] = (r > 0) && (m_lv[s] < A.top_level) && (r - m_wl[s] >= start_row) && (r + m_wr[s] <= end_row);
             surv = !m_merged[s];
             sflag[j] = m_merged[s] ? 1 : (A.last_stage ? 2 : 0);
-            if (!INV) sdst[j] = m_pos[s] | ((m_merged[s] || A.last_stage) ? (int32_t)0x80000000 : 0);
+            if (!INV) sdst[j] = m_pos[s] | ((m_merged[s] || (A.last_stage && !ROOTS)) ? (int32_t)0x80000000 : 0);
             if (m_merged[s]) atomicAdd(&hist[m_ht[s]], 1u);
         }
         const uint64_t bal = __ballot(surv);
@@ -286,11 +291,24 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
                 const uint32_t qc = c / (uint32_t)nwide, i = c - qc * (uint32_t)nwide;
                 wd[__mul24((int)ssurv[qc], nwide) + i] = spre_w[c];
             }
+        } else if (ROOTS) {
+            // last stage of a plan with root buffers (a truncated tree's top rows): the roots' low-pass rows come from the caller's
+            // two buffers -- the float places at their channels in the float buffer (row stride D), the wide channels from the
+            // float64 one -- instead of from Q
+            if (c4 < NF) for (uint32_t it = wid; (it << lr) < surv_cnt; it += nwv) {
+                const uint32_t qc = min((it << lr) + g, surv_cnt - 1);
+                const V16 x = ld_chunk<float>(A.root_buf + (int64_t)(surv_base + qc) * Df + goff);
+                *(V16 *)&ftile[__mul24((int)ssurv[qc], Fp) + fl * 4] = x;
+            }
+            for (uint32_t c = (uint32_t)tid; c < surv_cnt * (uint32_t)nwide; c += (uint32_t)nthreads) {
+                const uint32_t qc = c / (uint32_t)nwide, i = c - qc * (uint32_t)nwide;
+                wd[__mul24((int)ssurv[qc], nwide) + i] = P.root_w[(int64_t)surv_base * nwide + c];
+            }
         }
         sync_lds();
         load_steps(fl);
         // roots finalised by a last TILE stage come straight from Q as well: dequantize them in place (no butterfly will)
-        if (A.last_stage && c4 < NF) for (int it = wid; (it << lr) < nt; it += nwv) {
+        if (A.last_stage && !ROOTS && c4 < NF) for (int it = wid; (it << lr) < nt; it += nwv) {
             const int j = (it << lr) + g;
             if (j < nt && sflag[j] == 2) {
                 V16 *pr = (V16 *)&ftile[__mul24(j, Fp) + fl * 4];
@@ -308,7 +326,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s) {
             const int j = ((tid + (nthreads >> 1)) & (nthreads - 1)) + s * nthreads;
-            if (j < nt && (sflag[j] != 0)) widen_row(j, std::true_type());
+            if (j < nt && (ROOTS ? sflag[j] == 1 : sflag[j] != 0)) widen_row(j, std::true_type());   // (ROOTS: not the roots, 2)
         }
     }
 
@@ -518,14 +536,17 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             for (int c = tid; c < nt * nwide; c += nthreads) bw_[c] = wd[c];
         }
     } else {
-        // survivors, compacted, to the next stage's workspace (row images, two dense arrays)
-        if (!A.last_stage) {
-            float *bf = A.wsn + (int64_t)surv_base * Fp;
-            double *bw_ = P.wsn_w + (int64_t)surv_base * nwide;
+        // survivors, compacted, to the next stage's workspace (row images, two dense arrays); last stage of a plan with root
+        // buffers: the roots to the caller's two buffers (float: row stride D, each place at its channels; wide: n_wide doubles)
+        if (!A.last_stage || ROOTS) {
+            constexpr bool to_roots = ROOTS;
+            float *bf = to_roots ? A.root_buf + (int64_t)surv_base * Df : A.wsn + (int64_t)surv_base * Fp;
+            double *bw_ = (to_roots ? P.root_w : P.wsn_w) + (int64_t)surv_base * nwide;
+            const uint32_t ldb = (uint32_t)(to_roots ? Df : Fp), cb = (uint32_t)(to_roots ? goff : fl * 4);
             if (c4 < NF) for (uint32_t it = wid; (it << lr) < surv_cnt; it += nwv) {
                 const uint32_t q = min((it << lr) + g, surv_cnt - 1);
                 const V16 x = *(const V16 *)&ftile[__mul24((int)ssurv[q], Fp) + fl * 4];
-                st_chunk<float>(row_at(bf, q, (uint32_t)Fp, (uint32_t)(fl * 4)), x);
+                st_chunk<float>(row_at(bf, q, ldb, cb), x);
             }
             for (uint32_t c = (uint32_t)tid; c < surv_cnt * (uint32_t)nwide; c += (uint32_t)nthreads) {
                 const uint32_t q = c / (uint32_t)nwide, i = c - q * (uint32_t)nwide;
@@ -598,7 +619,13 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
 template <bool INV, bool IDENT, int SLOTS>
 __global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx(const TileArgs<float> A, const MxPtrs P, const StepTableMX ST)
 {
-    tile_body_mx<INV, IDENT, SLOTS>(A, P, ST, (int64_t)blockIdx.x);
+    tile_body_mx<INV, IDENT, SLOTS, false>(A, P, ST, (int64_t)blockIdx.x);
+}
+// the last stage of a plan with root buffers
+template <bool INV, bool IDENT, int SLOTS>
+__global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_roots(const TileArgs<float> A, const MxPtrs P, const StepTableMX ST)
+{
+    tile_body_mx<INV, IDENT, SLOTS, true>(A, P, ST, (int64_t)blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -618,9 +645,11 @@ struct TopArgsMX {
     const uint32_t *lev;
     int nlev, nbig;
     uint32_t small_start;
+    const uint32_t *root_rank;               // entry -> row of the root buffers (~0u: not a root)
+    float *root_f; double *root_w;           // the caller's root buffers (n_roots x D floats, n_roots x n_wide doubles), or nullptr
 };
 
-template <bool WIDE, bool INV>
+template <bool WIDE, bool INV, bool ROOTS>
 __device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableMX &ST, const int chunk)
 {
     typedef typename std::conditional<WIDE, double, float>::type T;
@@ -660,9 +689,12 @@ __device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableM
         const int idx = min(k * MX_TOP_THREADS + tid, max(nm - 1, 0));
         pj[k] = A.pj[idx]; ra[k] = ab[2 * idx]; rb[k] = ab[2 * idx + 1];
     }
-    uint32_t m_dst[MX_TOP_SLOTS];
+    uint32_t m_dst[MX_TOP_SLOTS], m_rr[MX_TOP_SLOTS];
 #pragma unroll
-    for (int k = 0; k < MX_TOP_SLOTS; ++k) m_dst[k] = A.e_pos[min(k * MX_TOP_THREADS + tid, n - 1)];
+    for (int k = 0; k < MX_TOP_SLOTS; ++k) {
+        m_dst[k] = A.e_pos[min(k * MX_TOP_THREADS + tid, n - 1)];
+        m_rr[k] = ROOTS ? A.root_rank[min(k * MX_TOP_THREADS + tid, n - 1)] : 0xffffffffu;
+    }
     // the entries
 #pragma unroll
     for (int k = 0; k < MX_TOP_SLOTS; ++k) {
@@ -682,6 +714,13 @@ __device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableM
                 for (int i = 0; i < VN; ++i) v.v[i] = live[i] ? (double)A.in_rows[(int64_t)e * A.ld_in + goff + i] : 0.0;
             } else {
                 v = ld_chunk<float>(A.in_rows + (int64_t)e * A.ld_in + goff);
+            }
+        } else if (m_rr[k] != 0xffffffffu) {                // a root: its low-pass row from the caller's root buffers
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int i = 0; i < VN; ++i) v.v[i] = live[i] ? A.root_w[(int64_t)m_rr[k] * nwide + goff + i] : 0.0;
+            } else {
+                v = ld_chunk<float>(A.root_f + (int64_t)m_rr[k] * A.D + goff);
             }
         } else {
             const int32_t *q = A.Q + (int64_t)m_dst[k] * A.ldq + goff;
@@ -765,6 +804,13 @@ __device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableM
             } else {
                 st_chunk<float>(A.out_rows + (int64_t)e * A.ld_out + goff, v);
             }
+        } else if (m_rr[k] != 0xffffffffu) {                // a root: still a low-pass value, the caller's top stage takes it
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int i = 0; i < VN; ++i) if (live[i]) A.root_w[(int64_t)m_rr[k] * nwide + goff + i] = v.v[i];
+            } else {
+                st_chunk<float>(A.root_f + (int64_t)m_rr[k] * A.D + goff, v);
+            }
         } else {
             int32_t *q = A.Q + (int64_t)m_dst[k] * A.ldq + goff;
             if constexpr (WIDE) {
@@ -789,8 +835,16 @@ template <bool INV>
 __global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx(const TopArgsMX A, const StepTableMX ST)
 {
     const int NW2 = (A.nwide + 1) >> 1;
-    if ((int)blockIdx.x < NW2) top_body_mx<true, INV>(A, ST, (int)blockIdx.x);
-    else top_body_mx<false, INV>(A, ST, (int)blockIdx.x - NW2);
+    if ((int)blockIdx.x < NW2) top_body_mx<true, INV, false>(A, ST, (int)blockIdx.x);
+    else top_body_mx<false, INV, false>(A, ST, (int)blockIdx.x - NW2);
+}
+// a plan with root buffers (a separate kernel, as for the tile stages)
+template <bool INV>
+__global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_roots(const TopArgsMX A, const StepTableMX ST)
+{
+    const int NW2 = (A.nwide + 1) >> 1;
+    if ((int)blockIdx.x < NW2) top_body_mx<true, INV, true>(A, ST, (int)blockIdx.x);
+    else top_body_mx<false, INV, true>(A, ST, (int)blockIdx.x - NW2);
 }
 
 // the wide columns of caller rows <-> a compact float64 matrix (fallback path only)
@@ -852,15 +906,24 @@ static void fill_steps_mx(StepTableMX &t, const double *steps, int n_steps, int 
     for (int i = 0; i < MX_MAX_WIDE; ++i) t.w[i] = i < nwide ? steps[n_steps == 1 ? 0 : i] : 1.0;
 }
 
-template <bool INV, bool IDENT, int SLOTS>
+template <bool INV, bool IDENT, int SLOTS, bool ROOTS>
 static int launch_tile_mx_one(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, unsigned n_tiles, size_t lds, hipStream_t s)
 {
+    const void *fn = ROOTS ? (const void *)tile_kernel_mx_roots<INV, IDENT, SLOTS> : (const void *)tile_kernel_mx<INV, IDENT, SLOTS>;
     static PerDeviceOnce attr;
     if (attr.first(current_device()))
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx<INV, IDENT, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((tile_kernel_mx<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
+        RAHT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if constexpr (ROOTS) hipLaunchKernelGGL((tile_kernel_mx_roots<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
+    else hipLaunchKernelGGL((tile_kernel_mx<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
+}
+
+template <bool INV, bool IDENT, bool ROOTS>
+static int launch_tile_mx_slots(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, unsigned n_tiles, size_t lds, hipStream_t s)
+{
+    return A.R <= MX_THREADS ? launch_tile_mx_one<INV, IDENT, 1, ROOTS>(A, P, st, n_tiles, lds, s)
+                             : launch_tile_mx_one<INV, IDENT, 2, ROOTS>(A, P, st, n_tiles, lds, s);
 }
 
 struct MxIO {
@@ -888,16 +951,21 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
         else { if (k == 0) { A.out_rows = io.C_out; A.ld_out = io.ldc; } else { A.out_img = ws_k; A.out_img_w = ws_k_w; } }
         A.Q = io.Q; A.ldq = io.ldq;
         A.e_pos = st.rows ? st.e_pos : p->inv_order;
+        A.root_rank = st.t_root;
+        A.root_f = (float *)p->root_buf; A.root_w = p->root_buf_w;      // (mx_check_args: both or neither)
         A.pj = st.t_pj; A.ab32 = st.t_ab32; A.ab64 = st.t_ab64;
         A.n = (int)st.n_entries; A.n_merges = (int)st.n_merges; A.D = D; A.nwide = g.nwide; A.Fp = g.Dp;
         A.lev = st.t_lev; A.nlev = st.t_nlev; A.nbig = st.t_nbig; A.small_start = st.t_small_start;
-        if (!A.e_pos || !A.pj || !A.ab32 || !A.ab64 || !A.lev || !A.Q) { set_error("mixed top stage: missing plan arrays"); return RAHT_ERR_INVALID; }
+        if (!A.e_pos || !A.pj || !A.ab32 || !A.ab64 || !A.lev || !A.Q || (A.root_f && !A.root_rank)) { set_error("mixed top stage: missing plan arrays"); return RAHT_ERR_INVALID; }
         const size_t n_small = st.n_merges - st.t_small_start;
         const size_t lds = (size_t)st.n_entries * 16 + ((n_small + 3) & ~(size_t)3) * 4 + n_small * 2 * sizeof(double);
         static PerDeviceOnce attr;
-        if (attr.first(current_device()))
+        if (attr.first(current_device())) {
             RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        hipLaunchKernelGGL((top_kernel_mx<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
+            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_roots<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+        }
+        if (A.root_f) hipLaunchKernelGGL((top_kernel_mx_roots<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
+        else hipLaunchKernelGGL((top_kernel_mx<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
         RAHT_HIP_CHECK(hipGetLastError());
         return RAHT_OK;
     }
@@ -910,7 +978,7 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
     else { A.lvl = p->lvl; A.wl = p->wl; A.wr = p->wr; A.inv_order = p->inv_order; }
     A.ht = st.e_ht;
     A.Q = io.Q; A.ldq = io.ldq;
-    A.top_level = p->top_level; A.root_buf = nullptr; A.dbg = 0; A.ref = nullptr; A.ld_ref = 0; A.sq_part = nullptr;
+    A.top_level = p->top_level; A.root_buf = A.last_stage ? (float *)p->root_buf : nullptr; A.dbg = 0; A.ref = nullptr; A.ld_ref = 0; A.sq_part = nullptr;
     A.ld_ws = g.Dp; A.wsn = ws_n;
     A.fin = nullptr; A.ld_fin = 0;
     if (!INV) { A.in = (k == 0) ? io.C_in : ws_k; A.ld_in = (k == 0) ? io.ldc : g.Dp; A.out = nullptr; A.ld_out = 0; }
@@ -932,13 +1000,13 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
     P.in_w = (!INV && k >= 1) ? ws_k_w : nullptr;
     P.out_w = (INV && k >= 1) ? ws_k_w : nullptr;
     P.wsn_w = ws_n_w;
+    P.root_w = A.last_stage ? p->root_buf_w : nullptr;
     const size_t lds = tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide, st.rows == nullptr);
-    const bool one = st.tile_rows <= MX_THREADS;
     const unsigned nt = (unsigned)st.n_tiles;
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
     int rc;
-    if (k == 0) rc = one ? launch_tile_mx_one<INV, true, 1>(A, P, stp, nt, lds, s) : launch_tile_mx_one<INV, true, 2>(A, P, stp, nt, lds, s);
-    else rc = one ? launch_tile_mx_one<INV, false, 1>(A, P, stp, nt, lds, s) : launch_tile_mx_one<INV, false, 2>(A, P, stp, nt, lds, s);
+    if (k == 0) rc = A.root_buf ? launch_tile_mx_slots<INV, true, true>(A, P, stp, nt, lds, s) : launch_tile_mx_slots<INV, true, false>(A, P, stp, nt, lds, s);
+    else rc = A.root_buf ? launch_tile_mx_slots<INV, false, true>(A, P, stp, nt, lds, s) : launch_tile_mx_slots<INV, false, false>(A, P, stp, nt, lds, s);
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
     return rc;
 }
@@ -953,8 +1021,29 @@ static int mx_check_args(const raht_plan *p, const void *a, const void *b, int D
     if (n_steps > MAX_STEP_CH) { set_error("%s: per-channel steps support D <= %d", what, MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
     for (int c = 0; c < n_steps; ++c)
         if (!(steps[c] > 0.0) || !((float)steps[c] > 0.0f)) { set_error("%s: step[%d] must be > 0 (also as float32)", what, c); return RAHT_ERR_INVALID; }
-    if (p->row_map || p->root_buf || p->top_level < 64) { set_error("%s: not available for row-mapped or truncated plans", what); return RAHT_ERR_UNSUPPORTED; }
+    if (p->row_map) { set_error("%s: not available for row-mapped plans", what); return RAHT_ERR_UNSUPPORTED; }
+    // root buffers: both (float n_roots x D, float64 n_roots x n_wide) or neither; a truncated plan's roots need them
+    if ((p->root_buf == nullptr) != (p->root_buf_w == nullptr)) {
+        set_error("%s: set both root buffers (raht_plan_set_root_buffer and raht_plan_set_root_buffer_wide) or neither", what);
+        return RAHT_ERR_UNSUPPORTED;
+    }
+    if (p->top_level < 64 && !p->root_buf) {
+        set_error("%s: a truncated plan needs both root buffers (raht_plan_set_root_buffer, raht_plan_set_root_buffer_wide)", what);
+        return RAHT_ERR_UNSUPPORTED;
+    }
     return RAHT_OK;
+}
+
+// fallback path: a float64 call over the compact wide columns, with the plan's root pointer on the wide root buffer (n_wide doubles
+// per root, i.e. that call's own row stride) for its duration
+template <typename F>
+static int with_wide_roots(raht_plan *p, F &&call)
+{
+    void *const saved = p->root_buf;
+    if (saved) p->root_buf = p->root_buf_w;
+    const int rc = call();
+    p->root_buf = saved;
+    return rc;
 }
 
 // schedule for the mixed tile kernels, or *sc_out = nullptr when this (plan, D, n_wide) takes the fallback
@@ -982,7 +1071,8 @@ static int fwd_quant_mixed_impl(const raht_plan *cp, const float *C, int64_t ldc
     RAHT_RET(mx_setup(p, D, n_wide, std::max(ldc, ldq), s, &sc, g));
     if (!sc) {
         // shapes / plans the mixed tile kernels do not cover (level engine, D - n_wide < 4, very wide rows): the float32 path for
-        // every channel, then the wide columns once more in float64 through a compact N x n_wide matrix
+        // every channel, then the wide columns once more in float64 through a compact N x n_wide matrix. Root buffers: the float32
+        // pass writes the float one, the float64 pass the wide one (the plan holds ONE root pointer: swapped around that call).
         float f[MAX_STEP_CH];
         for (int c = 0; c < n_steps; ++c) f[c] = (float)steps[c];
         RAHT_RET(raht_fwd_quant(p, C, ldc, D, f, n_steps, Q, ldq, stream));
@@ -991,7 +1081,7 @@ static int fwd_quant_mixed_impl(const raht_plan *cp, const float *C, int64_t ldc
         double *W = tmp.as<double>(), *TW = W + (size_t)p->N * n_wide;
         hipLaunchKernelGGL(mx_cols_to_f64_kernel, dim3((unsigned)ceil_div(p->N * n_wide, 256)), dim3(256), 0, s, C, ldc, p->N, n_wide, W);
         RAHT_HIP_CHECK(hipGetLastError());
-        RAHT_RET(raht_fwd_f64(p, W, n_wide, n_wide, TW, n_wide, nullptr, stream));
+        RAHT_RET(with_wide_roots(p, [&]() { return raht_fwd_f64(p, W, n_wide, n_wide, TW, n_wide, nullptr, stream); }));
         double ws[MX_MAX_WIDE];
         for (int i = 0; i < n_wide; ++i) ws[i] = steps[n_steps == 1 ? 0 : i];
         return raht_quant_reorder_f64(p, TW, n_wide, n_wide, ws, n_wide, Q, ldq, stream);
@@ -1024,7 +1114,7 @@ static int dequant_inv_mixed_impl(const raht_plan *cp, const int32_t *Q, int64_t
         double ws[MX_MAX_WIDE];
         for (int i = 0; i < n_wide; ++i) ws[i] = steps[n_steps == 1 ? 0 : i];
         RAHT_RET(raht_dequant_unreorder_f64(p, Q, ldq, n_wide, ws, n_wide, TW, n_wide, stream));
-        RAHT_RET(raht_inv_f64(p, TW, n_wide, n_wide, W, n_wide, stream));
+        RAHT_RET(with_wide_roots(p, [&]() { return raht_inv_f64(p, TW, n_wide, n_wide, W, n_wide, stream); }));
         hipLaunchKernelGGL(mx_cols_from_f64_kernel, dim3((unsigned)ceil_div(p->N * n_wide, 256)), dim3(256), 0, s, W, p->N, n_wide, C, ldc);
         RAHT_HIP_CHECK(hipGetLastError());
         return RAHT_OK;
@@ -1072,7 +1162,7 @@ int raht_plan_mixed_stats(raht_plan *plan, int D, int n_wide, int *tile_rows, in
         if (!plan || !tile_rows || !n_stages || D < 1 || n_wide < 1 || n_wide > MX_MAX_WIDE) { set_error("raht_plan_mixed_stats: bad argument"); return RAHT_ERR_INVALID; }
         RAHT_RET(check_plan_device(plan, "raht_plan_mixed_stats"));
         *tile_rows = 0; *n_stages = 0;
-        if (plan->row_map || plan->root_buf || plan->top_level < 64) return RAHT_OK;
+        if (plan->row_map) return RAHT_OK;
         Schedule *sc = nullptr;
         MxGeom g;
         RAHT_RET(mx_setup(plan, D, n_wide, D, nullptr, &sc, g));

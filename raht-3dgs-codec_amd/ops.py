@@ -150,6 +150,23 @@ class RahtPlan:
             raise ValueError(f"roots buffer must be a contiguous ({self.n_roots}, {D}) {dtype} tensor")
         check(_lib.lib().raht_plan_set_root_buffer(self._h, C.c_void_p(buf.data_ptr())))
 
+    def _set_mixed_roots(self, roots, roots_wide, D, n_wide):
+        """the two root buffers of the mixed-precision entries: (n_roots, D) float32 (columns [n_wide, D) meaningful) and
+        (n_roots, n_wide) float64; both or neither"""
+        if (roots is None) != (roots_wide is None):
+            raise ValueError("roots and roots_wide go together: pass both or neither")
+        if roots is None:
+            return
+        _need_cuda(roots_wide, "roots_wide")
+        if roots_wide.dtype != torch.float64 or tuple(roots_wide.shape) != (self.n_roots, n_wide) or not roots_wide.is_contiguous():
+            raise ValueError(f"roots_wide must be a contiguous ({self.n_roots}, {n_wide}) float64 tensor")
+        self._set_roots_buffer(roots, D, torch.float32)
+        check(_lib.lib().raht_plan_set_root_buffer_wide(self._h, C.c_void_p(roots_wide.data_ptr())))
+
+    def _reset_mixed_roots(self):
+        check(_lib.lib().raht_plan_set_root_buffer(self._h, None))
+        check(_lib.lib().raht_plan_set_root_buffer_wide(self._h, None))
+
     def __del__(self):
         try:
             if self._h:
@@ -395,11 +412,14 @@ class RahtPlan:
                                                      C.c_void_p(out.data_ptr()) if want_rec else None, D, C.c_void_p(ssd.data_ptr()), _stream()))
         return out, ssd
 
-    def forward_quant_mixed(self, Cmat, steps, n_wide=3):
+    def forward_quant_mixed(self, Cmat, steps, n_wide=3, roots=None, roots_wide=None):
         """Forward RAHT + quantize + reorder of a float32 matrix whose first ``n_wide`` channels (the xyz columns of a
         59-column frame, python/voxelize_pc.py:155) are carried in float64 -- the reference's precision
         (python/encode_3dgs.py:82-83,204) where float32 cannot hold the quotient -- in the same launches as the float32
-        channels. Wide columns: bit-identical to the float64 kernels; the others: bit-identical to ``forward_quant``."""
+        channels. Wide columns: bit-identical to the float64 kernels; the others: bit-identical to ``forward_quant``.
+        roots / roots_wide (together; a truncated plan needs them): (n_roots, D) float32 and (n_roots, n_wide) float64 buffers
+        receiving the roots' low-pass rows -- columns [n_wide, D) in the first (its columns [0, n_wide) are unspecified), columns
+        [0, n_wide) unrounded in the second; the roots' Q rows are left to the caller."""
         _need_cuda(Cmat, "C")
         X = Cmat.to(torch.float32)
         if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
@@ -407,23 +427,34 @@ class RahtPlan:
         D = X.shape[1]
         st = _steps64(steps, D)
         Q = torch.empty((self.N, D), dtype=torch.int32, device=X.device)
-        with torch.cuda.device(X.device):
-            check(_lib.lib().raht_fwd_quant_mixed(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, len(st), int(n_wide),
-                                                  C.c_void_p(Q.data_ptr()), D, _stream()))
+        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
+        try:
+            with torch.cuda.device(X.device):
+                check(_lib.lib().raht_fwd_quant_mixed(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, len(st), int(n_wide),
+                                                      C.c_void_p(Q.data_ptr()), D, _stream()))
+        finally:
+            if roots is not None:
+                self._reset_mixed_roots()
         return Q
 
-    def dequant_inverse_mixed(self, Q, steps, n_wide=3, out=None):
+    def dequant_inverse_mixed(self, Q, steps, n_wide=3, out=None, roots=None, roots_wide=None):
         """Un-reorder + dequantize + inverse RAHT -> float32 C, the first ``n_wide`` channels computed in float64 and
-        rounded once on output (counterpart of ``forward_quant_mixed``)."""
+        rounded once on output (counterpart of ``forward_quant_mixed``). roots / roots_wide: the two root buffers the
+        roots' low-pass rows are read from instead of Q (as ``forward_quant_mixed`` writes them)."""
         _need_cuda(Q, "Q")
         Q = Q.to(torch.int32).contiguous()
         D = Q.shape[1]
         st = _steps64(steps, D)
         if out is None:
             out = torch.empty((self.N, D), dtype=torch.float32, device=Q.device)
-        with torch.cuda.device(Q.device):
-            check(_lib.lib().raht_dequant_inv_mixed(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st), int(n_wide),
-                                                    C.c_void_p(out.data_ptr()), out.stride(0), _stream()))
+        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
+        try:
+            with torch.cuda.device(Q.device):
+                check(_lib.lib().raht_dequant_inv_mixed(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st), int(n_wide),
+                                                        C.c_void_p(out.data_ptr()), out.stride(0), _stream()))
+        finally:
+            if roots is not None:
+                self._reset_mixed_roots()
         return out
 
     def mixed_stats(self, D=59, n_wide=3):
@@ -551,24 +582,27 @@ def dequant_inverse_batch(plans, Qs, steps):
 
 
 def quant_rows(X, steps, pos, Q):
-    """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place (X float32 (n, D), pos int64 (n,), Q int32)."""
+    """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place (X float32 (n, D), pos int64 (n,), Q int32). X and Q may be
+    column slices of wider matrices (contiguous rows, any row stride)."""
     _need_cuda(X, "X")
     if X.shape[0] == 0:
         return Q
-    X = X.to(torch.float32).contiguous()
+    X = X.to(torch.float32)
+    if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        X = X.contiguous()
     n, D = X.shape
     st = _steps(steps, D)
     pos = pos.to(torch.int64).contiguous()
     if Q.dtype != torch.int32 or Q.stride(1) != 1:
         raise ValueError("Q must be an int32 matrix with contiguous rows")
     with torch.cuda.device(X.device):
-        check(_lib.lib().raht_quant_rows(C.c_void_p(X.data_ptr()), D, n, D, st, len(st), C.c_void_p(pos.data_ptr()),
+        check(_lib.lib().raht_quant_rows(C.c_void_p(X.data_ptr()), X.stride(0), n, D, st, len(st), C.c_void_p(pos.data_ptr()),
                                          C.c_void_p(Q.data_ptr()), Q.stride(0), _stream()))
     return Q
 
 
 def dequant_rows(Q, steps, pos, out=None):
-    """-> float32 (n, D): Q[pos[i], :] * step (written into ``out`` when given: a contiguous float32 (n, D) view)."""
+    """-> float32 (n, D): Q[pos[i], :] * step (written into ``out`` when given: a float32 (n, D) view with contiguous rows)."""
     _need_cuda(Q, "Q")
     if Q.dtype != torch.int32 or Q.stride(1) != 1:
         raise ValueError("Q must be an int32 matrix with contiguous rows")
@@ -576,11 +610,49 @@ def dequant_rows(Q, steps, pos, out=None):
     st = _steps(steps, D)
     pos = pos.to(torch.int64).contiguous()
     X = torch.empty((pos.shape[0], D), dtype=torch.float32, device=Q.device) if out is None else out
-    if X.dtype != torch.float32 or tuple(X.shape) != (pos.shape[0], D) or not X.is_contiguous():
-        raise ValueError("out must be a contiguous float32 (n, D) tensor")
+    if X.dtype != torch.float32 or tuple(X.shape) != (pos.shape[0], D) or (X.shape[0] > 0 and (X.stride(1) != 1 or X.stride(0) < D)):
+        raise ValueError("out must be a float32 (n, D) tensor with contiguous rows")
     with torch.cuda.device(Q.device):
         check(_lib.lib().raht_dequant_rows(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(pos.data_ptr()), pos.shape[0], D,
-                                           st, len(st), C.c_void_p(X.data_ptr()), D, _stream()))
+                                           st, len(st), C.c_void_p(X.data_ptr()), max(X.stride(0), D), _stream()))
+    return X
+
+
+def quant_rows_f64(X, steps, pos, Q):
+    """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place, in float64 (X float64 (n, D), float64 steps, IEEE double
+    division: the reference's arithmetic, python/encode_3dgs.py:204)."""
+    _need_cuda(X, "X")
+    if X.shape[0] == 0:
+        return Q
+    if X.dtype != torch.float64:
+        raise ValueError("quant_rows_f64: X must be float64")
+    if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        X = X.contiguous()
+    n, D = X.shape
+    st = _steps64(steps, D)
+    pos = pos.to(torch.int64).contiguous()
+    if Q.dtype != torch.int32 or Q.stride(1) != 1:
+        raise ValueError("Q must be an int32 matrix with contiguous rows")
+    with torch.cuda.device(X.device):
+        check(_lib.lib().raht_quant_rows_f64(C.c_void_p(X.data_ptr()), X.stride(0), n, D, st, len(st), C.c_void_p(pos.data_ptr()),
+                                             C.c_void_p(Q.data_ptr()), Q.stride(0), _stream()))
+    return Q
+
+
+def dequant_rows_f64(Q, steps, pos, out=None):
+    """-> float64 (n, D): Q[pos[i], :] * step in float64 (written into ``out`` when given: a float64 (n, D) view with contiguous rows)."""
+    _need_cuda(Q, "Q")
+    if Q.dtype != torch.int32 or Q.stride(1) != 1:
+        raise ValueError("Q must be an int32 matrix with contiguous rows")
+    D = Q.shape[1]
+    st = _steps64(steps, D)
+    pos = pos.to(torch.int64).contiguous()
+    X = torch.empty((pos.shape[0], D), dtype=torch.float64, device=Q.device) if out is None else out
+    if X.dtype != torch.float64 or tuple(X.shape) != (pos.shape[0], D) or (X.shape[0] > 0 and (X.stride(1) != 1 or X.stride(0) < D)):
+        raise ValueError("out must be a float64 (n, D) tensor with contiguous rows")
+    with torch.cuda.device(Q.device):
+        check(_lib.lib().raht_dequant_rows_f64(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(pos.data_ptr()), pos.shape[0], D,
+                                               st, len(st), C.c_void_p(X.data_ptr()), max(X.stride(0), D), _stream()))
     return X
 
 

@@ -96,6 +96,26 @@ class HipLocalOps:
         from .ops import dequant_rows
         return dequant_rows(Q, step, pos, out=out)
 
+    # mixed precision (n_wide > 0): the same at float64 for the wide columns of the top coefficients ...
+    @staticmethod
+    def quant_rows_f64(X, step, pos, Q):
+        from .ops import quant_rows_f64
+        return quant_rows_f64(X, step, pos, Q)
+
+    @staticmethod
+    def dequant_rows_f64(Q, step, pos, out):
+        from .ops import dequant_rows_f64
+        return dequant_rows_f64(Q, step, pos, out=out)
+
+    # ... and the shard-local fused passes with the wide columns in float64, roots through the two root buffers
+    @staticmethod
+    def forward_quant_mixed(plan, C, step, n_wide, roots=None, roots_wide=None):
+        return plan.forward_quant_mixed(C, step, n_wide, roots=roots, roots_wide=roots_wide)
+
+    @staticmethod
+    def dequant_inverse_mixed(plan, Q, step, n_wide, roots=None, roots_wide=None):
+        return plan.dequant_inverse_mixed(Q, step, n_wide, roots=roots, roots_wide=roots_wide)
+
     @staticmethod
     def rows_gather(src, pos, out):
         from .ops import rows_gather
@@ -131,8 +151,12 @@ class _DeviceArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
+MIXED_OPS = ("forward_quant_mixed", "dequant_inverse_mixed", "quant_rows_f64", "dequant_rows_f64")
+
+
 class ShardedRaht:
-    def __init__(self, keys_sorted, nbits, prefix_bits=9, group=None, local_ops=None, force_collectives=False, direct=False):
+    def __init__(self, keys_sorted, nbits, prefix_bits=9, group=None, local_ops=None, force_collectives=False, direct=False,
+                 n_wide=0):
         """keys_sorted: this rank's sorted, unique Morton keys (int64 tensor). Ranks must own disjoint,
         increasing ranges of the top ``prefix_bits`` bits (rank 0 the lowest prefixes).
         force_collectives: issue the all-gathers even in a one-rank group (exercises the RCCL path on one GPU).
@@ -143,8 +167,20 @@ class ShardedRaht:
         The process group is still used once per (D, dtype) to exchange the hipIpc handles. A peer that never arrives ends a
         bounded wait, not a hung GPU -- and leaves a status word: check_exchange() (called by close(), roundtrip_error(),
         check_against_unsharded()) raises on it, and every later direct gather of the object refuses to run. Call close()
-        (collective) before dropping the object."""
+        (collective) before dropping the object.
+        n_wide: > 0 (1..4) runs the quantized entries (forward_quant, dequant_inverse, step / local_step with a quantization
+        step) in MIXED precision: columns [0, n_wide) -- the xyz columns of a 59-column frame -- in float64 throughout (the
+        reference's integers, python/encode_3dgs.py:82-83,204), the others in float32 exactly as with n_wide = 0. The wide
+        roots travel in a buffer set of their own ((., n_wide) float64: a second, small gather per direction) and the
+        replicated top tree runs once more, in float64, on them. forward / inverse (unquantized) are unchanged."""
         self.ops = local_ops or HipLocalOps
+        self.n_wide = int(n_wide)
+        if self.n_wide:
+            if not 1 <= self.n_wide <= 4:
+                raise ValueError("n_wide must be 0 (float32) or 1..4")
+            missing = [f for f in MIXED_OPS if not hasattr(self.ops, f)]
+            if missing:
+                raise ValueError(f"ShardedRaht(n_wide={self.n_wide}): local_ops lacks {', '.join(missing)}")
         self.force = bool(force_collectives)
         self.direct = bool(direct)
         self._direct_failed = False
@@ -354,9 +390,15 @@ class ShardedRaht:
         if failed:
             raise RuntimeError("ShardedRaht(direct=True): a direct gather timed out waiting for a peer; results since then are not valid")
 
-    def _gather_roots(self, b, which):
-        gather = (lambda: self._direct_gather(b)) if "xchg" in b else (lambda: self._all_gather(b["send"], out=b["recv"]))
-        if self._ev is None or not b["send"].is_cuda:
+    def _gather_roots(self, *bs, which):
+        """the all-gathers of one direction (one buffer set; mixed precision: the float and the wide one), timed as one"""
+        def gather():
+            for b in bs:
+                if "xchg" in b:
+                    self._direct_gather(b)
+                else:
+                    self._all_gather(b["send"], out=b["recv"])
+        if self._ev is None or not bs[0]["send"].is_cuda:
             return gather()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -365,17 +407,21 @@ class ShardedRaht:
         self._ev[which].append((e0, e1))
 
     def gathered_bytes_per_step(self, D, elem=4):
-        """bytes every rank receives per direction x 2 directions"""
-        return 2 * self.gather_rows * D * elem if self.world > 1 else 0
+        """bytes every rank receives per direction x 2 directions (n_wide > 0: + the wide roots' float64 gathers)"""
+        if self.world == 1:
+            return 0
+        return 2 * self.gather_rows * (D * elem + self.n_wide * 8)
 
     # ---- transforms ------------------------------------------------------------------------------
-    def _top_forward(self, b):
-        self._gather_roots(b, "fwd")
-        self.top.forward(b["recv"], want_w=False, out=b["res"])
+    def _top_forward(self, *bs):
+        self._gather_roots(*bs, which="fwd")
+        for b in bs:
+            self.top.forward(b["recv"], want_w=False, out=b["res"])
 
-    def _top_inverse(self, b):
-        self._gather_roots(b, "inv")
-        self.top.inverse(b["recv"], out=b["res"])
+    def _top_inverse(self, *bs):
+        self._gather_roots(*bs, which="inv")
+        for b in bs:
+            self.top.inverse(b["recv"], out=b["res"])
 
     # A rank without rows (self.plan is None) has nothing to transform but still enters both collectives: every
     # method below reaches _top_forward / _top_inverse whatever N is.
@@ -397,6 +443,8 @@ class ShardedRaht:
 
     def forward_quant(self, C, step):
         """-> Q_local (int32, rank-local order_RAGFT order); the top coefficients are quantized too."""
+        if self.n_wide:
+            return self._forward_quant_mixed(C, step)
         b = self._buffers(C.shape[1], self.qdt)
         Q = (self.plan.forward_quant(C, step, roots=b["send_roots"]) if self.plan is not None
              else torch.empty(C.shape, dtype=torch.int32, device=C.device))
@@ -406,6 +454,8 @@ class ShardedRaht:
         return Q
 
     def dequant_inverse(self, Q, step):
+        if self.n_wide:
+            return self._dequant_inverse_mixed(Q, step)
         b = self._buffers(Q.shape[1], self.qdt)
         if self.n_roots:
             self.ops.dequant_rows(Q, step, self._root_positions(), b["send_roots"])
@@ -413,6 +463,49 @@ class ShardedRaht:
         if self.plan is None:
             return torch.empty(Q.shape, dtype=self.qdt, device=Q.device)
         return self.plan.dequant_inverse(Q, step, roots=b["mine"])
+
+    # ---- mixed precision (n_wide > 0) ------------------------------------------------------------------
+    def _mixed_steps(self, step, D):
+        """-> (steps of columns [n_wide, D), steps of columns [0, n_wide)): a scalar stays one; D per-channel values split"""
+        if isinstance(step, (int, float)):
+            return float(step), float(step)
+        st = [float(x) for x in (step.tolist() if hasattr(step, "tolist") else step)]
+        if len(st) == 1:
+            return st[0], st[0]
+        if len(st) != D:
+            raise ValueError("steps must be a scalar or have D entries")
+        return st[self.n_wide:], st[: self.n_wide]
+
+    def _mixed_buffers(self, D):
+        if D - self.n_wide < 1:
+            raise ValueError(f"ShardedRaht(n_wide={self.n_wide}): needs more than n_wide columns")
+        return self._buffers(D, self.qdt), self._buffers(self.n_wide, torch.float64)
+
+    def _forward_quant_mixed(self, C, step):
+        nw, D = self.n_wide, C.shape[1]
+        b, bw = self._mixed_buffers(D)
+        Q = (self.ops.forward_quant_mixed(self.plan, C, step, nw, roots=b["send_roots"], roots_wide=bw["send_roots"])
+             if self.plan is not None else torch.empty(C.shape, dtype=torch.int32, device=C.device))
+        self._top_forward(b, bw)                    # float32 top tree on (., D), float64 on (., n_wide)
+        if self.n_roots:
+            sf, sw = self._mixed_steps(step, D)
+            pos = self._root_positions()
+            self.ops.quant_rows(b["mine"][:, nw:], sf, pos, Q[:, nw:])
+            self.ops.quant_rows_f64(bw["mine"], sw, pos, Q[:, :nw])
+        return Q
+
+    def _dequant_inverse_mixed(self, Q, step):
+        nw, D = self.n_wide, Q.shape[1]
+        b, bw = self._mixed_buffers(D)
+        if self.n_roots:
+            sf, sw = self._mixed_steps(step, D)
+            pos = self._root_positions()
+            self.ops.dequant_rows(Q[:, nw:], sf, pos, b["send_roots"][:, nw:])
+            self.ops.dequant_rows_f64(Q[:, :nw], sw, pos, bw["send_roots"])
+        self._top_inverse(b, bw)
+        if self.plan is None:
+            return torch.empty(Q.shape, dtype=self.qdt, device=Q.device)
+        return self.ops.dequant_inverse_mixed(self.plan, Q, step, nw, roots=b["mine"], roots_wide=bw["mine"])
 
     # ---- bench helpers -----------------------------------------------------------------------------
     def step(self, C, quant_step=None):
@@ -426,6 +519,10 @@ class ShardedRaht:
         no top tree. Its output is not a transform of anything; it exists to be timed."""
         if self.plan is None:
             return None
+        if quant_step is not None and self.n_wide:
+            b, bw = self._mixed_buffers(C.shape[1])
+            Q = self.ops.forward_quant_mixed(self.plan, C, quant_step, self.n_wide, roots=b["send_roots"], roots_wide=bw["send_roots"])
+            return self.ops.dequant_inverse_mixed(self.plan, Q, quant_step, self.n_wide, roots=b["mine"], roots_wide=bw["mine"])
         dt = C.dtype if quant_step is None else self.qdt
         b = self._buffers(C.shape[1], dt)
         if quant_step is None:
@@ -486,6 +583,42 @@ class ShardedRaht:
                 out["max_dequantized_distance_over_step"] = worst / quant_step
                 out["ok"] = out["ok"] and worst <= 0.5 * quant_step * 1.0001
                 out["quantized_roundtrip_max_err_over_step"] = float((R - C).abs().max().item()) / quant_step
+        if self.direct:
+            st = self.exchange_status()
+            out["direct_exchange_status"] = st
+            out["ok"] = out["ok"] and st == 0
+        if self.world > 1:
+            flag = torch.tensor([[1 if out["ok"] else 0]], dtype=torch.int64, device=C.device)
+            out["ok"] = bool(self._all_gather(flag).min().item() == 1)
+        return out
+
+    def check_mixed_against_unsharded(self, C, steps, keys_sorted=None):
+        """Correctness gate of the mixed-precision step (n_wide > 0; not on the timed path): gather the whole scene, run the
+        UNSHARDED ``forward_quant_mixed`` on it on this rank, and compare this rank's integers with the sharded
+        ``forward_quant``'s, in row order, EXACTLY, on every column (the replicated top trees perform the same butterflies on
+        the same operands in the same precision as the unsharded kernels; the top rows are quantized with the same arithmetic)."""
+        if not self.n_wide:
+            raise ValueError("check_mixed_against_unsharded needs ShardedRaht(n_wide > 0)")
+        keys = self.plan_keys() if keys_sorted is None else keys_sorted
+        allk = self._gather_var(keys.reshape(-1, 1).to(torch.int64)).reshape(-1).contiguous()
+        allC = self._gather_var(C)
+        n_before = int(self._all_gather(torch.tensor([[self.N]], dtype=torch.int64, device=C.device)).reshape(-1)[: self.rank].sum().item()) if self.world > 1 else 0
+        full = self.ops.make_plan(allk, self.nbits)
+        Qf = self.ops.forward_quant_mixed(full, allC, steps, self.n_wide)
+        Q = self.forward_quant(C, steps)
+        D = int(C.shape[1])
+        out = {"kind": "sharded mixed == unsharded mixed (whole scene gathered, integers compared in row order)",
+               "rows_total": int(allk.shape[0]), "n_wide": self.n_wide}
+        if self.N:
+            mine = Qf[full.inv_order.to(Qf.device)][n_before: n_before + self.N]      # the whole scene's integers of this rank's rows
+            Qr = Q[self.plan.inv_order.to(Q.device)]
+            diff = (Qr != mine)
+            per_col = diff.sum(dim=0).tolist()
+        else:
+            per_col = [0] * D
+        out["mismatches_per_column"] = [int(x) for x in per_col]
+        out["mismatches"] = int(sum(per_col))
+        out["ok"] = out["mismatches"] == 0
         if self.direct:
             st = self.exchange_status()
             out["direct_exchange_status"] = st
