@@ -20,15 +20,22 @@ Workloads (`--workload`):
                   STRONG scaling -- the same scene (same seed on every rank) cut into N Morton-prefix shards
                   by `balanced_prefix_cuts`, one shard per rank, top-3-level all-gather per direction.
 
-Correctness gate: no value is printed for a wrong transform. N = 1: the float32 forward coefficients and
-the fused quantized integers are compared with the CPU oracle on the WHOLE scene (the float64 restatement
-of the reference's RAHT.py; the same run is the cpu_baseline measurement). N > 1: every rank compares its
-shard of the sharded transform with the same rows of an unsharded transform of the gathered scene.
+A plain run does what the headline figure needs and nothing else: it builds the scene and its plan, checks one
+forward + inverse round trip on the GPU, runs the settle and warm-up steps, times the steps, writes --dump-outputs
+and prints ONE JSON line (rank 0) with the driver's contract fields (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, ...).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (dominant kernel, HIP-event
-timed, algorithmic bytes), `cpu_baseline` (the C oracle on the host cores), `oracle_gate`, the reference-
-precision leg `f64`, the `cfg2` leg, and `prelude` (plan build / radix sort / voxelizer with their own
-algorithmic-bytes fractions).
+`--full` adds everything else, as it always ran:
+  correctness gate  no value is printed for a wrong transform. N = 1: the float32 forward coefficients and the
+                    fused quantized integers are compared with the CPU oracle on the WHOLE scene (the float64
+                    restatement of the reference's RAHT.py; the same run is the cpu_baseline measurement); cfg5:
+                    size-independent properties. N > 1: every rank compares its shard of the sharded transform
+                    with the same rows of an unsharded transform of the gathered scene.
+  figures           `roofline` (dominant kernel, HIP-event timed, algorithmic bytes), `breakdown_ms`,
+                    `cpu_baseline` (the C oracle on the host cores), the reference-precision leg `f64`, the `cfg2`
+                    and reference-shape legs, `prelude` (plan build / radix sort / voxelizer with their own
+                    algorithmic-bytes fractions), the two-stream loop, the frame batch, the whole frame codec, and
+                    `multi_gpu` for sharded runs.
 
 `--dump-outputs DIR` writes what the last timed step computed (quantized integers and reconstruction; a fixed, seeded
 sample of rows when larger than 64 MB) as DIR/<name>.npy, so that two builds can be compared output for output.
@@ -71,6 +78,9 @@ def parse():
     ap.add_argument("--tail-ch", type=int, default=0, help="channels per chunk of the stages >= 1 (0 = automatic)")
     ap.add_argument("--top-rows", type=int, default=0, help="entries at which the single-launch top stage takes over (0 = automatic)")
     ap.add_argument("--quant-step", type=float, default=0.01)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the correctness gate against the CPU oracle (or its stand-ins), cpu_baseline, the per-kernel breakdown and "
+                         "roofline, the prelude, the extra legs and the multi-GPU report; the --skip-* options below trim such a run")
     ap.add_argument("--skip-cpu-baseline", action="store_true", help="skip the single-core timing and the repeats of the oracle (the gate still runs it once)")
     ap.add_argument("--skip-oracle-gate", action="store_true", help="profiling runs only: the JSON line then says oracle_gate: skipped")
     ap.add_argument("--skip-prelude", action="store_true", help="do not time plan build / sort / voxelizer")
@@ -91,7 +101,7 @@ def parse():
     ap.add_argument("--f32-only", action="store_true",
                     help="frames with xyz columns (14 / 59 channels): time the all-float32 fused kernels instead of the mixed-precision ones "
                          "(raht_fwd_quant_mixed: xyz columns in float64, the reference's integers there)")
-    ap.add_argument("--ablate", type=int, default=0, help="kernel-timing experiment for the roofline probe only (0 = real kernel; needs a make ABLATE=1 library)")
+    ap.add_argument("--ablate", type=int, default=0, help="kernel-timing experiment for the roofline probe of --full only (0 = real kernel; needs a make ABLATE=1 library)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; "
                          "larger outputs as the same seeded sample of rows in every run, at most 64 MB in all)")
@@ -578,10 +588,11 @@ def cfg4_batch_main(a, R, synth, dev, real_stdout):
 
     def looped():
         return [p.dequant_inverse(p.forward_quant(c, qs), qs) for p, c in zip(plans, Cs)]
-    # gate: the batch is bit-identical to one call per scene (whose kernels the oracle checks scene by scene in the default
-    # run and in tests/test_gpu_fullsize.py), and every scene survives the float32 round trip
+    # gate: every scene survives the float32 round trip; --full: the batch is also bit-identical to one call per scene (whose
+    # kernels the oracle checks scene by scene in the --full cfg3 run and in tests/test_gpu_fullsize.py)
     Qb = ops.forward_quant_batch(plans, Cs, qs)
-    assert all(torch.equal(q, p.forward_quant(c, qs)) for q, p, c in zip(Qb, plans, Cs)), "batch != single-scene calls"
+    if a.full:
+        assert all(torch.equal(q, p.forward_quant(c, qs)) for q, p, c in zip(Qb, plans, Cs)), "batch != single-scene calls"
     Rb = ops.inverse_batch(plans, ops.forward_batch(plans, Cs))
     rt = max(float(((r - c).abs().max() / c.abs().max()).item()) for r, c in zip(Rb, Cs))
     assert rt <= 1e-5, f"round trip error {rt}"
@@ -603,7 +614,6 @@ def cfg4_batch_main(a, R, synth, dev, real_stdout):
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, {f"C_rec_scene{i}": r for i, r in enumerate(last[0])})
         last[0] = None
-    t_loop = timed(looped, min(a.steps, 20))
     alg = 2 * (8.0 * rows * D + 8.0 * rows)
     out = {"metric": "M-Gaussians/s fwd+inv RAHT, 59-ch SH3 3DGS", "value": round(rows / (dt / a.steps) / 1e6, 2), "unit": "M-Gaussians/s", "n_gpus": 1,
            "steps": a.steps, "warmup": a.warmup, "settle_steps": settle, "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True,
@@ -611,9 +621,13 @@ def cfg4_batch_main(a, R, synth, dev, real_stdout):
            "config": {"workload": f"cfg4 on ONE GPU: {K} scenes of {[p.N for p in plans]} Gaussians (J={J}, {D} channels) as a batch, "
                                   "fwd RAHT + quantize/reorder + dequantize/un-reorder + inv RAHT per scene, stage k of all scenes in one launch",
                       "rows_total": rows, "channels": D, "depth_J": J, "parallelism": "1 GPU, batched launches", "roundtrip_rel_err": rt},
-           "oracle_gate": {"kind": "batch == one call per scene (bit for bit) + round trip; the single-scene kernels are oracle-checked on whole scenes in the default run"},
-           "path_hbm": {"alg_bytes_fwd_inv": alg, "whole_step_frac_of_peak": round(alg / (dt / a.steps) / 1e9 / HBM_PEAK_GBS, 4)},
-           "one_call_per_scene_ms": round(t_loop, 4), "one_call_per_scene_value": round(rows / (t_loop * 1e-3) / 1e6, 2)}
+           "oracle_gate": {"kind": "batch == one call per scene (bit for bit) + round trip; the single-scene kernels are oracle-checked on whole scenes in the --full run"
+                           if a.full else "round trip (plain run: --full also compares the batch with one call per scene)"},
+           "path_hbm": {"alg_bytes_fwd_inv": alg, "whole_step_frac_of_peak": round(alg / (dt / a.steps) / 1e9 / HBM_PEAK_GBS, 4)}}
+    if a.full:
+        t_loop = timed(looped, min(a.steps, 20))
+        out["one_call_per_scene_ms"] = round(t_loop, 4)
+        out["one_call_per_scene_value"] = round(rows / (t_loop * 1e-3) / 1e6, 2)
     sys.stdout.flush()
     os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
@@ -698,7 +712,9 @@ def main():
         rt_err = (sc.Crec - sc.Cd).abs().max().item() / sc.Cd.abs().max().item()
         assert rt_err <= 1e-5, f"round trip error {rt_err}"
         ob = None
-        if V is not None and rank == 0 and not a.skip_oracle_gate:
+        if not a.full:
+            gate = {"kind": "round trip only (plain run: --full compares with the CPU oracle)", "roundtrip_rel_err": rt_err}
+        elif V is not None and rank == 0 and not a.skip_oracle_gate:
             ob = oracle_pass(V, Ch, J, 1 if a.skip_cpu_baseline else a.cpu_repeats, single_core=not a.skip_cpu_baseline)
             T32 = sc.T.cpu().numpy()
             Q32 = None
@@ -727,7 +743,7 @@ def main():
             e_out = sum(float((sc.T[:, c].double() ** 2).sum()) for c in range(D))
             assert abs(e_in - e_out) <= 1e-5 * e_in, "Parseval"
             gate = {"kind": "properties (no oracle at 50 M rows): round trip, Parseval, fused == two-call", "roundtrip_rel_err": rt_err,
-                    "note": "the same kernels are oracle-checked on whole 1 M / 3 M / 6 M scenes (tests/test_gpu_fullsize.py) and in the cfg3 run of this bench"}
+                    "note": "the same kernels are oracle-checked on whole 1 M / 3 M / 6 M scenes (tests/test_gpu_fullsize.py) and in the --full cfg3 run of this bench"}
             del Q2
     else:
         from raht_3dgs_codec_amd import sharded
@@ -745,7 +761,9 @@ def main():
         rt_err = sh.roundtrip_error(Cd)
         assert rt_err <= 1e-5, f"round trip error {rt_err}"
         # sharded == unsharded: gather the scene, transform it whole on this GPU, compare this rank's rows
-        if not a.skip_oracle_gate:
+        if not a.full:
+            gate = {"kind": "round trip only (plain run: --full compares with an unsharded transform)", "roundtrip_rel_err": rt_err}
+        elif not a.skip_oracle_gate:
             gate = sh.check_against_unsharded(Cd, qs)
             assert gate["ok"], f"sharded transform differs from the unsharded one: {gate}"
         else:
@@ -812,9 +830,10 @@ def main():
     if not solo:
         out["config"]["gathered_bytes_per_step"] = sh.gathered_bytes_per_step(D)
         out["config"]["roots_per_rank"] = sh.sizes
-        out["multi_gpu"] = sharded_report(a, sh, Cd, qs, dist, world, rank, dev, L, _lib)
+        if a.full:
+            out["multi_gpu"] = sharded_report(a, sh, Cd, qs, dist, world, rank, dev, L, _lib)
 
-    if rank == 0 and world == 1 and solo:
+    if rank == 0 and world == 1 and solo and a.full:
         plan, h = sc.plan, sc.plan._h
         vp = C.c_void_p
         # ---- per-stage breakdown (HIP events on the launch stream) ----

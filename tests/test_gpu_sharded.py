@@ -259,7 +259,7 @@ def test_bench_gpus_2_spawns_its_own_ranks(rt):
     relays rank 0's line and the children's status. gloo, both ranks on this box's one GPU: a strong-scaling cut of a small
     cfg5 scene; the line says how many ranks the collective backend saw and separates the exchange from the local work."""
     out = _run_bench(["--gpus", "2", "--backend", "gloo", "--workload", "cfg5", "--rows", "400000", "--steps", "3", "--warmup", "1",
-                      "--settle-steps", "0"])
+                      "--settle-steps", "0", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0
     assert out["oracle_gate"]["ok"] and out["oracle_gate"]["rows_total"] > out["config"]["rows_per_gpu"]
     mg = out["multi_gpu"]
@@ -272,7 +272,7 @@ def test_bench_gpus_2_spawns_its_own_ranks(rt):
 def test_bench_one_rank_rccl_group(rt):
     """The same path through RCCL, as far as one GPU goes: --sharded runs ShardedRaht in a one-rank NCCL group."""
     out = _run_bench(["--gpus", "1", "--backend", "nccl", "--sharded", "--workload", "cfg5", "--rows", "400000", "--steps", "3", "--warmup", "1",
-                      "--settle-steps", "0"])
+                      "--settle-steps", "0", "--full"])
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["oracle_gate"]["ok"]
     mg = out["multi_gpu"]
     assert mg["rccl_world"] == 1 and mg["collective_backend"] == "nccl"
@@ -410,6 +410,6 @@ def test_direct_exchange_equals_the_collective(rt, world):
 
 def test_bench_direct_exchange(rt):
     out = _run_bench(["--gpus", "2", "--backend", "gloo", "--direct", "--workload", "cfg5", "--rows", "400000", "--steps", "3", "--warmup", "1",
-                      "--settle-steps", "0"])
+                      "--settle-steps", "0", "--full"])
     assert out["oracle_gate"]["ok"] and out["multi_gpu"]["exchange"].startswith("direct") and out["multi_gpu"]["exchange_status"] == 0
     assert out["multi_gpu"]["collective_ms"]["forward_all_gather"] > 0

@@ -1,7 +1,7 @@
 # A/B by environment knob inside ONE box, interleaved: tools/ab_env.sh VAR val1 val2 ... [-- extra bench args]
 VAR=$1; shift
 VALS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do VALS+=("$1"); shift; done; [ "$1" = "--" ] && shift
-for i in 1 2 3; do for v in "${VALS[@]}"; do env $VAR=$v timeout -k 10 200 python bench.py --steps 100 --warmup 30 --skip-legs --skip-prelude --skip-oracle-gate "$@" 2>/dev/null | python -c "
+for i in 1 2 3; do for v in "${VALS[@]}"; do env $VAR=$v timeout -k 10 200 python bench.py --full --steps 100 --warmup 30 --skip-legs --skip-prelude --skip-oracle-gate "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['breakdown_ms']

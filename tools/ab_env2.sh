@@ -4,8 +4,8 @@
 knob="$1"; rounds="${2:-3}"; shift 2
 out=gpurun_out/ab_env2; mkdir -p $out
 for r in $(seq 1 $rounds); do
-  python bench.py --skip-oracle-gate --skip-cpu-baseline --skip-prelude "$@" > $out/a_$r.json 2> $out/a_$r.err || { tail -5 $out/a_$r.err; exit 1; }
-  env "$knob" python bench.py --skip-oracle-gate --skip-cpu-baseline --skip-prelude "$@" > $out/b_$r.json 2> $out/b_$r.err || { tail -5 $out/b_$r.err; exit 1; }
+  python bench.py --full --skip-oracle-gate --skip-cpu-baseline --skip-prelude "$@" > $out/a_$r.json 2> $out/a_$r.err || { tail -5 $out/a_$r.err; exit 1; }
+  env "$knob" python bench.py --full --skip-oracle-gate --skip-cpu-baseline --skip-prelude "$@" > $out/b_$r.json 2> $out/b_$r.err || { tail -5 $out/b_$r.err; exit 1; }
 done
 python - "$knob" $rounds <<'PY'
 import json,sys

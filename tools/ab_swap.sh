@@ -3,7 +3,7 @@
 P=raht-3dgs-codec_amd
 VARS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do VARS+=("$1"); shift; done; [ "$1" = "--" ] && shift
 cp $P/libraht_hip.so /tmp/lib_keep.so
-for i in 1 2 3; do for v in "${VARS[@]}"; do cp $P/lib_variant_$v.bin $P/libraht_hip.so; timeout -k 10 200 python bench.py --skip-oracle-gate --skip-legs --skip-prelude "$@" 2>/dev/null | python -c "
+for i in 1 2 3; do for v in "${VARS[@]}"; do cp $P/lib_variant_$v.bin $P/libraht_hip.so; timeout -k 10 200 python bench.py --full --skip-oracle-gate --skip-legs --skip-prelude "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['breakdown_ms']

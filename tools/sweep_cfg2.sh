@@ -1,6 +1,6 @@
 # cfg2 (1 M x 14): tile geometry sweep of the fused step
 for th in 512 256; do for tr in 0 448 384 320 256 192; do
-RAHT_TILE_THREADS=$th timeout -k 10 200 python bench.py --workload cfg2 --steps 200 --warmup 50 --skip-legs --skip-prelude --skip-oracle-gate --tile-rows $tr 2>/dev/null | python -c "
+RAHT_TILE_THREADS=$th timeout -k 10 200 python bench.py --full --workload cfg2 --steps 200 --warmup 50 --skip-legs --skip-prelude --skip-oracle-gate --tile-rows $tr 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['breakdown_ms']

@@ -1,7 +1,7 @@
 # later-stage tile geometry sweep on one box: tools/sweep_tail.sh [rows...]   (0 = automatic)
 ROWS=("$@"); [ ${#ROWS[@]} -eq 0 ] && ROWS=(0 64 96 128 256 384 512)
 for i in 1 2; do for tr in "${ROWS[@]}"; do
-timeout -k 10 200 python bench.py --steps 100 --warmup 30 --skip-legs --skip-prelude --skip-oracle-gate --tail-rows $tr 2>/dev/null | python -c "
+timeout -k 10 200 python bench.py --full --steps 100 --warmup 30 --skip-legs --skip-prelude --skip-oracle-gate --tail-rows $tr 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['breakdown_ms']
