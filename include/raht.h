@@ -296,7 +296,10 @@ int raht_plan_prepare(raht_plan *plan, int elem_size, int D, raht_stream_t strea
  * over quantization steps (python/encode_3dgs.py:199-275): the forward of step s + 1 does not depend on the inverse of step s,
  * and one direction's latency-bound tail stages then run under the other's HBM-bound first stage. Costs a second copy of the
  * workspaces (~5 % of a coefficient matrix); they are re-allocated by the next transform or raht_plan_prepare. Two calls of the
- * SAME direction still have to be ordered by the caller. */
+ * SAME direction still have to be ordered by the caller. The arrays derived from a tile schedule (tile heights; the mixed-precision
+ * kernels' tile programs) are written by kernels that the call building them enqueues on its own stream and does not wait for; a
+ * later call on ANOTHER stream first makes its stream wait for an event recorded behind them, so the first inverse may run on a
+ * side stream right behind the forward that built the schedule. */
 int raht_plan_set_concurrent_directions(raht_plan *plan, int on);
 
 /* Profiling aid: HIP events (hipEvent_t, created by the caller with timing enabled) recorded on the

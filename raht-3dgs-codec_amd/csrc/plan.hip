@@ -573,8 +573,10 @@ static void free_schedule(Schedule &sc)
         if (st.t_root) dev_free(st.t_root);
         if (st.t_lev) dev_free(st.t_lev);
         if (st.ws) dev_free(st.ws);
+        if (st.prog) dev_free(st.prog);
     }
     sc.stages.clear();
+    if (sc.ready) { (void)hipEventDestroy(sc.ready); sc.ready = nullptr; }
 }
 
 int ensure_workspace(Schedule *sc, size_t row_bytes, bool split)
@@ -775,6 +777,146 @@ static int launch_stage_heights(raht_plan *plan, Schedule &sc, hipStream_t s)
         if (H.n_stages == group) RAHT_RET(flush());
     }
     return flush();
+}
+
+// ---- tile programs of the mixed-precision tile kernels (Stage::prog, raht_common.h) -------------------
+// One wave per tile, one launch per tile stage. Same predicate and partner search as tile_heights_kernel (and the tile kernels
+// that resolved their butterflies at run time before); the heights come from Stage::e_ht. Records of one height touch disjoint
+// slots, so their order inside a height (here: the LDS cursor's) does not change any result.
+struct ProgStage {
+    const uint32_t *rows; const int32_t *wl, *wr; const uint8_t *lvl, *ht; const uint32_t *pos;
+    uint32_t *prog; int64_t n; int R; uint32_t stride, ab; int compact;
+};
+
+template <int SPL>
+__global__ __launch_bounds__(64) void tile_program_kernel(const ProgStage S, int64_t N, int top_level, const int64_t *__restrict__ wsum)
+{
+    extern __shared__ __align__(16) unsigned char pg_smem[];
+    __shared__ uint32_t s_hist[64], s_cur[64];
+    uint32_t *s_row = (uint32_t *)pg_smem;                  // [R], later stages only
+    const int R = S.R;
+    const int lane = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * R;
+    if (e0 >= S.n) return;
+    const uint32_t *__restrict__ rows = S.rows;
+    const int nt = (int)min((int64_t)R, S.n - e0);
+    const int64_t start_row = rows ? (int64_t)rows[e0] : e0;
+    const int64_t end_row = (e0 + R < S.n) ? (rows ? (int64_t)rows[e0 + R] : e0 + R) : N;
+    uint32_t *pg = S.prog + (size_t)blockIdx.x * S.stride;
+    uint32_t *rw = pg + 32, *rec = pg + 32 + R;
+    double *ab = (double *)(pg + S.ab);
+    int lv[SPL], ht[SPL];
+    int32_t wlv[SPL], wrv[SPL];
+    uint32_t pos[SPL];
+    int64_t r[SPL];
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) {                          // all loads first: one round trip
+        const int j = lane + s * 64;
+        lv[s] = 255; wlv[s] = 0; wrv[s] = 0; r[s] = 0; ht[s] = 0; pos[s] = 0;
+        if (j < nt) {
+            r[s] = rows ? (int64_t)rows[e0 + j] : e0 + j;
+            lv[s] = (int)S.lvl[e0 + j]; wlv[s] = S.wl[e0 + j]; wrv[s] = S.wr[e0 + j];
+            ht[s] = S.ht[e0 + j] & 63; pos[s] = S.pos[e0 + j];
+        }
+    }
+    s_hist[lane] = 0;
+    if (rows) {
+#pragma unroll
+        for (int s = 0; s < SPL; ++s) { const int j = lane + s * 64; if (j < nt) s_row[j] = (uint32_t)r[s]; }
+    }
+    __syncthreads();
+    bool merged[SPL];
+    int part[SPL];
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) {
+        const int j = lane + s * 64;
+        merged[s] = (j < nt) && (r[s] > 0) && (lv[s] < top_level) && (r[s] - wlv[s] >= start_row) && (r[s] + wrv[s] <= end_row);
+        part[s] = 0;
+        if (merged[s]) {
+            if (!rows) part[s] = j - wlv[s];
+            else {                                          // the partner row r - wl is an entry of this tile
+                const uint32_t want = (uint32_t)(r[s] - wlv[s]);
+                int lo = 0, hi = j - 1;
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_row[mid] < want) lo = mid + 1; else hi = mid; }
+                part[s] = lo;
+            }
+            atomicAdd(&s_hist[ht[s]], 1u);
+        }
+        if (j < nt) rw[j] = pos[s] | (merged[s] ? 0x80000000u : 0u);
+    }
+    __syncthreads();
+    const uint32_t c = s_hist[lane];
+    uint32_t inc = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    ((uint16_t *)pg)[lane] = (uint16_t)inc;
+    s_cur[lane] = inc - c;
+    const uint32_t n_merged = (uint32_t)__shfl((int)inc, 63, 64);
+    __syncthreads();
+    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t n_surv = 0;
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) {
+        const int j = lane + s * 64;
+        const bool surv = j < nt && !merged[s];
+        const uint64_t bal = __ballot(surv);
+        if (surv) rec[n_merged + n_surv + (uint32_t)__popcll(bal & lt)] = (uint32_t)j;
+        n_surv += (uint32_t)__popcll(bal);
+        if (merged[s]) {
+            const uint32_t k = atomicAdd(&s_cur[ht[s]], 1u);
+            if (S.compact) {
+                rec[k] = (uint32_t)j | ((uint32_t)wlv[s] << 10) | ((uint32_t)wrv[s] << 20);
+            } else {
+                double w0, w1;
+                pair_weights(r[s], wlv[s], wrv[s], wsum, w0, w1);
+                const double den = w0 + w1;
+                rec[k] = (uint32_t)part[s] | ((uint32_t)j << 16);
+                ab[2 * k] = sqrt(w0 / den);                  // RAHT.py:321-322
+                ab[2 * k + 1] = sqrt(w1 / den);
+            }
+        }
+    }
+}
+
+int build_tile_programs(raht_plan *plan, Schedule *sc, hipStream_t s)
+{
+    bool built = false;
+    for (auto &st : sc->stages) {
+        if (st.is_top || st.n_entries < 1 || st.prog) continue;
+        const int R = st.tile_rows;
+        if (R > HT_MAX_ROWS || !st.e_ht) { set_error("tile programs: %d rows per tile not supported", R); return RAHT_ERR_UNSUPPORTED; }
+        ProgStage P;
+        P.rows = st.rows;
+        P.wl = st.rows ? st.e_wl : plan->wl; P.wr = st.rows ? st.e_wr : plan->wr; P.lvl = st.rows ? st.e_lvl : plan->lvl;
+        P.pos = st.rows ? st.e_pos : plan->inv_order; P.ht = st.e_ht;
+        P.n = st.n_entries; P.R = R;
+        // compact records: stage 0 rows are tile slots, so a butterfly merged inside a tile of <= 1024 rows has extents <= 1023
+        P.compact = (st.rows == nullptr && plan->wsum == nullptr) ? 1 : 0;
+        P.ab = (uint32_t)(32 + 2 * R + 3) & ~3u;
+        P.stride = P.compact ? P.ab : P.ab + 4 * (uint32_t)R;
+        if (!P.wl || !P.wr || !P.lvl || !P.pos) { set_error("tile programs: missing plan arrays"); return RAHT_ERR_INVALID; }
+        RAHT_HIP_CHECK(dev_malloc(&st.prog, sizeof(uint32_t) * (size_t)P.stride * (size_t)st.n_tiles));
+        P.prog = st.prog;
+        const size_t lds = st.rows ? (size_t)R * 4 : 0;
+        const unsigned grid = (unsigned)st.n_tiles;
+        const int spl = (R + 63) / 64;
+        if (spl <= 3) hipLaunchKernelGGL(tile_program_kernel<3>, dim3(grid), dim3(64), lds, s, P, plan->N, plan->top_level, plan->wsum);
+        else if (spl <= 4) hipLaunchKernelGGL(tile_program_kernel<4>, dim3(grid), dim3(64), lds, s, P, plan->N, plan->top_level, plan->wsum);
+        else if (spl <= 8) hipLaunchKernelGGL(tile_program_kernel<8>, dim3(grid), dim3(64), lds, s, P, plan->N, plan->top_level, plan->wsum);
+        else hipLaunchKernelGGL(tile_program_kernel<16>, dim3(grid), dim3(64), lds, s, P, plan->N, plan->top_level, plan->wsum);
+        RAHT_HIP_CHECK(hipGetLastError());
+        st.prog_stride = P.stride; st.prog_ab = P.ab; st.prog_compact = P.compact != 0;
+        built = true;
+    }
+    if (built) {
+        if (!sc->ready) RAHT_HIP_CHECK(hipEventCreateWithFlags(&sc->ready, hipEventDisableTiming));
+        RAHT_HIP_CHECK(hipEventRecord(sc->ready, s));
+        sc->ready_on = s;
+    }
+    return RAHT_OK;
 }
 
 // ---- TOP stage: every butterfly still to do, resolved against the stage's entry list ----------------
@@ -1472,10 +1614,29 @@ static int build_schedule_fast(raht_plan *plan, int R0, int R1, int Rf, hipStrea
     return RAHT_OK;
 }
 
+static int build_schedule(raht_plan *plan, int R0, int R1, int Rf, hipStream_t s, Schedule **out);
+
+// The kernels that fill a new schedule's arrays (heights, later the tile programs) are enqueued on the building stream and
+// not waited for. A cached schedule handed to a caller on ANOTHER stream (raht_plan_set_concurrent_directions) first makes that
+// stream wait for them.
 int get_schedule(raht_plan *plan, int R0, int R1, int Rf, hipStream_t s, Schedule **out)
 {
     for (auto &sc : plan->schedules)
-        if (sc.tile_rows == R0 && sc.tail_rows == R1 && sc.final_rows == Rf) { *out = &sc; return RAHT_OK; }
+        if (sc.tile_rows == R0 && sc.tail_rows == R1 && sc.final_rows == Rf) {
+            if (sc.ready && sc.ready_on != s) RAHT_HIP_CHECK(hipStreamWaitEvent(s, sc.ready, 0));
+            *out = &sc;
+            return RAHT_OK;
+        }
+    RAHT_RET(build_schedule(plan, R0, R1, Rf, s, out));
+    Schedule &sc = **out;
+    if (!sc.ready) RAHT_HIP_CHECK(hipEventCreateWithFlags(&sc.ready, hipEventDisableTiming));
+    RAHT_HIP_CHECK(hipEventRecord(sc.ready, s));
+    sc.ready_on = s;
+    return RAHT_OK;
+}
+
+static int build_schedule(raht_plan *plan, int R0, int R1, int Rf, hipStream_t s, Schedule **out)
+{
     static const bool exact_only = getenv("RAHT_SCHEDULE_EXACT") != nullptr;     // A/B and debugging knob
     if (!exact_only && R0 >= 64 && R1 >= 64 && Rf >= 1 && Rf <= RAHT_TOP_MAX_ROWS) {
         Schedule sc;

@@ -216,6 +216,18 @@ struct Stage {
     int t_nbig = 0;                // the first t_nbig of them run on the whole workgroup (a barrier each); the rest
                                    // hold <= 64 butterflies each and are chained by ONE wave without barriers
     uint32_t t_small_start = 0;    // first butterfly of the chained part (its records are staged in LDS)
+    // tile PROGRAMS of the mixed-precision tile kernels (transform_mx.hip; built lazily by build_tile_programs): every
+    // butterfly of every tile resolved once per schedule. Tile t's program starts at word t * prog_stride:
+    //   words [0, 32)        64 uint16: end[h] = number of butterflies of height <= h (the rounds' offsets and counts)
+    //   words [32, 32 + R)   per row j: Q position (inv_order) | merged-in-this-tile << 31
+    //   words [32 + R, +R)   records k < end[63], sorted by height; then the survivor slots j in ascending order
+    //                        compact (stage 0 of an unweighted plan): j | l << 10 | r << 20 (left / right extent; p = j - l)
+    //                        full (all other tile stages): p | j << 16
+    //   words [prog_ab, +4R) full programs only: a, b of record k in float64
+    uint32_t *prog = nullptr;
+    uint32_t prog_stride = 0;      // words per tile (a multiple of 4)
+    uint32_t prog_ab = 0;          // word offset of the a, b pairs inside a tile's program
+    bool prog_compact = false;
 };
 
 struct Schedule {
@@ -226,6 +238,10 @@ struct Schedule {
     std::vector<Stage> stages;
     size_t ws_row_bytes = 0;   // bytes per workspace row currently allocated (D * elem_size)
     bool ws_split = false;     // the workspaces currently allocated hold one copy per direction
+    // recorded on `ready_on` behind the last kernel that writes schedule-derived arrays (heights, tile programs); get_schedule
+    // makes a caller on another stream wait for it (raht.h: raht_plan_set_concurrent_directions)
+    hipEvent_t ready = nullptr;
+    hipStream_t ready_on = nullptr;
 };
 
 }  // namespace raht
@@ -292,6 +308,8 @@ int get_schedule(raht_plan *plan, int tile_rows, int tail_rows, int final_rows, 
 // stage, in channel chunks.
 void pick_tail_geometry(const raht_plan *plan, int elem_size, int D, int stage0_rows, int *tail_rows, int *tail_chunk,
                         int *final_rows);
+// Tile programs of every tile stage of `sc` (Stage::prog), built on `s` unless present; records sc->ready behind them.
+int build_tile_programs(raht_plan *plan, Schedule *sc, hipStream_t s);
 // Make sure the per-stage workspaces of `sc` hold rows of at least row_bytes bytes (allocates on
 // first use / growth only).
 int ensure_workspace(Schedule *sc, size_t row_bytes, bool split = false);

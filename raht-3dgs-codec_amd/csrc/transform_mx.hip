@@ -42,7 +42,6 @@ __device__ unsigned long long g_phase_clk_mx[MX_CLK_TILES][MX_CLK_SLOTS];
 #endif
 
 constexpr int MX_MAX_WIDE = 4;          // the wide channels are the row's first 16 bytes
-constexpr int MX_PRE_ROWS = 12;         // survivor rows prefetched by the inverse before flags are known
 constexpr int MX_THREADS = 512;
 constexpr int MX_TOP_THREADS = 1024;
 constexpr int MX_TOP_SLOTS = RAHT_TOP_MAX_ROWS / MX_TOP_THREADS;
@@ -53,12 +52,12 @@ struct StepTableMX {
 };
 
 // (must match the carve-up in tile_body_mx)
-static size_t tile_lds_bytes_mx(int R, int NF, int nwide, bool ident)
+static size_t tile_lds_bytes_mx(int R, int NF, int nwide)
 {
     const size_t data = (size_t)R * NF * 16 + (((size_t)R * nwide * 8 + 15) & ~(size_t)15);   // float tile + wide tile (8 bytes per wide channel)
-    const size_t meta = (size_t)R * (16 + 4 + (ident ? 0 : 4) + 4 + 1);        // a, b (float64) + operand slots; row id; Q position; flag
+    const size_t meta = (size_t)R * (16 + 4 + 4);                             // a, b (float64) + operand slots; Q position
     const size_t surv = ((size_t)R * 2 + 15) & ~(size_t)15;
-    return data + ((meta + 15) & ~(size_t)15) + 1024 + surv;                  // (the inverse's survivor prefetch shares the records' bytes)
+    return data + meta + surv;
 }
 
 // the wide parts of the workspaces a stage touches (a workspace row is stored as two dense arrays: the float places of every
@@ -69,6 +68,9 @@ struct MxPtrs {
     double *wsn_w;           // wide part of ws_{k+1}
     double *root_w;          // last stage of a plan with root buffers: the roots' wide channels (n_wide doubles per root); their
                              // float channels go through TileArgs::root_buf (D floats per root, the wide columns' floats unspecified)
+    const uint32_t *prog;    // the stage's tile programs (Stage::prog): prog_stride words per tile, a / b pairs at word prog_ab
+    uint32_t prog_stride, prog_ab;
+    int prog_compact;
 };
 
 // ROOTS: last stage of a plan with root buffers (TileArgs::root_buf, MxPtrs::root_w): the roots' low-pass rows go to / come from
@@ -97,28 +99,10 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
     size_t off = 0;
     float *ftile = (float *)smem; off += (size_t)R * Fp * 4;              // float32 channels, NF places per row
     double *wd = (double *)(smem + off); off += ((size_t)R * nwide * 8 + 15) & ~(size_t)15;   // wide channels: nwide doubles per row
-    unsigned char *rec_base = smem + off;
     W16 *rec_ab = (W16 *)(smem + off); off += (size_t)R * 16;             // butterfly records: a, b in float64 ...
     uint32_t *rec_pj = (uint32_t *)(smem + off); off += (size_t)R * 4;    // ... and the two operand slots (partner | own << 16)
-    // inverse: the survivor rows prefetched at kernel start wait in the records' bytes (records are written once they have moved
-    // into their slots: P3b, a barrier, P3a) -- as many as fit, at most MX_PRE_ROWS
-    const int pre_rows = min(MX_PRE_ROWS, (R * 20 - 8) / (Fp * 4 + nwide * 8));      // (- 8: the wide part arrives in 16-byte chunks)
-    float *spre_f = (float *)rec_base;
-    double *spre_w = (double *)(rec_base + (size_t)pre_rows * Fp * 4);
-    int32_t *srow = (int32_t *)(smem + off); if (!IDENT) off += (size_t)R * 4;
-    int32_t *sdst = (int32_t *)(smem + off); off += (size_t)R * 4;
-    uint8_t *sflag = (uint8_t *)(smem + off); off += (size_t)R;
-    off = (off + 15) & ~(size_t)15;
-    uint32_t *hist = (uint32_t *)(smem + off);
-    uint32_t *loff = hist + 64;
-    uint32_t *cursor = hist + 128;
-    uint32_t *scnt = hist + 196;
-    off += 1024;
-    uint16_t *ssurv = (uint16_t *)(smem + off);
-    off += ((size_t)R * 2 + 15) & ~(size_t)15;
-
-    TileMeta<SLOTS> M;
-    load_tile_meta<float, IDENT, true, SLOTS>(A, tile_id, tid0, nthreads, M);
+    int32_t *sdst = (int32_t *)(smem + off); off += (size_t)R * 4;        // Q position | finalised here << 31
+    uint16_t *ssurv = (uint16_t *)(smem + off);                           // survivor slots, in rank order
 
     // lane geometry of the row loops, as in the float32 kernels: lane c4 of a group of 2^lg works on float place fl = min(c4, NF - 1)
     // of one row (channels goff .. goff + 3; lanes past the last place shadow it: same reads, same writes). The lane of place 0
@@ -150,17 +134,64 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
     lane_geom(tid, lane, wid, g, c4, fl, sp, goff, head);
     const int64_t e0 = tile_id * R;
     const int nt = (int)min((int64_t)R, A.n_entries - e0);
-    const int64_t start_row = M.start_row, end_row = M.end_row;
-    const uint32_t surv_base = (uint32_t)__builtin_amdgcn_readlane((int)M.surv_raw, 0);
-    const uint32_t surv_cnt = (uint32_t)__builtin_amdgcn_readlane((int)M.surv_raw, 1) - surv_base;
-    int32_t m_row[SLOTS], m_wl[SLOTS], m_wr[SLOTS], m_pos[SLOTS];
-    int m_lv[SLOTS], m_ht[SLOTS];
+    MX_STAMP(0);
+
+    // ---- P0a. the tile's program (plan.hip: tile_program_kernel; raht_common.h: Stage::prog), fetched first: every butterfly,
+    // survivor and destination of this tile, resolved once per schedule. Each wave reads the height offsets into its lanes
+    // (lane h: butterflies of height <= h), each thread the words of its slots.
+    const uint32_t *pg = P.prog + (uint64_t)tile_id * P.prog_stride;
+    const int end_v = ((const uint16_t *)pg)[lane];
+    const int endm_v = lane ? ((const uint16_t *)pg)[lane - 1] : 0;
+    const uint32_t surv_raw = A.surv_off ? A.surv_off[tile_id + (tid0 & 1)] : 0u;   // (lane-dependent: see TileMeta::surv_raw)
+    uint32_t m_rw[SLOTS], m_rec[SLOTS];
+    W16 m_ab[SLOTS];
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
-        m_row[s] = M.row[s]; m_wl[s] = M.wl[s]; m_wr[s] = M.wr[s]; m_pos[s] = M.pos[s]; m_lv[s] = M.lv[s]; m_ht[s] = M.ht[s] & 63;
+        const int j = tid0 + s * nthreads;
+        m_rw[s] = 0; m_rec[s] = 0; m_ab[s].v[0] = 0.0; m_ab[s].v[1] = 0.0;
+        if (j < nt) {
+            m_rw[s] = pg[32 + j];
+            m_rec[s] = pg[32 + R + j];
+            if (!P.prog_compact) m_ab[s] = ((const W16 *)(pg + P.prog_ab))[j];
+        }
     }
-    if (tid < 64) hist[tid] = 0;
-    MX_STAMP(0);
+    // (a row is finalised in this tile when it merges here, or when this is the last stage and its low-pass row goes to Q)
+    auto fin_of = [&](uint32_t rw) { return (rw >> 31) != 0 || (A.last_stage && !ROOTS); };
+    auto write_dst = [&]() {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const int j = tid0 + s * nthreads;
+            if (j < nt) sdst[j] = (int32_t)((m_rw[s] & 0x7fffffffu) | (fin_of(m_rw[s]) ? 0x80000000u : 0u));
+        }
+    };
+    auto write_survivors = [&](uint32_t n_merged) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint32_t k = (uint32_t)(tid0 + s * nthreads);
+            if (k >= n_merged && k < (uint32_t)nt) ssurv[k - n_merged] = (uint16_t)m_rec[s];
+        }
+    };
+    // record k -> LDS slot k (compact records: a, b from the extents, the expression pair_weights + RAHT.py:321-322 evaluate)
+    auto write_records = [&](uint32_t n_merged) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const uint32_t k = (uint32_t)(tid0 + s * nthreads);
+            if (k < n_merged) {
+                uint32_t pj = m_rec[s];
+                W16 ab = m_ab[s];
+                if (P.prog_compact) {
+                    const uint32_t j = pj & 1023u, l = (pj >> 10) & 1023u, r = (pj >> 20) & 1023u;
+                    const double w0 = (double)(int)l, w1 = (double)(int)r;
+                    const double den = w0 + w1;
+                    ab.v[0] = sqrt(w0 / den);
+                    ab.v[1] = sqrt(w1 / den);
+                    pj = (j - l) | (j << 16);
+                }
+                rec_ab[k] = ab;
+                rec_pj[k] = pj;
+            }
+        }
+    };
 
     // LDS-direct transfers, lane-linear: instruction `it` of a transfer fills LDS bytes [1024 it, 1024 it + 1024) of its region.
     //   contiguous: row images (both parts of a workspace row are stored as separate, dense arrays)
@@ -179,28 +210,25 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
         for (int it = wid; (it << 6) < total; it += nwv) {
             const int c = (it << 6) + lane;
             const int jr = (int)(((uint32_t)c * NFm) >> 20), ch = c - jr * NF;
-            if (c < total) glds16<1>(src(jr, (uint32_t)min(ch * 4, Df - 4)), lds0 + ((uint32_t)it << 10));
+            if (c < total) { const void *a = src(jr, (uint32_t)min(ch * 4, Df - 4)); if (a) glds16<1>(a, lds0 + ((uint32_t)it << 10)); }
         }
     };
     // Widening of the wide channels a caller row arrived with (the first n_wide elements of its first float chunk): float32 ->
-    // float64 (forward), int32 * float64 step (inverse, encode_3dgs.py:261), into the wide tile. One ROW per thread, after the
-    // barrier behind which every wave's rows have landed. (The float tile keeps those elements and carries them through its
-    // float32 butterflies like any other channel: the write-backs drop what comes out of that.)
-    auto widen_row = [&](int j, auto is_int) {
+    // float64 into the wide tile. One ROW per thread, after the barrier behind which every wave's rows have landed. (The float
+    // tile keeps those elements and carries them through its float32 butterflies like any other channel: the write-backs drop
+    // what comes out of that.)
+    auto widen_row = [&](int j) {
         double *row = wd + __mul24(j, nwide);
         const V16 raw = *(const V16 *)(ftile + __mul24(j, Fp));          // the row's first chunk, as it arrived
         double d[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (decltype(is_int)::value) d[i] = i < nwide ? (double)__float_as_int(raw.v[i]) * ST.w[i] : 0.0;
-            else d[i] = i < nwide ? (double)raw.v[i] : 0.0;
-        }
+        for (int i = 0; i < 4; ++i) d[i] = i < nwide ? (double)raw.v[i] : 0.0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) if (i < nwide) row[i] = d[i];
     };
 
-    // ---- P0b. transfers whose addresses do not depend on the plan metadata ----
     if constexpr (!INV) {
+        // ---- P0b. this stage's rows ----
         if constexpr (IDENT) {
             const uint32_t ldc = (uint32_t)A.ld_in;
             const float *src = A.in + e0 * (int64_t)ldc;
@@ -209,87 +237,48 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             load_linear(ftile, nt * NF, A.in + e0 * (int64_t)Fp);
             load_linear((const float *)wd, (nt * nwide + 1) >> 1, (const float *)(P.in_w + e0 * (int64_t)nwide));      // (16-byte chunks: may read one double past the tile's rows -- the next tile's, or the array's slack)
         }
+        const uint32_t n_merged = (uint32_t)__builtin_amdgcn_readlane(end_v, 63);
+        write_dst();
+        write_survivors(n_merged);
+        write_records(n_merged);
+        MX_STAMP(1);
+        wait_landed();                                                     // this wave's rows are in LDS
+        sync_lds();                                                        // sync #1: every wave's rows, the records
+        MX_STAMP(2);
+        if constexpr (IDENT) {
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                const int j = tid + s * nthreads;
+                if (j < nt) widen_row(j);
+            }
+            sync_lds();                                                    // sync #2
+        }
+        MX_STAMP(3);
+        MX_STAMP(4);
     } else {
-        const int npre = A.last_stage ? 0 : (int)min(surv_cnt, (uint32_t)pre_rows);
-        load_linear(spre_f, npre * NF, (const float *)A.wsn + (int64_t)surv_base * Fp);
-        load_linear((const float *)spre_w, (npre * nwide + 1) >> 1, (const float *)(P.wsn_w + (int64_t)surv_base * nwide));
-    }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const int j = tid + s * nthreads;
-        if (j < nt) { if (!IDENT) srow[j] = m_row[s]; if (INV) sdst[j] = m_pos[s]; }
-    }
-    MX_STAMP(1);
-    sync_lds();                                                            // sync #1
-    MX_STAMP(2);
-
-    if constexpr (INV) {
-        // every slot's quantized row (survivor slots are overwritten in P3b)
-        load_caller_rows(nt, [&](int jr, uint32_t go) {
-            return (const void *)row_far((const int32_t *)A.Q, (uint32_t)sdst[jr], (uint32_t)A.ldq, go); });
-    }
-
-    // ---- P1. which slots merge inside this tile; height histogram; survivor ranks ----
-    bool m_merged[SLOTS];
-    int m_rank[SLOTS];
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const int j = tid + s * nthreads;
-        m_merged[s] = false;
-        bool surv = false;
-        if (j < nt) {
-            const int64_t r = m_row[s];
-            m_merged[s] = (r > 0) && (m_lv[s] < A.top_level) && (r - m_wl[s] >= start_row) && (r + m_wr[s] <= end_row);
-            surv = !m_merged[s];
-            sflag[j] = m_merged[s] ? 1 : (A.last_stage ? 2 : 0);
-            if (!INV) sdst[j] = m_pos[s] | ((m_merged[s] || (A.last_stage && !ROOTS)) ? (int32_t)0x80000000 : 0);
-            if (m_merged[s]) atomicAdd(&hist[m_ht[s]], 1u);
-        }
-        const uint64_t bal = __ballot(surv);
-        m_rank[s] = __popcll(bal & lt);
-        if (lane == 0 && s * nwv + wid < 32) scnt[s * nwv + wid] = (uint32_t)__popcll(bal);
-    }
-    sync_lds();                                                            // sync #2
-    MX_STAMP(3);
-
-    // ---- P2. round offsets (wave 0); survivor destinations ----
-    if (wid == 0) {
-        const uint32_t c = hist[lane];
-        uint32_t inc = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        loff[lane] = inc - c;
-        cursor[lane] = inc - c;
-    }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const int j = tid + s * nthreads;
-        if (j < nt && !m_merged[s]) {
-            uint32_t before = 0;
-            for (int q = 0; q < s * nwv + wid; ++q) before += scnt[q];
-            ssurv[before + (uint32_t)m_rank[s]] = (uint16_t)j;
-        }
-    }
-    if constexpr (INV) wait_landed();                                      // this wave's Q rows (and survivor prefetch) are in LDS
-    sync_lds();                                                            // sync #3 (inverse: every row has landed)
-    MX_STAMP(4);
-    if constexpr (INV) {
-        // ---- P3b (first part): the prefetched survivor rows (images, from the stage above) move into their slots; the butterfly
-        // records are then written over the bytes they waited in, hence the barrier
+        const uint32_t n_merged = (uint32_t)__builtin_amdgcn_readlane(end_v, 63);
+        write_dst();
+        write_survivors(n_merged);
+        MX_STAMP(1);
+        sync_lds();                                                        // sync #1: destinations and survivor slots
+        MX_STAMP(2);
+        // ---- P0b. every finalised slot's quantized row (survivor rows come from the stage above and are not read from Q at all)
+        load_caller_rows(nt, [&](int jr, uint32_t go) -> const void * {
+            const uint32_t d = (uint32_t)sdst[jr];
+            return (d >> 31) ? (const void *)row_far((const int32_t *)A.Q, d & 0x7fffffffu, (uint32_t)A.ldq, go) : nullptr; });
+        write_records(n_merged);
+        const uint32_t surv_base = (uint32_t)__builtin_amdgcn_readlane((int)surv_raw, 0);
+        const uint32_t surv_cnt = (uint32_t)__builtin_amdgcn_readlane((int)surv_raw, 1) - surv_base;
         if (!A.last_stage) {
-            const uint32_t n_pre = min(surv_cnt, (uint32_t)pre_rows);
-            if (c4 < NF) for (uint32_t it = wid; (it << lr) < n_pre; it += nwv) {
-                const uint32_t qc = min((it << lr) + g, n_pre - 1);
-                const V16 x = *(const V16 *)&spre_f[__mul24((int)qc, Fp) + fl * 4];
+            // the survivors, from the stage above (row images) into their slots
+            if (c4 < NF) for (uint32_t it = wid; (it << lr) < surv_cnt; it += nwv) {
+                const uint32_t qc = min((it << lr) + g, surv_cnt - 1);
+                const V16 x = ld_chunk<float>(row_at((const float *)A.wsn + (int64_t)surv_base * Fp, qc, (uint32_t)Fp, (uint32_t)(fl * 4)));
                 *(V16 *)&ftile[__mul24((int)ssurv[qc], Fp) + fl * 4] = x;
             }
-            for (uint32_t c = (uint32_t)tid; c < n_pre * (uint32_t)nwide; c += (uint32_t)nthreads) {
+            for (uint32_t c = (uint32_t)tid; c < surv_cnt * (uint32_t)nwide; c += (uint32_t)nthreads) {
                 const uint32_t qc = c / (uint32_t)nwide, i = c - qc * (uint32_t)nwide;
-                wd[__mul24((int)ssurv[qc], nwide) + i] = spre_w[c];
+                wd[__mul24((int)ssurv[qc], nwide) + i] = P.wsn_w[(int64_t)surv_base * nwide + c];
             }
         } else if (ROOTS) {
             // last stage of a plan with root buffers (a truncated tree's top rows): the roots' low-pass rows come from the caller's
@@ -305,90 +294,42 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
                 wd[__mul24((int)ssurv[qc], nwide) + i] = P.root_w[(int64_t)surv_base * nwide + c];
             }
         }
-        sync_lds();
+        MX_STAMP(3);
+        wait_landed();                                                     // this wave's Q rows are in LDS
+        sync_lds();                                                        // sync #2: every row, every record
+        MX_STAMP(4);
         load_steps(fl);
-        // roots finalised by a last TILE stage come straight from Q as well: dequantize them in place (no butterfly will)
-        if (A.last_stage && !ROOTS && c4 < NF) for (int it = wid; (it << lr) < nt; it += nwv) {
-            const int j = (it << lr) + g;
-            if (j < nt && sflag[j] == 2) {
-                V16 *pr = (V16 *)&ftile[__mul24(j, Fp) + fl * 4];
-                const I16 raw = *(const I16 *)pr;
-                V16 x;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)       // encode_3dgs.py:261 (the wide elements stay raw: widen_row reads them in this phase)
-                    x.v[i] = (head && i < nwide) ? __int_as_float(raw.v[i]) : (float)raw.v[i] * my_step[i];
-                *pr = x;
-            }
-        }
-        // the wide channels of the rows finalised here (survivor slots are filled by P3b, with images)
-        // (by the thread half a workgroup away from the row's own: tiles of <= 256 rows keep waves 0 .. 3 busy with P3a
-        // below, the widening then runs next to it on the idle ones; sflag: 0 = survivor)
+        // the wide channels of the rows finalised here, from the raw integers that arrived with them (one ROW per thread)
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s) {
-            const int j = ((tid + (nthreads >> 1)) & (nthreads - 1)) + s * nthreads;
-            if (j < nt && (ROOTS ? sflag[j] == 1 : sflag[j] != 0)) widen_row(j, std::true_type());   // (ROOTS: not the roots, 2)
-        }
-    }
-
-    // ---- P3a. resolve every butterfly of this tile into a record, bucketed by height ----
+            const int j = tid0 + s * nthreads;
+            if (j < nt && fin_of(m_rw[s])) {
+                double *row = wd + __mul24(j, nwide);
+                const I16 raw = *(const I16 *)(ftile + __mul24(j, Fp));
 #pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const int j = tid + s * nthreads;
-        if (j < nt && m_merged[s]) {
-            const int64_t r = m_row[s];
-            const int l = m_wl[s];
-            int p;
-            if (IDENT) {
-                p = j - l;
-            } else {
-                const int32_t want = (int32_t)(r - l);
-                int lo = 0, hi = j - 1;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (srow[mid] < want) lo = mid + 1; else hi = mid;
+                for (int i = 0; i < 4; ++i) if (i < nwide) row[i] = (double)raw.v[i] * ST.w[i];
+            }
+        }
+        if (A.last_stage && !ROOTS) {
+            // roots finalised by a last TILE stage come straight from Q as well: dequantize them in place (no butterfly will; the
+            // wide elements stay raw: the widening above reads them)
+            const uint32_t n_fin = (uint32_t)nt - n_merged;
+            if (c4 < NF) for (uint32_t it = wid; (it << lr) < n_fin; it += nwv) {
+                const uint32_t qc = (it << lr) + g;
+                if (qc < n_fin) {
+                    V16 *pr = (V16 *)&ftile[__mul24((int)ssurv[qc], Fp) + fl * 4];
+                    const I16 raw = *(const I16 *)pr;
+                    V16 x;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)       // encode_3dgs.py:261
+                        x.v[i] = (head && i < nwide) ? __int_as_float(raw.v[i]) : (float)raw.v[i] * my_step[i];
+                    *pr = x;
                 }
-                p = lo;
-            }
-            double w0, w1;
-            pair_weights(r, l, m_wr[s], A.wsum, w0, w1);
-            const double den = w0 + w1;
-            W16 ab;
-            ab.v[0] = sqrt(w0 / den);                     // RAHT.py:321-322 (float64; the float32 lanes round it once)
-            ab.v[1] = sqrt(w1 / den);
-            const uint32_t pos = atomicAdd(&cursor[m_ht[s]], 1u);
-            rec_ab[pos] = ab;
-            rec_pj[pos] = (uint32_t)p | ((uint32_t)j << 16);
-        }
-    }
-    // ---- P3b (second part) ----
-    if (INV && !A.last_stage) {
-        // (second part: the survivors past the prefetched ones, straight from the workspace)
-        if (c4 < NF) for (uint32_t it = wid; pre_rows + (it << lr) < surv_cnt; it += nwv) {
-            const uint32_t qc = min(pre_rows + (it << lr) + g, surv_cnt - 1);
-            const V16 x = ld_chunk<float>(row_at((const float *)A.wsn + (int64_t)surv_base * Fp, qc, (uint32_t)Fp, (uint32_t)(fl * 4)));
-            *(V16 *)&ftile[__mul24((int)ssurv[qc], Fp) + fl * 4] = x;
-        }
-        for (uint32_t c = (uint32_t)(pre_rows * nwide) + (uint32_t)tid; c < surv_cnt * (uint32_t)nwide; c += (uint32_t)nthreads) {
-            const uint32_t qc = c / (uint32_t)nwide, i = c - qc * (uint32_t)nwide;
-            wd[__mul24((int)ssurv[qc], nwide) + i] = P.wsn_w[(int64_t)surv_base * nwide + c];
-        }
-    }
-    if constexpr (!INV) {
-        wait_landed();                                                     // this wave's rows are in LDS
-        if constexpr (IDENT) {
-            sync_lds();                                                    // every wave's
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                const int j = tid + s * nthreads;
-                if (j < nt) widen_row(j, std::false_type());
             }
         }
-        sync_lds();                                                        // sync #4
-    } else {
-        __syncthreads();
+        sync_lds();                                                        // sync #3
     }
     MX_STAMP(5);
-
     // ---- P4. butterflies, one round per height present ----
     // The float32 channels run exactly as in the float32 kernels: a lane group per butterfly (head and idle lanes shadow the
     // group's last float lane: same reads, same writes, no exec-mask juggling). The wide channels of a level are a SEPARATE, dense
@@ -404,7 +345,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
         const uint32_t bw = 64u >> lgw;                        // wide butterflies per wave instruction
         const uint32_t cf = (uint32_t)fl * 4u;
         bool chained = false;
-        const int loff_v = (int)loff[lane], hist_v = (int)hist[lane];
+        const int loff_v = endm_v, hist_v = end_v - endm_v;
         uint64_t mask = __ballot(hist_v > 0);
         while (mask) {
             const int l = INV ? (63 - __clzll((long long)mask)) : (__ffsll((long long)mask) - 1);
@@ -539,6 +480,8 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
         // survivors, compacted, to the next stage's workspace (row images, two dense arrays); last stage of a plan with root
         // buffers: the roots to the caller's two buffers (float: row stride D, each place at its channels; wide: n_wide doubles)
         if (!A.last_stage || ROOTS) {
+            const uint32_t surv_base = (uint32_t)__builtin_amdgcn_readlane((int)surv_raw, 0);
+            const uint32_t surv_cnt = (uint32_t)__builtin_amdgcn_readlane((int)surv_raw, 1) - surv_base;
             constexpr bool to_roots = ROOTS;
             float *bf = to_roots ? A.root_buf + (int64_t)surv_base * Df : A.wsn + (int64_t)surv_base * Fp;
             double *bw_ = (to_roots ? P.root_w : P.wsn_w) + (int64_t)surv_base * nwide;
@@ -885,7 +828,7 @@ static bool mx_geometry(const raht_plan *p, int D, int nwide, MxGeom &g)
     pick_tail_geometry(p, 4, D, 512, &r1, &dc1, &g.Rf);
     const size_t budget = (size_t)42 * 1280;              // three workgroups per CU
     auto fit = [&](int hi, bool ident, size_t cap) {
-        for (int R = hi; R >= 64; --R) if (tile_lds_bytes_mx(R, NF, nwide, ident) <= cap) return R;
+        for (int R = hi; R >= 64; --R) if (tile_lds_bytes_mx(R, NF, nwide) <= cap) return R;
         return 0;
     };
     g.R0 = p->tile_rows_override > 0 ? fit(std::min(p->tile_rows_override, TILE_MAX_SLOTS * MX_THREADS), true, (size_t)128 * 1280)
@@ -1001,7 +944,9 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
     P.out_w = (INV && k >= 1) ? ws_k_w : nullptr;
     P.wsn_w = ws_n_w;
     P.root_w = A.last_stage ? p->root_buf_w : nullptr;
-    const size_t lds = tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide, st.rows == nullptr);
+    P.prog = st.prog; P.prog_stride = st.prog_stride; P.prog_ab = st.prog_ab; P.prog_compact = st.prog_compact ? 1 : 0;
+    if (!P.prog) { set_error("mixed tile stage %d: missing tile programs", k); return RAHT_ERR_INVALID; }
+    const size_t lds = tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide);
     const unsigned nt = (unsigned)st.n_tiles;
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
     int rc;
@@ -1055,6 +1000,7 @@ static int mx_setup(raht_plan *p, int D, int n_wide, int64_t max_ld, hipStream_t
     Schedule *sc = nullptr;
     RAHT_RET(get_schedule(p, g.R0, g.R1, g.Rf, s, &sc));
     if (!sc->valid) return RAHT_OK;
+    RAHT_RET(build_tile_programs(p, sc, s));
     RAHT_RET(ensure_workspace(sc, (size_t)g.Dp * 4 + (size_t)g.nwide * 8 + 8, p->split_ws));      // float chunks + n_wide doubles (+ slack: the wide part is fetched in 16-byte chunks)
     *sc_out = sc;
     return RAHT_OK;
