@@ -261,6 +261,30 @@ int raht_fwd_quant_mixed(const raht_plan *plan, const float *C, int64_t ldc, int
                          int n_wide, int32_t *Q, int64_t ldq, raht_stream_t stream);
 int raht_dequant_inv_mixed(const raht_plan *plan, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps,
                            int n_wide, float *C, int64_t ldc, raht_stream_t stream);
+/* The two driver-loop fusions of the float32 entries (raht_fwd_quant_multi, raht_dequant_inv_sqdiff) in mixed precision: a
+ * 59-column frame gets the fusions AND the reference's integers on its wide columns.
+ *   raht_fwd_quant_mixed_multi : ONE mixed forward pass, k quantizations. steps: HOST double[k], one scalar step per output
+ *     matrix; Q: HOST array of k distinct DEVICE matrices (N x D int32, row stride ldq). Q[i] is bit-identical to
+ *     raht_fwd_quant_mixed(plan, C, ldc, D, &steps[i], 1, n_wide, Q[i], ldq, stream). Any k >= 1 (chunked internally by 12
+ *     matrices per pass). Argument rules: those of raht_fwd_quant_mixed for every steps[i] (n_wide 1..4 and <= D, steps[i] > 0
+ *     also as float32, no row-mapped plans, both root buffers or neither), plus k >= 1 and no two Q[i] the same.
+ *   raht_dequant_inv_mixed_sqdiff : raht_dequant_inv_mixed whose stage-0 kernel compares every row it writes with C_ref.
+ *     C_rec, when not NULL, is bit-identical to raht_dequant_inv_mixed's; with C_rec == NULL nothing is written there.
+ *     sqdiff: DEVICE double[D], sqdiff[c] = sum over rows of (C_rec[i, c] - C_ref[i, c])^2, taken from the float32 values the
+ *     mixed inverse writes (the wide columns after their one rounding to float32, as raht_dequant_inv_sqdiff defines it):
+ *     differences in float32, squares and sums in float64, summed in a fixed order (deterministic); equal to
+ *     raht_sqdiff_columns(C_ref, C_rec) up to the order of the float64 additions. Argument rules: those of
+ *     raht_dequant_inv_mixed, plus C_ref and sqdiff set.
+ * Shapes outside the mixed tile kernels (raht_plan_mixed_stats(...) tile_rows == 0: level engine, D - n_wide < 4, D > 68),
+ * trees of one launch and plans with root buffers (truncated plans) run the single calls inside, with the same results: k x
+ * raht_fwd_quant_mixed, or raht_dequant_inv_mixed into C_rec (or a scratch matrix) followed by raht_sqdiff_columns. Under
+ * raht_plan_set_concurrent_directions, multi is a forward-direction call and sqdiff an inverse-direction call: each uses that
+ * direction's workspaces and the schedule and tile programs of the single mixed calls. */
+int raht_fwd_quant_mixed_multi(const raht_plan *plan, const float *C, int64_t ldc, int D, const double *steps, int k,
+                               int n_wide, int32_t *const *Q, int64_t ldq, raht_stream_t stream);
+int raht_dequant_inv_mixed_sqdiff(const raht_plan *plan, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps,
+                                  int n_wide, const float *C_ref, int64_t ld_ref, float *C_rec, int64_t ldc, double *sqdiff,
+                                  raht_stream_t stream);
 /* Tile rows / stage sizes the mixed kernels use for (D, n_wide); *tile_rows = 0 when the shape takes the two-pass path. */
 int raht_plan_mixed_stats(raht_plan *plan, int D, int n_wide, int *tile_rows, int *n_stages, int64_t *rows_per_stage,
                           int max_stages);

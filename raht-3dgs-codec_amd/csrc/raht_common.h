@@ -320,4 +320,7 @@ int pick_tile_rows(const raht_plan *plan, int elem_size, int chunk_channels);
 int pick_chunk_channels(int elem_size, int D);
 
 size_t tile_lds_bytes(int R, int elem_size, int Dc, bool ident, bool qm);
+// Per-column totals of the fused distortion kernels' per-tile partials (transform.hip: sq_final_kernel): part holds ncv float64
+// per tile, element 4 p + i = channel min(4 p, D - 4) + i of the row; out[c] for c < D, summed in a fixed order.
+int launch_sq_final(const double *part, int64_t n_tiles, int D, int ncv, double *out, hipStream_t s);
 }  // namespace raht

@@ -830,6 +830,13 @@ __global__ __launch_bounds__(256) void sq_final_kernel(const double *__restrict_
     if (threadIdx.x == 0) out[ch] = red[0];
 }
 
+int launch_sq_final(const double *part, int64_t n_tiles, int D, int ncv, double *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(sq_final_kernel, dim3((unsigned)D), dim3(256), 0, s, part, n_tiles, D, ncv, out);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
 // FORWARD CHAINING of the later tile stages (round 3). Stage k + 1's tile P can run as soon as the tiles of stage k that
 // feed it are done, and those are a handful of CONSECUTIVE tiles. So stages 1 .. last tile stage go out as ONE launch with one
 // workgroup per stage-1 tile: a workgroup that finishes a tile adds the number of survivors it delivered to the arrival

@@ -73,11 +73,22 @@ struct MxPtrs {
     int prog_compact;
 };
 
+// raht_fwd_quant_mixed_multi: k scalar steps, one output matrix each (the float32 entry's MultiQ, with the steps in float64: the
+// wide channels divide by step[i], the float lanes by (float)step[i])
+struct MxMultiQ {
+    int k;
+    uint32_t fast_div;                  // bit i: (float)step[i] within [2^-100, 2^100] (the single call's rule, raht_device.h: quantize_one)
+    double step[MULTI_Q_MAX];
+    int32_t *Q[MULTI_Q_MAX];
+};
+
 // ROOTS: last stage of a plan with root buffers (TileArgs::root_buf, MxPtrs::root_w): the roots' low-pass rows go to / come from
 // the caller's buffers instead of Q. A kernel of its own (tile_kernel_mx_roots), so that every other launch runs the code it ran
-// without them.
-template <bool INV, bool IDENT, int SLOTS, bool ROOTS>
-__device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &ST, const int64_t tile_id)
+// without them. MULTI (forward) and SQ (inverse, stage 0) are the fused driver-loop variants, each a kernel of its own as well
+// (tile_kernel_mx_multi, tile_kernel_mx_sq): only their write-backs differ.
+template <bool INV, bool IDENT, int SLOTS, bool ROOTS, bool MULTI = false, bool SQ = false>
+__device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &ST, const int64_t tile_id,
+                                             const MxMultiQ *MQ = nullptr)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     typedef RegChunk<float> V16;
@@ -440,6 +451,11 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             // narrower store instruction becomes a partial-line write of its own: the fused forward took 0.92 ms instead of
             // 0.31 ms that way (rows are 236 bytes: every line is shared by two rows)
             float *base = A.out + e0 * A.ld_out;
+            // SQ (raht_dequant_inv_mixed_sqdiff): every row is also compared with A.ref on its way out, chunk for chunk -- the
+            // head lane's chunk with the wide channels already rounded to float32 -- differences in float32, squares and sums in
+            // float64 per lane; A.out == nullptr: nothing is stored
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            const float *rbase = SQ ? A.ref + e0 * A.ld_ref : nullptr;
             // Two row instructions per trip. The head lanes alone read their rows' wide results (clamped indices: no branch per
             // channel, all reads of a trip in flight together); what follows is branch-free -- selects, then ONE store instruction
             // per row group, pinned behind an empty asm so that the compiler cannot sink it into a head / non-head diamond again
@@ -447,6 +463,12 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             // every wide channel was its own LDS round trip)
             if (rowlane) for (int it = wid; (it << lr) < nt; it += 2 * nwv) {
                 int j[2]; V16 x[2]; double w[2][4] = {};
+                V16 c[2];
+                if constexpr (SQ) {
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+                        c[u] = ld_chunk<float, true>(row_at(rbase, (uint32_t)min(((it + u * nwv) << lr) + g, nt - 1), (uint32_t)A.ld_ref, (uint32_t)goff));
+                }
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     j[u] = min(((it + u * nwv) << lr) + g, nt - 1);
@@ -465,8 +487,37 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { const float f = (float)w[u][i]; x[u].v[i] = (head && i < nwide) ? f : x[u].v[i]; }
                     asm volatile("" : "+v"(x[u].v[0]), "+v"(x[u].v[1]), "+v"(x[u].v[2]), "+v"(x[u].v[3]));
-                    if (u == 0 || ((it + nwv) << lr) < nt)                  // (wave-uniform)
+                    if constexpr (SQ) {
+                        if (u == 0 || ((it + nwv) << lr) < nt) {            // (wave-uniform)
+                            if (A.out) st_chunk<float, true>(row_at(base, (uint32_t)j[u], (uint32_t)A.ld_out, (uint32_t)goff), x[u]);
+                            if (((it + u * nwv) << lr) + g < nt) {
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) { const float d = x[u].v[i] - c[u].v[i]; acc[i] += (double)d * (double)d; }
+                            }
+                        }
+                    } else if (u == 0 || ((it + nwv) << lr) < nt) {         // (wave-uniform)
                         st_chunk<float, true>(row_at(base, (uint32_t)j[u], (uint32_t)A.ld_out, (uint32_t)goff), x[u]);
+                    }
+                }
+            }
+            if constexpr (SQ) {
+                // per tile, in a fixed order: a chunk place's lanes across the wave's row groups (shuffles), then the waves (LDS)
+                // -> one float64 per float place element in sq_part (the element layout sq_final_kernel reads: 4 NF per tile)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    for (int sh = 1 << lg; sh < 64; sh <<= 1) acc[i] += __shfl_xor(acc[i], sh, 64);
+                }
+                __syncthreads();                                                  // every wave has read its rows: the tile's LDS is free
+                double *sacc = (double *)smem;                                    // [nwv][4 NF]
+                if (g == 0 && rowlane) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sacc[(wid * NF + c4) * 4 + i] = acc[i];
+                }
+                __syncthreads();
+                if (tid0 < NF * 4) {
+                    double t = 0.0;
+                    for (int w = 0; w < nwv; ++w) t += sacc[w * NF * 4 + tid0];
+                    A.sq_part[tile_id * (NF * 4) + tid0] = t;
                 }
             }
         } else {
@@ -496,65 +547,125 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
                 bw_[c] = wd[__mul24((int)ssurv[q], nwide) + i];
             }
         }
-        // rows finalised here, quantized to Q[inv_order[row]] (encode_3dgs.py:204,210,215).
-        // (a) the wide channels: one ROW per thread -- the IEEE double division is ~40 instructions a channel, so it runs on
-        //     whole waves of rows -- and the integers go back into the row's first wide place (a row finalised here is nobody's
-        //     survivor)
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            const int j = tid0 + s * nthreads;
-            if (j < nt && ((uint32_t)sdst[j] >> 31)) {
-                double *row = &wd[__mul24(j, nwide)];
-                double d[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (i < nwide) d[i] = row[i];
-                asm volatile("" ::: "memory");                // (the integers go over the doubles they were made of: every read is above)
-                int32_t *qrow = (int32_t *)row;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (i < nwide) qrow[i] = quantize_one_f64(d[i], ST.w[i]);
-            }
-        }
-        sync_lds();
-        MX_STAMP(7);
-        // (b) ONE store instruction per row group writes whole rows of Q: the float lanes their quantized chunks, the head lane the
-        //     row's first 16 bytes = the wide integers and, behind them, the first 4 - n_wide float channels quantized once more
-        //     (same values as their own lane's). See the inverse's write-back for why.
-        load_steps(sp);
-        auto store_final = [&](auto fast_div) {
-            if (rowlane) for (int it = wid; (it << lr) < nt; it += 2 * nwv) {
-                int jc[2]; V16 x[2]; I16 qi[2] = {}; uint32_t dv[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    jc[u] = min(((it + u * nwv) << lr) + g, nt - 1);
-                    x[u] = *(const V16 *)&ftile[__mul24(jc[u], Fp) + sp * 4];
-                    dv[u] = (uint32_t)sdst[jc[u]];
-                }
-                if (head) {                                   // (only the head lanes; clamped indices: no branch per channel)
+        if constexpr (MULTI) {
+            // raht_fwd_quant_mixed_multi: the write-back below ((a), then (b)) once per step. The wide doubles must outlive every
+            // quantization, so the integers of step kk go to an area of their own: the butterfly records' (16 bytes per row >=
+            // n_wide int32), free since the last butterfly round. One barrier after (a) -- (b) reads other threads' rows -- and
+            // one after (b), before the next step's (a) overwrites the area.
+            int32_t *qa = (int32_t *)rec_ab;
+            auto store_step = [&](auto fast_div, int32_t *Qd) {
+                if (rowlane) for (int it = wid; (it << lr) < nt; it += 2 * nwv) {
+                    int jc[2]; V16 x[2]; I16 qi[2] = {}; uint32_t dv[2];
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
-                        const int32_t *qrow = (const int32_t *)&wd[__mul24(jc[u], nwide)];
+                        jc[u] = min(((it + u * nwv) << lr) + g, nt - 1);
+                        x[u] = *(const V16 *)&ftile[__mul24(jc[u], Fp) + sp * 4];
+                        dv[u] = (uint32_t)sdst[jc[u]];
+                    }
+                    if (head) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) qi[u].v[i] = qrow[min(i, nwide - 1)];
+                        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) qi[u].v[i] = qa[__mul24(jc[u], nwide) + min(i, nwide - 1)];
+                        }
+                    }
+                    asm volatile("" : "+v"(x[0].v[0]), "+v"(x[1].v[0]), "+v"(qi[0].v[0]), "+v"(qi[0].v[1]), "+v"(qi[0].v[2]), "+v"(qi[0].v[3]),
+                                 "+v"(qi[1].v[0]), "+v"(qi[1].v[1]), "+v"(qi[1].v[2]), "+v"(qi[1].v[3]));
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        I16 qv;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int32_t q = quantize_one(x[u].v[i], my_step[i], my_rcp[i], decltype(fast_div)::value);
+                            qv.v[i] = (head && i < nwide) ? qi[u].v[i] : q;
+                        }
+                        asm volatile("" : "+v"(qv.v[0]), "+v"(qv.v[1]), "+v"(qv.v[2]), "+v"(qv.v[3]));
+                        if ((dv[u] >> 31) && (u == 0 || ((it + nwv) << lr) < nt))
+                            st_chunk<int32_t, true>(row_far(Qd, dv[u] & 0x7fffffffu, (uint32_t)A.ldq, (uint32_t)goff), qv);
                     }
                 }
-                asm volatile("" : "+v"(x[0].v[0]), "+v"(x[1].v[0]), "+v"(qi[0].v[0]), "+v"(qi[0].v[1]), "+v"(qi[0].v[2]), "+v"(qi[0].v[3]),
-                             "+v"(qi[1].v[0]), "+v"(qi[1].v[1]), "+v"(qi[1].v[2]), "+v"(qi[1].v[3]));
+            };
+            for (int kk = 0; kk < MQ->k; ++kk) {
+                const double sw = MQ->step[kk];
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    // branch-free up to ONE store instruction per row group (see the inverse's write-back)
-                    I16 qv;
+                for (int s = 0; s < SLOTS; ++s) {
+                    const int j = tid0 + s * nthreads;
+                    if (j < nt && ((uint32_t)sdst[j] >> 31)) {
+                        const double *row = &wd[__mul24(j, nwide)];
+                        int32_t *qrow = &qa[__mul24(j, nwide)];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int32_t q = quantize_one(x[u].v[i], my_step[i], my_rcp[i], decltype(fast_div)::value);
-                        qv.v[i] = (head && i < nwide) ? qi[u].v[i] : q;
+                        for (int i = 0; i < 4; ++i) if (i < nwide) qrow[i] = quantize_one_f64(row[i], sw);
                     }
-                    asm volatile("" : "+v"(qv.v[0]), "+v"(qv.v[1]), "+v"(qv.v[2]), "+v"(qv.v[3]));
-                    if ((dv[u] >> 31) && (u == 0 || ((it + nwv) << lr) < nt))
-                        st_chunk<int32_t, true>(row_far(A.Q, dv[u] & 0x7fffffffu, (uint32_t)A.ldq, (uint32_t)goff), qv);
+                }
+                sync_lds();
+                const float sf = (float)sw, rf = refined_rcp(sf);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { my_step[i] = sf; my_rcp[i] = rf; }
+                if ((MQ->fast_div >> kk) & 1u) store_step(std::true_type(), MQ->Q[kk]);
+                else store_step(std::false_type(), MQ->Q[kk]);
+                sync_lds();
+            }
+        } else {
+            // rows finalised here, quantized to Q[inv_order[row]] (encode_3dgs.py:204,210,215).
+            // (a) the wide channels: one ROW per thread -- the IEEE double division is ~40 instructions a channel, so it runs on
+            //     whole waves of rows -- and the integers go back into the row's first wide place (a row finalised here is nobody's
+            //     survivor)
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                const int j = tid0 + s * nthreads;
+                if (j < nt && ((uint32_t)sdst[j] >> 31)) {
+                    double *row = &wd[__mul24(j, nwide)];
+                    double d[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) if (i < nwide) d[i] = row[i];
+                    asm volatile("" ::: "memory");                // (the integers go over the doubles they were made of: every read is above)
+                    int32_t *qrow = (int32_t *)row;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) if (i < nwide) qrow[i] = quantize_one_f64(d[i], ST.w[i]);
                 }
             }
-        };
-        if (ST.f.fast_div) store_final(std::true_type()); else store_final(std::false_type());
+            sync_lds();
+            MX_STAMP(7);
+            // (b) ONE store instruction per row group writes whole rows of Q: the float lanes their quantized chunks, the head lane the
+            //     row's first 16 bytes = the wide integers and, behind them, the first 4 - n_wide float channels quantized once more
+            //     (same values as their own lane's). See the inverse's write-back for why.
+            load_steps(sp);
+            auto store_final = [&](auto fast_div) {
+                if (rowlane) for (int it = wid; (it << lr) < nt; it += 2 * nwv) {
+                    int jc[2]; V16 x[2]; I16 qi[2] = {}; uint32_t dv[2];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        jc[u] = min(((it + u * nwv) << lr) + g, nt - 1);
+                        x[u] = *(const V16 *)&ftile[__mul24(jc[u], Fp) + sp * 4];
+                        dv[u] = (uint32_t)sdst[jc[u]];
+                    }
+                    if (head) {                                   // (only the head lanes; clamped indices: no branch per channel)
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            const int32_t *qrow = (const int32_t *)&wd[__mul24(jc[u], nwide)];
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) qi[u].v[i] = qrow[min(i, nwide - 1)];
+                        }
+                    }
+                    asm volatile("" : "+v"(x[0].v[0]), "+v"(x[1].v[0]), "+v"(qi[0].v[0]), "+v"(qi[0].v[1]), "+v"(qi[0].v[2]), "+v"(qi[0].v[3]),
+                                 "+v"(qi[1].v[0]), "+v"(qi[1].v[1]), "+v"(qi[1].v[2]), "+v"(qi[1].v[3]));
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        // branch-free up to ONE store instruction per row group (see the inverse's write-back)
+                        I16 qv;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int32_t q = quantize_one(x[u].v[i], my_step[i], my_rcp[i], decltype(fast_div)::value);
+                            qv.v[i] = (head && i < nwide) ? qi[u].v[i] : q;
+                        }
+                        asm volatile("" : "+v"(qv.v[0]), "+v"(qv.v[1]), "+v"(qv.v[2]), "+v"(qv.v[3]));
+                        if ((dv[u] >> 31) && (u == 0 || ((it + nwv) << lr) < nt))
+                            st_chunk<int32_t, true>(row_far(A.Q, dv[u] & 0x7fffffffu, (uint32_t)A.ldq, (uint32_t)goff), qv);
+                    }
+                }
+            };
+            if (ST.f.fast_div) store_final(std::true_type()); else store_final(std::false_type());
+        }
     }
     MX_STAMP(8);
 }
@@ -569,6 +680,18 @@ template <bool INV, bool IDENT, int SLOTS>
 __global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_roots(const TileArgs<float> A, const MxPtrs P, const StepTableMX ST)
 {
     tile_body_mx<INV, IDENT, SLOTS, true>(A, P, ST, (int64_t)blockIdx.x);
+}
+// raht_fwd_quant_mixed_multi: every stage of the forward, k quantizations per finalised row
+template <bool IDENT, int SLOTS>
+__global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_multi(const TileArgs<float> A, const MxPtrs P, const StepTableMX ST, const MxMultiQ M)
+{
+    tile_body_mx<false, IDENT, SLOTS, false, true, false>(A, P, ST, (int64_t)blockIdx.x, &M);
+}
+// raht_dequant_inv_mixed_sqdiff: stage 0 of the inverse, comparing its rows with TileArgs::ref on the way out
+template <int SLOTS>
+__global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_sq(const TileArgs<float> A, const MxPtrs P, const StepTableMX ST)
+{
+    tile_body_mx<true, true, SLOTS, false, false, true>(A, P, ST, (int64_t)blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -592,8 +715,8 @@ struct TopArgsMX {
     float *root_f; double *root_w;           // the caller's root buffers (n_roots x D floats, n_roots x n_wide doubles), or nullptr
 };
 
-template <bool WIDE, bool INV, bool ROOTS>
-__device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableMX &ST, const int chunk)
+template <bool WIDE, bool INV, bool ROOTS, bool MULTI = false>
+__device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableMX &ST, const int chunk, const MxMultiQ *MQ = nullptr)
 {
     typedef typename std::conditional<WIDE, double, float>::type T;
     constexpr int VN = WIDE ? 2 : 4;
@@ -754,6 +877,27 @@ __device__ __forceinline__ void top_body_mx(const TopArgsMX &A, const StepTableM
             } else {
                 st_chunk<float>(A.root_f + (int64_t)m_rr[k] * A.D + goff, v);
             }
+        } else if constexpr (MULTI) {
+            // raht_fwd_quant_mixed_multi: one quantization per step, each into its own matrix
+            for (int kk = 0; kk < MQ->k; ++kk) {
+                int32_t *q = MQ->Q[kk] + (int64_t)m_dst[k] * A.ldq + goff;
+                if constexpr (WIDE) {
+#pragma unroll
+                    for (int i = 0; i < VN; ++i) if (live[i]) q[i] = quantize_one_f64(v.v[i], MQ->step[kk]);
+                } else {
+                    const float sf = (float)MQ->step[kk], rf = refined_rcp(sf);
+                    const int fd = (int)((MQ->fast_div >> kk) & 1u);
+                    RegChunk<int32_t> qv;
+#pragma unroll
+                    for (int i = 0; i < VN; ++i) qv.v[i] = quantize_one(v.v[i], sf, rf, fd);
+                    if (chunk == 0) {
+#pragma unroll
+                        for (int i = 0; i < VN; ++i) if (live[i]) q[i] = qv.v[i];
+                    } else {
+                        st_chunk<int32_t>(q, qv);
+                    }
+                }
+            }
         } else {
             int32_t *q = A.Q + (int64_t)m_dst[k] * A.ldq + goff;
             if constexpr (WIDE) {
@@ -788,6 +932,14 @@ __global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_roots(const TopA
     const int NW2 = (A.nwide + 1) >> 1;
     if ((int)blockIdx.x < NW2) top_body_mx<true, INV, true>(A, ST, (int)blockIdx.x);
     else top_body_mx<false, INV, true>(A, ST, (int)blockIdx.x - NW2);
+}
+
+// raht_fwd_quant_mixed_multi (plans without root buffers)
+__global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_multi(const TopArgsMX A, const StepTableMX ST, const MxMultiQ M)
+{
+    const int NW2 = (A.nwide + 1) >> 1;
+    if ((int)blockIdx.x < NW2) top_body_mx<true, false, false, true>(A, ST, (int)blockIdx.x, &M);
+    else top_body_mx<false, false, false, true>(A, ST, (int)blockIdx.x - NW2, &M);
 }
 
 // the wide columns of caller rows <-> a compact float64 matrix (fallback path only)
@@ -849,29 +1001,50 @@ static void fill_steps_mx(StepTableMX &t, const double *steps, int n_steps, int 
     for (int i = 0; i < MX_MAX_WIDE; ++i) t.w[i] = i < nwide ? steps[n_steps == 1 ? 0 : i] : 1.0;
 }
 
-template <bool INV, bool IDENT, int SLOTS, bool ROOTS>
-static int launch_tile_mx_one(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, unsigned n_tiles, size_t lds, hipStream_t s)
+// KIND: which tile kernel a stage launches -- the plain one (tile_kernel_mx / _roots), the forward multi-step one, or the
+// inverse's comparing stage 0
+enum { MX_PLAIN = 0, MX_MULTI = 1, MX_SQ = 2 };
+
+template <bool INV, bool IDENT, int SLOTS, bool ROOTS, int KIND>
+static int launch_tile_mx_one(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, const MxMultiQ *M, unsigned n_tiles,
+                              size_t lds, hipStream_t s)
 {
-    const void *fn = ROOTS ? (const void *)tile_kernel_mx_roots<INV, IDENT, SLOTS> : (const void *)tile_kernel_mx<INV, IDENT, SLOTS>;
     static PerDeviceOnce attr;
-    if (attr.first(current_device()))
-        RAHT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if constexpr (ROOTS) hipLaunchKernelGGL((tile_kernel_mx_roots<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
-    else hipLaunchKernelGGL((tile_kernel_mx<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
+    if constexpr (KIND == MX_MULTI) {
+        static_assert(!INV && !ROOTS, "multi: forward, no root buffers");
+        if (attr.first(current_device()))
+            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx_multi<IDENT, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((tile_kernel_mx_multi<IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st, *M);
+    } else if constexpr (KIND == MX_SQ) {
+        static_assert(INV && IDENT && !ROOTS, "sqdiff: inverse stage 0, no root buffers");
+        if (attr.first(current_device()))
+            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx_sq<SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL((tile_kernel_mx_sq<SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
+    } else {
+        const void *fn = ROOTS ? (const void *)tile_kernel_mx_roots<INV, IDENT, SLOTS> : (const void *)tile_kernel_mx<INV, IDENT, SLOTS>;
+        if (attr.first(current_device()))
+            RAHT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if constexpr (ROOTS) hipLaunchKernelGGL((tile_kernel_mx_roots<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
+        else hipLaunchKernelGGL((tile_kernel_mx<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
+    }
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }
 
-template <bool INV, bool IDENT, bool ROOTS>
-static int launch_tile_mx_slots(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, unsigned n_tiles, size_t lds, hipStream_t s)
+template <bool INV, bool IDENT, bool ROOTS, int KIND>
+static int launch_tile_mx_slots(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, const MxMultiQ *M, unsigned n_tiles,
+                                size_t lds, hipStream_t s)
 {
-    return A.R <= MX_THREADS ? launch_tile_mx_one<INV, IDENT, 1, ROOTS>(A, P, st, n_tiles, lds, s)
-                             : launch_tile_mx_one<INV, IDENT, 2, ROOTS>(A, P, st, n_tiles, lds, s);
+    return A.R <= MX_THREADS ? launch_tile_mx_one<INV, IDENT, 1, ROOTS, KIND>(A, P, st, M, n_tiles, lds, s)
+                             : launch_tile_mx_one<INV, IDENT, 2, ROOTS, KIND>(A, P, st, M, n_tiles, lds, s);
 }
 
 struct MxIO {
     const float *C_in = nullptr; float *C_out = nullptr; int64_t ldc = 0;
     int32_t *Q = nullptr; int64_t ldq = 0;
+    const MxMultiQ *multi = nullptr;                       // forward: raht_fwd_quant_mixed_multi's steps and matrices (Q unused)
+    const float *ref = nullptr; int64_t ld_ref = 0;        // inverse stage 0, sqdiff: the reference rows ...
+    double *sq_part = nullptr;                             // ... and the per-tile partial sums (C_out may then be NULL)
 };
 
 template <bool INV>
@@ -907,7 +1080,14 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
             RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
             RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_roots<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
         }
-        if (A.root_f) hipLaunchKernelGGL((top_kernel_mx_roots<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
+        if (!INV && io.multi) {
+            static PerDeviceOnce attr_m;
+            if (attr_m.first(current_device()))
+                RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+            if (A.root_f) { set_error("mixed multi top stage: root buffers"); return RAHT_ERR_INVALID; }
+            hipLaunchKernelGGL(top_kernel_mx_multi, dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp, *io.multi);
+        }
+        else if (A.root_f) hipLaunchKernelGGL((top_kernel_mx_roots<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
         else hipLaunchKernelGGL((top_kernel_mx<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
         RAHT_HIP_CHECK(hipGetLastError());
         return RAHT_OK;
@@ -933,7 +1113,9 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
         else if (!A.last_stage && (!A.wsn || !A.surv_off)) bad = "survivor workspace of a non-final stage";
         else if (!A.Q || !A.inv_order) bad = "Q / inv_order";
         else if (!INV && !A.in) bad = "forward input";
-        else if (INV && !A.out) bad = "inverse output";
+        else if (INV && !A.out && !(k == 0 && io.sq_part)) bad = "inverse output";
+        else if (k == 0 && io.sq_part && (!INV || !io.ref || A.root_buf || (int64_t)st.tile_rows * io.ld_ref * 4 >= ((int64_t)1 << 31))) bad = "sqdiff reference rows";
+        else if (!INV && io.multi && A.root_buf) bad = "multi-step write-back without root buffers";
         else if ((st.rows == nullptr) != (k == 0)) bad = "stage order";
         else if (st.tile_rows < 1 || st.tile_rows > TILE_MAX_SLOTS * MX_THREADS ||
                  (int64_t)st.tile_rows * std::max<int64_t>(io.ldc, g.Dp) * 4 >= ((int64_t)1 << 31)) bad = "tile geometry (32-bit row offsets)";
@@ -950,8 +1132,24 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
     const unsigned nt = (unsigned)st.n_tiles;
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
     int rc;
-    if (k == 0) rc = A.root_buf ? launch_tile_mx_slots<INV, true, true>(A, P, stp, nt, lds, s) : launch_tile_mx_slots<INV, true, false>(A, P, stp, nt, lds, s);
-    else rc = A.root_buf ? launch_tile_mx_slots<INV, false, true>(A, P, stp, nt, lds, s) : launch_tile_mx_slots<INV, false, false>(A, P, stp, nt, lds, s);
+    if constexpr (!INV) {
+        if (io.multi) {
+            rc = k == 0 ? launch_tile_mx_slots<false, true, false, MX_MULTI>(A, P, stp, io.multi, nt, lds, s)
+                        : launch_tile_mx_slots<false, false, false, MX_MULTI>(A, P, stp, io.multi, nt, lds, s);
+            if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
+            return rc;
+        }
+    } else {
+        if (k == 0 && io.sq_part) {
+            A.out = io.C_out; A.ld_out = io.C_out ? io.ldc : 0;
+            A.ref = io.ref; A.ld_ref = io.ld_ref; A.sq_part = io.sq_part;
+            rc = launch_tile_mx_slots<true, true, false, MX_SQ>(A, P, stp, nullptr, nt, lds, s);
+            if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
+            return rc;
+        }
+    }
+    if (k == 0) rc = A.root_buf ? launch_tile_mx_slots<INV, true, true, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s) : launch_tile_mx_slots<INV, true, false, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s);
+    else rc = A.root_buf ? launch_tile_mx_slots<INV, false, true, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s) : launch_tile_mx_slots<INV, false, false, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s);
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
     return rc;
 }
@@ -1074,6 +1272,90 @@ static int dequant_inv_mixed_impl(const raht_plan *cp, const int32_t *Q, int64_t
     return RAHT_OK;
 }
 
+/* One mixed forward pass, k scalar steps: Q[i] bit-identical to raht_fwd_quant_mixed(..., &steps[i], 1, n_wide, Q[i], ...). The
+ * stages, survivors and workspaces are the single call's; only the write-back of every finalised row runs once per step. */
+static int fwd_quant_mixed_multi_impl(const raht_plan *cp, const float *C, int64_t ldc, int D, const double *steps, int k, int n_wide,
+                                      int32_t *const *Q, int64_t ldq, raht_stream_t stream)
+{
+    const char *what = "raht_fwd_quant_mixed_multi";
+    raht_plan *p = const_cast<raht_plan *>(cp);
+    hipStream_t s = (hipStream_t)stream;
+    if (!p || !C || !Q || !steps || k < 1) { set_error("%s: bad argument (plan, C, Q, steps must be set, k >= 1)", what); return RAHT_ERR_INVALID; }
+    for (int i = 0; i < k; ++i) {
+        if (!Q[i]) { set_error("%s: Q[%d] is NULL", what, i); return RAHT_ERR_INVALID; }
+        for (int j = 0; j < i; ++j) if (Q[j] == Q[i]) { set_error("%s: Q[%d] and Q[%d] are the same matrix", what, j, i); return RAHT_ERR_INVALID; }
+    }
+    for (int i = 0; i < k; ++i) RAHT_RET(mx_check_args(p, C, Q[i], D, ldc, ldq, &steps[i], 1, n_wide, what));
+    Schedule *sc = nullptr;
+    MxGeom g;
+    if (!p->root_buf) RAHT_RET(mx_setup(p, D, n_wide, std::max(ldc, ldq), s, &sc, g));
+    if (!sc) {
+        // the single calls' fallback shapes, and plans with root buffers (every call writes the same roots): one call per step
+        for (int i = 0; i < k; ++i) RAHT_RET(fwd_quant_mixed_impl(p, C, ldc, D, &steps[i], 1, n_wide, Q[i], ldq, stream));
+        return RAHT_OK;
+    }
+    const int K = (int)sc->stages.size();
+    for (int k0 = 0; k0 < k; k0 += MULTI_Q_MAX) {
+        MxMultiQ M;
+        M.k = std::min(MULTI_Q_MAX, k - k0);
+        M.fast_div = 0;
+        for (int i = 0; i < MULTI_Q_MAX; ++i) {
+            M.step[i] = steps[k0 + std::min(i, M.k - 1)];
+            M.Q[i] = Q[k0 + std::min(i, M.k - 1)];
+            const float f = (float)M.step[i];
+            if (f >= 0x1p-100f && f <= 0x1p100f) M.fast_div |= 1u << i;        // (fill_step_table's rule, per step)
+        }
+        StepTableMX stp;
+        fill_steps_mx(stp, &steps[k0], 1, n_wide);
+        MxIO io;
+        io.C_in = C; io.ldc = ldc; io.Q = M.Q[0]; io.ldq = ldq; io.multi = &M;
+        for (int kk = 0; kk < K; ++kk) RAHT_RET((launch_stage_mx<false>(p, *sc, kk, io, D, g, stp, s)));
+    }
+    return RAHT_OK;
+}
+
+/* raht_dequant_inv_mixed whose stage 0 also compares every row it writes with C_ref: per-column sums of squared differences of
+ * the float32 values the mixed inverse writes (the wide channels after their one rounding), the fixed-order reduction of
+ * raht_dequant_inv_sqdiff. C_rec == NULL: the reconstruction is not written. */
+static int dequant_inv_mixed_sqdiff_impl(const raht_plan *cp, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps,
+                                         int n_wide, const float *Cref, int64_t ldref, float *Crec, int64_t ldc, double *sq,
+                                         raht_stream_t stream)
+{
+    const char *what = "raht_dequant_inv_mixed_sqdiff";
+    raht_plan *p = const_cast<raht_plan *>(cp);
+    hipStream_t s = (hipStream_t)stream;
+    if (!p || !Q || !Cref || !sq || D < 1 || ldref < D || (Crec && ldc < D)) { set_error("%s: bad argument (plan, Q, C_ref, sqdiff must be set)", what); return RAHT_ERR_INVALID; }
+    RAHT_RET(mx_check_args(p, Q, Cref, D, ldq, ldref, steps, n_steps, n_wide, what));
+    Schedule *sc = nullptr;
+    MxGeom g;
+    if (!p->root_buf) RAHT_RET(mx_setup(p, D, n_wide, std::max(std::max(ldq, ldref), Crec ? ldc : (int64_t)D), s, &sc, g));
+    if (!sc || sc->stages.size() < 2 || sc->stages[0].is_top) {
+        // shapes outside the mixed tile kernels, one-launch trees, plans with root buffers: the mixed inverse, then the sums
+        Scratch tmp(Crec ? 16 : sizeof(float) * (size_t)p->N * (size_t)D, s);
+        if (!tmp.ok()) return RAHT_ERR_NOMEM;
+        float *out = Crec ? Crec : tmp.as<float>();
+        const int64_t ldo = Crec ? ldc : D;
+        RAHT_RET(dequant_inv_mixed_impl(p, Q, ldq, D, steps, n_steps, n_wide, out, ldo, stream));
+        return raht_sqdiff_columns(Cref, ldref, out, ldo, p->N, D, RAHT_F32, sq, stream);
+    }
+    const int ncv = g.Dp;                                  // 4 NF partials per tile
+    const Stage &st0 = sc->stages[0];
+    Scratch part(sizeof(double) * (size_t)st0.n_tiles * (size_t)ncv, s);
+    if (!part.ok()) return RAHT_ERR_NOMEM;
+    if ((size_t)(MX_THREADS / 64) * (size_t)ncv * 8 > tile_lds_bytes_mx(st0.tile_rows, g.Dp / 4, g.nwide)) {
+        set_error("%s: unexpected stage-0 geometry", what);
+        return RAHT_ERR_INVALID;
+    }
+    StepTableMX stp;
+    fill_steps_mx(stp, steps, n_steps, n_wide);
+    MxIO io;
+    io.C_out = Crec; io.ldc = Crec ? ldc : 0; io.Q = const_cast<int32_t *>(Q); io.ldq = ldq;
+    io.ref = Cref; io.ld_ref = ldref; io.sq_part = part.as<double>();
+    const int K = (int)sc->stages.size();
+    for (int k = K - 1; k >= 0; --k) RAHT_RET((launch_stage_mx<true>(p, *sc, k, io, D, g, stp, s)));
+    return launch_sq_final(part.as<double>(), (int64_t)st0.n_tiles, D, ncv, sq, s);
+}
+
 }  // namespace raht
 
 using namespace raht;
@@ -1090,6 +1372,20 @@ int raht_dequant_inv_mixed(const raht_plan *plan, const int32_t *Q, int64_t ldq,
                            float *C, int64_t ldc, raht_stream_t stream)
 {
     return guarded("raht_dequant_inv_mixed", [&]() { return dequant_inv_mixed_impl(plan, Q, ldq, D, steps, n_steps, n_wide, C, ldc, stream); });
+}
+
+int raht_fwd_quant_mixed_multi(const raht_plan *plan, const float *C, int64_t ldc, int D, const double *steps, int k, int n_wide,
+                               int32_t *const *Q, int64_t ldq, raht_stream_t stream)
+{
+    return guarded("raht_fwd_quant_mixed_multi", [&]() { return fwd_quant_mixed_multi_impl(plan, C, ldc, D, steps, k, n_wide, Q, ldq, stream); });
+}
+
+int raht_dequant_inv_mixed_sqdiff(const raht_plan *plan, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps,
+                                  int n_wide, const float *C_ref, int64_t ld_ref, float *C_rec, int64_t ldc, double *sqdiff,
+                                  raht_stream_t stream)
+{
+    return guarded("raht_dequant_inv_mixed_sqdiff", [&]() {
+        return dequant_inv_mixed_sqdiff_impl(plan, Q, ldq, D, steps, n_steps, n_wide, C_ref, ld_ref, C_rec, ldc, sqdiff, stream); });
 }
 
 #ifdef RAHT_PHASE_CLOCKS

@@ -457,6 +457,55 @@ class RahtPlan:
                 self._reset_mixed_roots()
         return out
 
+    def forward_quant_mixed_multi(self, Cmat, steps, n_wide=3, roots=None, roots_wide=None):
+        """ONE mixed-precision forward pass, one quantization per (scalar) step: -> [Q_0, ..., Q_{k-1}], each bit-identical to
+        ``forward_quant_mixed(C, steps[i], n_wide)`` -- the nine steps of a frame (python/encode_3dgs.py:28,199-217) with the
+        reference's integers on the first ``n_wide`` columns. roots / roots_wide: as for ``forward_quant_mixed``."""
+        _need_cuda(Cmat, "C")
+        X = Cmat.to(torch.float32)
+        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+            X = X.contiguous()
+        D = X.shape[1]
+        k = len(steps)
+        st = (C.c_double * k)(*[float(s) for s in steps])
+        Qs = [torch.empty((self.N, D), dtype=torch.int32, device=X.device) for _ in range(k)]
+        ptrs = (C.c_void_p * k)(*[q.data_ptr() for q in Qs])
+        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
+        try:
+            with torch.cuda.device(X.device):
+                check(_lib.lib().raht_fwd_quant_mixed_multi(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, k, int(n_wide), ptrs, D,
+                                                            _stream()))
+        finally:
+            if roots is not None:
+                self._reset_mixed_roots()
+        return Qs
+
+    def dequant_inverse_mixed_sqdiff(self, Q, steps, C_ref, n_wide=3, want_rec=True, roots=None, roots_wide=None):
+        """``dequant_inverse_mixed`` that also compares its output with the original attributes on the way out: -> (C_rec or None,
+        float64[D] per-column sums of (C_rec - C_ref)^2, from the float32 values C_rec holds). With ``want_rec=False`` C_rec is
+        never written. roots / roots_wide: as for ``dequant_inverse_mixed``."""
+        _need_cuda(Q, "Q")
+        _need_cuda(C_ref, "C_ref")
+        Q = Q.to(torch.int32).contiguous()
+        D = Q.shape[1]
+        X = C_ref.to(torch.float32)
+        if X.stride(1) != 1 or X.stride(0) < D:
+            X = X.contiguous()
+        st = _steps64(steps, D)
+        out = torch.empty((self.N, D), dtype=torch.float32, device=Q.device) if want_rec else None
+        ssd = torch.empty(D, dtype=torch.float64, device=Q.device)
+        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
+        try:
+            with torch.cuda.device(Q.device):
+                check(_lib.lib().raht_dequant_inv_mixed_sqdiff(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st), int(n_wide),
+                                                               C.c_void_p(X.data_ptr()), X.stride(0),
+                                                               C.c_void_p(out.data_ptr()) if want_rec else None, D,
+                                                               C.c_void_p(ssd.data_ptr()), _stream()))
+        finally:
+            if roots is not None:
+                self._reset_mixed_roots()
+        return out, ssd
+
     def mixed_stats(self, D=59, n_wide=3):
         """Tile rows and rows per stage of the mixed-precision schedule (tile_rows 0: the shape takes the two-pass path)."""
         tr, ns = C.c_int(0), C.c_int(0)
