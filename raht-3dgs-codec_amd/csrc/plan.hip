@@ -440,18 +440,6 @@ __global__ void __launch_bounds__(EXT_THREADS) order_scatter_kernel(const uint8_
     }
 }
 
-__global__ void order_to_identity_kernel(uint32_t *order, int64_t N)
-{
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < N) order[k] = (uint32_t)k;
-}
-
-__global__ void invert_perm_kernel(const uint32_t *__restrict__ order, int64_t N, uint32_t *__restrict__ inv)
-{
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < N) inv[order[k]] = (uint32_t)k;
-}
-
 // ---- tile schedule -----------------------------------------------------------------------------
 // Entry j of a stage (row r = rows ? rows[j] : j) is merged inside its tile iff the whole subtree
 // [r - wl, r + wr) lies inside the tile's row range; otherwise it survives to the next stage.
@@ -491,8 +479,6 @@ static int fit_chunk_channels(int elem_size, int D, int max_dc)
 
 int pick_chunk_channels(int elem_size, int D)
 {
-    static const int forced = getenv("RAHT_STAGE0_CH") ? atoi(getenv("RAHT_STAGE0_CH")) : 0;     // tuning knob: channel chunks at stage 0
-    if (forced >= 16 / elem_size && forced < D) return fit_chunk_channels(elem_size, D, forced);
     return fit_chunk_channels(elem_size, D, 64);
 }
 
@@ -565,7 +551,6 @@ static void free_schedule(Schedule &sc)
         if (st.e_wr) dev_free(st.e_wr);
         if (st.e_lvl) dev_free(st.e_lvl);
         if (st.e_ht) dev_free(st.e_ht);
-        if (st.arrive) dev_free(st.arrive);
         if (st.e_pos) dev_free(st.e_pos);
         if (st.t_pj) dev_free(st.t_pj);
         if (st.t_ab32) dev_free(st.t_ab32);
@@ -1790,7 +1775,6 @@ __global__ void plan_begin_kernel(const uint64_t *__restrict__ keys_in, uint64_t
 static int finish_plan(raht_plan *p, const int64_t *leaf_weights, hipStream_t s, const uint64_t *keys_in)
 {
     const int64_t N = p->N;
-    const unsigned gb = (unsigned)ceil_div(N, 256);
     const unsigned nblk = (unsigned)ceil_div(N, EXT_THREADS);
     // scratch: error word | level starts [64] | (order bucket + level) histograms / positions [(ORDER_BUCKETS + 64) x nblk]
     //          | search queue [EXT_QCAP x nblk] + counts [nblk] | bucket ids [N]
@@ -1823,10 +1807,6 @@ static int finish_plan(raht_plan *p, const int64_t *leaf_weights, hipStream_t s,
     // heights on a third next to the whole schedule build -- 0.245 / 0.235 ms against 0.226 ms on one stream: a cross-queue
     // dependency costs ~13 us, and kernels this small slow each other down when they share the chip.)
     hipLaunchKernelGGL(order_scatter_kernel, dim3(nblk), dim3(EXT_THREADS), 0, s, bucket, N, bhist, bin_total, p->order, p->inv_order, lhist);
-    if (getenv("RAHT_DEBUG_IDENTITY_ORDER")) {    // timing experiments only: order_RAGFT := identity
-        hipLaunchKernelGGL(order_to_identity_kernel, dim3(gb), dim3(256), 0, s, p->order, N);
-        hipLaunchKernelGGL(invert_perm_kernel, dim3(gb), dim3(256), 0, s, p->order, N, p->inv_order);
-    }
     // The error word and the level histogram travel with the schedule builder's read-back (ONE host round trip per
     // plan). Everything up to it is enqueued speculatively: kernels running on unsorted keys read and write inside
     // their arrays all the same, and their results are thrown away with the plan.

@@ -137,13 +137,11 @@ __device__ __forceinline__ P *row_far(P *base, uint32_t row, uint32_t ld, uint32
 // that LDS is being written, so it neither drains the load at the next LDS access it cannot tell apart from the
 // destination (every one, with one dynamic LDS block) nor counts it -- its own s_waitcnt vmcnt(n) are then merely
 // stricter than needed (the counter retires in order). The kernel waits for the data itself: tile_kernel, sync #3.
-template <int MODE = 0>      // 0: default policy; 1: nontemporal (matrices touched once: C, T, Q); 2: agent-coherent (sc1: rows another
-                             // workgroup of the SAME launch has just written through -- forward chaining, tile_kernel_chain)
+template <int MODE = 0>      // 0: default policy; 1: nontemporal (matrices touched once: C, T, Q)
 __device__ __forceinline__ void glds16(const void *g, uint32_t lds_base)
 {
     const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_base);
     if constexpr (MODE == 1) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" :: "v"(g), "s"(b) : "memory");
-    else if constexpr (MODE == 2) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" :: "v"(g), "s"(b) : "memory");
     else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(g), "s"(b) : "memory");
 }
 

@@ -26,7 +26,6 @@
 #include "tile_engine.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -144,16 +143,7 @@ __device__ unsigned long long g_phase_clk[PHASE_CLK_TILES][PHASE_CLK_SLOTS];
 #define PHASE_STAMP(k) do { } while (0)
 #endif
 
-// 16 bytes written THROUGH the XCD's L2 (sc1: agent scope): visible to the other XCDs once the store has been acknowledged
-// (s_waitcnt vmcnt(0)), without the L2 write-back an agent-scope release fence costs
-template <typename T>
-__device__ __forceinline__ void st_chunk_wt(T *p, const RegChunk<T> &x)
-{
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 v;
-    __builtin_memcpy(&v, &x, 16);
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(p), "v"(v) : "memory");
-}
+constexpr int TILE_THREADS = 512;      // threads per workgroup of every tile stage
 
 // IDENT = true is stage 0 (entries are the rows themselves: the HBM-heavy launch); IDENT = false
 // are the later, much smaller stages. QM = true fuses quantize+reorder (forward) / un-reorder+
@@ -170,7 +160,7 @@ __device__ __forceinline__ void st_chunk_wt(T *p, const RegChunk<T> &x)
 //
 // tile_body is the kernel; tile_kernel runs it for ONE scene (workgroup b takes tiles b, b + gridDim.x, ...), tile_kernel_batch
 // for several scenes in one launch (workgroup b takes ONE tile of the scene whose tile range holds b).
-template <typename T, bool INV, bool IDENT, bool QM, int SLOTS, bool WT = false, bool SQ = false, bool MULTI = false>
+template <typename T, bool INV, bool IDENT, bool QM, int SLOTS, bool SQ = false, bool MULTI = false>
 __device__ __forceinline__ void tile_body(const TileArgs<T> &A, const typename std::conditional<QM, typename StepsFor<T>::type, NoSteps>::type &ST,
                                           const int64_t first_tile, const int64_t tile_stride, const int chunk_y, const MultiQ *MQ = nullptr)
 {
@@ -308,7 +298,7 @@ __device__ __forceinline__ void tile_body(const TileArgs<T> &A, const typename s
         // forward: this stage's entries, entry order (C or ws_k); plain inverse of stage 0: T rows [e0, e0+nt)
         const uint32_t lds = (uint32_t)(INV ? A.ld_fin : A.ld_in);
         const T *src = (INV ? (const T *)A.fin : A.in) + e0 * (int64_t)lds;      // wave-uniform
-        load_rows(std::integral_constant<int, (WT && !IDENT) ? 2 : (IDENT ? 1 : 0)>(), tile, nt,      // stage 0: C (or T) itself, touched once
+        load_rows(std::integral_constant<bool, IDENT>(), tile, nt,      // stage 0: C (or T) itself, touched once
                   [&](int jr, uint32_t go) { return row_at(src, (uint32_t)jr, lds, go); });
     }
     if (INV) {
@@ -729,9 +719,7 @@ __device__ __forceinline__ void tile_body(const TileArgs<T> &A, const typename s
             if (active) for (uint32_t it = wid; (it << lr) < surv_cnt; it += nw) {
                 const uint32_t q = min((it << lr) + g, surv_cnt - 1);
                 const V16 x = *(const V16 *)&tile[__mul24((int)ssurv[q], Dp) + coff];
-                if constexpr (WT) { if (!A.last_stage) st_chunk_wt<T>(row_at(dstb + (int64_t)surv_base * ldb, q, (uint32_t)ldb, (uint32_t)goff), x);
-                                    else st_chunk<T>(row_at(dstb + (int64_t)surv_base * ldb, q, (uint32_t)ldb, (uint32_t)goff), x); }
-                else st_chunk<T>(row_at(dstb + (int64_t)surv_base * ldb, q, (uint32_t)ldb, (uint32_t)goff), x);
+                st_chunk<T>(row_at(dstb + (int64_t)surv_base * ldb, q, (uint32_t)ldb, (uint32_t)goff), x);
             }
         }
         // rows finalised here: T[row], or, fused, quantized to Q[inv_order[row]] (encode_3dgs.py:204,210,215)
@@ -791,7 +779,7 @@ __device__ __forceinline__ void tile_body(const TileArgs<T> &A, const typename s
 }
 
 template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-__global__ __launch_bounds__(512, (sizeof(T) == 4 ? 6 : 4)) void tile_kernel(const TileArgs<T> A,
+__global__ __launch_bounds__(TILE_THREADS, (sizeof(T) == 4 ? 6 : 4)) void tile_kernel(const TileArgs<T> A,
                                                    const typename std::conditional<QM, typename StepsFor<T>::type, NoSteps>::type ST)
 {
     tile_body<T, INV, IDENT, QM, SLOTS>(A, ST, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)blockIdx.y);
@@ -799,16 +787,16 @@ __global__ __launch_bounds__(512, (sizeof(T) == 4 ? 6 : 4)) void tile_kernel(con
 
 // raht_fwd_quant_multi: the fused forward kernels writing one quantization per step table (tile_body / top_body, MULTI)
 template <bool IDENT, int SLOTS>
-__global__ __launch_bounds__(512, 6) void tile_kernel_multi(const TileArgs<float> A, const StepTable ST, const MultiQ M)
+__global__ __launch_bounds__(TILE_THREADS, 6) void tile_kernel_multi(const TileArgs<float> A, const StepTable ST, const MultiQ M)
 {
-    tile_body<float, false, IDENT, true, SLOTS, false, false, true>(A, ST, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)blockIdx.y, &M);
+    tile_body<float, false, IDENT, true, SLOTS, false, true>(A, ST, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)blockIdx.y, &M);
 }
 
 // stage 0 of raht_dequant_inv_sqdiff (tile_body, SQ): the fused inverse that compares its output with a reference matrix on the way out
 template <int SLOTS>
-__global__ __launch_bounds__(512, 6) void tile_kernel_sq(const TileArgs<float> A, const StepTable ST)
+__global__ __launch_bounds__(TILE_THREADS, 6) void tile_kernel_sq(const TileArgs<float> A, const StepTable ST)
 {
-    tile_body<float, true, true, true, SLOTS, false, true>(A, ST, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)blockIdx.y);
+    tile_body<float, true, true, true, SLOTS, true>(A, ST, (int64_t)blockIdx.x, (int64_t)gridDim.x, (int)blockIdx.y);
 }
 
 // out[ch] = sum over tiles of the partial that holds channel ch (a row's last chunk is the 16 bytes that END the row: when D is not
@@ -837,78 +825,6 @@ int launch_sq_final(const double *part, int64_t n_tiles, int D, int ncv, double 
     return RAHT_OK;
 }
 
-// FORWARD CHAINING of the later tile stages (round 3). Stage k + 1's tile P can run as soon as the tiles of stage k that
-// feed it are done, and those are a handful of CONSECUTIVE tiles. So stages 1 .. last tile stage go out as ONE launch with one
-// workgroup per stage-1 tile: a workgroup that finishes a tile adds the number of survivors it delivered to the arrival
-// counter of each parent tile it fed (at most two: the next stage's tiles are at least as long as this one's); whoever
-// completes a parent's count runs that parent next, in the same workgroup, and so on upwards. Nobody ever waits, so nothing
-// can deadlock; every tile of every chained stage is run exactly once (by the last of its children to arrive). Ordering
-// (the parent may run on another XCD, whose L2 is a different one): survivor rows are written THROUGH the L2 (st_chunk_wt,
-// sc1), every thread waits for its stores' acknowledgement, barrier, one relaxed agent-scope atomic; the taker loads the rows
-// past its own L2 (glds16<2>). Counters return to zero (the taker resets them). MEASURED, OFF by default (RAHT_CHAIN=1):
-// fused cfg3 forward 0.3038 -> 0.3112 ms -- the acknowledgement wait, the atomic and the parent's coherent loads are three
-// ~2 us round trips on every tile's way up, more than the 4.6 us launch gap and the ~6 us of stage-2 work the chaining hides
-// (the first version, with agent-scope fences = L2 write-backs instead of write-through stores: 0.339 ms).
-// Only with all D channels in one chunk (D <= 64). The pending parents (depth-first, at most one per stage above) live at
-// the end of the dynamic LDS block, behind what tile_body uses.
-constexpr int CHAIN_MAX = 6;
-template <typename T>
-struct TileChain {
-    TileArgs<T> a[CHAIN_MAX];
-    uint32_t *arrive[CHAIN_MAX];       // arrive[i]: counters of a[i]'s tiles (i >= 1)
-    int n;
-    uint32_t stack_off;                // byte offset of the pending list in the dynamic LDS block
-};
-
-template <typename T, bool QM, int SLOTS>
-__global__ __launch_bounds__(512, (sizeof(T) == 4 ? 6 : 4)) void tile_kernel_chain(const TileChain<T> C,
-                                                   const typename std::conditional<QM, typename StepsFor<T>::type, NoSteps>::type ST)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *pend = (uint32_t *)(smem + C.stack_off);      // [0] = count, [1 + i] = stage << 24 | tile
-    int stage = 0;
-    int64_t tile = blockIdx.x;
-    if (threadIdx.x == 0) pend[0] = 0;
-    for (;;) {
-        tile_body<T, false, false, QM, SLOTS, true>(C.a[stage], ST, tile, (int64_t)1 << 40, 0);      // (ends with a barrier)
-        if (stage + 1 < C.n) {
-            // this tile's survivor rows were written THROUGH the L2 (st_chunk_wt): once every thread's stores are acknowledged
-            // they are visible device-wide, and the parent tile loads them past its own XCD's L2 (glds16<2>). No fence: an
-            // agent-scope release is a write-back of the whole L2 (round 3, first version: the chained launch 35 us SLOWER than
-            // the separate launches; with a fence in every thread 220 us instead of 31).
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const TileArgs<T> &A = C.a[stage];
-                const uint32_t sb = A.surv_off[tile], se = A.surv_off[tile + 1];
-                const uint32_t Rn = (uint32_t)C.a[stage + 1].R, n_next = (uint32_t)C.a[stage + 1].n_entries;
-                uint32_t *arr = C.arrive[stage + 1];
-                for (uint32_t lo = sb; lo < se;) {
-                    const uint32_t pt = lo / Rn, hi = min(se, (pt + 1) * Rn), add = hi - lo;
-                    const uint32_t target = min(Rn, n_next - pt * Rn);
-                    const uint32_t old = atomicAdd(&arr[pt], add);
-                    if (old + add == target) {
-                        arr[pt] = 0;                           // ours now; ready for the next launch
-                        const uint32_t c = pend[0];
-                        pend[1 + c] = ((uint32_t)(stage + 1) << 24) | pt;
-                        pend[0] = c + 1;
-                    }
-                    lo = hi;
-                }
-            }
-            __syncthreads();
-        }
-        const uint32_t c = pend[0];
-        if (c == 0) break;
-        const uint32_t top = pend[c];
-        __syncthreads();                                      // everybody has read the entry before it is popped / overwritten
-        if (threadIdx.x == 0) pend[0] = c - 1;
-        stage = (int)(top >> 24);
-        tile = (int64_t)(top & 0xffffffu);
-        __syncthreads();
-    }
-}
-
 // Several scenes, one launch (raht_*_batch): the same stage of up to TILE_BATCH_MAX scenes. first_tile[s] = number of tiles of the
 // scenes before s; a workgroup finds its scene with a handful of scalar compares and runs ONE tile of it. A frame of ~1 M
 // Gaussians fills the chip's 768 workgroup slots two and a half times and then waits ~20 us for its tail stages (a third of
@@ -922,7 +838,7 @@ struct TileBatch {
 };
 
 template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-__global__ __launch_bounds__(512, (sizeof(T) == 4 ? 6 : 4)) void tile_kernel_batch(const TileBatch<T> B,
+__global__ __launch_bounds__(TILE_THREADS, (sizeof(T) == 4 ? 6 : 4)) void tile_kernel_batch(const TileBatch<T> B,
                                                    const typename std::conditional<QM, typename StepsFor<T>::type, NoSteps>::type ST)
 {
     int s = 0;
@@ -1193,51 +1109,6 @@ __global__ void node_weight_kernel(const int32_t *__restrict__ wl, const int32_t
     w[i] = (T)(w0 + w1);
 }
 
-static int tile_threads()
-{
-    static int t = 0;
-    if (t == 0) {
-        const char *e = getenv("RAHT_TILE_THREADS");      // tuning knob: 512 (default) or 256
-        const int v = e ? atoi(e) : 512;
-        t = (v == 256 || v == 512) ? v : 512;
-    }
-    return t;
-}
-
-// threads per workgroup of the stages >= 1 (tuning knob RAHT_TAIL_THREADS: 256 or 512; default = tile_threads())
-static int tail_threads()
-{
-    static int t = 0;
-    if (t == 0) {
-        const char *e = getenv("RAHT_TAIL_THREADS");
-        const int v = e ? atoi(e) : tile_threads();
-        t = (v == 256 || v == 512) ? v : tile_threads();
-    }
-    return t;
-}
-
-static int device_cus()
-{
-    static int n[RAHT_MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (n[dev] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n[dev] = v;
-        else n[dev] = 256;                                  // MI355X
-    }
-    return n[dev];
-}
-
-// RAHT_TILE_PERSIST (tuning knob): 0 / unset = one tile per workgroup (default, measured fastest);
-// 1 = as many workgroups as the chip keeps resident, each walking tiles b, b + grid, ...;
-// k >= 2 = k tiles per workgroup.
-static int persist_mode()
-{
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("RAHT_TILE_PERSIST"); v = e ? std::max(0, atoi(e)) : 0; }
-    return v;
-}
-
 static int lp_shift_for(int Dc)
 {
     int s = 0;
@@ -1258,11 +1129,10 @@ struct XformIO {
 // "launch" enqueues one scene's stage, "launch_*_batch" the same stage of several scenes in one launch ----
 struct TileGeom {
     int64_t n_tiles = 0;
-    unsigned grid_x = 0, nchunks = 0;
-    int threads = 0;
+    unsigned nchunks = 0;
     size_t lds = 0;
     bool one = true, ident = true;
-    bool same_shape(const TileGeom &o) const { return nchunks == o.nchunks && threads == o.threads && lds == o.lds && one == o.one && ident == o.ident; }
+    bool same_shape(const TileGeom &o) const { return nchunks == o.nchunks && lds == o.lds && one == o.one && ident == o.ident; }
 };
 
 template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
@@ -1280,32 +1150,32 @@ static int tile_kernel_attr()
 }
 
 template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-static int launch_tile_one(const TileArgs<T> &A, const XformIO<T> &io, dim3 grid, int threads, size_t lds, hipStream_t s)
+static int launch_tile_one(const TileArgs<T> &A, const XformIO<T> &io, dim3 grid, size_t lds, hipStream_t s)
 {
     RAHT_RET((tile_kernel_attr<T, INV, IDENT, QM, SLOTS>()));
     if constexpr (QM) {
         typename StepsFor<T>::type st;
         fill_step_table(st, io.steps, io.n_steps);
-        hipLaunchKernelGGL((tile_kernel<T, INV, IDENT, true, SLOTS>), grid, dim3(threads), lds, s, A, st);
+        hipLaunchKernelGGL((tile_kernel<T, INV, IDENT, true, SLOTS>), grid, dim3(TILE_THREADS), lds, s, A, st);
     } else {
         NoSteps ns{0, 0};
-        hipLaunchKernelGGL((tile_kernel<T, INV, IDENT, false, SLOTS>), grid, dim3(threads), lds, s, A, ns);
+        hipLaunchKernelGGL((tile_kernel<T, INV, IDENT, false, SLOTS>), grid, dim3(TILE_THREADS), lds, s, A, ns);
     }
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }
 
 template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-static int launch_tile_batch_one(const TileBatch<T> &B, const XformIO<T> &io, dim3 grid, int threads, size_t lds, hipStream_t s)
+static int launch_tile_batch_one(const TileBatch<T> &B, const XformIO<T> &io, dim3 grid, size_t lds, hipStream_t s)
 {
     RAHT_RET((tile_kernel_attr<T, INV, IDENT, QM, SLOTS>()));
     if constexpr (QM) {
         typename StepsFor<T>::type st;
         fill_step_table(st, io.steps, io.n_steps);
-        hipLaunchKernelGGL((tile_kernel_batch<T, INV, IDENT, true, SLOTS>), grid, dim3(threads), lds, s, B, st);
+        hipLaunchKernelGGL((tile_kernel_batch<T, INV, IDENT, true, SLOTS>), grid, dim3(TILE_THREADS), lds, s, B, st);
     } else {
         NoSteps ns{0, 0};
-        hipLaunchKernelGGL((tile_kernel_batch<T, INV, IDENT, false, SLOTS>), grid, dim3(threads), lds, s, B, ns);
+        hipLaunchKernelGGL((tile_kernel_batch<T, INV, IDENT, false, SLOTS>), grid, dim3(TILE_THREADS), lds, s, B, ns);
     }
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
@@ -1407,8 +1277,7 @@ static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, con
     A.wsum = p->wsum;
     if (st.rows) { A.lvl = st.e_lvl; A.wl = st.e_wl; A.wr = st.e_wr; A.inv_order = st.e_pos; }
     else { A.lvl = p->lvl; A.wl = p->wl; A.wr = p->wr; A.inv_order = p->inv_order; }
-    static const bool rounds_by_level = getenv("RAHT_ROUNDS_BY_LEVEL") != nullptr;    // A/B knob: one round per binary level present (rounds 1-2)
-    A.ht = rounds_by_level ? A.lvl : st.e_ht;
+    A.ht = st.e_ht;
     A.Q = io.Q; A.ldq = io.ldq;
     A.top_level = p->top_level; A.root_buf = (T *)p->root_buf;
     A.dbg = dbg; A.nwide = 0; A.ref = nullptr; A.ld_ref = 0; A.sq_part = nullptr;
@@ -1441,21 +1310,12 @@ static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, con
     }
     G.nchunks = (unsigned)((D + Dc - 1) / Dc);
     G.lds = tile_lds_bytes(st.tile_rows, (int)sizeof(T), Dc, st.rows == nullptr, QM);
-    G.threads = (k == 0) ? tile_threads() : tail_threads();
-    if (st.tile_rows > TILE_MAX_SLOTS * G.threads) {
-        set_error("tile_rows %d too large for %d threads", st.tile_rows, G.threads);
+    if (st.tile_rows > TILE_MAX_SLOTS * TILE_THREADS) {
+        set_error("tile_rows %d too large for %d threads", st.tile_rows, TILE_THREADS);
         return RAHT_ERR_UNSUPPORTED;
     }
-    // persistent workgroups: as many as the chip keeps resident (LDS granules of 1280 B, 32 waves
-    // per CU), each walking tiles blockIdx.x, blockIdx.x + gridDim.x, ...
-    const int per_cu = std::max(1, std::min((int)(128 / ((G.lds + 1279) / 1280)), 32 / (G.threads / 64)));
-    const int64_t resident = (int64_t)per_cu * device_cus();
-    const int pm = persist_mode();
-    const int64_t gx = pm == 1 ? std::min<int64_t>(st.n_tiles, std::max<int64_t>(1, resident / G.nchunks))
-                     : pm >= 2 ? ceil_div(st.n_tiles, (int64_t)pm) : st.n_tiles;
-    G.n_tiles = st.n_tiles;
-    G.grid_x = (unsigned)gx;
-    G.one = st.tile_rows <= G.threads;
+    G.n_tiles = st.n_tiles;                               // one tile per workgroup
+    G.one = st.tile_rows <= TILE_THREADS;
     G.ident = st.rows == nullptr;
     return RAHT_OK;
 }
@@ -1486,83 +1346,12 @@ static int launch_stage_impl(const raht_plan *p, const Schedule &sc, int k, cons
     TileArgs<T> A;
     TileGeom G;
     RAHT_RET((prepare_tile_stage<T, INV, QM>(p, sc, k, io, D, Dc0, dbg, A, G)));
-    const dim3 grid(G.grid_x, G.nchunks);
+    const dim3 grid((unsigned)G.n_tiles, G.nchunks);
     if (G.ident)
-        return G.one ? launch_tile_one<T, INV, true, QM, 1>(A, io, grid, G.threads, G.lds, s)
-                     : launch_tile_one<T, INV, true, QM, 2>(A, io, grid, G.threads, G.lds, s);
-    return G.one ? launch_tile_one<T, INV, false, QM, 1>(A, io, grid, G.threads, G.lds, s)
-                 : launch_tile_one<T, INV, false, QM, 2>(A, io, grid, G.threads, G.lds, s);
-}
-
-// stages k0 .. k1 (tile stages of one launch shape, forward direction, one channel chunk) as ONE chained launch
-template <typename T, bool QM>
-static int launch_tile_chain(raht_plan *p, Schedule &sc, int k0, int k1, const XformIO<T> &io, int D, int Dc0, hipStream_t s)
-{
-    TileChain<T> C;
-    TileGeom G0;
-    C.n = k1 - k0 + 1;
-    for (int i = 0; i < CHAIN_MAX; ++i) C.arrive[i] = nullptr;
-    for (int k = k0; k <= k1; ++k) {
-        Stage &st = sc.stages[(size_t)k];
-        TileGeom G;
-        RAHT_RET((prepare_tile_stage<T, false, QM>(p, sc, k, io, D, Dc0, 0, C.a[k - k0], G)));
-        if (G.nchunks != 1) { set_error("tile chain: channel-chunked stage"); return RAHT_ERR_INVALID; }
-        if (k == k0) G0 = G;
-        else if (!G.same_shape(G0) || st.tile_rows < sc.stages[(size_t)k - 1].tile_rows) { set_error("tile chain: stages of different launch shapes"); return RAHT_ERR_INVALID; }
-        if (k > k0 && !st.arrive) {
-            RAHT_HIP_CHECK(dev_malloc(&st.arrive, sizeof(uint32_t) * (size_t)st.n_tiles));
-            RAHT_HIP_CHECK(hipMemsetAsync(st.arrive, 0, sizeof(uint32_t) * (size_t)st.n_tiles, s));
-        }
-        C.arrive[k - k0] = st.arrive;
-    }
-    for (int i = C.n; i < CHAIN_MAX; ++i) C.a[i] = C.a[0];
-    C.stack_off = (uint32_t)((G0.lds + 15) & ~(size_t)15);
-    const size_t lds = C.stack_off + 64;
-    const dim3 grid((unsigned)G0.n_tiles, 1);
-    static PerDeviceOnce attr1, attr2;
-    if (G0.one) {
-        if (attr1.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_chain<T, QM, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    } else {
-        if (attr2.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_chain<T, QM, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    if constexpr (QM) {
-        typename StepsFor<T>::type st;
-        fill_step_table(st, io.steps, io.n_steps);
-        if (G0.one) hipLaunchKernelGGL((tile_kernel_chain<T, true, 1>), grid, dim3(G0.threads), lds, s, C, st);
-        else hipLaunchKernelGGL((tile_kernel_chain<T, true, 2>), grid, dim3(G0.threads), lds, s, C, st);
-    } else {
-        NoSteps ns{0, 0};
-        if (G0.one) hipLaunchKernelGGL((tile_kernel_chain<T, false, 1>), grid, dim3(G0.threads), lds, s, C, ns);
-        else hipLaunchKernelGGL((tile_kernel_chain<T, false, 2>), grid, dim3(G0.threads), lds, s, C, ns);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
-}
-
-// the forward direction's stage sequence: stage 0, the later tile stages (optionally chained into one launch: see below), the top stage
-template <typename T, bool QM>
-static int launch_forward_stages(raht_plan *p, Schedule &sc, const XformIO<T> &io, int D, int Dc, hipStream_t s)
-{
-    // MEASURED, OFF by default (RAHT_CHAIN=1 switches it on): parity-green, but the fused cfg3 forward takes 0.339 ms chained
-    // against 0.304 ms with one launch per stage -- every tile's agent-scope release is a write-back of its XCD's L2 (the survivor
-    // rows must be visible to a parent that may run on another XCD), 705 of them cost more than the one launch (4.6 us) and the
-    // ~6 us of stage-2 work they hide. (With the fence in every thread: 0.50 ms.)
-    static const bool chain_on = getenv("RAHT_CHAIN") && atoi(getenv("RAHT_CHAIN")) != 0;
-    const int K = (int)sc.stages.size();
-    int k1 = K - 1;
-    while (k1 >= 1 && sc.stages[(size_t)k1].is_top) --k1;          // last tile stage
-    int r1 = 0, dc1 = 0, rf = 0;
-    pick_tail_geometry(p, (int)sizeof(T), D, sc.tile_rows, &r1, &dc1, &rf);
-    const bool chain = chain_on && k1 >= 2 && k1 <= CHAIN_MAX && dc1 >= D && !p->row_map;
-    for (int k = 0; k < K; ++k) {
-        if (chain && k == 1) {
-            RAHT_RET((launch_tile_chain<T, QM>(p, sc, 1, k1, io, D, Dc, s)));
-            k = k1;
-            continue;
-        }
-        RAHT_RET((launch_tile_stage<T, false, QM>(p, sc, k, io, D, Dc, s)));
-    }
-    return RAHT_OK;
+        return G.one ? launch_tile_one<T, INV, true, QM, 1>(A, io, grid, G.lds, s)
+                     : launch_tile_one<T, INV, true, QM, 2>(A, io, grid, G.lds, s);
+    return G.one ? launch_tile_one<T, INV, false, QM, 1>(A, io, grid, G.lds, s)
+                 : launch_tile_one<T, INV, false, QM, 2>(A, io, grid, G.lds, s);
 }
 
 // the same tile stage of m <= TILE_BATCH_MAX scenes (equal launch shape) in one launch, one tile per workgroup
@@ -1581,10 +1370,10 @@ static int launch_tile_batch(int m, const TileArgs<T> *As, const TileGeom *Gs, c
     const TileGeom &G = Gs[0];
     const dim3 grid(tot, G.nchunks);
     if (G.ident)
-        return G.one ? launch_tile_batch_one<T, INV, true, QM, 1>(B, io, grid, G.threads, G.lds, s)
-                     : launch_tile_batch_one<T, INV, true, QM, 2>(B, io, grid, G.threads, G.lds, s);
-    return G.one ? launch_tile_batch_one<T, INV, false, QM, 1>(B, io, grid, G.threads, G.lds, s)
-                 : launch_tile_batch_one<T, INV, false, QM, 2>(B, io, grid, G.threads, G.lds, s);
+        return G.one ? launch_tile_batch_one<T, INV, true, QM, 1>(B, io, grid, G.lds, s)
+                     : launch_tile_batch_one<T, INV, true, QM, 2>(B, io, grid, G.lds, s);
+    return G.one ? launch_tile_batch_one<T, INV, false, QM, 1>(B, io, grid, G.lds, s)
+                 : launch_tile_batch_one<T, INV, false, QM, 2>(B, io, grid, G.lds, s);
 }
 
 template <typename T>
@@ -1679,11 +1468,7 @@ static int run_transform(const raht_plan *cp, const T *src, int64_t ld_src, int 
         XformIO<T> io;
         io.src = src; io.ld_src = ld_src; io.dst = dst; io.ld_dst = ld_dst;
         const int K = (int)sc->stages.size();
-        if constexpr (!INV) {
-            rc = launch_forward_stages<T, false>(p, *sc, io, D, Dc, s);
-        } else {
-            for (int q = 0; q < K && rc == RAHT_OK; ++q) rc = launch_tile_stage<T, INV, false>(p, *sc, K - 1 - q, io, D, Dc, s);
-        }
+        for (int q = 0; q < K && rc == RAHT_OK; ++q) rc = launch_tile_stage<T, INV, false>(p, *sc, INV ? K - 1 - q : q, io, D, Dc, s);
     }
     if (rc == RAHT_OK && w && p->row_map) { set_error("node weights are not available from a row-mapped plan"); return RAHT_ERR_UNSUPPORTED; }
     if (rc == RAHT_OK && w) {
@@ -1739,7 +1524,9 @@ static int fwd_quant_impl(const raht_plan *cp, const T *C, int64_t ldc, int D, c
     }
     XformIO<T> io;
     io.src = C; io.ld_src = ldc; io.Q = Q; io.ldq = ldq; io.steps = steps; io.n_steps = n_steps;
-    return launch_forward_stages<T, true>(p, *sc, io, D, Dc, s);
+    const int K = (int)sc->stages.size();
+    for (int k = 0; k < K; ++k) RAHT_RET((launch_tile_stage<T, false, true>(p, *sc, k, io, D, Dc, s)));
+    return RAHT_OK;
 }
 
 /* Fused un-reorder + dequantize + inverse RAHT (encode_3dgs.py:261,267-268,274 in one pass). */
@@ -1817,17 +1604,17 @@ static int fwd_quant_multi_impl(const raht_plan *cp, const float *C, int64_t ldc
                 TileArgs<float> A;
                 TileGeom G;
                 RAHT_RET((prepare_tile_stage<float, false, true>(p, *sc, kk, io, D, Dc, 0, A, G)));
-                const dim3 grid(G.grid_x, G.nchunks);
+                const dim3 grid((unsigned)G.n_tiles, G.nchunks);
                 static PerDeviceOnce a11, a12, a01, a02;
                 if (kk == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
                 if (G.ident && G.one) { if (a11.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                                        hipLaunchKernelGGL((tile_kernel_multi<true, 1>), grid, dim3(G.threads), G.lds, s, A, st, M); }
+                                        hipLaunchKernelGGL((tile_kernel_multi<true, 1>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
                 else if (G.ident) { if (a12.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                                    hipLaunchKernelGGL((tile_kernel_multi<true, 2>), grid, dim3(G.threads), G.lds, s, A, st, M); }
+                                    hipLaunchKernelGGL((tile_kernel_multi<true, 2>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
                 else if (G.one) { if (a01.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                                  hipLaunchKernelGGL((tile_kernel_multi<false, 1>), grid, dim3(G.threads), G.lds, s, A, st, M); }
+                                  hipLaunchKernelGGL((tile_kernel_multi<false, 1>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
                 else { if (a02.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                       hipLaunchKernelGGL((tile_kernel_multi<false, 2>), grid, dim3(G.threads), G.lds, s, A, st, M); }
+                       hipLaunchKernelGGL((tile_kernel_multi<false, 2>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
                 if (kk == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
             }
             RAHT_HIP_CHECK(hipGetLastError());
@@ -1877,7 +1664,7 @@ static int dequant_inv_sqdiff_impl(const raht_plan *cp, const int32_t *Q, int64_
     if (!part.ok()) return RAHT_ERR_NOMEM;
     A.out = Crec; A.ld_out = Crec ? ldc : 0;
     A.ref = Cref; A.ld_ref = ldref; A.sq_part = part.as<double>();
-    if (G.nchunks != 1 || !G.ident || G.grid_x != (unsigned)G.n_tiles || (size_t)G.threads / 64 * (size_t)ncv * 8 > G.lds) {
+    if (G.nchunks != 1 || !G.ident || (size_t)(TILE_THREADS / 64) * (size_t)ncv * 8 > G.lds) {
         set_error("raht_dequant_inv_sqdiff: unexpected stage-0 geometry");
         return RAHT_ERR_INVALID;
     }
@@ -1887,10 +1674,10 @@ static int dequant_inv_sqdiff_impl(const raht_plan *cp, const int32_t *Q, int64_
     if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
     if (G.one) {
         if (attr1.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_sq<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((tile_kernel_sq<1>), dim3(G.grid_x), dim3(G.threads), G.lds, s, A, st);
+        hipLaunchKernelGGL((tile_kernel_sq<1>), dim3((unsigned)G.n_tiles), dim3(TILE_THREADS), G.lds, s, A, st);
     } else {
         if (attr2.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_sq<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((tile_kernel_sq<2>), dim3(G.grid_x), dim3(G.threads), G.lds, s, A, st);
+        hipLaunchKernelGGL((tile_kernel_sq<2>), dim3((unsigned)G.n_tiles), dim3(TILE_THREADS), G.lds, s, A, st);
     }
     if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
     hipLaunchKernelGGL(sq_final_kernel, dim3((unsigned)D), dim3(256), 0, s, part.as<double>(), G.n_tiles, D, ncv, sq);

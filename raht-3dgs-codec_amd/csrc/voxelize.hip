@@ -562,7 +562,7 @@ static int voxelize_impl(const float *PC, int64_t ldpc, int64_t N, int d, const 
                          int J, uint64_t *keys_sorted, int64_t *sort_idx, int64_t *voxel_indices, float *PCvox,
                          int64_t *Vvox, int64_t *n_vox, float vmin_out[3], double *width_out,
                          double *voxel_size_out, raht_stream_t stream, uint64_t *voxel_keys,
-                         float *PCsorted = nullptr, float *DeltaPC = nullptr, hipEvent_t keys_ready = nullptr,
+                         float *PCsorted = nullptr, float *DeltaPC = nullptr,
                          float *merge_means = nullptr, int merge = 0 /* 1: weight = opacity, 2: weight = 1 */)
 {
     if (!PC || N < 1 || d < 0 || ldpc < 3 + d || J < 1 || J > 21 || !n_vox) { set_error("raht_voxelize: bad argument"); return RAHT_ERR_INVALID; }
@@ -617,16 +617,6 @@ static int voxelize_impl(const float *PC, int64_t ldpc, int64_t N, int d, const 
         for (int attempt = 0; attempt < 2; ++attempt) {
             RAHT_RET(sort_keys_u32idx(keys, N, 3 * J, ks, idx, s, sort_err, sort_idx, &G, attempt == 0));
             RAHT_RET(run_starts_u64(ks, N, vstart, voxel_indices, voxel_keys, nv_dev, s));
-            if (keys_ready) {
-                // raht_voxelize_plan: the voxel count comes back NOW, and the event marks the voxel keys as complete -- the plan is
-                // then built from them on a second stream while this one forms the means (the read-back at the end is skipped)
-                RAHT_HIP_CHECK(hipGetLastError());
-                uint32_t back[2] = {0, 0};
-                RAHT_RET(read_back_u32(back, sort_err, 2, nullptr, nullptr, 0, s));
-                nv = back[1];
-                if (back[0]) { g_sort_fallbacks.fetch_add(1, std::memory_order_relaxed); continue; }
-                RAHT_HIP_CHECK(hipEventRecord(keys_ready, s));
-            }
             if (PCvox || Vvox || want_res) {
                 const unsigned gv = (unsigned)std::min<int64_t>(ceil_div(N, 64), 8192);        // (N >= the voxel count)
                 if (merge) {
@@ -643,7 +633,6 @@ static int voxelize_impl(const float *PC, int64_t ldpc, int64_t N, int d, const 
                 }
             }
             RAHT_HIP_CHECK(hipGetLastError());
-            if (keys_ready) break;
             uint32_t back[2] = {0, 0};                       // { sort error, voxel count }: adjacent device words
             RAHT_RET(read_back_u32(back, sort_err, 2, nullptr, nullptr, 0, s));
             nv = back[1];
@@ -680,7 +669,7 @@ int raht_voxelize_merge(const float *G, int64_t ldg, int64_t N, int color_dim, i
 {
     if (color_dim < 0 || !Gvox) { set_error("raht_voxelize_merge: bad argument"); return RAHT_ERR_INVALID; }
     return voxelize_impl(G, ldg, N, 8 + color_dim, vmin_in, width_in, J, keys_sorted, sort_idx, voxel_indices, Gvox, nullptr, n_vox, vmin_out, width_out,
-                         voxel_size_out, stream, nullptr, nullptr, nullptr, nullptr, merged_means, weight_by_opacity ? 1 : 2);
+                         voxel_size_out, stream, nullptr, nullptr, nullptr, merged_means, weight_by_opacity ? 1 : 2);
 }
 
 int raht_voxelize_all(const float *PC, int64_t ldpc, int64_t N, int d, const float *vmin_in, double width_in,
@@ -700,34 +689,12 @@ int raht_voxelize_plan(const float *PC, int64_t ldpc, int64_t N, int d, const fl
     if (!voxel_keys || !plan) { set_error("raht_voxelize_plan: NULL argument"); return RAHT_ERR_INVALID; }
     *plan = nullptr;
     int64_t nv = 0;
-    // The plan needs the voxels' sorted keys only, the per-voxel means (the HBM-bound half of the voxelizer: a gather of every
-    // point's row) need the plan not at all: the voxelizer reads the voxel count back as soon as the keys are there, enqueues the
-    // mean kernel on the caller's stream and returns; the plan is built on a side stream meanwhile (a chain of small,
-    // latency-bound launches with a host round trip of its own); the caller's stream then waits for it.
-    // MEASURED, OFF by default (RAHT_VOXPLAN_OVERLAP=1 switches it on): 0.847 ms per cfg3 frame against 0.825 ms on one stream --
-    // next to a kernel that keeps every CU busy the plan's dozen small launches get their workgroup slots late and stretch from
-    // 0.2 to ~0.35 ms, which is the mean kernel's own length: nothing is hidden.
-    static const bool serial = !(getenv("RAHT_VOXPLAN_OVERLAP") && atoi(getenv("RAHT_VOXPLAN_OVERLAP")) != 0);
-    static hipStream_t side[RAHT_MAX_DEVICES] = {};
-    static hipEvent_t ev_keys[RAHT_MAX_DEVICES] = {}, ev_plan[RAHT_MAX_DEVICES] = {};
-    const int dev = current_device();
-    hipStream_t s = (hipStream_t)stream;
-    if (!serial && !side[dev]) {
-        RAHT_HIP_CHECK(hipStreamCreateWithFlags(&side[dev], hipStreamNonBlocking));
-        RAHT_HIP_CHECK(hipEventCreateWithFlags(&ev_keys[dev], hipEventDisableTiming));
-        RAHT_HIP_CHECK(hipEventCreateWithFlags(&ev_plan[dev], hipEventDisableTiming));
-    }
     RAHT_RET(voxelize_impl(PC, ldpc, N, d, vmin_in, width_in, J, nullptr, nullptr, voxel_indices, PCvox, nullptr, &nv, vmin_out,
-                           width_out, voxel_size_out, stream, voxel_keys, nullptr, nullptr, serial ? nullptr : ev_keys[dev]));
+                           width_out, voxel_size_out, stream, voxel_keys));
     if (n_vox) *n_vox = nv;
     // the voxels' keys are sorted and unique by construction; the plan build checks them anyway (it reads them to find the
     // levels) and BORROWS the caller's array
-    if (serial) return raht_plan_create_from_keys_borrowed(voxel_keys, nv, 3 * J, nullptr, stream, plan);
-    RAHT_HIP_CHECK(hipStreamWaitEvent(side[dev], ev_keys[dev], 0));
-    const int rc = raht_plan_create_from_keys_borrowed(voxel_keys, nv, 3 * J, nullptr, (raht_stream_t)side[dev], plan);
-    RAHT_HIP_CHECK(hipEventRecord(ev_plan[dev], side[dev]));
-    RAHT_HIP_CHECK(hipStreamWaitEvent(s, ev_plan[dev], 0));     // (also after a failed build: whatever it enqueued is ordered before the caller's next work)
-    return rc;
+    return raht_plan_create_from_keys_borrowed(voxel_keys, nv, 3 * J, nullptr, stream, plan);
 }
 
 }  // extern "C"
