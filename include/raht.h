@@ -308,6 +308,36 @@ int raht_fwd_quant_batch(int n, raht_plan *const *plans, const float *const *C, 
 int raht_dequant_inv_batch(int n, raht_plan *const *plans, const int32_t *const *Q, const int64_t *ldq, int D,
                            const float *steps, int n_steps, float *const *C, const int64_t *ldc, raht_stream_t stream);
 
+/* The same for the MIXED-PRECISION fused entries (59-column frames: the xyz columns in float64, above): scene i's output is
+ * BIT-IDENTICAL to raht_fwd_quant_mixed(plans[i], C[i], ldc[i], D, steps, n_steps, n_wide, Q[i], ldq[i], stream), resp.
+ * raht_dequant_inv_mixed(plans[i], Q[i], ldq[i], D, steps, n_steps, n_wide, C[i], ldc[i], stream)
+ * (tests/test_gpu_mixed_batch.py). What is batched: round r of the forward carries stage r of every scene that has one (the
+ * inverse walks the rounds backwards from the deepest schedule); within a round the tile stages of equal launch shape go out
+ * up to 8 scenes per launch and the top stages likewise (blockIdx.y = scene); a group of one is the single call's own launch.
+ * What runs through raht_fwd_quant_mixed / raht_dequant_inv_mixed inside the same call, in place in the stream and with the
+ * same results: scenes whose shape takes the two-pass path (raht_plan_mixed_stats(...) tile_rows == 0: level engine,
+ * D - n_wide < 4, D > 68, a row stride > 2^18), plans with root buffers (truncated plans, the shard-local half of a sharded
+ * step) and plans with stage-0 events set (raht_plan_set_stage0_events). What is refused: row-mapped plans
+ * (RAHT_ERR_UNSUPPORTED, as in the single calls), and with RAHT_ERR_INVALID every breach of the single calls' argument rules
+ * for any scene (n_wide 1..4 and <= D, n_steps 1 or D, steps > 0 also as float32, row strides >= D, both root buffers or
+ * neither) or of the batch rules above (n >= 1, HOST arrays of pointers / strides all set, distinct plans on the current
+ * device). The rules that need no plan are checked first, before any plan is dereferenced and before any HIP call; nothing is
+ * launched for any scene unless every scene passed. raht_last_error() names the function and, where it applies, the scene.
+ * Under raht_plan_set_concurrent_directions the forward batch is a forward-direction call and the inverse batch an
+ * inverse-direction call of every plan in it. */
+int raht_fwd_quant_mixed_batch(int n, raht_plan *const *plans, const float *const *C, const int64_t *ldc, int D,
+                               const double *steps, int n_steps, int n_wide,
+                               int32_t *const *Q, const int64_t *ldq, raht_stream_t stream);
+int raht_dequant_inv_mixed_batch(int n, raht_plan *const *plans, const int32_t *const *Q, const int64_t *ldq, int D,
+                                 const double *steps, int n_steps, int n_wide,
+                                 float *const *C, const int64_t *ldc, raht_stream_t stream);
+/* Dry run of the grouping those two calls perform (the same function, told to count instead of launching): the number of
+ * batched or single-stage tile launches, of top-stage launches and of scenes that would run through the single-scene call, for
+ * contiguous rows (row stride D) and the plans' present root buffers / events (a truncated plan counts as a single-scene call).
+ * May build schedules and tile programs, as raht_plan_mixed_stats does; launches no transform kernel. */
+int raht_mixed_batch_stats(int n, raht_plan *const *plans, int D, int n_wide, int inverse,
+                           int *tile_launches, int *top_launches, int *single_scene_calls);
+
 /* Pre-build the tile schedule and the per-stage workspaces for (elem_size in {4, 8}, D). The
  * first transform with a new (element type, D) does this implicitly (allocating and synchronising
  * once); after raht_plan_prepare the transform entry points only enqueue kernels (hipGraph-safe).

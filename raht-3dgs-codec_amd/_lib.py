@@ -28,6 +28,7 @@ EXPORTS = [
     "raht_fwd_quant_mixed", "raht_dequant_inv_mixed", "raht_dequant_inv_sqdiff", "raht_fwd_quant_multi", "raht_plan_mixed_stats",
     "raht_fwd_quant_mixed_multi", "raht_dequant_inv_mixed_sqdiff",
     "raht_fwd_batch", "raht_inv_batch", "raht_fwd_quant_batch", "raht_dequant_inv_batch",
+    "raht_fwd_quant_mixed_batch", "raht_dequant_inv_mixed_batch", "raht_mixed_batch_stats",
     "raht_rlgr_bound", "raht_rlgr_encode", "raht_rlgr_decode", "raht_rlgr_encode_channels", "raht_rlgr_decode_channels", "raht_transpose_i32", "raht_i32_equal", "raht_sqdiff_columns", "raht_merge_clusters", "raht_voxelize_merge", "raht_rlgr_seg_encode", "raht_rlgr_seg_decode", "raht_rlgr_seg_encode_strided", "raht_rlgr_seg_decode_strided", "raht_rlgr_seg_encode_batch", "raht_rlgr_seg_decode_batch", "raht_rlgr_seg_decode_batch_check", "raht_debug_rlgr_decode_out", "raht_debug_rlgr_encode_out",
     "raht_xchg_bytes", "raht_xchg_alloc", "raht_xchg_open", "raht_xchg_close", "raht_xchg_free", "raht_xchg_gather", "raht_xchg_buffer", "raht_xchg_status",
 ]
@@ -110,6 +111,9 @@ def lib():
     L.raht_inv_batch.argtypes = [i32, pp, pp, pi64, i32, pp, pi64, vp]
     L.raht_fwd_quant_batch.argtypes = [i32, pp, pp, pi64, i32, C.POINTER(C.c_float), i32, pp, pi64, vp]
     L.raht_dequant_inv_batch.argtypes = [i32, pp, pp, pi64, i32, C.POINTER(C.c_float), i32, pp, pi64, vp]
+    L.raht_fwd_quant_mixed_batch.argtypes = [i32, pp, pp, pi64, i32, C.POINTER(dbl), i32, i32, pp, pi64, vp]
+    L.raht_dequant_inv_mixed_batch.argtypes = [i32, pp, pp, pi64, i32, C.POINTER(dbl), i32, i32, pp, pi64, vp]
+    L.raht_mixed_batch_stats.argtypes = [i32, pp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.raht_plan_set_max_stages.argtypes = [vp, i32]
     L.raht_plan_set_concurrent_directions.argtypes = [vp, i32]
     L.raht_plan_set_row_map.argtypes = [vp, vp, i64, vp]

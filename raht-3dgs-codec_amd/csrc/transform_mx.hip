@@ -27,7 +27,9 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
+#include <vector>
 
 namespace raht {
 
@@ -694,6 +696,28 @@ __global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_sq(const TileArg
     tile_body_mx<true, true, SLOTS, false, false, true>(A, P, ST, (int64_t)blockIdx.x);
 }
 
+// Several scenes, one launch (raht_fwd_quant_mixed_batch / raht_dequant_inv_mixed_batch): the same stage of up to MX_BATCH_MAX
+// scenes, as tile_kernel_batch does for the float32 engine (transform.hip). first_tile[q] = number of tiles of the scenes before q;
+// a workgroup finds its scene with scalar compares on blockIdx.x and runs ONE tile of it through tile_body_mx, reading that
+// scene's arguments where they lie in the kernarg segment (a scalar offset, no private copy of the struct).
+constexpr int MX_BATCH_MAX = 8;
+struct TileBatchMX {
+    TileArgs<float> a[MX_BATCH_MAX];
+    MxPtrs p[MX_BATCH_MAX];
+    uint32_t first_tile[MX_BATCH_MAX + 1];
+    int n;
+};
+static_assert(sizeof(TileBatchMX) + sizeof(StepTableMX) <= 4096, "tile_kernel_mx_batch: arguments exceed the 4 KB kernarg segment");
+
+template <bool INV, bool IDENT, int SLOTS>
+__global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_batch(const TileBatchMX B, const StepTableMX ST)
+{
+    int s = 0;
+#pragma unroll
+    for (int q = 1; q < MX_BATCH_MAX; ++q) s += (q < B.n && blockIdx.x >= B.first_tile[q]) ? 1 : 0;
+    tile_body_mx<INV, IDENT, SLOTS, false>(B.a[s], B.p[s], ST, (int64_t)(blockIdx.x - B.first_tile[s]));
+}
+
 // ------------------------------------------------------------------------------------------------
 // TOP stage, mixed: one workgroup per chunk place keeps that place of ALL entries in LDS (transform.hip: top_kernel);
 // workgroups [0, NW2) run the float64 instantiation on the wide places, the others the float32 one.
@@ -934,6 +958,19 @@ __global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_roots(const TopA
     else top_body_mx<false, INV, true>(A, ST, (int)blockIdx.x - NW2);
 }
 
+// the top stages of several scenes in one launch (the mixed batch entries): blockIdx.y = scene, blockIdx.x = chunk place
+struct TopBatchMX { TopArgsMX a[MX_BATCH_MAX]; };
+static_assert(sizeof(TopBatchMX) + sizeof(StepTableMX) <= 4096, "top_kernel_mx_batch: arguments exceed the 4 KB kernarg segment");
+
+template <bool INV>
+__global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_batch(const TopBatchMX B, const StepTableMX ST)
+{
+    const TopArgsMX &A = B.a[blockIdx.y];
+    const int NW2 = (A.nwide + 1) >> 1;
+    if ((int)blockIdx.x < NW2) top_body_mx<true, INV, false>(A, ST, (int)blockIdx.x);
+    else top_body_mx<false, INV, false>(A, ST, (int)blockIdx.x - NW2);
+}
+
 // raht_fwd_quant_mixed_multi (plans without root buffers)
 __global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_multi(const TopArgsMX A, const StepTableMX ST, const MxMultiQ M)
 {
@@ -1047,9 +1084,19 @@ struct MxIO {
     double *sq_part = nullptr;                             // ... and the per-tile partial sums (C_out may then be NULL)
 };
 
+// What one (scene, stage, direction) launches: the kernel arguments, filled and validated by prepare_stage_mx, and the launch
+// shape. The single-scene calls launch it as it is (launch_prepared_mx); the batch entries collect stages of equal shape into one
+// launch (run_batch_mx).
+struct MxStageLaunch {
+    bool is_top = false;
+    TopArgsMX T;                                           // top stage
+    TileArgs<float> A; MxPtrs P;                           // tile stage
+    unsigned n_tiles = 0;
+    size_t lds = 0;
+};
+
 template <bool INV>
-static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const MxIO &io, int D, const MxGeom &g,
-                           const StepTableMX &stp, hipStream_t s)
+static int prepare_stage_mx(const raht_plan *p, const Schedule &sc, int k, const MxIO &io, int D, const MxGeom &g, MxStageLaunch &L)
 {
     const Stage &st = sc.stages[(size_t)k];
     const int K = (int)sc.stages.size();
@@ -1059,8 +1106,9 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
     double *ws_k_w = ws_k ? (double *)(ws_k + (size_t)st.n_entries * g.Dp) : nullptr;
     double *ws_n_w = ws_n ? (double *)(ws_n + (size_t)sc.stages[(size_t)k + 1].n_entries * g.Dp) : nullptr;
     if (k >= 1 && !ws_k) { set_error("mixed stage %d: missing stage workspace", k); return RAHT_ERR_INVALID; }
+    L.is_top = st.is_top;
     if (st.is_top) {
-        TopArgsMX A;
+        TopArgsMX &A = L.T;
         A.in_rows = nullptr; A.ld_in = 0; A.in_img = nullptr; A.in_img_w = nullptr;
         A.out_rows = nullptr; A.ld_out = 0; A.out_img = nullptr; A.out_img_w = nullptr;
         if (!INV) { if (k == 0) { A.in_rows = io.C_in; A.ld_in = io.ldc; } else { A.in_img = ws_k; A.in_img_w = ws_k_w; } }
@@ -1073,26 +1121,13 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
         A.n = (int)st.n_entries; A.n_merges = (int)st.n_merges; A.D = D; A.nwide = g.nwide; A.Fp = g.Dp;
         A.lev = st.t_lev; A.nlev = st.t_nlev; A.nbig = st.t_nbig; A.small_start = st.t_small_start;
         if (!A.e_pos || !A.pj || !A.ab32 || !A.ab64 || !A.lev || !A.Q || (A.root_f && !A.root_rank)) { set_error("mixed top stage: missing plan arrays"); return RAHT_ERR_INVALID; }
+        if (!INV && io.multi && A.root_f) { set_error("mixed multi top stage: root buffers"); return RAHT_ERR_INVALID; }
         const size_t n_small = st.n_merges - st.t_small_start;
-        const size_t lds = (size_t)st.n_entries * 16 + ((n_small + 3) & ~(size_t)3) * 4 + n_small * 2 * sizeof(double);
-        static PerDeviceOnce attr;
-        if (attr.first(current_device())) {
-            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_roots<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        }
-        if (!INV && io.multi) {
-            static PerDeviceOnce attr_m;
-            if (attr_m.first(current_device()))
-                RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            if (A.root_f) { set_error("mixed multi top stage: root buffers"); return RAHT_ERR_INVALID; }
-            hipLaunchKernelGGL(top_kernel_mx_multi, dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp, *io.multi);
-        }
-        else if (A.root_f) hipLaunchKernelGGL((top_kernel_mx_roots<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
-        else hipLaunchKernelGGL((top_kernel_mx<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
-        RAHT_HIP_CHECK(hipGetLastError());
+        L.lds = (size_t)st.n_entries * 16 + ((n_small + 3) & ~(size_t)3) * 4 + n_small * 2 * sizeof(double);
+        L.n_tiles = 0;
         return RAHT_OK;
     }
-    TileArgs<float> A;
+    TileArgs<float> &A = L.A;
     A.rows = st.rows; A.surv_off = st.surv_off; A.n_entries = st.n_entries; A.N = p->N; A.R = st.tile_rows;
     A.D = D; A.Dc = D; A.Dp = g.Dp; A.lg = g.lg; A.nwide = g.nwide;
     A.last_stage = (k == K - 1) ? 1 : 0;
@@ -1121,15 +1156,50 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
                  (int64_t)st.tile_rows * std::max<int64_t>(io.ldc, g.Dp) * 4 >= ((int64_t)1 << 31)) bad = "tile geometry (32-bit row offsets)";
         if (bad) { set_error("mixed tile stage %d (%s): missing %s", k, INV ? "inverse" : "forward", bad); return RAHT_ERR_INVALID; }
     }
-    MxPtrs P;
+    MxPtrs &P = L.P;
     P.in_w = (!INV && k >= 1) ? ws_k_w : nullptr;
     P.out_w = (INV && k >= 1) ? ws_k_w : nullptr;
     P.wsn_w = ws_n_w;
     P.root_w = A.last_stage ? p->root_buf_w : nullptr;
     P.prog = st.prog; P.prog_stride = st.prog_stride; P.prog_ab = st.prog_ab; P.prog_compact = st.prog_compact ? 1 : 0;
     if (!P.prog) { set_error("mixed tile stage %d: missing tile programs", k); return RAHT_ERR_INVALID; }
-    const size_t lds = tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide);
-    const unsigned nt = (unsigned)st.n_tiles;
+    L.lds = tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide);
+    L.n_tiles = (unsigned)st.n_tiles;
+    if (INV && k == 0 && io.sq_part) {                     // the comparing stage 0 (raht_dequant_inv_mixed_sqdiff)
+        A.out = io.C_out; A.ld_out = io.C_out ? io.ldc : 0;
+        A.ref = io.ref; A.ld_ref = io.ld_ref; A.sq_part = io.sq_part;
+    }
+    return RAHT_OK;
+}
+
+// one prepared stage of ONE scene: the launch of the single-scene calls
+template <bool INV>
+static int launch_prepared_mx(const raht_plan *p, int k, const MxIO &io, const MxStageLaunch &L, const MxGeom &g,
+                              const StepTableMX &stp, hipStream_t s)
+{
+    if (L.is_top) {
+        const TopArgsMX &A = L.T;
+        const size_t lds = L.lds;
+        static PerDeviceOnce attr;
+        if (attr.first(current_device())) {
+            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_roots<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+        }
+        if (!INV && io.multi) {
+            static PerDeviceOnce attr_m;
+            if (attr_m.first(current_device()))
+                RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+            hipLaunchKernelGGL(top_kernel_mx_multi, dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp, *io.multi);
+        }
+        else if (A.root_f) hipLaunchKernelGGL((top_kernel_mx_roots<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
+        else hipLaunchKernelGGL((top_kernel_mx<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
+        RAHT_HIP_CHECK(hipGetLastError());
+        return RAHT_OK;
+    }
+    const TileArgs<float> &A = L.A;
+    const MxPtrs &P = L.P;
+    const size_t lds = L.lds;
+    const unsigned nt = L.n_tiles;
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
     int rc;
     if constexpr (!INV) {
@@ -1141,8 +1211,6 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
         }
     } else {
         if (k == 0 && io.sq_part) {
-            A.out = io.C_out; A.ld_out = io.C_out ? io.ldc : 0;
-            A.ref = io.ref; A.ld_ref = io.ld_ref; A.sq_part = io.sq_part;
             rc = launch_tile_mx_slots<true, true, false, MX_SQ>(A, P, stp, nullptr, nt, lds, s);
             if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
             return rc;
@@ -1152,6 +1220,15 @@ static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const 
     else rc = A.root_buf ? launch_tile_mx_slots<INV, false, true, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s) : launch_tile_mx_slots<INV, false, false, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s);
     if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
     return rc;
+}
+
+template <bool INV>
+static int launch_stage_mx(const raht_plan *p, const Schedule &sc, int k, const MxIO &io, int D, const MxGeom &g,
+                           const StepTableMX &stp, hipStream_t s)
+{
+    MxStageLaunch L;
+    RAHT_RET((prepare_stage_mx<INV>(p, sc, k, io, D, g, L)));
+    return launch_prepared_mx<INV>(p, k, io, L, g, stp, s);
 }
 
 static int mx_check_args(const raht_plan *p, const void *a, const void *b, int D, int64_t lda, int64_t ldb, const double *steps,
@@ -1356,6 +1433,258 @@ static int dequant_inv_mixed_sqdiff_impl(const raht_plan *cp, const int32_t *Q, 
     return launch_sq_final(part.as<double>(), (int64_t)st0.n_tiles, D, ncv, sq, s);
 }
 
+// ---- several scenes, one set of launches (raht_fwd_quant_mixed_batch / raht_dequant_inv_mixed_batch) ---------------------------
+// Round r of the forward direction carries stage r of every scene that has one; the inverse walks the rounds backwards from the
+// deepest schedule. Within a round the tile stages of equal launch shape go out up to MX_BATCH_MAX scenes per launch
+// (tile_kernel_mx_batch), the top stages likewise (top_kernel_mx_batch, blockIdx.y = scene); a group of one is the single-scene
+// launch. Scenes the batch kernels do not cover run through the single-scene entry, in place in the stream.
+struct MxScene {
+    raht_plan *p = nullptr;
+    Schedule *sc = nullptr;                                // nullptr: the single-scene call
+    MxGeom g;
+    MxIO io;
+};
+struct MxBatchCounts { int tile = 0, top = 0, single = 0; };
+
+// the batch kernels cover: a mixed tile schedule, no root buffers (a truncated plan always has them here: mx_check_args), no
+// stage-0 events (they bracket ONE scene's stage-0 launch)
+static bool mx_batchable(const raht_plan *p, const Schedule *sc)
+{
+    return sc && !p->root_buf && !p->root_buf_w && p->top_level >= 64 && !p->ev_before;
+}
+
+// what makes two tile stages one launch: the kernel instantiation (IDENT, SLOTS), the LDS bytes and the row layout
+struct MxShape {
+    bool ident; int slots; size_t lds; int nwide, NCp, Dp, lg;
+    bool operator==(const MxShape &o) const
+    { return ident == o.ident && slots == o.slots && lds == o.lds && nwide == o.nwide && NCp == o.NCp && Dp == o.Dp && lg == o.lg; }
+};
+static MxShape mx_tile_shape(const Stage &st, int k, const MxGeom &g)
+{
+    return MxShape{k == 0, st.tile_rows <= MX_THREADS ? 1 : 2, tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide), g.nwide, g.NCp, g.Dp, g.lg};
+}
+
+// THE grouping of a batch: calls single(i) for every scene outside the batch kernels, then, round by round, tile(m, idx, k) /
+// top(m, idx, k) for every launch (stage k of the m scenes idx[0..m)), and counts what it called. The runner passes callbacks
+// that launch, raht_mixed_batch_stats callbacks that do nothing.
+template <bool INV, typename FS, typename FT, typename FP>
+static int group_batch_mx(int n, const MxScene *scn, MxBatchCounts &cnt, FS &&single, FT &&tile, FP &&top)
+{
+    int maxK = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!scn[i].sc) { ++cnt.single; RAHT_RET(single(i)); }
+        else maxK = std::max(maxK, (int)scn[i].sc->stages.size());
+    }
+    for (int r = 0; r < maxK; ++r) {
+        const int k = INV ? maxK - 1 - r : r;
+        int idx_tile[MX_BATCH_MAX], idx_top[MX_BATCH_MAX], n_tile = 0, n_top = 0;
+        MxShape shape{};
+        auto flush_tile = [&]() -> int {
+            if (n_tile == 0) return RAHT_OK;
+            const int m = n_tile;
+            n_tile = 0;
+            ++cnt.tile;
+            return tile(m, idx_tile, k);
+        };
+        auto flush_top = [&]() -> int {
+            if (n_top == 0) return RAHT_OK;
+            const int m = n_top;
+            n_top = 0;
+            ++cnt.top;
+            return top(m, idx_top, k);
+        };
+        for (int i = 0; i < n; ++i) {
+            const Schedule *sc = scn[i].sc;
+            if (!sc || k >= (int)sc->stages.size()) continue;
+            const Stage &st = sc->stages[(size_t)k];
+            if (st.is_top) {
+                if (n_top > 0 && !(scn[i].g.NCp == scn[idx_top[0]].g.NCp && scn[i].g.Dp == scn[idx_top[0]].g.Dp)) RAHT_RET(flush_top());
+                idx_top[n_top++] = i;
+                if (n_top == MX_BATCH_MAX) RAHT_RET(flush_top());
+            } else {
+                const MxShape sh = mx_tile_shape(st, k, scn[i].g);
+                if (n_tile > 0 && !(sh == shape)) RAHT_RET(flush_tile());          // another launch shape: its own launch
+                shape = sh;
+                idx_tile[n_tile++] = i;
+                if (n_tile == MX_BATCH_MAX) RAHT_RET(flush_tile());
+            }
+        }
+        RAHT_RET(flush_tile());
+        RAHT_RET(flush_top());
+    }
+    return RAHT_OK;
+}
+
+template <bool INV, bool IDENT, int SLOTS>
+static int launch_tile_batch_mx_one(const TileBatchMX &B, const StepTableMX &stp, unsigned n_tiles, size_t lds, hipStream_t s)
+{
+    static PerDeviceOnce attr;
+    if (attr.first(current_device()))
+        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx_batch<INV, IDENT, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((tile_kernel_mx_batch<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, B, stp);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+// the same tile stage of m <= MX_BATCH_MAX scenes (equal launch shape) in one launch, one tile per workgroup. (Tile counts: a
+// plan's rows are indexed with 32 bits and a tile holds >= 64 of them, so eight scenes stay far below 2^32 tiles.)
+template <bool INV>
+static int launch_tile_batch_mx(int m, const MxStageLaunch *const *Ls, bool ident, const StepTableMX &stp, hipStream_t s)
+{
+    TileBatchMX B;
+    B.n = m;
+    uint32_t tot = 0;
+    for (int i = 0; i < MX_BATCH_MAX; ++i) {
+        B.a[i] = Ls[i < m ? i : 0]->A;
+        B.p[i] = Ls[i < m ? i : 0]->P;
+        B.first_tile[i] = tot;
+        if (i < m) tot += Ls[i]->n_tiles;
+    }
+    B.first_tile[MX_BATCH_MAX] = tot;
+    const size_t lds = Ls[0]->lds;
+    const bool one = Ls[0]->A.R <= MX_THREADS;
+    if (ident) return one ? launch_tile_batch_mx_one<INV, true, 1>(B, stp, tot, lds, s) : launch_tile_batch_mx_one<INV, true, 2>(B, stp, tot, lds, s);
+    return one ? launch_tile_batch_mx_one<INV, false, 1>(B, stp, tot, lds, s) : launch_tile_batch_mx_one<INV, false, 2>(B, stp, tot, lds, s);
+}
+
+// the top stages of m scenes: one launch, blockIdx.y = scene; the dynamic LDS block is the largest scene's
+template <bool INV>
+static int launch_top_batch_mx(int m, const MxStageLaunch *const *Ls, int NCp, const StepTableMX &stp, hipStream_t s)
+{
+    TopBatchMX B;
+    size_t lds = 0;
+    for (int i = 0; i < MX_BATCH_MAX; ++i) B.a[i] = Ls[i < m ? i : 0]->T;
+    for (int i = 0; i < m; ++i) lds = std::max(lds, Ls[i]->lds);
+    static PerDeviceOnce attr;
+    if (attr.first(current_device()))
+        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_batch<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+    hipLaunchKernelGGL((top_kernel_mx_batch<INV>), dim3((unsigned)NCp, (unsigned)m), dim3(MX_TOP_THREADS), lds, s, B, stp);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+// Everything that can be judged from the arguments alone, before any plan is dereferenced and before any HIP call (a / b: the
+// input and output matrices of the direction)
+static int mx_batch_check_args(const char *what, int n, raht_plan *const *plans, const void *const *a, const int64_t *lda,
+                               const void *const *b, const int64_t *ldb, int D, const double *steps, int n_steps, int n_wide)
+{
+    if (n < 1 || !plans || !a || !lda || !b || !ldb || D < 1) { set_error("%s: bad argument (n >= 1, D >= 1, the arrays of plans, matrices and strides must be set)", what); return RAHT_ERR_INVALID; }
+    if (n_wide < 1 || n_wide > MX_MAX_WIDE || n_wide > D) { set_error("%s: n_wide must be 1..%d (and <= D)", what, MX_MAX_WIDE); return RAHT_ERR_INVALID; }
+    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("%s: n_steps must be 1 or D", what); return RAHT_ERR_INVALID; }
+    if (n_steps > MAX_STEP_CH) { set_error("%s: per-channel steps support D <= %d", what, MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
+    for (int c = 0; c < n_steps; ++c)
+        if (!(steps[c] > 0.0) || !((float)steps[c] > 0.0f)) { set_error("%s: step[%d] must be > 0 (also as float32)", what, c); return RAHT_ERR_INVALID; }
+    for (int i = 0; i < n; ++i) {
+        if (!plans[i]) { set_error("%s: NULL plan (scene %d)", what, i); return RAHT_ERR_INVALID; }
+        if (!a[i] || !b[i] || lda[i] < D || ldb[i] < D) { set_error("%s: bad matrix argument (scene %d: NULL pointer or row stride < D)", what, i); return RAHT_ERR_INVALID; }
+        for (int j = 0; j < i; ++j)
+            if (plans[j] == plans[i]) { set_error("%s: scenes %d and %d share a plan (a plan owns its workspaces)", what, j, i); return RAHT_ERR_INVALID; }
+    }
+    return RAHT_OK;
+}
+
+// the single calls' plan rules for scene i (device, row map, root buffers), the scene named in the error
+static int mx_batch_check_plan(const char *what, int i, const raht_plan *p, const void *a, const void *b, int D, int64_t lda, int64_t ldb,
+                               const double *steps, int n_steps, int n_wide)
+{
+    const int rc = mx_check_args(p, a, b, D, lda, ldb, steps, n_steps, n_wide, what);
+    if (rc != RAHT_OK) {
+        const std::string msg = raht_last_error();
+        set_error("%s (scene %d)", msg.c_str(), i);
+    }
+    return rc;
+}
+
+template <bool INV>
+static int run_batch_mx(const char *what, int n, raht_plan *const *plans, const MxIO *ios, int D, const double *steps, int n_steps,
+                        int n_wide, hipStream_t s)
+{
+    std::vector<MxScene> scn((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const MxIO &io = ios[i];
+        const void *a = INV ? (const void *)io.Q : (const void *)io.C_in, *b = INV ? (const void *)io.C_out : (const void *)io.Q;
+        RAHT_RET(mx_batch_check_plan(what, i, plans[i], a, b, D, INV ? io.ldq : io.ldc, INV ? io.ldc : io.ldq, steps, n_steps, n_wide));
+    }
+    // schedules, tile programs, workspaces; then the arguments of every (scene, stage): nothing is launched unless all are there
+    std::vector<size_t> first((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        MxScene &S = scn[(size_t)i];
+        S.p = plans[i]; S.io = ios[i];
+        Schedule *sc = nullptr;
+        RAHT_RET(mx_setup(S.p, D, n_wide, std::max(S.io.ldc, S.io.ldq), s, &sc, S.g));
+        S.sc = mx_batchable(S.p, sc) ? sc : nullptr;
+        first[(size_t)i + 1] = first[(size_t)i] + (S.sc ? S.sc->stages.size() : 0);
+    }
+    std::vector<MxStageLaunch> prep(first[(size_t)n]);
+    for (int i = 0; i < n; ++i) {
+        const MxScene &S = scn[(size_t)i];
+        if (!S.sc) continue;
+        for (int k = 0; k < (int)S.sc->stages.size(); ++k) {
+            const int rc = prepare_stage_mx<INV>(S.p, *S.sc, k, S.io, D, S.g, prep[first[(size_t)i] + (size_t)k]);
+            if (rc != RAHT_OK) {
+                const std::string msg = raht_last_error();
+                set_error("%s: %s (scene %d)", what, msg.c_str(), i);
+                return rc;
+            }
+        }
+    }
+    StepTableMX stp;
+    fill_steps_mx(stp, steps, n_steps, n_wide);
+    auto stage_of = [&](int i, int k) -> const MxStageLaunch & { return prep[first[(size_t)i] + (size_t)k]; };
+    auto single = [&](int i) -> int {
+        const MxIO &io = scn[(size_t)i].io;
+        if constexpr (INV) return dequant_inv_mixed_impl(scn[(size_t)i].p, io.Q, io.ldq, D, steps, n_steps, n_wide, io.C_out, io.ldc, (raht_stream_t)s);
+        else return fwd_quant_mixed_impl(scn[(size_t)i].p, io.C_in, io.ldc, D, steps, n_steps, n_wide, io.Q, io.ldq, (raht_stream_t)s);
+    };
+    auto tile = [&](int m, const int *idx, int k) -> int {
+        if (m == 1) return launch_prepared_mx<INV>(scn[(size_t)idx[0]].p, k, scn[(size_t)idx[0]].io, stage_of(idx[0], k), scn[(size_t)idx[0]].g, stp, s);
+        const MxStageLaunch *Ls[MX_BATCH_MAX];
+        for (int q = 0; q < m; ++q) Ls[q] = &stage_of(idx[q], k);
+        return launch_tile_batch_mx<INV>(m, Ls, k == 0, stp, s);
+    };
+    auto top = [&](int m, const int *idx, int k) -> int {
+        if (m == 1) return launch_prepared_mx<INV>(scn[(size_t)idx[0]].p, k, scn[(size_t)idx[0]].io, stage_of(idx[0], k), scn[(size_t)idx[0]].g, stp, s);
+        const MxStageLaunch *Ls[MX_BATCH_MAX];
+        for (int q = 0; q < m; ++q) Ls[q] = &stage_of(idx[q], k);
+        return launch_top_batch_mx<INV>(m, Ls, scn[(size_t)idx[0]].g.NCp, stp, s);
+    };
+    MxBatchCounts cnt;
+    return group_batch_mx<INV>(n, scn.data(), cnt, single, tile, top);
+}
+
+// the dry run of the grouping: schedules and tile programs may be built, no transform kernel is launched
+static int mixed_batch_stats_impl(int n, raht_plan *const *plans, int D, int n_wide, int inverse, int *tile_launches, int *top_launches,
+                                  int *single_scene_calls)
+{
+    const char *what = "raht_mixed_batch_stats";
+    if (n < 1 || !plans || !tile_launches || !top_launches || !single_scene_calls || D < 1 || n_wide < 1 || n_wide > MX_MAX_WIDE || n_wide > D) {
+        set_error("%s: bad argument", what);
+        return RAHT_ERR_INVALID;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!plans[i]) { set_error("%s: NULL plan (scene %d)", what, i); return RAHT_ERR_INVALID; }
+        for (int j = 0; j < i; ++j)
+            if (plans[j] == plans[i]) { set_error("%s: scenes %d and %d share a plan", what, j, i); return RAHT_ERR_INVALID; }
+    }
+    std::vector<MxScene> scn((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        MxScene &S = scn[(size_t)i];
+        S.p = plans[i];
+        RAHT_RET(check_plan_device(S.p, what));
+        if (S.p->row_map) { set_error("%s: not available for row-mapped plans (scene %d)", what, i); return RAHT_ERR_UNSUPPORTED; }
+        Schedule *sc = nullptr;
+        RAHT_RET(mx_setup(S.p, D, n_wide, D, nullptr, &sc, S.g));
+        S.sc = mx_batchable(S.p, sc) ? sc : nullptr;
+    }
+    MxBatchCounts cnt;
+    auto none1 = [](int) { return (int)RAHT_OK; };
+    auto none3 = [](int, const int *, int) { return (int)RAHT_OK; };
+    if (inverse) RAHT_RET((group_batch_mx<true>(n, scn.data(), cnt, none1, none3, none3)));
+    else RAHT_RET((group_batch_mx<false>(n, scn.data(), cnt, none1, none3, none3)));
+    *tile_launches = cnt.tile; *top_launches = cnt.top; *single_scene_calls = cnt.single;
+    return RAHT_OK;
+}
+
 }  // namespace raht
 
 using namespace raht;
@@ -1386,6 +1715,37 @@ int raht_dequant_inv_mixed_sqdiff(const raht_plan *plan, const int32_t *Q, int64
 {
     return guarded("raht_dequant_inv_mixed_sqdiff", [&]() {
         return dequant_inv_mixed_sqdiff_impl(plan, Q, ldq, D, steps, n_steps, n_wide, C_ref, ld_ref, C_rec, ldc, sqdiff, stream); });
+}
+
+int raht_fwd_quant_mixed_batch(int n, raht_plan *const *plans, const float *const *C, const int64_t *ldc, int D,
+                               const double *steps, int n_steps, int n_wide, int32_t *const *Q, const int64_t *ldq, raht_stream_t stream)
+{
+    const char *what = "raht_fwd_quant_mixed_batch";
+    return guarded(what, [&]() -> int {
+        RAHT_RET(mx_batch_check_args(what, n, plans, (const void *const *)C, ldc, (const void *const *)Q, ldq, D, steps, n_steps, n_wide));
+        std::vector<MxIO> ios((size_t)n);
+        for (int i = 0; i < n; ++i) { MxIO &io = ios[(size_t)i]; io.C_in = C[i]; io.ldc = ldc[i]; io.Q = Q[i]; io.ldq = ldq[i]; }
+        return run_batch_mx<false>(what, n, plans, ios.data(), D, steps, n_steps, n_wide, (hipStream_t)stream);
+    });
+}
+
+int raht_dequant_inv_mixed_batch(int n, raht_plan *const *plans, const int32_t *const *Q, const int64_t *ldq, int D,
+                                 const double *steps, int n_steps, int n_wide, float *const *C, const int64_t *ldc, raht_stream_t stream)
+{
+    const char *what = "raht_dequant_inv_mixed_batch";
+    return guarded(what, [&]() -> int {
+        RAHT_RET(mx_batch_check_args(what, n, plans, (const void *const *)Q, ldq, (const void *const *)C, ldc, D, steps, n_steps, n_wide));
+        std::vector<MxIO> ios((size_t)n);
+        for (int i = 0; i < n; ++i) { MxIO &io = ios[(size_t)i]; io.C_out = C[i]; io.ldc = ldc[i]; io.Q = const_cast<int32_t *>(Q[i]); io.ldq = ldq[i]; }
+        return run_batch_mx<true>(what, n, plans, ios.data(), D, steps, n_steps, n_wide, (hipStream_t)stream);
+    });
+}
+
+int raht_mixed_batch_stats(int n, raht_plan *const *plans, int D, int n_wide, int inverse, int *tile_launches, int *top_launches,
+                           int *single_scene_calls)
+{
+    return guarded("raht_mixed_batch_stats", [&]() {
+        return mixed_batch_stats_impl(n, plans, D, n_wide, inverse, tile_launches, top_launches, single_scene_calls); });
 }
 
 #ifdef RAHT_PHASE_CLOCKS

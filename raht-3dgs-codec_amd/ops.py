@@ -630,6 +630,75 @@ def dequant_inverse_batch(plans, Qs, steps):
     return outs
 
 
+class _batch_mixed_roots:
+    """the root buffers of every scene that brings some, set for the duration of a mixed batch call (one entry per scene, None
+    allowed) and reset afterwards, also when setting one of them or the call itself raises"""
+
+    def __init__(self, plans, roots, roots_wide, D, n_wide):
+        n = len(plans)
+        self.roots = [None] * n if roots is None else list(roots)
+        self.wide = [None] * n if roots_wide is None else list(roots_wide)
+        if len(self.roots) != n or len(self.wide) != n:
+            raise ValueError("batch: roots / roots_wide need one entry per plan (None allowed)")
+        self.plans, self.D, self.n_wide, self.touched = plans, D, n_wide, []
+
+    def __enter__(self):
+        try:
+            for p, r, w in zip(self.plans, self.roots, self.wide):
+                if r is not None or w is not None:
+                    self.touched.append(p)
+                p._set_mixed_roots(r, w, self.D, self.n_wide)
+        except Exception:
+            self.__exit__(None, None, None)
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.touched:
+            p._reset_mixed_roots()
+        self.touched = []
+        return False
+
+
+def forward_quant_mixed_batch(plans, Cs, steps, n_wide=3, roots=None, roots_wide=None):
+    """[Q_i] = ``plans[i].forward_quant_mixed(Cs[i], steps, n_wide)`` of every scene in one set of launches, bit for bit (the
+    frames of a 59-column sequence: the reference's xyz integers and the batch's shared tail launches at once). roots /
+    roots_wide: optional lists, one entry per scene (None allowed), with the meaning they have in ``forward_quant_mixed``; a
+    scene with root buffers (a truncated plan needs them) runs through the single-scene call inside."""
+    n, D, ms, hp, mp, ld = _batch_arrays(plans, Cs, torch.float32, "C")
+    st = _steps64(steps, D)
+    outs, op, old = _batch_out(plans, D, torch.int32, ms[0].device)
+    with _batch_mixed_roots(plans, roots, roots_wide, D, int(n_wide)):
+        with torch.cuda.device(ms[0].device):
+            check(_lib.lib().raht_fwd_quant_mixed_batch(n, hp, mp, ld, D, st, len(st), int(n_wide), op, old, _stream()))
+    return outs
+
+
+def dequant_inverse_mixed_batch(plans, Qs, steps, n_wide=3, roots=None, roots_wide=None):
+    """[C_i] = ``plans[i].dequant_inverse_mixed(Qs[i], steps, n_wide)`` of every scene in one set of launches, bit for bit
+    (counterpart of ``forward_quant_mixed_batch``; roots / roots_wide as there, read instead of written)."""
+    n, D, ms, hp, mp, ld = _batch_arrays(plans, Qs, torch.int32, "Q")
+    st = _steps64(steps, D)
+    outs, op, old = _batch_out(plans, D, torch.float32, ms[0].device)
+    with _batch_mixed_roots(plans, roots, roots_wide, D, int(n_wide)):
+        with torch.cuda.device(ms[0].device):
+            check(_lib.lib().raht_dequant_inv_mixed_batch(n, hp, mp, ld, D, st, len(st), int(n_wide), op, old, _stream()))
+    return outs
+
+
+def mixed_batch_stats(plans, D, n_wide, inverse=False):
+    """What a mixed batch of these plans launches (a dry run of the grouping; no transform kernel runs): tile launches, top-stage
+    launches, and scenes that run through the single-scene call (two-pass shapes, truncated plans, plans with stage-0 events)."""
+    n = len(plans)
+    if n < 1:
+        raise ValueError("batch: at least one plan")
+    hp = (C.c_void_p * n)(*[p._h for p in plans])
+    t, u, v = C.c_int(0), C.c_int(0), C.c_int(0)
+    with torch.cuda.device(plans[0].device):
+        check(_lib.lib().raht_mixed_batch_stats(n, hp, int(D), int(n_wide), 1 if inverse else 0, C.byref(t), C.byref(u), C.byref(v)))
+    return {"tile_launches": t.value, "top_launches": u.value, "single_scene_calls": v.value}
+
+
 def quant_rows(X, steps, pos, Q):
     """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place (X float32 (n, D), pos int64 (n,), Q int32). X and Q may be
     column slices of wider matrices (contiguous rows, any row stride)."""
