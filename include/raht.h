@@ -592,14 +592,40 @@ int raht_rlgr_seg_decode(const uint8_t *in, int64_t in_bytes, const uint32_t *se
  * two functions above) or ROW-MAJOR (chan_stride = 1, sym_stride = ld >= D: symbol n of channel c at Q[n * ld + c], i.e. Q exactly
  * as raht_fwd_quant leaves it and raht_dequant_inv takes it -- no raht_transpose_i32 in front of the encoder or behind the
  * decoder: the lanes of a wave are then neighbouring channels at the same position of their segments, so every step of the wave
- * reads / writes one contiguous piece of a row). Same segments, same container, byte for byte. The container is limited to 4 GiB
- * (32-bit segment offsets): inputs whose worst case could exceed it are refused (RAHT_ERR_INVALID). */
+ * reads / writes one contiguous piece of a row). Same segments, same container, byte for byte. With these 32-bit offset tables the
+ * container is limited to 4 GiB: inputs whose worst case could exceed it are refused (RAHT_ERR_INVALID) -- they go through
+ * raht_rlgr_seg_encode64 / raht_rlgr_seg_decode64 below; raht_rlgr_seg_offsets_width says which of the two a shape needs. */
 int raht_rlgr_seg_encode_strided(const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len,
                                  int flag_signed, uint32_t *seg_bytes, uint32_t *seg_off, uint8_t *out, int64_t cap,
                                  int64_t *total_bytes, raht_stream_t stream);
 int raht_rlgr_seg_decode_strided(const uint8_t *in, int64_t in_bytes, const uint32_t *seg_off, const uint32_t *seg_bytes, int64_t N,
                                  int D, int seg_len, int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride,
                                  uint32_t *bad_dev, raht_stream_t stream);
+
+/* Frames of any size: 64-BIT OFFSET TABLES. The 32-bit entry points above refuse every shape whose WORST case
+ * ((raht_rlgr_bound(seg_len) + 4) * D * nseg bytes: every symbol an escape) reaches 4 GiB -- at seg_len = 2048 that is
+ * N x D >= 330 M symbols, e.g. 6 M x 56 -- because their offsets and totals could wrap. The container on the wire never
+ * held offsets (a length per segment, uint32, and an int64 payload size), so only the device-side table changes width:
+ *   raht_rlgr_seg_offsets_width : HOST arithmetic, no device call. 32: the 32-bit entry points take (N, D, seg_len); 64: they
+ *                                 refuse it for its size and the *64 ones are needed; RAHT_ERR_INVALID: nobody takes it (N < 1,
+ *                                 D < 1, seg_len < 64, 2^31 segments or more, a seg_len whose worst-case segment does not fit
+ *                                 the uint32 length table). The one place the rule lives.
+ *   raht_rlgr_seg_encode64      : raht_rlgr_seg_encode_strided with seg_off: DEVICE uint64[D * nseg + 1]. Takes EVERY valid
+ *                                 shape, small ones too, and then writes the same seg_bytes and the same streams as the 32-bit
+ *                                 form, offsets equal as integers. *total_bytes and the size RAHT_ERR_NOMEM reports may be
+ *                                 4 GiB and more. Synchronises.
+ *   raht_rlgr_seg_decode64      : raht_rlgr_seg_decode_strided from such a table. An offset is checked against in_bytes as the
+ *                                 64-bit number it is (alignment, past the end, length past the end) before anything is
+ *                                 read: a bad entry decodes as zeros and sets *bad_dev. Does not synchronise.
+ * Everything else -- layouts, argument rules, one pass into slots + compaction with the two exact passes behind it -- is that
+ * of the 32-bit forms; lengths stay uint32. */
+int raht_rlgr_seg_offsets_width(int64_t N, int D, int seg_len);
+int raht_rlgr_seg_encode64(const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len,
+                           int flag_signed, uint32_t *seg_bytes, uint64_t *seg_off, uint8_t *out, int64_t cap,
+                           int64_t *total_bytes, raht_stream_t stream);
+int raht_rlgr_seg_decode64(const uint8_t *in, int64_t in_bytes, const uint64_t *seg_off, const uint32_t *seg_bytes, int64_t N,
+                           int D, int seg_len, int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride,
+                           uint32_t *bad_dev, raht_stream_t stream);
 
 /* k frames of ONE shape in one set of launches -- the quantization steps of a frame (python/encode_3dgs.py:199-275 codes them one
  * after the other; nothing connects them). One frame of 3 M x 56 symbols is 1.25 waves per SIMD of independent streams, and the
@@ -623,6 +649,18 @@ int raht_rlgr_seg_decode_batch_check(int k, const uint8_t *const *in, const int6
                                      const uint32_t *const *seg_bytes, int64_t N, int D, int seg_len, int flag_signed,
                                      int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride, int64_t chan_stride,
                                      uint32_t *bad_dev, raht_stream_t stream);
+
+/* The batch entry points with 64-bit offset tables (seg_off[j]: DEVICE uint64[D * nseg + 1]), for the shapes
+ * raht_rlgr_seg_offsets_width calls 64 and any other. raht_rlgr_seg_encode_batch64 = raht_rlgr_seg_encode_batch.
+ * raht_rlgr_seg_decode_batch64 is both decoders: expect == NULL decodes as raht_rlgr_seg_decode_batch does (either layout,
+ * bad_dev may be NULL); otherwise as raht_rlgr_seg_decode_batch_check (row-major frames, bad_dev required, no expect[j] NULL). */
+int raht_rlgr_seg_encode_batch64(int k, const int32_t *const *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride,
+                                 int seg_len, int flag_signed, uint32_t *const *seg_bytes, uint64_t *const *seg_off,
+                                 uint8_t *const *out, const int64_t *cap, int64_t *total_bytes, raht_stream_t stream);
+int raht_rlgr_seg_decode_batch64(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint64_t *const *seg_off,
+                                 const uint32_t *const *seg_bytes, int64_t N, int D, int seg_len, int flag_signed,
+                                 int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride, int64_t chan_stride,
+                                 uint32_t *bad_dev, raht_stream_t stream);
 
 /* How the decoders' symbols leave the lanes: -1 = chosen by the number of lanes in flight (default: one 4-byte store per symbol
  * below 200 000 lanes, where the L2 still gathers a lane's line; above, a 16-word LDS column per lane written out as aligned

@@ -130,6 +130,10 @@ void dev_free(void *p);
 // uint32*, may be NULL) receives the sum. Allocates its own small workspace (plan/voxelize time
 // only -- never called from the transform entry points).
 int exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *total, hipStream_t s);
+// The same with 64-bit sums: n uint32 values -> uint64 exclusive prefix sums; `total` (device uint64*, 8-byte aligned, may
+// be NULL) receives the sum. Not in place (the items are half as wide as the sums). The offset scan of an RLGR container
+// that may pass 4 GiB (rlgr_seg.hip).
+int exclusive_scan_u32_u64(const uint32_t *in, uint64_t *out, int64_t n, uint64_t *total, hipStream_t s);
 
 // One stable LSD radix pass on `bits`-wide digits (bits <= 8) taken at `shift`.
 // keys are uint64; payload is uint32. keys_out / vals_in / vals_out may be NULL

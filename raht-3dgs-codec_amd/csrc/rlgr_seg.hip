@@ -481,10 +481,25 @@ static int decode_lds_in()
     return e ? (e[0] == 'l') : 1;
 }
 
+// The offset tables come in two widths (OffT): uint32_t -- containers below 4 GiB, the raht_rlgr_seg_* entry points -- and
+// uint64_t -- the raht_rlgr_seg_*64 ones, for frames whose worst case is larger. Lengths stay uint32 (one segment is at most
+// 16 + 13 seg_len bytes). A kernel loads its offset in the table's width and from there on carries it in 64 bits, as the 32-bit
+// kernels always did: the two instantiations differ by that load (and the store of seg_off[G]). The flag words of frame j:
+// [overflow bits, container bytes] for 32-bit tables, [overflow bits, -, container bytes (64 bits, 8-byte aligned)] for 64-bit ones.
+template <typename OffT> struct SegFlags;
+template <> struct SegFlags<uint32_t> {
+    static constexpr int WORDS = 2;
+    static __host__ __device__ __forceinline__ uint32_t *total(uint32_t *flags, int j) { return flags + 2 * j + 1; }
+};
+template <> struct SegFlags<uint64_t> {
+    static constexpr int WORDS = 4;
+    static __host__ __device__ __forceinline__ uint64_t *total(uint32_t *flags, int j) { return (uint64_t *)(flags + 4 * j + 2); }
+};
+
 // segment g = c * nseg + s  <->  symbols [s * S, min(N, (s + 1) * S)) of channel c
-template <bool WRITE>
+template <bool WRITE, typename OffT = uint32_t>
 __global__ __launch_bounds__(64) void seg_encode_kernel(const int32_t *__restrict__ Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
-                                                        int flag_signed, uint32_t *__restrict__ seg_bytes, const uint32_t *__restrict__ seg_off,
+                                                        int flag_signed, uint32_t *__restrict__ seg_bytes, const OffT *__restrict__ seg_off,
                                                         uint8_t *__restrict__ out, uint64_t cap, uint32_t *__restrict__ overflow)
 {
     // thread t -> segment g = c * nseg + s. Channel-major input (sym_stride == 1): t = g, a lane walks its own contiguous run.
@@ -541,14 +556,16 @@ __global__ __launch_bounds__(64) void seg_encode_slots_kernel(const int32_t *__r
 }
 
 // one wave per segment: its words from the slot to its offset in the container
+template <typename OffT>
 __global__ __launch_bounds__(256) void seg_compact_kernel(const uint8_t *__restrict__ slots, uint32_t slot, const uint32_t *__restrict__ seg_bytes,
-                                                          const uint32_t *__restrict__ seg_off, int64_t G, uint8_t *__restrict__ out, uint64_t cap,
+                                                          const OffT *__restrict__ seg_off, int64_t G, uint8_t *__restrict__ out, uint64_t cap,
                                                           uint32_t *__restrict__ overflow)
 {
     const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (g >= G) return;
     const uint32_t nw = (seg_bytes[g] + 3u) >> 2;
+    if (4ull * nw > slot) return;                                     // it outgrew its slot (the encoder raised the flag): nothing of it is there
     const uint64_t off = seg_off[g];
     if (off + 4ull * nw > cap) { if (lane == 0) atomicOr(overflow, 2u); return; }
     const uint32_t *src = (const uint32_t *)(slots + (size_t)g * slot);
@@ -563,7 +580,15 @@ __global__ void seg_pad_kernel(const uint32_t *__restrict__ seg_bytes, int64_t n
     if (g < n) padded[g] = (seg_bytes[g] + 3u) & ~3u;
 }
 
-__global__ __launch_bounds__(64) void seg_decode_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const uint32_t *__restrict__ seg_off,
+// a segment whose table entry reaches outside the buffer: n zeros, and nothing is read (raht.h: "decodes as zeros". An empty
+// RLGR stream is not that: zero bits decode to a pattern of 0 and -1)
+__device__ __forceinline__ void zero_segment(int32_t *__restrict__ seq, int n, int64_t sstr)
+{
+    for (int i = 0; i < n; ++i, seq += sstr) *seq = 0;
+}
+
+template <typename OffT>
+__global__ __launch_bounds__(64) void seg_decode_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const OffT *__restrict__ seg_off,
                                                         const uint32_t *__restrict__ seg_bytes, int64_t N, int D, int S, int nseg, int flag_signed,
                                                         int32_t *__restrict__ Q, int64_t sym_stride, int64_t chan_stride, uint32_t *__restrict__ bad, int out_mode,
                                                         int sync_rows)
@@ -581,10 +606,15 @@ __global__ __launch_bounds__(64) void seg_decode_kernel(const uint8_t *__restric
     const int64_t g = (int64_t)c * nseg + s;
     const int64_t i0 = (int64_t)s * S;
     const int n = (int)min((int64_t)S, N - i0);
-    // the tables come off the wire: a segment never reaches outside the buffer (its last word is read whole: 4-byte slots)
+    // the tables come off the wire: a segment never reaches outside the buffer (its last word is read whole: 4-byte slots).
+    // (the whole offset is judged, in 64 bits, whatever the table's width: nothing below sees a narrowed one)
     const uint64_t off = seg_off[g];
-    uint32_t nb = seg_bytes[g];
-    if ((off & 3) || off > in_bytes || (uint64_t)((nb + 3u) & ~3u) > in_bytes - off) { nb = 0; if (bad) atomicOr(bad, 1u); }
+    const uint32_t nb = seg_bytes[g];                               // (padded in 64 bits: 2^32 - 1 must not wrap to 0)
+    if ((off & 3) || off > in_bytes || (((uint64_t)nb + 3u) & ~(uint64_t)3) > in_bytes - off) {
+        if (bad) atomicOr(bad, 1u);
+        zero_segment(Q + (int64_t)c * chan_stride + i0 * sym_stride, n, sym_stride);
+        return;
+    }
     // (16-byte stores of four buffered symbols measured SLOWER than one 4-byte store per symbol -- 4.2 against 3.0 ms for 3 M x 56
     // at 2048 per segment: the component selects cost more instructions than the stores save; kept behind this switch)
     const bool aligned = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0);
@@ -602,18 +632,21 @@ __global__ __launch_bounds__(64) void seg_decode_kernel(const uint8_t *__restric
 // nothing between them: coded by ONE launch (blockIdx.y = frame) they fill every wave slot of the chip. Each frame keeps
 // its own tables and container: the bytes are those of the one-frame entry points.
 constexpr int SEG_BATCH_MAX = RAHT_RLGR_BATCH_MAX;
+template <typename OffT>
 struct SegEncJobs {
-    const int32_t *Q[SEG_BATCH_MAX]; uint32_t *seg_bytes[SEG_BATCH_MAX]; uint32_t *seg_off[SEG_BATCH_MAX]; uint8_t *out[SEG_BATCH_MAX];
+    const int32_t *Q[SEG_BATCH_MAX]; uint32_t *seg_bytes[SEG_BATCH_MAX]; OffT *seg_off[SEG_BATCH_MAX]; uint8_t *out[SEG_BATCH_MAX];
     uint64_t cap[SEG_BATCH_MAX];
 };
+template <typename OffT>
 struct SegDecJobs {
-    const uint8_t *in[SEG_BATCH_MAX]; uint64_t in_bytes[SEG_BATCH_MAX]; const uint32_t *seg_off[SEG_BATCH_MAX]; const uint32_t *seg_bytes[SEG_BATCH_MAX];
+    const uint8_t *in[SEG_BATCH_MAX]; uint64_t in_bytes[SEG_BATCH_MAX]; const OffT *seg_off[SEG_BATCH_MAX]; const uint32_t *seg_bytes[SEG_BATCH_MAX];
     int32_t *Q[SEG_BATCH_MAX];
     const int32_t *expect[SEG_BATCH_MAX];        // (may be NULL) what Q[j] should become: compared inside the row-major decoder
 };
 
-// flags: two words per frame (overflow bits, container bytes)
-__global__ __launch_bounds__(64) void seg_encode_slots_batch_kernel(const SegEncJobs J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
+// flags: SegFlags<OffT>::WORDS words per frame (overflow bits, container bytes)
+template <typename OffT>
+__global__ __launch_bounds__(64) void seg_encode_slots_batch_kernel(const SegEncJobs<OffT> J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
                                                                     int flag_signed, uint8_t *__restrict__ slots, uint32_t slot, uint32_t *__restrict__ flags,
                                                                     int lds_out)
 {
@@ -636,34 +669,38 @@ __global__ __launch_bounds__(64) void seg_encode_slots_batch_kernel(const SegEnc
     if (lds_out) nb = vec ? encode_segment<true, true, true>(seq, n, flag_signed, o, slot, 1, s_col) : encode_segment<true, false, true>(seq, n, flag_signed, o, slot, sym_stride, s_col);
     else nb = vec ? encode_segment<true, true>(seq, n, flag_signed, o, slot) : encode_segment<true, false>(seq, n, flag_signed, o, slot, sym_stride);
     J.seg_bytes[j][g] = nb;
-    if (((nb + 3u) & ~3u) > slot) atomicOr(flags + 2 * j, 1u);
+    if (((nb + 3u) & ~3u) > slot) atomicOr(flags + SegFlags<OffT>::WORDS * j, 1u);
 }
 
-__global__ void seg_pad_batch_kernel(const SegEncJobs J, int64_t G, uint32_t *__restrict__ padded)
+template <typename OffT>
+__global__ void seg_pad_batch_kernel(const SegEncJobs<OffT> J, int64_t G, uint32_t *__restrict__ padded)
 {
     const int j = blockIdx.y;
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < G) padded[(size_t)j * (size_t)G + g] = (J.seg_bytes[j][g] + 3u) & ~3u;
 }
 
-// (also closes every frame's offset table: seg_off[G] = its container's bytes, left in flags[2 j + 1] by the scan)
-__global__ __launch_bounds__(256) void seg_compact_batch_kernel(const SegEncJobs J, const uint8_t *__restrict__ slots, uint32_t slot, int64_t G,
+// (also closes every frame's offset table: seg_off[G] = its container's bytes, left in the frame's flag words by the scan)
+template <typename OffT>
+__global__ __launch_bounds__(256) void seg_compact_batch_kernel(const SegEncJobs<OffT> J, const uint8_t *__restrict__ slots, uint32_t slot, int64_t G,
                                                                 uint32_t *__restrict__ flags)
 {
     const int j = blockIdx.y;
     const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
-    if (blockIdx.x == 0 && threadIdx.x == 0) J.seg_off[j][G] = flags[2 * j + 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) J.seg_off[j][G] = *SegFlags<OffT>::total(flags, j);
     if (g >= G) return;
     const uint32_t nw = (J.seg_bytes[j][g] + 3u) >> 2;
+    if (4ull * nw > slot) return;                                     // it outgrew its slot (the encoder raised the flag): nothing of it is there
     const uint64_t off = J.seg_off[j][g];
-    if (off + 4ull * nw > J.cap[j]) { if (lane == 0) atomicOr(flags + 2 * j, 2u); return; }
+    if (off + 4ull * nw > J.cap[j]) { if (lane == 0) atomicOr(flags + SegFlags<OffT>::WORDS * j, 2u); return; }
     const uint32_t *src = (const uint32_t *)(slots + ((size_t)j * (size_t)G + (size_t)g) * slot);
     uint32_t *dst = (uint32_t *)(J.out[j] + off);
     for (uint32_t i = lane; i < nw; i += 64) dst[i] = src[i];
 }
 
-__global__ __launch_bounds__(64) void seg_decode_batch_kernel(const SegDecJobs J, int64_t N, int D, int S, int nseg, int flag_signed, int64_t sym_stride,
+template <typename OffT>
+__global__ __launch_bounds__(64) void seg_decode_batch_kernel(const SegDecJobs<OffT> J, int64_t N, int D, int S, int nseg, int flag_signed, int64_t sym_stride,
                                                               int64_t chan_stride, uint32_t *__restrict__ bad, int out_mode, int lds_in, int sync_rows)
 {
     __shared__ int32_t s_col[DEC_LDS_WORDS];
@@ -678,9 +715,13 @@ __global__ __launch_bounds__(64) void seg_decode_batch_kernel(const SegDecJobs J
     const int64_t i0 = (int64_t)s * S;
     const int n = (int)min((int64_t)S, N - i0);
     const uint64_t off = J.seg_off[j][g], in_bytes = J.in_bytes[j];
-    uint32_t nb = J.seg_bytes[j][g];
-    if ((off & 3) || off > in_bytes || (uint64_t)((nb + 3u) & ~3u) > in_bytes - off) { nb = 0; if (bad) atomicOr(bad, 1u << j); }
+    const uint32_t nb = J.seg_bytes[j][g];
     int32_t *Q = J.Q[j];
+    if ((off & 3) || off > in_bytes || (((uint64_t)nb + 3u) & ~(uint64_t)3) > in_bytes - off) {
+        if (bad) atomicOr(bad, 1u << j);
+        zero_segment(Q + (int64_t)c * chan_stride + i0 * sym_stride, n, sym_stride);
+        return;
+    }
     const bool aligned = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0);
     const uint64_t o = nb ? off : 0;
     if (sym_stride != 1 && (sync_rows || J.expect[j])) {
@@ -701,7 +742,248 @@ __global__ __launch_bounds__(64) void seg_decode_batch_kernel(const SegDecJobs J
 
 using namespace raht;
 
+namespace {
+
+using rlgr_seg::SegFlags;
+
+template <typename OffT> int scan_offsets(const uint32_t *padded, OffT *off, int64_t n, OffT *total, hipStream_t s);
+template <> inline int scan_offsets<uint32_t>(const uint32_t *padded, uint32_t *off, int64_t n, uint32_t *total, hipStream_t s)
+{
+    return exclusive_scan_u32(padded, off, n, total, s);
+}
+template <> inline int scan_offsets<uint64_t>(const uint32_t *padded, uint64_t *off, int64_t n, uint64_t *total, hipStream_t s)
+{
+    return exclusive_scan_u32_u64(padded, off, n, total, s);
+}
+
+// frame j's container bytes out of the flag words as they were read back
+template <typename OffT> inline uint64_t total_of(const uint32_t *back, int j)
+{
+    const uint32_t *w = back + SegFlags<OffT>::WORDS * j;
+    return sizeof(OffT) == 8 ? ((uint64_t)w[3] << 32) | w[2] : (uint64_t)w[1];
+}
+
+// nseg, G of a shape and the width its offsets need: refuses what no entry point takes ("too many segments") and, for the
+// 32-bit tables, what raht_rlgr_seg_offsets_width sends to the 64-bit ones. (Arguments already checked: N, D >= 1, seg_len >= 64.)
+template <typename OffT>
+int seg_shape(const char *fn, int64_t N, int D, int seg_len, int64_t *nseg, int64_t *G)
+{
+    *nseg = (N - 1) / seg_len + 1;
+    *G = *nseg < ((int64_t)1 << 31) ? *nseg * D : (int64_t)1 << 31;
+    if (*nseg >= ((int64_t)1 << 31) || *G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
+    const int width = raht_rlgr_seg_offsets_width(N, D, seg_len);
+    if (sizeof(OffT) == 4 && width != 32) {
+        set_error("%s: %lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): split the frame", fn, (long long)N, D);
+        return RAHT_ERR_INVALID;
+    }
+    if (width < 0) { set_error("%s: seg_len = %d: the length of a segment may not fit 32 bits", fn, seg_len); return RAHT_ERR_INVALID; }
+    return RAHT_OK;
+}
+
+template <typename OffT>
+int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
+                    uint32_t *seg_bytes, OffT *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
+{
+    if (!Q || !seg_bytes || !seg_off || !out || !total_bytes || N < 1 || D < 1 || sym_stride < 1 || chan_stride < 1 || seg_len < 64 || cap < 16 || ((uintptr_t)out & 3) ||
+        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
+        set_error("%s: bad argument (channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn);
+        return RAHT_ERR_INVALID;
+    }
+    // 32-bit tables: segment offsets and the container's total could wrap for what raht_rlgr_seg_offsets_width calls 64 (worst
+    // case: every symbol escapes -- 8 bytes and a bit -- plus the 4-byte padding of every segment): refused there
+    int64_t nseg, G;
+    RAHT_RET(seg_shape<OffT>(fn, N, D, seg_len, &nseg, &G));
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int FW = SegFlags<OffT>::WORDS;
+    return guarded(fn, [&]() -> int {
+        const size_t npad = ((size_t)G + 1) & ~(size_t)1;                   // (the flag words behind it stay 8-byte aligned)
+        Scratch tmp(sizeof(uint32_t) * (npad + FW), s);
+        if (!tmp.ok()) return RAHT_ERR_NOMEM;
+        uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + npad;      // flags[0] = overflow, SegFlags::total = total
+        OffT *dtotal = SegFlags<OffT>::total(flags, 0);
+        RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW, s));
+        const unsigned gb = (unsigned)ceil_div(G, 64);
+        // ONE encoding pass into fixed slots + a compaction, when a scratch buffer of the raw size is to be had; the two exact
+        // passes (sizes, then streams) otherwise, and whenever a segment outgrows its slot
+        static const bool two_pass_only = getenv("RAHT_RLGR_TWO_PASS") != nullptr;      // A/B knob
+        const uint32_t slot = 4u * (uint32_t)seg_len + 16u;                             // (fits: raht_rlgr_bound(seg_len) < 2^32)
+        if (!two_pass_only && (uint64_t)G * slot < ((uint64_t)1 << 33)) {
+            Scratch slots((size_t)G * slot, s);
+            if (slots.ok()) {
+                hipLaunchKernelGGL(rlgr_seg::seg_encode_slots_kernel, dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
+                                   seg_bytes, slots.as<uint8_t>(), slot, flags);
+                hipLaunchKernelGGL(rlgr_seg::seg_pad_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, seg_bytes, G, padded);
+                RAHT_RET(scan_offsets<OffT>(padded, seg_off, G, dtotal, s));
+                RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, dtotal, sizeof(OffT), hipMemcpyDeviceToDevice, s));
+                hipLaunchKernelGGL(rlgr_seg::seg_compact_kernel<OffT>, dim3((unsigned)ceil_div(G * 64, 256)), dim3(256), 0, s, slots.as<uint8_t>(), slot,
+                                   (const uint32_t *)seg_bytes, (const OffT *)seg_off, G, out, (uint64_t)cap, flags);
+                RAHT_HIP_CHECK(hipGetLastError());
+                uint32_t back[FW] = {0};
+                RAHT_RET(read_back_u32(back, flags, FW, nullptr, nullptr, 0, s));    // (synchronises: the scratch may go back to the pool)
+                if (!(back[0] & 1u)) {
+                    const uint64_t total = total_of<OffT>(back, 0);
+                    *total_bytes = (int64_t)total;
+                    if ((back[0] & 2u) || (int64_t)total > cap) { set_error("%s: %llu bytes needed, cap = %lld", fn, (unsigned long long)total, (long long)cap); return RAHT_ERR_NOMEM; }
+                    return RAHT_OK;
+                }
+                RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW, s));                  // a segment outgrew its slot: the exact passes
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        hipLaunchKernelGGL((rlgr_seg::seg_encode_kernel<false, OffT>), dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
+                           seg_bytes, (const OffT *)nullptr, (uint8_t *)nullptr, (uint64_t)0, flags);
+        hipLaunchKernelGGL(rlgr_seg::seg_pad_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, seg_bytes, G, padded);
+        RAHT_RET(scan_offsets<OffT>(padded, seg_off, G, dtotal, s));
+        RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, dtotal, sizeof(OffT), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL((rlgr_seg::seg_encode_kernel<true, OffT>), dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
+                           seg_bytes, (const OffT *)seg_off, out, (uint64_t)cap, flags);
+        RAHT_HIP_CHECK(hipGetLastError());
+        uint32_t back[FW] = {0};
+        RAHT_RET(read_back_u32(back, flags, FW, nullptr, nullptr, 0, s));
+        const uint64_t total = total_of<OffT>(back, 0);
+        *total_bytes = (int64_t)total;
+        if (back[0] || (int64_t)total > cap) { set_error("%s: %llu bytes needed, cap = %lld", fn, (unsigned long long)total, (long long)cap); return RAHT_ERR_NOMEM; }
+        return RAHT_OK;
+    });
+}
+
+template <typename OffT>
+int seg_decode_impl(const char *fn, const uint8_t *in, int64_t in_bytes, const OffT *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
+                    int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
+{
+    if (!in || in_bytes < 0 || (in_bytes & 3) || !seg_off || !seg_bytes || !Q || N < 1 || D < 1 || seg_len < 64 || ((uintptr_t)in & 3) ||
+        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
+        set_error("%s: bad argument", fn);
+        return RAHT_ERR_INVALID;
+    }
+    const int64_t nseg = (N - 1) / seg_len + 1, G = nseg < ((int64_t)1 << 31) ? nseg * D : (int64_t)1 << 31;
+    if (G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
+    hipLaunchKernelGGL(rlgr_seg::seg_decode_kernel<OffT>, dim3((unsigned)ceil_div(G, 64)), dim3(64), 0, (hipStream_t)stream, in, (uint64_t)in_bytes, seg_off, seg_bytes, N, D,
+                       seg_len, (int)nseg, flag_signed, Q, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode(G), rlgr_seg::decode_sync_rows() ? (rlgr_seg::decode_lds_in() ? 2 : 1) : 0);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+// fn: the batch entry point's name; fn1: the one-frame entry point of the same width (the frame-by-frame fallback reports as it)
+template <typename OffT>
+int seg_encode_batch_impl(const char *fn, const char *fn1, int k, const int32_t *const *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len,
+                          int flag_signed, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
+                          raht_stream_t stream)
+{
+    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !Q || !seg_bytes || !seg_off || !out || !cap || !total_bytes) {
+        set_error("%s: bad argument (1 <= k <= %d)", fn, RAHT_RLGR_BATCH_MAX);
+        return RAHT_ERR_INVALID;
+    }
+    if (N < 1 || D < 1 || sym_stride < 1 || chan_stride < 1 || seg_len < 64 ||
+        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
+        set_error("%s: bad argument (channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn);
+        return RAHT_ERR_INVALID;
+    }
+    for (int j = 0; j < k; ++j)
+        if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
+    int64_t nseg, G;
+    RAHT_RET(seg_shape<OffT>(fn, N, D, seg_len, &nseg, &G));
+    hipStream_t s = (hipStream_t)stream;
+    auto one_by_one = [&]() -> int {
+        int rc_all = RAHT_OK;
+        for (int j = 0; j < k; ++j) {
+            const int rc = seg_encode_impl<OffT>(fn1, Q[j], N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j], stream);
+            if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
+            if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
+        }
+        return rc_all;
+    };
+    static const bool no_batch = getenv("RAHT_RLGR_NO_BATCH") != nullptr;          // A/B knob
+    if (k == 1 || no_batch) return one_by_one();
+    // slots of whole 64-byte pieces (16-byte aligned starts are what the LDS-column output needs; 64: whole pieces)
+    const uint32_t slot = (4u * (uint32_t)seg_len + 16u + 63u) & ~63u;
+    static const char *enc_out = getenv("RAHT_RLGR_ENCODE_OUT");                  // A/B knob: word | lds
+    const int lds_out = rlgr_seg::g_encode_out >= 0 ? (rlgr_seg::g_encode_out == rlgr_seg::OUT_LDS)
+                                                    : enc_out ? (enc_out[0] == 'l') : ((int64_t)k * G >= 200000);
+    constexpr int FW = SegFlags<OffT>::WORDS;
+    int rc = guarded(fn, [&]() -> int {
+        const size_t npad = ((size_t)k * (size_t)G + 1) & ~(size_t)1;           // (the flag words behind it stay 8-byte aligned)
+        Scratch tmp(sizeof(uint32_t) * (npad + FW * (size_t)k), s);
+        Scratch slots((size_t)k * (size_t)G * slot, s);
+        if (!tmp.ok() || !slots.ok()) { (void)hipGetLastError(); return RAHT_ERR_UNSUPPORTED; }      // no room for k sets of slots: frame by frame
+        uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + npad;
+        RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW * (size_t)k, s));
+        rlgr_seg::SegEncJobs<OffT> J;
+        for (int j = 0; j < RAHT_RLGR_BATCH_MAX; ++j) {
+            const int q = j < k ? j : 0;
+            J.Q[j] = Q[q]; J.seg_bytes[j] = seg_bytes[q]; J.seg_off[j] = seg_off[q]; J.out[j] = out[q]; J.cap[j] = (uint64_t)cap[q];
+        }
+        hipLaunchKernelGGL(rlgr_seg::seg_encode_slots_batch_kernel<OffT>, dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len,
+                           (int)nseg, flag_signed, slots.as<uint8_t>(), slot, flags, lds_out);
+        hipLaunchKernelGGL(rlgr_seg::seg_pad_batch_kernel<OffT>, dim3((unsigned)ceil_div(G, 256), (unsigned)k), dim3(256), 0, s, J, G, padded);
+        for (int j = 0; j < k; ++j) RAHT_RET(scan_offsets<OffT>(padded + (size_t)j * (size_t)G, seg_off[j], G, SegFlags<OffT>::total(flags, j), s));
+        hipLaunchKernelGGL(rlgr_seg::seg_compact_batch_kernel<OffT>, dim3((unsigned)ceil_div(G * 64, 256), (unsigned)k), dim3(256), 0, s, J, (const uint8_t *)slots.as<uint8_t>(), slot, G, flags);
+        RAHT_HIP_CHECK(hipGetLastError());
+        uint32_t back[FW * RAHT_RLGR_BATCH_MAX] = {0};
+        RAHT_RET(read_back_u32(back, flags, FW * k, nullptr, nullptr, 0, s));       // (synchronises: the scratch may go back to the pool)
+        int rc2 = RAHT_OK;
+        for (int j = 0; j < k; ++j) {
+            if (back[FW * j] & 1u) return RAHT_ERR_UNSUPPORTED;                       // a segment outgrew its slot (incompressible data): the exact passes
+            const uint64_t total = total_of<OffT>(back, j);
+            total_bytes[j] = (int64_t)total;
+            if ((back[FW * j] & 2u) || (int64_t)total > cap[j]) {
+                set_error("%s: frame %d needs %llu bytes, cap = %lld", fn, j, (unsigned long long)total, (long long)cap[j]);
+                rc2 = RAHT_ERR_NOMEM;
+            }
+        }
+        return rc2;
+    });
+    if (rc == RAHT_ERR_UNSUPPORTED) return one_by_one();
+    return rc;
+}
+
+template <typename OffT>
+int seg_decode_batch_impl(const char *fn, int k, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes,
+                          int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
+                          int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
+{
+    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !in || !in_bytes || !seg_off || !seg_bytes || !Q || N < 1 || D < 1 || seg_len < 64 ||
+        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
+        set_error("%s: bad argument (1 <= k <= %d)", fn, RAHT_RLGR_BATCH_MAX);
+        return RAHT_ERR_INVALID;
+    }
+    for (int j = 0; j < k; ++j)
+        if (!in[j] || in_bytes[j] < 0 || (in_bytes[j] & 3) || ((uintptr_t)in[j] & 3) || !seg_off[j] || !seg_bytes[j] || !Q[j]) {
+            set_error("%s: bad argument (frame %d)", fn, j);
+            return RAHT_ERR_INVALID;
+        }
+    const int64_t nseg = (N - 1) / seg_len + 1, G = nseg < ((int64_t)1 << 31) ? nseg * D : (int64_t)1 << 31;
+    if (G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
+    rlgr_seg::SegDecJobs<OffT> J;
+    for (int j = 0; j < RAHT_RLGR_BATCH_MAX; ++j) {
+        const int q = j < k ? j : 0;
+        J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
+        J.expect[j] = expect ? expect[q] : nullptr;
+    }
+    hipLaunchKernelGGL(rlgr_seg::seg_decode_batch_kernel<OffT>, dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, (hipStream_t)stream, J, N, D, seg_len, (int)nseg,
+                       flag_signed, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode((int64_t)k * G), rlgr_seg::decode_lds_in(), rlgr_seg::decode_sync_rows());
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+/* Which offset tables a shape needs. HOST arithmetic only. 32: raht_rlgr_seg_encode* take it -- the container stays below 4 GiB
+ * whatever the data (worst case: every symbol escapes, 8 bytes and a bit, raht_rlgr_bound(seg_len) per segment, plus the 4-byte
+ * padding of every segment). 64: they refuse it and raht_rlgr_seg_encode64 / _batch64 take it. RAHT_ERR_INVALID: nobody does. */
+int raht_rlgr_seg_offsets_width(int64_t N, int D, int seg_len)
+{
+    if (N < 1 || D < 1 || seg_len < 64) { set_error("raht_rlgr_seg_offsets_width: bad argument (N, D >= 1, seg_len >= 64)"); return RAHT_ERR_INVALID; }
+    const int64_t nseg = (N - 1) / seg_len + 1;
+    if (nseg >= ((int64_t)1 << 31) || nseg * D >= ((int64_t)1 << 31)) { set_error("raht_rlgr_seg_offsets_width: too many segments"); return RAHT_ERR_INVALID; }
+    const int64_t G = nseg * D, per_seg = raht_rlgr_bound(seg_len) + 4;       // < 2^35
+    // the lengths of the segments stay uint32 in either table
+    if (raht_rlgr_bound(seg_len) >= ((int64_t)1 << 32)) { set_error("raht_rlgr_seg_offsets_width: seg_len = %d: the length of a segment may not fit 32 bits", seg_len); return RAHT_ERR_INVALID; }
+    return per_seg * G >= ((int64_t)1 << 32) ? 64 : 32;                         // (< 2^66 / 2: G < 2^31, per_seg < 2^32 -- no overflow)
+}
 
 /* Segmented RLGR on the device. Q: DEVICE int32, channel-major (symbol n of channel c at Q[c * chan_stride + n], what
  * raht_transpose_i32 produces); seg_len symbols per segment (>= 64), nseg = ceil(N / seg_len) segments per channel.
@@ -719,67 +1001,15 @@ int raht_rlgr_seg_encode(const int32_t *Q, int64_t N, int D, int64_t chan_stride
 int raht_rlgr_seg_encode_strided(const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
                                  uint32_t *seg_bytes, uint32_t *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
 {
-    if (!Q || !seg_bytes || !seg_off || !out || !total_bytes || N < 1 || D < 1 || sym_stride < 1 || chan_stride < 1 || seg_len < 64 || cap < 16 || ((uintptr_t)out & 3) ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("raht_rlgr_seg_encode: bad argument (channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)");
-        return RAHT_ERR_INVALID;
-    }
-    const int64_t nseg = ceil_div(N, seg_len), G = nseg * D;
-    if (nseg >= ((int64_t)1 << 31) || G >= ((int64_t)1 << 31)) { set_error("raht_rlgr_seg_encode: too many segments"); return RAHT_ERR_INVALID; }
-    // segment offsets and the container's total are 32-bit: refuse what could wrap them (worst case: every symbol escapes --
-    // 8 bytes and a bit -- plus the 4-byte padding of every segment)
-    if (raht_rlgr_bound(seg_len) * G + 4 * G >= ((int64_t)1 << 32)) {
-        set_error("raht_rlgr_seg_encode: %lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): split the frame", (long long)N, D);
-        return RAHT_ERR_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    return guarded("raht_rlgr_seg_encode", [&]() -> int {
-        Scratch tmp(sizeof(uint32_t) * ((size_t)G + 2), s);
-        if (!tmp.ok()) return RAHT_ERR_NOMEM;
-        uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + G;          // flags[0] = overflow, flags[1] = total
-        RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 8, s));
-        const unsigned gb = (unsigned)ceil_div(G, 64);
-        // ONE encoding pass into fixed slots + a compaction, when a scratch buffer of the raw size is to be had; the two exact
-        // passes (sizes, then streams) otherwise, and whenever a segment outgrows its slot
-        static const bool two_pass_only = getenv("RAHT_RLGR_TWO_PASS") != nullptr;      // A/B knob
-        const uint32_t slot = 4u * (uint32_t)seg_len + 16u;
-        if (!two_pass_only && (uint64_t)G * slot < ((uint64_t)1 << 33)) {
-            Scratch slots((size_t)G * slot, s);
-            if (slots.ok()) {
-                hipLaunchKernelGGL(rlgr_seg::seg_encode_slots_kernel, dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
-                                   seg_bytes, slots.as<uint8_t>(), slot, flags);
-                hipLaunchKernelGGL(rlgr_seg::seg_pad_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, seg_bytes, G, padded);
-                RAHT_RET(exclusive_scan_u32(padded, seg_off, G, flags + 1, s));
-                RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, flags + 1, 4, hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(rlgr_seg::seg_compact_kernel, dim3((unsigned)ceil_div(G * 64, 256)), dim3(256), 0, s, slots.as<uint8_t>(), slot, seg_bytes,
-                                   seg_off, G, out, (uint64_t)cap, flags);
-                RAHT_HIP_CHECK(hipGetLastError());
-                uint32_t back[2] = {0, 0};
-                RAHT_RET(read_back_u32(back, flags, 2, nullptr, nullptr, 0, s));    // (synchronises: the scratch may go back to the pool)
-                if (!(back[0] & 1u)) {
-                    *total_bytes = (int64_t)back[1];
-                    if ((back[0] & 2u) || (int64_t)back[1] > cap) { set_error("raht_rlgr_seg_encode: %u bytes needed, cap = %lld", back[1], (long long)cap); return RAHT_ERR_NOMEM; }
-                    return RAHT_OK;
-                }
-                RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 8, s));                       // a segment outgrew its slot: the exact passes
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        hipLaunchKernelGGL(rlgr_seg::seg_encode_kernel<false>, dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
-                           seg_bytes, (const uint32_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, flags);
-        hipLaunchKernelGGL(rlgr_seg::seg_pad_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, seg_bytes, G, padded);
-        RAHT_RET(exclusive_scan_u32(padded, seg_off, G, flags + 1, s));       // (32-bit offsets: containers below 4 GiB)
-        RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, flags + 1, 4, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(rlgr_seg::seg_encode_kernel<true>, dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
-                           seg_bytes, seg_off, out, (uint64_t)cap, flags);
-        RAHT_HIP_CHECK(hipGetLastError());
-        uint32_t back[2] = {0, 0};
-        RAHT_RET(read_back_u32(back, flags, 2, nullptr, nullptr, 0, s));
-        *total_bytes = (int64_t)back[1];
-        if (back[0] || (int64_t)back[1] > cap) { set_error("raht_rlgr_seg_encode: %u bytes needed, cap = %lld", back[1], (long long)cap); return RAHT_ERR_NOMEM; }
-        return RAHT_OK;
-    });
+    return seg_encode_impl<uint32_t>("raht_rlgr_seg_encode", Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
+}
+
+/* The same with 64-bit offsets (seg_off: DEVICE uint64[D * nseg + 1]) for the shapes raht_rlgr_seg_offsets_width calls 64 -- and
+ * for any other: same seg_bytes, same streams, offsets equal as integers. */
+int raht_rlgr_seg_encode64(const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
+                           uint32_t *seg_bytes, uint64_t *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
+{
+    return seg_encode_impl<uint64_t>("raht_rlgr_seg_encode64", Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
 }
 
 /* The inverse: streams `in` (DEVICE, 4-byte aligned, in_bytes long -- a multiple of 4) with their offsets / lengths (DEVICE, as
@@ -796,17 +1026,14 @@ int raht_rlgr_seg_decode(const uint8_t *in, int64_t in_bytes, const uint32_t *se
 int raht_rlgr_seg_decode_strided(const uint8_t *in, int64_t in_bytes, const uint32_t *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
                                  int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
-    if (!in || in_bytes < 0 || (in_bytes & 3) || !seg_off || !seg_bytes || !Q || N < 1 || D < 1 || seg_len < 64 || ((uintptr_t)in & 3) ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("raht_rlgr_seg_decode: bad argument");
-        return RAHT_ERR_INVALID;
-    }
-    const int64_t nseg = ceil_div(N, seg_len), G = nseg * D;
-    if (G >= ((int64_t)1 << 31)) { set_error("raht_rlgr_seg_decode: too many segments"); return RAHT_ERR_INVALID; }
-    hipLaunchKernelGGL(rlgr_seg::seg_decode_kernel, dim3((unsigned)ceil_div(G, 64)), dim3(64), 0, (hipStream_t)stream, in, (uint64_t)in_bytes, seg_off, seg_bytes, N, D,
-                       seg_len, (int)nseg, flag_signed, Q, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode(G), rlgr_seg::decode_sync_rows() ? (rlgr_seg::decode_lds_in() ? 2 : 1) : 0);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return seg_decode_impl<uint32_t>("raht_rlgr_seg_decode", in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, sym_stride, chan_stride, bad_dev, stream);
+}
+
+/* ... from 64-bit offsets (the whole offset is checked against in_bytes before anything is read) */
+int raht_rlgr_seg_decode64(const uint8_t *in, int64_t in_bytes, const uint64_t *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
+                           int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
+{
+    return seg_decode_impl<uint64_t>("raht_rlgr_seg_decode64", in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, sym_stride, chan_stride, bad_dev, stream);
 }
 
 int raht_debug_rlgr_decode_out(int mode)
@@ -833,85 +1060,26 @@ int raht_rlgr_seg_encode_batch(int k, const int32_t *const *Q, int64_t N, int D,
                                uint32_t *const *seg_bytes, uint32_t *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
                                raht_stream_t stream)
 {
-    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !Q || !seg_bytes || !seg_off || !out || !cap || !total_bytes) {
-        set_error("raht_rlgr_seg_encode_batch: bad argument (1 <= k <= %d)", RAHT_RLGR_BATCH_MAX);
-        return RAHT_ERR_INVALID;
-    }
-    if (N < 1 || D < 1 || sym_stride < 1 || chan_stride < 1 || seg_len < 64 ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("raht_rlgr_seg_encode_batch: bad argument (channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)");
-        return RAHT_ERR_INVALID;
-    }
-    for (int j = 0; j < k; ++j)
-        if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("raht_rlgr_seg_encode_batch: bad argument (frame %d)", j); return RAHT_ERR_INVALID; }
-    const int64_t nseg = ceil_div(N, seg_len), G = nseg * D;
-    if (nseg >= ((int64_t)1 << 31) || G >= ((int64_t)1 << 31)) { set_error("raht_rlgr_seg_encode_batch: too many segments"); return RAHT_ERR_INVALID; }
-    if (raht_rlgr_bound(seg_len) * G + 4 * G >= ((int64_t)1 << 32)) {
-        set_error("raht_rlgr_seg_encode_batch: %lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): split the frame", (long long)N, D);
-        return RAHT_ERR_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    auto one_by_one = [&]() -> int {
-        int rc_all = RAHT_OK;
-        for (int j = 0; j < k; ++j) {
-            const int rc = raht_rlgr_seg_encode_strided(Q[j], N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j], stream);
-            if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
-            if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
-        }
-        return rc_all;
-    };
-    static const bool no_batch = getenv("RAHT_RLGR_NO_BATCH") != nullptr;          // A/B knob
-    if (k == 1 || no_batch) return one_by_one();
-    // slots of whole 64-byte pieces (16-byte aligned starts are what the LDS-column output needs; 64: whole pieces)
-    const uint32_t slot = (4u * (uint32_t)seg_len + 16u + 63u) & ~63u;
-    static const char *enc_out = getenv("RAHT_RLGR_ENCODE_OUT");                  // A/B knob: word | lds
-    const int lds_out = rlgr_seg::g_encode_out >= 0 ? (rlgr_seg::g_encode_out == rlgr_seg::OUT_LDS)
-                                                    : enc_out ? (enc_out[0] == 'l') : ((int64_t)k * G >= 200000);
-    int rc = guarded("raht_rlgr_seg_encode_batch", [&]() -> int {
-        Scratch tmp(sizeof(uint32_t) * ((size_t)k * (size_t)G + 2 * (size_t)k), s);
-        Scratch slots((size_t)k * (size_t)G * slot, s);
-        if (!tmp.ok() || !slots.ok()) { (void)hipGetLastError(); return RAHT_ERR_UNSUPPORTED; }      // no room for k sets of slots: frame by frame
-        uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + (size_t)k * (size_t)G;
-        RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 8 * (size_t)k, s));
-        rlgr_seg::SegEncJobs J;
-        for (int j = 0; j < RAHT_RLGR_BATCH_MAX; ++j) {
-            const int q = j < k ? j : 0;
-            J.Q[j] = Q[q]; J.seg_bytes[j] = seg_bytes[q]; J.seg_off[j] = seg_off[q]; J.out[j] = out[q]; J.cap[j] = (uint64_t)cap[q];
-        }
-        hipLaunchKernelGGL(rlgr_seg::seg_encode_slots_batch_kernel, dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len,
-                           (int)nseg, flag_signed, slots.as<uint8_t>(), slot, flags, lds_out);
-        hipLaunchKernelGGL(rlgr_seg::seg_pad_batch_kernel, dim3((unsigned)ceil_div(G, 256), (unsigned)k), dim3(256), 0, s, J, G, padded);
-        for (int j = 0; j < k; ++j) RAHT_RET(exclusive_scan_u32(padded + (size_t)j * (size_t)G, seg_off[j], G, flags + 2 * j + 1, s));
-        hipLaunchKernelGGL(rlgr_seg::seg_compact_batch_kernel, dim3((unsigned)ceil_div(G * 64, 256), (unsigned)k), dim3(256), 0, s, J, slots.as<uint8_t>(), slot, G, flags);
-        RAHT_HIP_CHECK(hipGetLastError());
-        uint32_t back[2 * RAHT_RLGR_BATCH_MAX] = {0};
-        RAHT_RET(read_back_u32(back, flags, 2 * k, nullptr, nullptr, 0, s));        // (synchronises: the scratch may go back to the pool)
-        int rc2 = RAHT_OK;
-        for (int j = 0; j < k; ++j) {
-            if (back[2 * j] & 1u) return RAHT_ERR_UNSUPPORTED;                        // a segment outgrew its slot (incompressible data): the exact passes
-            total_bytes[j] = (int64_t)back[2 * j + 1];
-            if ((back[2 * j] & 2u) || (int64_t)back[2 * j + 1] > cap[j]) {
-                set_error("raht_rlgr_seg_encode_batch: frame %d needs %u bytes, cap = %lld", j, back[2 * j + 1], (long long)cap[j]);
-                rc2 = RAHT_ERR_NOMEM;
-            }
-        }
-        return rc2;
-    });
-    if (rc == RAHT_ERR_UNSUPPORTED) return one_by_one();
-    return rc;
+    return seg_encode_batch_impl<uint32_t>("raht_rlgr_seg_encode_batch", "raht_rlgr_seg_encode", k, Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes, seg_off,
+                                           out, cap, total_bytes, stream);
+}
+
+int raht_rlgr_seg_encode_batch64(int k, const int32_t *const *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
+                                 uint32_t *const *seg_bytes, uint64_t *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
+                                 raht_stream_t stream)
+{
+    return seg_encode_batch_impl<uint64_t>("raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_encode64", k, Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes,
+                                           seg_off, out, cap, total_bytes, stream);
 }
 
 /* The inverse for k frames of one shape: in[j] / in_bytes[j] / seg_off[j] / seg_bytes[j] -> Q[j], one launch. Does not
  * synchronise. *bad_dev (DEVICE uint32, may be NULL): bit j set when a table entry of frame j reached outside in[j]. */
-static int seg_decode_batch_impl(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint32_t *const *seg_off, const uint32_t *const *seg_bytes,
-                                 int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
-                                 int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream);
-
 int raht_rlgr_seg_decode_batch(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint32_t *const *seg_off, const uint32_t *const *seg_bytes,
                                int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, int64_t sym_stride, int64_t chan_stride,
                                uint32_t *bad_dev, raht_stream_t stream)
 {
-    return seg_decode_batch_impl(k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, nullptr, sym_stride, chan_stride, bad_dev, stream);
+    return seg_decode_batch_impl<uint32_t>("raht_rlgr_seg_decode_batch", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, nullptr, sym_stride, chan_stride,
+                                           bad_dev, stream);
 }
 
 /* ... and compares every frame with what it should decode to (expect[j]: DEVICE, the layout and strides of Q[j]; ROW-MAJOR only:
@@ -924,35 +1092,23 @@ int raht_rlgr_seg_decode_batch_check(int k, const uint8_t *const *in, const int6
     if (!expect || !bad_dev || chan_stride != 1) { set_error("raht_rlgr_seg_decode_batch_check: needs expect[], bad_dev and row-major frames (chan_stride 1)"); return RAHT_ERR_INVALID; }
     for (int j = 0; j < k && j < RAHT_RLGR_BATCH_MAX; ++j)
         if (!expect[j]) { set_error("raht_rlgr_seg_decode_batch_check: expect[%d] is NULL", j); return RAHT_ERR_INVALID; }
-    return seg_decode_batch_impl(k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, expect, sym_stride, chan_stride, bad_dev, stream);
+    return seg_decode_batch_impl<uint32_t>("raht_rlgr_seg_decode_batch", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, expect, sym_stride, chan_stride,
+                                           bad_dev, stream);
 }
 
-static int seg_decode_batch_impl(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint32_t *const *seg_off, const uint32_t *const *seg_bytes,
+/* Both of them from 64-bit offsets: expect == NULL decodes (any layout, bad_dev may be NULL); expect != NULL also compares
+ * (row-major frames, bad_dev required, every expect[j] set). */
+int raht_rlgr_seg_decode_batch64(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint64_t *const *seg_off, const uint32_t *const *seg_bytes,
                                  int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
                                  int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
-    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !in || !in_bytes || !seg_off || !seg_bytes || !Q || N < 1 || D < 1 || seg_len < 64 ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("raht_rlgr_seg_decode_batch: bad argument (1 <= k <= %d)", RAHT_RLGR_BATCH_MAX);
-        return RAHT_ERR_INVALID;
+    if (expect) {
+        if (!bad_dev || chan_stride != 1) { set_error("raht_rlgr_seg_decode_batch64: expect[] needs bad_dev and row-major frames (chan_stride 1)"); return RAHT_ERR_INVALID; }
+        for (int j = 0; j < k && j < RAHT_RLGR_BATCH_MAX; ++j)
+            if (!expect[j]) { set_error("raht_rlgr_seg_decode_batch64: expect[%d] is NULL", j); return RAHT_ERR_INVALID; }
     }
-    for (int j = 0; j < k; ++j)
-        if (!in[j] || in_bytes[j] < 0 || (in_bytes[j] & 3) || ((uintptr_t)in[j] & 3) || !seg_off[j] || !seg_bytes[j] || !Q[j]) {
-            set_error("raht_rlgr_seg_decode_batch: bad argument (frame %d)", j);
-            return RAHT_ERR_INVALID;
-        }
-    const int64_t nseg = ceil_div(N, seg_len), G = nseg * D;
-    if (G >= ((int64_t)1 << 31)) { set_error("raht_rlgr_seg_decode_batch: too many segments"); return RAHT_ERR_INVALID; }
-    rlgr_seg::SegDecJobs J;
-    for (int j = 0; j < RAHT_RLGR_BATCH_MAX; ++j) {
-        const int q = j < k ? j : 0;
-        J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
-        J.expect[j] = expect ? expect[q] : nullptr;
-    }
-    hipLaunchKernelGGL(rlgr_seg::seg_decode_batch_kernel, dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, (hipStream_t)stream, J, N, D, seg_len, (int)nseg,
-                       flag_signed, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode((int64_t)k * G), rlgr_seg::decode_lds_in(), rlgr_seg::decode_sync_rows());
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return seg_decode_batch_impl<uint64_t>("raht_rlgr_seg_decode_batch64", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, expect, sym_stride, chan_stride,
+                                           bad_dev, stream);
 }
 
 }  // extern "C"

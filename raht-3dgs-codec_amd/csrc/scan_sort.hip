@@ -307,6 +307,122 @@ int exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *t
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same scan with 64-bit sums: uint32 items (the padded lengths of the segments of an RLGR container
+// that may pass 4 GiB, rlgr_seg.hip) -> uint64 exclusive offsets and a uint64 grand total. A thread's eight
+// items already sum past 32 bits, so everything above the single item is carried in 64 bits. The second
+// level (block sums of a scan of more than SCAN_FUSE_BLOCKS blocks) scans uint64 items with the same kernel.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t block_excl_scan_256_u64(uint64_t v, uint64_t *block_total)
+{
+    __shared__ uint64_t wsum[4];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = __shfl_up((uint32_t)inc, d, 64), hi = __shfl_up((uint32_t)(inc >> 32), d, 64);
+        if (lane >= d) inc += ((uint64_t)hi << 32) | lo;
+    }
+    if (lane == 63) wsum[wid] = inc;
+    __syncthreads();
+    uint64_t base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint64_t s = wsum[w];
+        if (w < wid) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *block_total = tot;
+    return base + inc - v;
+}
+
+template <typename In>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_block_u64_kernel(const In *in,    // may alias out (In = uint64_t)
+                                                                      uint64_t *out, uint64_t *sums, int64_t n,
+                                                                      uint64_t *total)  // single-block scans only
+{
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
+    uint64_t v[SCAN_ITEMS];
+    uint64_t tsum = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) {
+        v[k] = (base + k < n) ? (uint64_t)in[base + k] : 0ull;
+        tsum += v[k];
+    }
+    uint64_t tot;
+    uint64_t ex = block_excl_scan_256_u64(tsum, &tot);
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) {
+        if (base + k < n) out[base + k] = ex;
+        ex += v[k];
+    }
+    if (threadIdx.x == 0 && sums) sums[blockIdx.x] = tot;
+    if (threadIdx.x == 0 && total) *total = tot;
+}
+
+// (scan_finish_kernel with 64-bit sums: up to SCAN_FUSE_BLOCKS blocks, every block adds up the totals before it)
+__global__ __launch_bounds__(SCAN_THREADS) void scan_finish_u64_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ sums,
+                                                                       int64_t n, uint64_t *__restrict__ total)
+{
+    uint64_t part = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += SCAN_THREADS) part += sums[b];
+    uint64_t add;
+    (void)block_excl_scan_256_u64(part, &add);
+    if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = add + sums[blockIdx.x];
+    if (blockIdx.x == 0) return;
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k)
+        if (base + k < n) out[base + k] += add;
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void scan_add_u64_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ sums, int64_t n)
+{
+    const uint64_t add = sums[blockIdx.x];
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k)
+        if (base + k < n) out[base + k] += add;
+}
+
+// one or two launches: n items in up to SCAN_FUSE_BLOCKS blocks (sums: one uint64 per block)
+template <typename In>
+static void scan_fused_u64(const In *in, uint64_t *out, int64_t n, uint64_t *sums, uint64_t *total, hipStream_t s)
+{
+    const int64_t nb = ceil_div(n, SCAN_BLOCK);
+    if (nb == 1) {
+        hipLaunchKernelGGL(scan_block_u64_kernel<In>, dim3(1), dim3(SCAN_THREADS), 0, s, in, out, (uint64_t *)nullptr, n, total);
+    } else {
+        hipLaunchKernelGGL(scan_block_u64_kernel<In>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n, (uint64_t *)nullptr);
+        hipLaunchKernelGGL(scan_finish_u64_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n, total);
+    }
+}
+
+int exclusive_scan_u32_u64(const uint32_t *in, uint64_t *out, int64_t n, uint64_t *total, hipStream_t s)
+{
+    if (n <= 0) {
+        if (total) RAHT_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(uint64_t), s));
+        return RAHT_OK;
+    }
+    const int64_t nb = ceil_div(n, SCAN_BLOCK), nb2 = ceil_div(nb, SCAN_BLOCK);
+    // two levels reach SCAN_FUSE_BLOCKS * SCAN_BLOCK blocks of SCAN_BLOCK items: 2^33 items
+    if (nb2 > SCAN_FUSE_BLOCKS) { set_error("exclusive_scan_u32_u64: too many items"); return RAHT_ERR_INVALID; }
+    Scratch ws(sizeof(uint64_t) * (size_t)(nb + nb2), s);
+    if (!ws.ok()) return RAHT_ERR_NOMEM;
+    uint64_t *sums = ws.as<uint64_t>();
+    if (nb <= SCAN_FUSE_BLOCKS) {
+        scan_fused_u64(in, out, n, sums, total, s);
+    } else {
+        // block-local offsets and block sums; the sums scanned in place (their total is the grand total); added back
+        hipLaunchKernelGGL(scan_block_u64_kernel<uint32_t>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n, (uint64_t *)nullptr);
+        scan_fused_u64((const uint64_t *)sums, sums, nb, sums + nb, total, s);
+        hipLaunchKernelGGL(scan_add_u64_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n);
+    }
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Stable LSD radix pass. A block owns RP_BLOCK consecutive items; its 4 waves own consecutive
 // quarter-chunks and walk them in rounds of 64 (one item per lane), so "earlier" in memory order is
 // (block, wave, round, lane) -- ranks are assigned in exactly that order, which makes the pass stable.

@@ -52,7 +52,9 @@ def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=to
     inverts and accumulates the PSNR columns' sums of squares (raht_dequant_inv_sqdiff); rows then carry ``C_rec = None``.
     entropy="gpu": the RLGR stage on the device, segmented (rlgr.SegmentedCoder: every ``seg_len`` symbols of a channel an
     independent stream, byte-identical to the reference coder's output for that slice): the integers never leave the GPU, only
-    the container's bytes do (``D2H_time``). Rates then count the container (streams + 4 bytes per segment).
+    the container's bytes do (``D2H_time``). Rates then count the container (streams + 4 bytes per segment). Frames of any
+    size: above 330 M symbols (at ``seg_len = 2048``; e.g. 6 M x 56) the coder keeps 64-bit segment offsets on the device
+    (``SegmentedCoder.wide``, chosen by raht_rlgr_seg_offsets_width); smaller frames go through the 32-bit tables as before.
     batch_steps=True (entropy="gpu", float32, scalar steps): ALL steps of the frame at once -- one forward transform with every
     step's quantizer (raht_fwd_quant_multi), one set of coder launches for all steps' integers (raht_rlgr_seg_encode_batch: k times
     the independent streams, which is what the coder's speed depends on), one decoder launch; same rows, same bytes. Stage times of

@@ -177,17 +177,29 @@ class SegmentedCoder:
     segment an independent RLGR stream -- byte-identical to the reference coder's output for that slice -- one lane per
     segment. ``encode`` takes the channel-major (D, N) int32 device tensor (``transpose_on_device`` of the quantized
     coefficients) and leaves the streams on the device; ``container()`` is what goes on the wire; ``decode`` rebuilds the
-    (D, N) tensor on the device. Nothing but the compressed bytes ever crosses PCIe."""
+    (D, N) tensor on the device. Nothing but the compressed bytes ever crosses PCIe.
+
+    ``wide``: the width of the device-side offset table. ``None`` (default) asks ``raht_rlgr_seg_offsets_width``: 32-bit offsets
+    (``seg_off`` is ``torch.int32``) for every shape whose worst case stays below 4 GiB, 64-bit ones (``torch.int64``, the
+    ``raht_rlgr_seg_*64`` entry points) above -- at ``seg_len = 2048`` from 330 M symbols per frame, e.g. 6 M x 56. ``True``
+    forces the 64-bit table on any shape (same bytes), ``False`` the 32-bit one (which refuses the large shapes). The
+    container on the wire holds no offsets and is the same either way."""
     MAGIC = b"RLGS0001"
 
-    def __init__(self, N, D, seg_len=2048, flag_signed=1, device="cuda", payload_cap=None):
+    def __init__(self, N, D, seg_len=2048, flag_signed=1, device="cuda", payload_cap=None, wide=None):
         import torch
         self.N, self.D, self.S, self.flag = int(N), int(D), int(seg_len), int(flag_signed)
         self.nseg = (self.N + self.S - 1) // self.S
         self.G = self.nseg * self.D
         self.device = torch.device(device)
+        if wide is None:
+            width = _lib.lib().raht_rlgr_seg_offsets_width(self.N, self.D, self.S)
+            if width < 0:
+                check(width)
+            wide = width == 64
+        self.wide = bool(wide)
         self.seg_bytes = torch.empty(self.G, dtype=torch.int32, device=self.device)
-        self.seg_off = torch.empty(self.G + 1, dtype=torch.int32, device=self.device)
+        self.seg_off = torch.empty(self.G + 1, dtype=torch.int64 if self.wide else torch.int32, device=self.device)
         # encoder: what a raw dump would take, + slack (grown on demand); decoder (from_container): the payload it was handed
         self.cap = 4 * self.N * self.D + 64 * self.G if payload_cap is None else max(16, int(payload_cap))
         self.out = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
@@ -216,11 +228,12 @@ class SegmentedCoder:
         sym, chan = self._strides(Q, "encode")
         Qcm = Q
         tot = C.c_int64()
+        fn = _lib.lib().raht_rlgr_seg_encode64 if self.wide else _lib.lib().raht_rlgr_seg_encode_strided
         for attempt in (0, 1):
             with torch.cuda.device(self.device):
-                rc = _lib.lib().raht_rlgr_seg_encode_strided(C.c_void_p(Qcm.data_ptr()), self.N, self.D, sym, chan, self.S, self.flag,
-                                                             C.c_void_p(self.seg_bytes.data_ptr()), C.c_void_p(self.seg_off.data_ptr()),
-                                                             C.c_void_p(self.out.data_ptr()), self.cap, C.byref(tot), self._stream())
+                rc = fn(C.c_void_p(Qcm.data_ptr()), self.N, self.D, sym, chan, self.S, self.flag,
+                        C.c_void_p(self.seg_bytes.data_ptr()), C.c_void_p(self.seg_off.data_ptr()),
+                        C.c_void_p(self.out.data_ptr()), self.cap, C.byref(tot), self._stream())
             if rc == _lib.RAHT_OK or attempt == 1 or tot.value <= self.cap:
                 check(rc)
                 break
@@ -248,8 +261,9 @@ class SegmentedCoder:
         return hdr + lens.tobytes() + payload.tobytes()
 
     @classmethod
-    def from_container(cls, blob, device="cuda", max_symbols=None):
-        """max_symbols: refuse containers whose header announces more than this many symbols (N x D): decode() allocates
+    def from_container(cls, blob, device="cuda", max_symbols=None, wide=None):
+        """wide: as in the constructor; the default also takes the 64-bit table when the payload itself is 4 GiB or more.
+        max_symbols: refuse containers whose header announces more than this many symbols (N x D): decode() allocates
         4 N D bytes for them, and the header comes off the wire."""
         import torch
         m = len(cls.MAGIC)
@@ -266,13 +280,15 @@ class SegmentedCoder:
             raise ValueError("segmented RLGR container: shorter than its header says")
         if max_symbols is not None and N * D > int(max_symbols):
             raise ValueError(f"segmented RLGR container: {N} x {D} symbols, more than the caller allows ({max_symbols})")
-        sc = cls(N, D, S, flag, device, payload_cap=total)     # (the payload only: a decoder never needs the encoder's raw-size buffer)
+        if wide is None and total >= 2 ** 32:
+            wide = True
+        sc = cls(N, D, S, flag, device, payload_cap=total, wide=wide)     # (the payload only: a decoder never needs the encoder's raw-size buffer)
         lens = np.frombuffer(blob, np.uint32, sc.G, m + 40).astype(np.int64)
         if total % 4 or total > len(blob) - (m + 40 + 4 * sc.G) or int(((lens + 3) // 4 * 4).sum()) != total:
             raise ValueError("segmented RLGR container: inconsistent length table")
         off = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
         sc.seg_bytes.copy_(torch.from_numpy(lens.astype(np.int32)))
-        sc.seg_off.copy_(torch.from_numpy(off.astype(np.int64).astype(np.int32)))
+        sc.seg_off.copy_(torch.from_numpy(off.astype(np.int64) if sc.wide else off.astype(np.int64).astype(np.int32)))
         if total > sc.cap:
             sc.cap, sc.out = total, torch.empty(total, dtype=torch.uint8, device=sc.device)
         sc.out[:total].copy_(torch.from_numpy(np.frombuffer(blob, np.uint8, total, m + 40 + 4 * sc.G).copy()))
@@ -286,10 +302,11 @@ class SegmentedCoder:
         if out is None:
             out = torch.empty((self.N, self.D) if row_major else (self.D, self.N), dtype=torch.int32, device=self.device)
         sym, chan = self._strides(out, "decode")
+        fn = _lib.lib().raht_rlgr_seg_decode64 if self.wide else _lib.lib().raht_rlgr_seg_decode_strided
         with torch.cuda.device(self.device):
-            check(_lib.lib().raht_rlgr_seg_decode_strided(C.c_void_p(self.out.data_ptr()), (self.total + 3) // 4 * 4, C.c_void_p(self.seg_off.data_ptr()),
-                                                          C.c_void_p(self.seg_bytes.data_ptr()), self.N, self.D, self.S, self.flag,
-                                                          C.c_void_p(out.data_ptr()), sym, chan, C.c_void_p(self.bad.data_ptr()), self._stream()))
+            check(fn(C.c_void_p(self.out.data_ptr()), (self.total + 3) // 4 * 4, C.c_void_p(self.seg_off.data_ptr()),
+                     C.c_void_p(self.seg_bytes.data_ptr()), self.N, self.D, self.S, self.flag,
+                     C.c_void_p(out.data_ptr()), sym, chan, C.c_void_p(self.bad.data_ptr()), self._stream()))
         return out
 
     BATCH_MAX = 12                                            # RAHT_RLGR_BATCH_MAX
@@ -298,8 +315,8 @@ class SegmentedCoder:
     def _same_shape(coders, what):
         c0 = coders[0]
         for c in coders[1:]:
-            if (c.N, c.D, c.S, c.flag, c.device) != (c0.N, c0.D, c0.S, c0.flag, c0.device):
-                raise ValueError(f"SegmentedCoder.{what}: the coders of a batch share N, D, seg_len, flag and device")
+            if (c.N, c.D, c.S, c.flag, c.device, c.wide) != (c0.N, c0.D, c0.S, c0.flag, c0.device, c0.wide):
+                raise ValueError(f"SegmentedCoder.{what}: the coders of a batch share N, D, seg_len, flag, device and offset width")
         return c0
 
     @classmethod
@@ -317,6 +334,7 @@ class SegmentedCoder:
             raise ValueError("SegmentedCoder.encode_batch: the inputs of a batch share their layout and strides")
         sym, chan = st[0]
         L = _lib.lib()
+        fn = L.raht_rlgr_seg_encode_batch64 if c0.wide else L.raht_rlgr_seg_encode_batch
         for lo in range(0, len(coders), cls.BATCH_MAX):
             cs, qs = coders[lo: lo + cls.BATCH_MAX], Qs[lo: lo + cls.BATCH_MAX]
             k = len(cs)
@@ -324,9 +342,9 @@ class SegmentedCoder:
             tot = I64()
             for attempt in (0, 1):
                 with torch.cuda.device(c0.device):
-                    rc = L.raht_rlgr_seg_encode_batch(k, VP(*[q.data_ptr() for q in qs]), c0.N, c0.D, sym, chan, c0.S, c0.flag,
-                                                      VP(*[c.seg_bytes.data_ptr() for c in cs]), VP(*[c.seg_off.data_ptr() for c in cs]),
-                                                      VP(*[c.out.data_ptr() for c in cs]), I64(*[c.cap for c in cs]), tot, c0._stream())
+                    rc = fn(k, VP(*[q.data_ptr() for q in qs]), c0.N, c0.D, sym, chan, c0.S, c0.flag,
+                            VP(*[c.seg_bytes.data_ptr() for c in cs]), VP(*[c.seg_off.data_ptr() for c in cs]),
+                            VP(*[c.out.data_ptr() for c in cs]), I64(*[c.cap for c in cs]), tot, c0._stream())
                 if rc == _lib.RAHT_OK or attempt == 1 or all(int(tot[j]) <= cs[j].cap for j in range(k)):
                     check(rc)
                     break
@@ -371,11 +389,13 @@ class SegmentedCoder:
                     c0.N, c0.D, c0.S, c0.flag, VP(*[o.data_ptr() for o in os_]))
             bad = cs[0].bad                                       # (every chunk reports into its own first coder)
             with torch.cuda.device(c0.device):
-                if expect is None:
+                if expect is None and c0.wide:
+                    check(L.raht_rlgr_seg_decode_batch64(*args, None, sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
+                elif expect is None:
                     check(L.raht_rlgr_seg_decode_batch(*args, sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
                 else:
                     ex = expect[lo: lo + cls.BATCH_MAX]
-                    check(L.raht_rlgr_seg_decode_batch_check(*args, VP(*[e.data_ptr() for e in ex]), sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
+                    check((L.raht_rlgr_seg_decode_batch64 if c0.wide else L.raht_rlgr_seg_decode_batch_check)(*args, VP(*[e.data_ptr() for e in ex]), sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
         return outs
 
     @classmethod
