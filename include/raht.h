@@ -683,6 +683,47 @@ int raht_sqdiff_columns(const void *A, int64_t lda, const void *B, int64_t ldb, 
  * round-trip assertion, python/encode_3dgs.py:242-245, on 10^8 symbols). */
 int raht_i32_equal(const int32_t *a, const int32_t *b, int64_t n, int nthreads, int64_t *first_diff);
 
+/* ------------------------------------------------------------------------------------------------
+ * Octree geometry (csrc/octree.hip): the lossless code of the occupied voxels, i.e. of the sorted Morton keys every plan is
+ * built from. With it a frame leaves the machine as bytes that decode on their own (python: geometry.py, bitstream.py).
+ *
+ * Input: N >= 1 strictly ascending keys < 8^J, 1 <= J <= 21, digits as raht_morton writes them (digit = z + 2 y + 4 x, the
+ * finest digit in bits 0-2).
+ *   node of level g (0 = root ... J = voxel) : a distinct value of key >> 3 (J - g); n_g of them, n_0 = 1, n_J = N
+ *   occupancy byte of an internal node       : bit d set <=> the child with digit d exists (never 0)
+ *   occupancy stream                         : the bytes of level 0, then level 1, ... level J - 1, ascending key order inside
+ *                                              a level; n_nodes = n_0 + ... + n_(J-1) bytes
+ *   geometry section  : "OCTG0001" | int64 J, N, mode, n_nodes, seg_len | int64 n_0 ... n_J | body
+ *                       mode 0: the n_nodes bytes. mode 1: byte_of_rank[256], then the body of a segmented RLGR container
+ *                       (raht_rlgr_seg_*) of ONE unsigned channel of n_nodes symbols: the uint32 length of every segment, then
+ *                       the streams in 4-byte slots. Symbol = rank of the occupancy byte; ranks by descending count over the
+ *                       whole stream, ties by ascending byte value, so the table is unique. Byte 0 never occurs: its rank is the
+ *                       number of byte values in use, and a symbol at or above it is an error.
+ *   frame container   : "RAHTF001" | int64 J, N, D, n_wide, n_steps | float64 steps[n_steps] | float64 vmin[3], width |
+ *                       int64 length + geometry section | int64 length + the attribute container ("RLGS0001" ...).
+ *                       n_wide = 0: the float32 path (raht_fwd_quant / raht_dequant_inv, steps cast to float32 on both sides);
+ *                       n_wide > 0: the mixed path (raht_fwd_quant_mixed / raht_dequant_inv_mixed, float64 steps).
+ *
+ *   raht_octree_counts  : counts[0 .. J] (HOST) = n_0 ... n_J from one pass over the keys, which also checks them:
+ *                         RAHT_ERR_INVALID when they are not strictly ascending or not below 8^J. Synchronises (it returns sizes).
+ *   raht_octree_encode  : occ[n_nodes] from the keys and the counts of raht_octree_counts. Level by level, bottom-up; enqueues only.
+ *   raht_octree_decode  : keys[counts[J]] from the stream. counts (HOST) come from a header: they must satisfy n_0 = 1,
+ *                         n_g <= n_(g+1) <= 8 n_g < 2^31 (RAHT_ERR_INVALID otherwise) and size everything -- no synchronisation,
+ *                         and EVERY store is bounded by them whatever the bytes say. A zero byte, or a level whose popcounts do
+ *                         not add up to the next count, sets *bad (DEVICE int32, never cleared here); keys then hold garbage.
+ *   raht_octree_symbols : sym[i] (DEVICE int32) = rank of occ[i]; byte_of_rank[256] (HOST) = the table. Synchronises.
+ *   raht_octree_bytes   : the inverse with a table from a header (HOST; must be a permutation of 0 .. 255); a symbol outside
+ *                         the ranks in use sets *bad and decodes as 0. Enqueues only.
+ *   raht_demorton       : V (N x 3 int64) from keys: the inverse of raht_morton.
+ * All pointers DEVICE unless marked HOST; sym 4-byte aligned. */
+int raht_octree_counts(const uint64_t *keys_sorted, int64_t N, int J, int64_t *counts, raht_stream_t stream);
+int raht_octree_encode(const uint64_t *keys_sorted, int64_t N, int J, const int64_t *counts, uint8_t *occ, raht_stream_t stream);
+int raht_octree_decode(const uint8_t *occ, const int64_t *counts, int J, uint64_t *keys, int32_t *bad, raht_stream_t stream);
+int raht_octree_symbols(const uint8_t *occ, int64_t n_nodes, uint8_t *byte_of_rank, int32_t *sym, raht_stream_t stream);
+int raht_octree_bytes(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_of_rank, uint8_t *occ, int32_t *bad,
+                      raht_stream_t stream);
+int raht_demorton(const uint64_t *keys, int64_t N, int J, int64_t *V, raht_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -877,6 +877,19 @@ def get_morton_code(V, J):
 
 
 @torch.no_grad()
+def demorton(keys, J):
+    """Inverse of ``get_morton_code``: (N,) int64 / uint64 Morton keys on the GPU -> (N, 3) int64 voxel coordinates."""
+    _need_cuda(keys, "keys")
+    if keys.dtype not in (torch.int64, torch.uint64) or keys.dim() != 1:
+        raise ValueError("keys must be a 1-D int64/uint64 tensor")
+    k = keys.contiguous()
+    out = torch.empty((k.shape[0], 3), dtype=torch.int64, device=k.device)
+    with torch.cuda.device(k.device):
+        check(_lib.lib().raht_demorton(C.c_void_p(k.data_ptr()), k.shape[0], int(J), C.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+@torch.no_grad()
 def voxel_keys(PC, vmin, width, J):
     """Unsorted 3J-bit Morton keys (int64) of the points of PC (n, >= 3) float32 for a given bounding box: the
     voxelizer's first phase (reference python/voxelize_pc.py:92-100)."""
