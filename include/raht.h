@@ -662,6 +662,32 @@ int raht_rlgr_seg_decode_batch64(int k, const uint8_t *const *in, const int64_t 
                                  int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride, int64_t chan_stride,
                                  uint32_t *bad_dev, raht_stream_t stream);
 
+/* The SIZE of that container at k quantization steps, and the squared quantization error beside it, from ONE read of the
+ * coefficients (csrc/rlgr_rate.hip): the rate-distortion curve of a frame without a quantized matrix, a slot buffer or a stream
+ * being written. A lane walks one segment of one channel and advances up to RAHT_RLGR_RATE_MAX independent coder states, each
+ * quantizing the coefficient it loaded with its own step and COUNTING the bits the coder above would emit (larger k: several
+ * passes, RAHT_RLGR_RATE_MAX steps each).
+ *   T        : DEVICE, N x D coefficients of dtype RAHT_F32 or RAHT_F64 in CODED order (row i is row i of the quantized matrix:
+ *              behind the order_RAGFT reorder), row-major, row stride ldt >= D elements
+ *   steps    : HOST, k x n_steps values of T's dtype, n_steps 1 or D: step j of channel c = steps[j * n_steps + (n_steps == 1 ? 0 : c)]
+ *   seg_bytes: DEVICE uint32[k * G], G = D * ceil(N / seg_len), segment g = c * nseg + s as above. seg_bytes[j * G + g] = unpadded
+ *              length of the RLGR stream of q = floor(T / step_j + 0.5) over symbols [s * seg_len, min(N, (s + 1) * seg_len)) of channel
+ *              c: entry for entry the seg_bytes table raht_rlgr_seg_encode_strided leaves for the matrix raht_quant_rows (float32) /
+ *              raht_quant_rows_f64 (float64) makes of the same T and step. The container of step j then takes
+ *              8 + 40 + 4 G + sum over g of ((seg_bytes[j * G + g] + 3) & ~3) bytes.
+ *   seg_sse  : DEVICE double[k * G] or NULL (not computed): seg_sse[j * G + g] = sum over the segment's symbols, in symbol order,
+ *              of ((double)T - (double)q * (double)step_j)^2 -- a fixed order: deterministic.
+ * RAHT_ERR_INVALID (nothing enqueued, no device touched): T, steps or seg_bytes NULL; an unknown dtype; N < 1, D < 1, ldt < D, k < 1,
+ * n_steps not 1 or D; a (N, D, seg_len) raht_rlgr_seg_encode_strided refuses (seg_len < 64, 2^31 segments, a worst case of 4 GiB);
+ * flag_signed not 0 or 1; a step that is not finite and positive, or, float32, outside [2^-100, 2^100] (the range in which the
+ * float32 quantizer's division needs no scaling). Quotients beyond int32 are undefined, as in every quantizer of this library.
+ * Device memory: the k * n_steps steps, nothing else. Enqueues only: `steps` goes to the device with an asynchronous copy on
+ * `stream`, which has read pageable memory by the time the call returns; a table in page-locked memory must stay unchanged
+ * until the stream has passed this call. */
+#define RAHT_RLGR_RATE_MAX 8     /* steps walked per pass; larger k is chunked inside */
+int raht_rlgr_seg_rate(const void *T, int dtype, int64_t ldt, int64_t N, int D, const void *steps, int k, int n_steps, int seg_len,
+                       int flag_signed, uint32_t *seg_bytes, double *seg_sse, raht_stream_t stream);
+
 /* How the decoders' symbols leave the lanes: -1 = chosen by the number of lanes in flight (default: one 4-byte store per symbol
  * below 200 000 lanes, where the L2 still gathers a lane's line; above, a 16-word LDS column per lane written out as aligned
  * 64-byte pieces -- with the steps of a frame decoded together the one-word stores cost 5.9 x the symbols' bytes in HBM writes),

@@ -56,12 +56,97 @@ def encode_frame_bytes(V_int, attributes, J, step, device="cuda", n_wide=0, seg_
         sc = SegmentedCoder(N, D, seg_len, 1, dev)
         sc.encode(Q)
         att = sc.container()
+    return _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att)
+
+
+def _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att):
     box = [0.0, 0.0, 0.0] if vmin is None else [float(x) for x in vmin]
     if len(box) != 3:
         raise ValueError("encode_frame_bytes: vmin must have 3 entries")
     box.append(0.0 if width is None else float(width))
     return (MAGIC + np.array([J, N, D, n_wide, len(steps)], np.int64).tobytes() + np.array(steps + box, np.float64).tobytes()
             + np.array([len(geo)], np.int64).tobytes() + geo + np.array([len(att)], np.int64).tobytes() + att)
+
+
+def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scale_range=(2 ** -10, 2 ** 10), rounds=3, n_wide=0,
+                              seg_len=2048, geometry="rlgr", vmin=None, width=None, device="cuda"):
+    """A frame in at most ``target_bytes`` bytes: the quantization table is ``step * m`` (``step``: a scalar or one entry per column)
+    and the multiplier m is the smallest the search finds inside ``scale_range`` whose frame fits. The geometry is coded once; every
+    round asks ``RahtPlan.rate_curve`` for the exact attribute bytes at ``SegmentedCoder.RATE_MAX`` geometrically spaced multipliers
+    (one transform, one read of the coefficients, nothing coded), takes the smallest that fits and narrows the bracket to
+    (the next finer grid point, that one]. RLGR sizes need not be monotone in the step: taking a grid point that was SEEN to fit
+    keeps the result valid whatever the curve looks like. The frame is then coded by the ordinary path at the chosen table and its
+    length checked; should it not fit (it cannot while the sizes are exact), the next coarser multiplier that was tried is taken.
+    -> (blob, info): an ordinary RAHTF001 frame for ``decode_frame_bytes``; info: multiplier, steps, predicted_attribute_bytes,
+    attribute_bytes, tried (every (multiplier, bytes) in evaluation order), sse (float64 [D] at the chosen point).
+    ``ValueError`` when the geometry alone exceeds the target or not even the coarsest multiplier fits."""
+    import torch
+    from . import ops
+    dev = torch.device(device)
+    J = int(J)
+    target = int(target_bytes)
+    V = torch.as_tensor(V_int).to(dev, torch.int64)
+    A = torch.as_tensor(attributes).to(dev, torch.float32)
+    if V.dim() != 2 or V.shape[1] != 3 or A.dim() != 2 or A.shape[0] != V.shape[0] or V.shape[0] < 1:
+        raise ValueError("encode_frame_bytes_target: expected (N, 3) coordinates and (N, D) attributes, N >= 1")
+    if not 1 <= J <= MAX_J:
+        raise ValueError("encode_frame_bytes_target: J outside 1 .. 21")
+    N, D = A.shape
+    n_wide = int(n_wide)
+    if not 0 <= n_wide <= D:
+        raise ValueError("encode_frame_bytes_target: n_wide outside 0 .. D")
+    base = _step_list(SegmentedCoder.step_row(step), D)                  # (any scalar or sequence, as rate and rate_curve take them)
+    lo, hi = float(scale_range[0]), float(scale_range[1])
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi) or int(rounds) < 1:
+        raise ValueError("encode_frame_bytes_target: scale_range must be 0 < lo <= hi, rounds >= 1")
+    K = SegmentedCoder.RATE_MAX
+    with torch.cuda.device(dev):
+        keys = ops.get_morton_code(V, J)
+        geo = OctreeCoder.encode(keys, J, entropy=geometry)               # (also refuses rows that are not sorted and unique)
+        # the frame around the attribute container: header, steps + box, the geometry section and the two length words
+        budget = target - (len(MAGIC) + 40 + 8 * (len(base) + 4)) - (8 + len(geo)) - 8
+        if budget < 0:
+            raise ValueError(f"encode_frame_bytes_target: the geometry section and the header alone take {target - budget} bytes, target {target}")
+        plan = ops.RahtPlan.from_keys(keys, 3 * J)
+        tried, sse_of, fits = [], {}, {}
+        chosen = None
+        for rnd in range(int(rounds)):
+            if rnd == 0:                                                 # the whole range, both ends included
+                grid = [lo] if hi == lo else [lo * (hi / lo) ** (i / (K - 1)) for i in range(K - 1)] + [hi]
+            else:                                                        # strictly inside (lo, hi): lo did not fit, hi = chosen did
+                grid = [lo * (hi / lo) ** ((i + 1) / (K + 1)) for i in range(K)]
+            rc = plan.rate_curve(A, [[s * m for s in base] for m in grid], n_wide, seg_len)
+            for m, nb, e in zip(grid, rc["bytes"], rc["sse"]):
+                tried.append((m, int(nb)))
+                sse_of[m] = e
+                fits[m] = int(nb) <= budget
+            ok = [i for i, m in enumerate(grid) if fits[m]]
+            if not ok:
+                break                                                    # round 0: nothing fits at all; later: hi stays the answer
+            i = ok[0]
+            chosen = grid[i]
+            if i == 0 and rnd == 0:
+                break                                                    # the finest multiplier of the range fits
+            lo, hi = (grid[i - 1] if i else lo), chosen
+            if not lo < hi:
+                break
+        if chosen is None:
+            raise ValueError(f"encode_frame_bytes_target: no multiplier in [{scale_range[0]}, {scale_range[1]}] brings the attributes "
+                             f"below {budget} bytes (smallest seen: {min(b for _, b in tried)})")
+        predicted = dict(tried)
+        # the candidates that were seen to fit, from the chosen one towards coarser steps
+        for m in sorted(x for x in fits if fits[x] and x >= chosen):
+            steps = [s * m for s in base]
+            Q = plan.forward_quant_mixed(A, steps, n_wide) if n_wide else plan.forward_quant(A, steps)
+            sc = SegmentedCoder(N, D, seg_len, 1, dev)
+            sc.encode(Q)
+            att = sc.container()
+            blob = _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att)
+            if len(blob) <= target:
+                info = dict(multiplier=m, steps=steps, predicted_attribute_bytes=predicted[m], attribute_bytes=len(att), tried=tried,
+                            sse=sse_of[m])
+                return blob, info
+    raise ValueError("encode_frame_bytes_target: no candidate that was predicted to fit did fit")
 
 
 def parse_frame(blob, max_voxels=None):

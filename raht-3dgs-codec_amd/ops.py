@@ -506,6 +506,63 @@ class RahtPlan:
                 self._reset_mixed_roots()
         return out, ssd
 
+    def rate_curve(self, Cmat, steps, n_wide=0, seg_len=2048):
+        """The rate-distortion curve of a frame from ONE forward transform and one read of its coefficients: for each of the k
+        ``steps`` (scalars, or tables of D entries) the bytes of the attribute container ``bitstream.encode_frame_bytes`` would write
+        (``SegmentedCoder.size_bytes`` of ``forward_quant(C, step)``; with ``n_wide`` > 0 of ``forward_quant_mixed(C, step, n_wide)``)
+        and the squared quantization error per column, in the coefficient domain -- RAHT is orthonormal, so up to the transform's
+        rounding this is the attributes' squared error. Nothing is quantized, coded or written but two small tables
+        (rlgr.SegmentedCoder.rate). -> {"bytes": int64 numpy [k], "sse": float64 numpy [k, D]}.
+        ``n_wide`` > 0: the first n_wide columns through the float64 transform (the mixed kernels' integers on those columns are
+        the float64 path's), the others through the float32 one. Row-mapped and truncated plans raise ``ValueError``."""
+        from .rlgr import SegmentedCoder
+        _need_cuda(Cmat, "C")
+        if self.map_rows is not None or self.n_roots != 1:
+            raise ValueError("rate_curve: not available for row-mapped or truncated plans")
+        n_wide = int(n_wide)
+        if Cmat.dim() != 2 or Cmat.shape[0] != self.N or not 0 <= n_wide <= Cmat.shape[1]:
+            raise ValueError(f"rate_curve: expected an ({self.N}, D) matrix and 0 <= n_wide <= D")
+        D = int(Cmat.shape[1])
+        rows = []
+        for st in steps:
+            r = SegmentedCoder.step_row(st)
+            if len(r) not in (1, D):
+                raise ValueError("rate_curve: every step must be a scalar or have D entries")
+            rows.append(r * D if len(r) == 1 else r)
+        if not rows:
+            raise ValueError("rate_curve: no steps")
+        k = len(rows)
+        scalar = all(len(set(r)) == 1 for r in rows)
+        order = self.order_RAGFT
+        parts = []                                                   # (column range, coefficients in coded order)
+        with torch.cuda.device(self.device):
+            # the float32 transform runs over all D columns, as forward_quant_mixed's float32 launches do (tests/test_gpu_rate.py
+            # holds the sizes to that path's integers exactly); transforming columns [n_wide, D) alone gives the same bits
+            # (DESIGN.md 15) but needs a contiguous copy of them first, which moves what it saves: 3 of 59 columns for a frame
+            if n_wide:
+                Tw = self.forward(Cmat[:, :n_wide].to(torch.float64).contiguous(), want_w=False)
+                Twq = torch.empty_like(Tw)
+                rows_gather(Tw, order, Twq)
+                parts.append((0, n_wide, Twq))
+                del Tw
+            if n_wide < D:
+                T = self.forward(Cmat.to(torch.float32), want_w=False)
+                Tq = torch.empty_like(T)
+                rows_gather(T, order, Tq)
+                parts.append((n_wide, D, Tq[:, n_wide:] if n_wide else Tq))
+                del T
+            payload = 0
+            sse = torch.empty((k, D), dtype=torch.float64, device=self.device)
+            G = 0
+            for lo, hi, Tp in parts:
+                st = [r[lo] for r in rows] if scalar else [r[lo:hi] for r in rows]
+                nbytes, seg_bytes, e = SegmentedCoder.rate(Tp, st, seg_len, 1, True)
+                Gp = seg_bytes.shape[1]
+                payload = payload + (nbytes - SegmentedCoder.container_size(Gp, 0))     # (the padded streams of this part)
+                G += Gp
+                sse[:, lo:hi] = e
+        return {"bytes": SegmentedCoder.container_size(G, payload), "sse": sse.cpu().numpy()}
+
     def mixed_stats(self, D=59, n_wide=3):
         """Tile rows and rows per stage of the mixed-precision schedule (tile_rows 0: the shape takes the two-pass path)."""
         tr, ns = C.c_int(0), C.c_int(0)

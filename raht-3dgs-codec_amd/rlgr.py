@@ -408,6 +408,56 @@ class SegmentedCoder:
             out += [lo + j for j in range(min(cls.BATCH_MAX, len(coders) - lo)) if (w >> j) & 1 or (w >> (16 + j)) & 1]
         return out
 
+    RATE_MAX = 8                                              # RAHT_RLGR_RATE_MAX: steps walked per pass over the coefficients
+
+    @staticmethod
+    def rate(T, steps, seg_len=2048, flag_signed=1, want_sse=True):
+        """How many bytes the container takes at every one of k quantization steps, WITHOUT quantizing or coding anything
+        (raht_rlgr_seg_rate): one read of the coefficients, k coder states per lane that only count their bits.
+        T: (N, D) float32 or float64 CUDA tensor with unit column stride, rows in coded order (row i is row i of the quantized
+        matrix); steps: k scalars or k tables of D entries, in T's precision.
+        -> (container_bytes int64 numpy [k], seg_bytes (k, G) int32 CUDA tensor, sse (k, D) float64 CUDA tensor or None):
+        ``container_bytes[j]`` is ``size_bytes`` of a coder that encoded floor(T / steps[j] + 0.5), ``seg_bytes[j]`` its length table,
+        ``sse[j, c]`` the sum over channel c of (T - q * step)^2 in float64. Synchronises (it returns sizes)."""
+        import torch
+        if not isinstance(T, torch.Tensor) or not T.is_cuda or T.dim() != 2 or T.dtype not in (torch.float32, torch.float64) or \
+                (T.shape[1] > 1 and T.stride(1) != 1) or T.shape[0] < 1 or T.shape[1] < 1 or (T.shape[0] > 1 and T.stride(0) < T.shape[1]):
+            raise ValueError("SegmentedCoder.rate: expected an (N, D) float32 or float64 CUDA tensor with unit column stride")
+        N, D = int(T.shape[0]), int(T.shape[1])
+        f64 = T.dtype == torch.float64
+        rows = [SegmentedCoder.step_row(st) for st in steps]
+        k = len(rows)
+        if k < 1 or any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) not in (1, D):
+            raise ValueError("SegmentedCoder.rate: steps must be k scalars or k tables of D entries")
+        n_steps = len(rows[0])
+        flat = [x for r in rows for x in r]
+        st = ((C.c_double if f64 else C.c_float) * len(flat))(*flat)
+        S = int(seg_len)
+        G = ((N + S - 1) // S) * D if S > 0 else 0
+        seg_bytes = torch.empty((k, max(G, 1)), dtype=torch.int32, device=T.device)
+        seg_sse = torch.empty((k, max(G, 1)), dtype=torch.float64, device=T.device) if want_sse else None
+        with torch.cuda.device(T.device):
+            check(_lib.lib().raht_rlgr_seg_rate(C.c_void_p(T.data_ptr()), _lib.RAHT_F64 if f64 else _lib.RAHT_F32, T.stride(0) if N > 1 else D,
+                                                N, D, st, k, n_steps, S, int(flag_signed), C.c_void_p(seg_bytes.data_ptr()),
+                                                C.c_void_p(seg_sse.data_ptr()) if want_sse else None,
+                                                C.c_void_p(torch.cuda.current_stream(T.device).cuda_stream)))
+        sse = seg_sse.view(k, D, G // D).sum(dim=2) if want_sse else None          # (segments of a channel in segment order)
+        padded = (seg_bytes.to(torch.int64) + 3) // 4 * 4
+        container = SegmentedCoder.container_size(G, padded.sum(dim=1).cpu().numpy())
+        return container, seg_bytes, sse
+
+    @staticmethod
+    def step_row(st):
+        """one quantization step as a list of floats: [st] for a scalar (Python or numpy number, 0-d array or tensor), else its
+        entries"""
+        return [float(st)] if np.ndim(st) == 0 else [float(x) for x in st]
+
+    @staticmethod
+    def container_size(G, payload):
+        """``size_bytes`` of a container of G segments whose padded streams take ``payload`` bytes (number or array); with
+        ``payload`` 0 what the container takes besides its streams"""
+        return len(SegmentedCoder.MAGIC) + 5 * 8 + 4 * int(G) + np.asarray(payload, np.int64)
+
     def segment(self, c, s):
         """the bytes of segment s of channel c (host copy; tests)"""
         g = c * self.nseg + s

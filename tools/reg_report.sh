@@ -1,5 +1,6 @@
 #!/bin/bash
-# VGPRs / spills / occupancy of every tile and top kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
+# VGPRs / SGPRs / spills / occupancy of every tile, top and rate kernel instantiation of a source file (default transform.hip;
+# hipcc -Rpass-analysis=kernel-resource-usage).
 # Any spill is a regression: a kernel that touches scratch at all lost 30 %.
 cd "$(dirname "$0")/../raht-3dgs-codec_amd/csrc" || exit 1
 # a private object file: a fixed name under /tmp can belong to another user of the machine
@@ -12,13 +13,13 @@ cur=None; rows=[]
 for line in sys.stdin:
     m=re.search(r'Function Name: (\S+)', line)
     if m: cur={'name':m.group(1)}; rows.append(cur); continue
-    for k,pat in (('vgpr',r' VGPRs: (\d+)'),('spill',r'VGPRs Spill: (\d+)'),('occ',r'Occupancy \[waves/SIMD\]: (\d+)'),('scratch',r'ScratchSize \[bytes/lane\]: (\d+)')):
+    for k,pat in (('vgpr',r' VGPRs: (\d+)'),('sgpr',r'SGPRs: (\d+)'),('spill',r'VGPRs Spill: (\d+)'),('occ',r'Occupancy \[waves/SIMD\]: (\d+)'),('scratch',r'ScratchSize \[bytes/lane\]: (\d+)')):
         m=re.search(pat,line)
         if m and cur is not None: cur[k]=int(m.group(1))
 import subprocess
 for r in rows:
-    if 'tile_kernel' in r['name'] or 'top_kernel' in r['name']:
+    if any(k in r['name'] for k in ('tile_kernel', 'top_kernel', 'rate_kernel')):
         d=subprocess.run(['c++filt',r['name']],capture_output=True,text=True).stdout.strip()
         d=re.sub(r'\(.*','',d).replace('void raht::','')
-        print(f\"{d:48s} vgpr {r.get('vgpr')} spill {r.get('spill')} scratch {r.get('scratch')} occ {r.get('occ')}\")
+        print(f\"{d:48s} vgpr {r.get('vgpr')} sgpr {r.get('sgpr')} spill {r.get('spill')} scratch {r.get('scratch')} occ {r.get('occ')}\")
 "
