@@ -691,11 +691,13 @@ int raht_rlgr_seg_rate(const void *T, int dtype, int64_t ldt, int64_t N, int D, 
 /* How the decoders' symbols leave the lanes: -1 = chosen by the number of lanes in flight (default: one 4-byte store per symbol
  * below 200 000 lanes, where the L2 still gathers a lane's line; above, a 16-word LDS column per lane written out as aligned
  * 64-byte pieces -- with the steps of a frame decoded together the one-word stores cost 5.9 x the symbols' bytes in HBM writes),
- * 0 = words, 1 = 16-byte register groups, 2 = LDS columns. Same output in every mode (tests walk all of them); a tuning and
- * testing knob, process-wide. Returns the previous setting. */
+ * 0 = words, 2 = LDS columns. Row-major output: 4 = from the per-lane decoder with strided stores, 3 = from the symbol-synchronous
+ * one again (the default). Any other value restores the default, as -1 does. Same output in every mode (tests walk all of them); a
+ * testing hook, process-wide. Returns the previous setting. */
 int raht_debug_rlgr_decode_out(int mode);
-/* The same for the words of the batched ENCODER's streams on their way into its slots: -1 = by the lanes in flight, 0 = one
- * 4-byte store per word, 2 = LDS columns, 64-byte pieces (9 steps of a 3 M x 56 frame: 0.79 -> 0.71 ms per step). */
+/* The same for the words of the ENCODER's streams on their way into its slots (one frame or k, by the lanes in flight as above):
+ * -1 = by the lanes in flight, 0 = one 4-byte store per word, 2 = LDS columns, 64-byte pieces (9 steps of a 3 M x 56 frame:
+ * 0.79 -> 0.71 ms per step). */
 int raht_debug_rlgr_encode_out(int mode);
 
 /* out[c] = sum over rows of (A[i, c] - B[i, c])^2, DEVICE double[D]: what the drivers' five PSNR columns are made of

@@ -16,6 +16,7 @@
 // the sequential coder leaves issue slots empty (a wave per SIMD waits out every dependent instruction), the others fill them.
 #include "raht_common.h"
 #include "raht_device.h"
+#include "rlgr_seg_lane.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,7 +24,10 @@
 namespace raht {
 namespace rlgr_rate {
 
-constexpr uint32_t L = 4, U0 = 3, U1 = 2;        // membuf.h:18-22 (D0 = D1 = 1 are folded below, as in rlgr_seg.hip)
+using rlgr_seg::L;
+using rlgr_seg::U0;
+using rlgr_seg::U1;
+static_assert(rlgr_seg::D0 == 1 && rlgr_seg::D1 == 1, "Chain::step folds the two decrements, as rlgr_seg.hip does");
 constexpr int KMAX = RAHT_RLGR_RATE_MAX;
 
 // one coder state (membuf.cpp:340-423 without the bits)
@@ -73,21 +77,18 @@ template <> struct Quant<double> {
     __device__ __forceinline__ int32_t q(double x) const { return quantize_one_f64(x, sp); }
 };
 
-// thread t -> (s, c) = (t / D, t % D), as the row-major encoder: the lanes of a wave are neighbouring channels at the same
-// position of their segments. steps: DEVICE, kact x n_steps; chains j >= kact repeat chain kact - 1 and are not stored.
+// thread -> segment as the row-major encoder (SegLane): the lanes of a wave are neighbouring channels at the same position of
+// their segments. steps: DEVICE, kact x n_steps; chains j >= kact repeat chain kact - 1 and are not stored.
 // seg_bytes / seg_sse: already offset to the first step of this launch; row j at + j * G.
 template <typename T, int KS, bool SSE>
 __global__ __launch_bounds__(64) void seg_rate_kernel(const T *__restrict__ X, int64_t ldt, int64_t N, int D, int S, int nseg, int flag_signed,
                                                       const T *__restrict__ steps, int n_steps, int kact, uint32_t *__restrict__ seg_bytes,
                                                       double *__restrict__ seg_sse)
 {
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    const int64_t G = (int64_t)D * nseg;
-    if (t >= G) return;
-    const int s = (int)(t / D), c = (int)(t - (int64_t)s * D);
-    const int64_t g = (int64_t)c * nseg + s;
-    const int64_t i0 = (int64_t)s * S;
-    const int n = (int)min((int64_t)S, N - i0);
+    rlgr_seg::SegLane ln;
+    if (!ln.init(N, D, S, nseg, true)) return;
+    const int64_t G = (int64_t)D * nseg, g = ln.g;
+    const int c = ln.c, n = ln.n;
     Chain ch[KS];
     Quant<T> qz[KS];
     double sse[KS];
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(64) void seg_rate_kernel(const T *__restrict__ X, i
         qz[j].set(steps[(int64_t)min(j, kact - 1) * n_steps + (n_steps == 1 ? 0 : c)]);
         sse[j] = 0.0;
     }
-    const T *rp = X + i0 * ldt + c;                                  // (walked by pointer: a 64-bit multiply per symbol otherwise)
+    const T *rp = X + ln.at(ldt, 1);                                 // (walked by pointer: a 64-bit multiply per symbol otherwise)
     T nxt = *rp;                                                     // n >= 1
     for (int i = 0; i < n; ++i) {
         const T x = nxt;

@@ -14,13 +14,10 @@
 // table + concatenated segments) is this repo's: the reference has no segmented format. Cost of the restarts: the coder
 // re-adapts within a few dozen symbols; tests / DESIGN.md quote the measured size difference.
 #include "raht_common.h"
-
-#include <cstdlib>
+#include "rlgr_seg_lane.h"
 
 namespace raht {
 namespace rlgr_seg {
-
-constexpr uint32_t L = 4, U0 = 3, D0 = 1, U1 = 2, D1 = 1;
 
 // MSB-first bit writer, same byte stream as membuf::write / flush (and as BitWriter of rlgr.hip): < 32 bits pending after
 // every put, whole 32-bit words leave big-endian. WRITE = false only counts. `out` is 4-byte aligned.
@@ -305,16 +302,13 @@ struct DevBitReaderT {
 // OUT_LDS: a lane parks its symbols in a 16-word column of LDS ([16][64] words: the bank is the lane, no conflicts) and
 // writes them as one aligned 64-byte piece (4 x 16 bytes, back to back) whenever the column is full. Needs unit symbol stride
 // and 16-byte aligned segment starts.
-// OUT_VEC (kept behind a switch, round 3): four symbols buffered in registers, 16-byte stores -- slower than OUT_WORD on one
-// frame (the component selects cost more than the stores save).
-enum { OUT_WORD = 0, OUT_VEC = 1, OUT_LDS = 2 };
+enum { OUT_WORD = 0, OUT_LDS = 2 };
 constexpr int DEC_LDS_WORDS = 16 * 64;
 
 template <int OUT, bool LDSIN = false>
 __device__ __forceinline__ void decode_segment(const uint32_t *in32, uint32_t nbytes, int n, int flag_signed, int32_t *__restrict__ seq, int64_t sstr = 1,
                                                int32_t *lds = nullptr, int32_t *lds_in = nullptr, int64_t hi_words = 0)
 {
-    constexpr bool VEC = OUT == OUT_VEC;
     DevBitReaderT<LDSIN> r;
     r.in32 = in32; r.size = nbytes;
     if (LDSIN) { r.col = (uint32_t *)lds_in + (threadIdx.x & 63); r.w0 = (uint32_t)(((uintptr_t)in32 & 31) >> 2); r.hi_words = hi_words; }
@@ -323,7 +317,6 @@ __device__ __forceinline__ void decode_segment(const uint32_t *in32, uint32_t nb
     // than a 64-bit decoder would, inside the same bounds (every store is at i < n, every read below `size`).
     uint32_t k_P = 0, k_RP = 2 * L;
     int i = 0;
-    int4 buf = make_int4(0, 0, 0, 0);
     int32_t *col = lds + (threadIdx.x & 63);                          // OUT_LDS: this lane's column
     auto emit = [&](int32_t v) {
         if (OUT == OUT_LDS) {
@@ -336,11 +329,6 @@ __device__ __forceinline__ void decode_segment(const uint32_t *in32, uint32_t nb
 #pragma unroll
                 for (int q = 0; q < 4; ++q) *(int4 *)(seq + i - 16 + 4 * q) = x[q];
             }
-        } else if (VEC) {
-            const int q = i & 3;
-            if (q == 0) buf.x = v; else if (q == 1) buf.y = v; else if (q == 2) buf.z = v; else buf.w = v;
-            ++i;
-            if ((i & 3) == 0) *(int4 *)(seq + i - 4) = buf;
         } else {
             seq[(int64_t)i * sstr] = v;
             ++i;
@@ -375,12 +363,6 @@ __device__ __forceinline__ void decode_segment(const uint32_t *in32, uint32_t nb
     if (OUT == OUT_LDS && (i & 15)) {                                // the last, partial column
         const int b = i & ~15;
         for (int q = 0; q < (i & 15); ++q) seq[b + q] = col[q * 64];
-    }
-    if (VEC && (i & 3)) {                                            // the last, partial group (n not a multiple of four)
-        const int b = i & ~3;
-        seq[b] = buf.x;
-        if ((i & 3) > 1) seq[b + 1] = buf.y;
-        if ((i & 3) > 2) seq[b + 2] = buf.z;
     }
 }
 
@@ -450,36 +432,22 @@ __device__ __forceinline__ bool decode_segment_sync(const uint32_t *in32, uint32
 }
 static_assert(D0 == 1 && D1 == 1, "decode_segment_sync folds the two decrements");
 
-// which way the decoded symbols leave (see OUT_*): RAHT_RLGR_DECODE_OUT=word|vec|lds overrides (A/B knob)
-// Default: by the number of lanes in flight. One 3 M x 56 frame (82 k lanes, 1.25 waves per SIMD) is bound by ONE wave's
-// instruction stream and the L2 still gathers its lines: OUT_WORD 2.86 ms, OUT_LDS 3.36 ms, OUT_VEC 3.97 ms. Nine such frames by
-// one launch (738 k lanes): OUT_WORD 1.76 ms per frame (HBM writes 5.9 x the symbols), OUT_LDS 0.99 ms, OUT_VEC 1.81 ms.
-static int g_decode_out = -1;                                       // raht_debug_rlgr_decode_out
-static int g_encode_out = -1;                                       // raht_debug_rlgr_encode_out (the batched encoder: words or LDS columns)
-static int decode_out_mode(int64_t lanes)
-{
-    static const char *e = getenv("RAHT_RLGR_DECODE_OUT");
-    if (g_decode_out >= 0) return g_decode_out;
-    if (e) return e[0] == 'l' ? OUT_LDS : e[0] == 'v' ? OUT_VEC : OUT_WORD;
-    return lanes >= 200000 ? OUT_LDS : OUT_WORD;
-}
+// Which way the decoded symbols leave (see OUT_*): by the number of lanes in flight. One 3 M x 56 frame (82 k lanes, 1.25 waves
+// per SIMD) is bound by ONE wave's instruction stream and the L2 still gathers its lines: OUT_WORD 2.86 ms, OUT_LDS 3.36 ms. Nine
+// such frames by one launch (738 k lanes): OUT_WORD 1.76 ms per frame (HBM writes 5.9 x the symbols), OUT_LDS 0.99 ms. (Four
+// symbols buffered in registers and stored as 16 bytes: 3.97 ms and 1.81 ms -- the component selects cost more than the stores
+// save.) The words of the encoder's streams go the same way on their way into the slots (DevBitWriter). The tests force a mode
+// through raht_debug_rlgr_decode_out / _encode_out: their frames are far too small to reach the LDS columns by themselves.
+constexpr int64_t LDS_FROM_LANES = 200000;
+static int g_decode_out = -1;                                       // raht_debug_rlgr_decode_out: -1, OUT_WORD or OUT_LDS
+static int g_encode_out = -1;                                       // raht_debug_rlgr_encode_out: the same
+static int decode_out_mode(int64_t lanes) { return g_decode_out >= 0 ? g_decode_out : lanes >= LDS_FROM_LANES ? OUT_LDS : OUT_WORD; }
+static bool encode_lds_out(int64_t lanes) { return g_encode_out >= 0 ? g_encode_out == OUT_LDS : lanes >= LDS_FROM_LANES; }
 
-// row-major output: the symbol-synchronous decoder (RAHT_RLGR_DECODE_SYNC=0: the per-lane one with strided stores; A/B knob;
-// raht_debug_rlgr_decode_out(3) / (4) force it on / off for the tests)
+// row-major output comes from the symbol-synchronous decoder; raht_debug_rlgr_decode_out(4) / (3) switch to the per-lane one with
+// strided stores and back, for the tests
 static int g_decode_sync = -1;
-static int decode_sync_rows()
-{
-    static const char *e = getenv("RAHT_RLGR_DECODE_SYNC");
-    if (g_decode_sync >= 0) return g_decode_sync;
-    return e ? atoi(e) != 0 : 1;
-}
-
-// (with OUT_LDS) the streams' words through LDS as well: RAHT_RLGR_DECODE_IN=word switches it off (A/B knob)
-static int decode_lds_in()
-{
-    static const char *e = getenv("RAHT_RLGR_DECODE_IN");
-    return e ? (e[0] == 'l') : 1;
-}
+static bool decode_sync_rows() { return g_decode_sync != 0; }
 
 // The offset tables come in two widths (OffT): uint32_t -- containers below 4 GiB, the raht_rlgr_seg_* entry points -- and
 // uint64_t -- the raht_rlgr_seg_*64 ones, for frames whose worst case is larger. Lengths stay uint32 (one segment is at most
@@ -496,88 +464,26 @@ template <> struct SegFlags<uint64_t> {
     static __host__ __device__ __forceinline__ uint64_t *total(uint32_t *flags, int j) { return (uint64_t *)(flags + 4 * j + 2); }
 };
 
-// segment g = c * nseg + s  <->  symbols [s * S, min(N, (s + 1) * S)) of channel c
+// The two EXACT passes over one frame (thread -> segment: SegLane): WRITE = false sizes every segment; WRITE = true, behind the
+// offset scan, writes it at its place in the container.
 template <bool WRITE, typename OffT = uint32_t>
 __global__ __launch_bounds__(64) void seg_encode_kernel(const int32_t *__restrict__ Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
                                                         int flag_signed, uint32_t *__restrict__ seg_bytes, const OffT *__restrict__ seg_off,
                                                         uint8_t *__restrict__ out, uint64_t cap, uint32_t *__restrict__ overflow)
 {
-    // thread t -> segment g = c * nseg + s. Channel-major input (sym_stride == 1): t = g, a lane walks its own contiguous run.
-    // Row-major input (the quantized coefficients as the transform kernels leave them: symbol n of channel c at Q[n * ld + c]):
-    // t = s * D + c -- the lanes of a wave are NEIGHBOURING CHANNELS at the same position of their segments, so every step of
-    // the wave reads (writes) one contiguous piece of a row: no transpose in front of (behind) the coder.
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (int64_t)D * nseg) return;
-    int c, s;
-    if (sym_stride == 1) { c = (int)(t / nseg); s = (int)(t - (int64_t)c * nseg); }
-    else { s = (int)(t / D); c = (int)(t - (int64_t)s * D); }
-    const int64_t g = (int64_t)c * nseg + s;
-    const int64_t i0 = (int64_t)s * S;
-    const int n = (int)min((int64_t)S, N - i0);
-    const int32_t *seq = Q + (int64_t)c * chan_stride + i0 * sym_stride;
-    // 16-byte loads: segment starts aligned and a whole group of four readable behind the last symbol (wave-uniform choice)
-    const bool vec = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0) && ((N & 3) == 0 || chan_stride >= ((N + 3) & ~(int64_t)3));
+    SegLane ln;
+    if (!ln.init(N, D, S, nseg, sym_stride != 1)) return;
+    const int32_t *seq = Q + ln.at(sym_stride, chan_stride);
+    const bool vec = seg_aligned16(Q, sym_stride, chan_stride, S);
     if (!WRITE) {
-        seg_bytes[g] = vec ? encode_segment<false, true>(seq, n, flag_signed, nullptr) : encode_segment<false, false>(seq, n, flag_signed, nullptr, 0xffffffffu, sym_stride);
+        seg_bytes[ln.g] = vec ? encode_segment<false, true>(seq, ln.n, flag_signed, nullptr) : encode_segment<false, false>(seq, ln.n, flag_signed, nullptr, 0xffffffffu, sym_stride);
     } else {
-        const uint64_t off = seg_off[g];                              // 4-byte aligned
-        const uint32_t need = (seg_bytes[g] + 3u) & ~3u;
+        const uint64_t off = seg_off[ln.g];                           // 4-byte aligned
+        const uint32_t need = (seg_bytes[ln.g] + 3u) & ~3u;
         if (off + need > cap) { atomicOr(overflow, 1u); return; }
-        if (vec) (void)encode_segment<true, true>(seq, n, flag_signed, (uint32_t *)(out + off));
-        else (void)encode_segment<true, false>(seq, n, flag_signed, (uint32_t *)(out + off), 0xffffffffu, sym_stride);
+        if (vec) (void)encode_segment<true, true>(seq, ln.n, flag_signed, (uint32_t *)(out + off));
+        else (void)encode_segment<true, false>(seq, ln.n, flag_signed, (uint32_t *)(out + off), 0xffffffffu, sym_stride);
     }
-}
-
-// ONE encoding pass: every segment into a fixed slot of `slot` bytes (what the raw integers would take, + 16) of a scratch
-// buffer, its exact length recorded; seg_compact_kernel then moves the streams to their places in the container. A segment that
-// does not fit its slot (incompressible data) raises *overflow and the caller falls back to the two exact passes.
-__global__ __launch_bounds__(64) void seg_encode_slots_kernel(const int32_t *__restrict__ Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
-                                                              int flag_signed, uint32_t *__restrict__ seg_bytes, uint8_t *__restrict__ slots, uint32_t slot,
-                                                              uint32_t *__restrict__ overflow)
-{
-    // thread t -> segment g = c * nseg + s. Channel-major input (sym_stride == 1): t = g, a lane walks its own contiguous run.
-    // Row-major input (the quantized coefficients as the transform kernels leave them: symbol n of channel c at Q[n * ld + c]):
-    // t = s * D + c -- the lanes of a wave are NEIGHBOURING CHANNELS at the same position of their segments, so every step of
-    // the wave reads (writes) one contiguous piece of a row: no transpose in front of (behind) the coder.
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (int64_t)D * nseg) return;
-    int c, s;
-    if (sym_stride == 1) { c = (int)(t / nseg); s = (int)(t - (int64_t)c * nseg); }
-    else { s = (int)(t / D); c = (int)(t - (int64_t)s * D); }
-    const int64_t g = (int64_t)c * nseg + s;
-    const int64_t i0 = (int64_t)s * S;
-    const int n = (int)min((int64_t)S, N - i0);
-    const int32_t *seq = Q + (int64_t)c * chan_stride + i0 * sym_stride;
-    const bool vec = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0);
-    uint32_t *o = (uint32_t *)(slots + (size_t)g * slot);
-    const uint32_t nb = vec ? encode_segment<true, true>(seq, n, flag_signed, o, slot) : encode_segment<true, false>(seq, n, flag_signed, o, slot, sym_stride);
-    seg_bytes[g] = nb;
-    if (((nb + 3u) & ~3u) > slot) atomicOr(overflow, 1u);
-}
-
-// one wave per segment: its words from the slot to its offset in the container
-template <typename OffT>
-__global__ __launch_bounds__(256) void seg_compact_kernel(const uint8_t *__restrict__ slots, uint32_t slot, const uint32_t *__restrict__ seg_bytes,
-                                                          const OffT *__restrict__ seg_off, int64_t G, uint8_t *__restrict__ out, uint64_t cap,
-                                                          uint32_t *__restrict__ overflow)
-{
-    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (g >= G) return;
-    const uint32_t nw = (seg_bytes[g] + 3u) >> 2;
-    if (4ull * nw > slot) return;                                     // it outgrew its slot (the encoder raised the flag): nothing of it is there
-    const uint64_t off = seg_off[g];
-    if (off + 4ull * nw > cap) { if (lane == 0) atomicOr(overflow, 2u); return; }
-    const uint32_t *src = (const uint32_t *)(slots + (size_t)g * slot);
-    uint32_t *dst = (uint32_t *)(out + off);
-    for (uint32_t i = lane; i < nw; i += 64) dst[i] = src[i];
-}
-
-// padded size of every segment (its slot in the container): the input of the offset scan
-__global__ void seg_pad_kernel(const uint32_t *__restrict__ seg_bytes, int64_t n, uint32_t *__restrict__ padded)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n) padded[g] = (seg_bytes[g] + 3u) & ~3u;
 }
 
 // a segment whose table entry reaches outside the buffer: n zeros, and nothing is read (raht.h: "decodes as zeros". An empty
@@ -587,105 +493,70 @@ __device__ __forceinline__ void zero_segment(int32_t *__restrict__ seq, int n, i
     for (int i = 0; i < n; ++i, seq += sstr) *seq = 0;
 }
 
-template <typename OffT>
-__global__ __launch_bounds__(64) void seg_decode_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const OffT *__restrict__ seg_off,
-                                                        const uint32_t *__restrict__ seg_bytes, int64_t N, int D, int S, int nseg, int flag_signed,
-                                                        int32_t *__restrict__ Q, int64_t sym_stride, int64_t chan_stride, uint32_t *__restrict__ bad, int out_mode,
-                                                        int sync_rows)
-{
-    __shared__ int32_t s_col[DEC_LDS_WORDS];
-    // thread t -> segment g = c * nseg + s. Channel-major input (sym_stride == 1): t = g, a lane walks its own contiguous run.
-    // Row-major input (the quantized coefficients as the transform kernels leave them: symbol n of channel c at Q[n * ld + c]):
-    // t = s * D + c -- the lanes of a wave are NEIGHBOURING CHANNELS at the same position of their segments, so every step of
-    // the wave reads (writes) one contiguous piece of a row: no transpose in front of (behind) the coder.
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (int64_t)D * nseg) return;
-    int c, s;
-    if (sym_stride == 1) { c = (int)(t / nseg); s = (int)(t - (int64_t)c * nseg); }
-    else { s = (int)(t / D); c = (int)(t - (int64_t)s * D); }
-    const int64_t g = (int64_t)c * nseg + s;
-    const int64_t i0 = (int64_t)s * S;
-    const int n = (int)min((int64_t)S, N - i0);
-    // the tables come off the wire: a segment never reaches outside the buffer (its last word is read whole: 4-byte slots).
-    // (the whole offset is judged, in 64 bits, whatever the table's width: nothing below sees a narrowed one)
-    const uint64_t off = seg_off[g];
-    const uint32_t nb = seg_bytes[g];                               // (padded in 64 bits: 2^32 - 1 must not wrap to 0)
-    if ((off & 3) || off > in_bytes || (((uint64_t)nb + 3u) & ~(uint64_t)3) > in_bytes - off) {
-        if (bad) atomicOr(bad, 1u);
-        zero_segment(Q + (int64_t)c * chan_stride + i0 * sym_stride, n, sym_stride);
-        return;
-    }
-    // (16-byte stores of four buffered symbols measured SLOWER than one 4-byte store per symbol -- 4.2 against 3.0 ms for 3 M x 56
-    // at 2048 per segment: the component selects cost more instructions than the stores save; kept behind this switch)
-    const bool aligned = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0);
-    if (sym_stride != 1 && sync_rows == 2) decode_segment_sync<2>((const uint32_t *)(in + (nb ? off : 0)), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0 * sym_stride, sym_stride, s_col);
-    else if (sym_stride != 1 && sync_rows) decode_segment_sync<0>((const uint32_t *)(in + (nb ? off : 0)), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0 * sym_stride, sym_stride);
-    else if (aligned && out_mode == OUT_LDS) decode_segment<OUT_LDS>((const uint32_t *)(in + (nb ? off : 0)), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0, 1, s_col);
-    else if (aligned && out_mode == OUT_VEC) decode_segment<OUT_VEC>((const uint32_t *)(in + (nb ? off : 0)), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0);
-    else decode_segment<OUT_WORD>((const uint32_t *)(in + (nb ? off : 0)), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0 * sym_stride, sym_stride);
-}
-
-// ---- several frames of ONE shape in one set of launches ------------------------------------------------------------
+// ---- k frames of ONE shape in one set of launches (blockIdx.y = frame) ----------------------------------------------
 // What bounds the coders is the number of independent lanes: one frame (3 M x 56 at 2048 symbols per segment) is 1.25 waves
 // per SIMD, and a wave that is alone on its SIMD waits out the latency of every one of its ~480 k dependent instructions.
 // The quantization steps of a frame (python/encode_3dgs.py:199-275: nine of them) are nine such frames of the same shape with
-// nothing between them: coded by ONE launch (blockIdx.y = frame) they fill every wave slot of the chip. Each frame keeps
-// its own tables and container: the bytes are those of the one-frame entry points.
-constexpr int SEG_BATCH_MAX = RAHT_RLGR_BATCH_MAX;
-template <typename OffT>
+// nothing between them: coded by ONE launch they fill every wave slot of the chip. Each frame keeps its own tables and
+// container. The one-frame entry points are k = 1 of the same kernels: the bytes of a frame cannot depend on its company.
+// K: the entries of the job table a kernel is built for. RAHT_RLGR_BATCH_MAX: a batch. 1: the one-frame entry points' own instantiation
+// -- no blockIdx.y, a table of one entry and, in the decoder, neither the comparison with expect[] nor the stream words' way
+// through LDS: a lone wave per SIMD pays for every instruction on its chain (measured with the batch instantiation on one 3 M x 56
+// frame: decode 1.73 -> 1.77 ms).
+template <typename OffT, int K>
 struct SegEncJobs {
-    const int32_t *Q[SEG_BATCH_MAX]; uint32_t *seg_bytes[SEG_BATCH_MAX]; OffT *seg_off[SEG_BATCH_MAX]; uint8_t *out[SEG_BATCH_MAX];
-    uint64_t cap[SEG_BATCH_MAX];
+    const int32_t *Q[K]; uint32_t *seg_bytes[K]; OffT *seg_off[K]; uint8_t *out[K];
+    uint64_t cap[K];
 };
-template <typename OffT>
+template <typename OffT, int K>
 struct SegDecJobs {
-    const uint8_t *in[SEG_BATCH_MAX]; uint64_t in_bytes[SEG_BATCH_MAX]; const OffT *seg_off[SEG_BATCH_MAX]; const uint32_t *seg_bytes[SEG_BATCH_MAX];
-    int32_t *Q[SEG_BATCH_MAX];
-    const int32_t *expect[SEG_BATCH_MAX];        // (may be NULL) what Q[j] should become: compared inside the row-major decoder
+    const uint8_t *in[K]; uint64_t in_bytes[K]; const OffT *seg_off[K]; const uint32_t *seg_bytes[K];
+    int32_t *Q[K];
+    const int32_t *expect[K];                    // (may be NULL) what Q[j] should become: compared inside the row-major decoder (K > 1)
 };
+template <int K> __device__ __forceinline__ int seg_frame() { return K == 1 ? 0 : (int)blockIdx.y; }
 
-// flags: SegFlags<OffT>::WORDS words per frame (overflow bits, container bytes)
-template <typename OffT>
-__global__ __launch_bounds__(64) void seg_encode_slots_batch_kernel(const SegEncJobs<OffT> J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
-                                                                    int flag_signed, uint8_t *__restrict__ slots, uint32_t slot, uint32_t *__restrict__ flags,
-                                                                    int lds_out)
+// ONE encoding pass: every segment into a fixed slot of `slot` bytes (what the raw integers would take, + 16) of a scratch buffer, its exact length recorded; seg_compact_kernel then moves the streams to their places in the
+// containers. A segment that does not fit its slot (incompressible data) raises bit 0 of its frame's flag words and the caller
+// falls back to the two exact passes. flags: SegFlags<OffT>::WORDS words per frame (overflow bits, container bytes).
+// LDSOUT: the streams' words leave through LDS columns (DevBitWriter; the host's choice: encode_lds_out).
+template <typename OffT, int K, bool LDSOUT>
+__global__ __launch_bounds__(64) void seg_encode_slots_kernel(const SegEncJobs<OffT, K> J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
+                                                              int flag_signed, uint8_t *__restrict__ slots, uint32_t slot, uint32_t *__restrict__ flags)
 {
-    __shared__ uint32_t s_col[16 * 64];
-    const int j = blockIdx.y;
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    const int64_t G = (int64_t)D * nseg;
-    if (t >= G) return;
-    int c, s;
-    if (sym_stride == 1) { c = (int)(t / nseg); s = (int)(t - (int64_t)c * nseg); }
-    else { s = (int)(t / D); c = (int)(t - (int64_t)s * D); }
-    const int64_t g = (int64_t)c * nseg + s;
-    const int64_t i0 = (int64_t)s * S;
-    const int n = (int)min((int64_t)S, N - i0);
+    uint32_t *col = nullptr;
+    if constexpr (LDSOUT) {
+        __shared__ uint32_t s_col[16 * 64];
+        col = s_col;
+    }
+    const int j = seg_frame<K>();
+    SegLane ln;
+    if (!ln.init(N, D, S, nseg, sym_stride != 1)) return;
     const int32_t *Q = J.Q[j];
-    const int32_t *seq = Q + (int64_t)c * chan_stride + i0 * sym_stride;
-    const bool vec = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0);
-    uint32_t *o = (uint32_t *)(slots + ((size_t)j * (size_t)G + (size_t)g) * slot);
-    uint32_t nb;
-    if (lds_out) nb = vec ? encode_segment<true, true, true>(seq, n, flag_signed, o, slot, 1, s_col) : encode_segment<true, false, true>(seq, n, flag_signed, o, slot, sym_stride, s_col);
-    else nb = vec ? encode_segment<true, true>(seq, n, flag_signed, o, slot) : encode_segment<true, false>(seq, n, flag_signed, o, slot, sym_stride);
-    J.seg_bytes[j][g] = nb;
+    const int32_t *seq = Q + ln.at(sym_stride, chan_stride);
+    uint32_t *o = (uint32_t *)(slots + ((size_t)j * (size_t)D * (size_t)nseg + (size_t)ln.g) * slot);
+    const uint32_t nb = seg_aligned16(Q, sym_stride, chan_stride, S) ? encode_segment<true, true, LDSOUT>(seq, ln.n, flag_signed, o, slot, 1, col)
+                                                                     : encode_segment<true, false, LDSOUT>(seq, ln.n, flag_signed, o, slot, sym_stride, col);
+    J.seg_bytes[j][ln.g] = nb;
     if (((nb + 3u) & ~3u) > slot) atomicOr(flags + SegFlags<OffT>::WORDS * j, 1u);
 }
 
-template <typename OffT>
-__global__ void seg_pad_batch_kernel(const SegEncJobs<OffT> J, int64_t G, uint32_t *__restrict__ padded)
+// padded size of every segment (its place in the container): the input of the offset scan
+template <typename OffT, int K>
+__global__ void seg_pad_kernel(const SegEncJobs<OffT, K> J, int64_t G, uint32_t *__restrict__ padded)
 {
-    const int j = blockIdx.y;
+    const int j = seg_frame<K>();
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < G) padded[(size_t)j * (size_t)G + g] = (J.seg_bytes[j][g] + 3u) & ~3u;
 }
 
+// one wave per segment: its words from the slot to its offset in the container
 // (also closes every frame's offset table: seg_off[G] = its container's bytes, left in the frame's flag words by the scan)
-template <typename OffT>
-__global__ __launch_bounds__(256) void seg_compact_batch_kernel(const SegEncJobs<OffT> J, const uint8_t *__restrict__ slots, uint32_t slot, int64_t G,
-                                                                uint32_t *__restrict__ flags)
+template <typename OffT, int K>
+__global__ __launch_bounds__(256) void seg_compact_kernel(const SegEncJobs<OffT, K> J, const uint8_t *__restrict__ slots, uint32_t slot, int64_t G,
+                                                          uint32_t *__restrict__ flags)
 {
-    const int j = blockIdx.y;
+    const int j = seg_frame<K>();
     const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (blockIdx.x == 0 && threadIdx.x == 0) J.seg_off[j][G] = *SegFlags<OffT>::total(flags, j);
@@ -699,42 +570,45 @@ __global__ __launch_bounds__(256) void seg_compact_batch_kernel(const SegEncJobs
     for (uint32_t i = lane; i < nw; i += 64) dst[i] = src[i];
 }
 
-template <typename OffT>
-__global__ __launch_bounds__(64) void seg_decode_batch_kernel(const SegDecJobs<OffT> J, int64_t N, int D, int S, int nseg, int flag_signed, int64_t sym_stride,
-                                                              int64_t chan_stride, uint32_t *__restrict__ bad, int out_mode, int lds_in, int sync_rows)
+// bad: bit j when a table entry of frame j reached outside in[j]; bit 16 + j when a symbol of frame j differs from expect[j]
+template <typename OffT, int K>
+__global__ __launch_bounds__(64) void seg_decode_kernel(const SegDecJobs<OffT, K> J, int64_t N, int D, int S, int nseg, int flag_signed, int64_t sym_stride,
+                                                        int64_t chan_stride, uint32_t *__restrict__ bad, int out_mode, int sync_rows)
 {
     __shared__ int32_t s_col[DEC_LDS_WORDS];
-    __shared__ int32_t s_in[8 * 64];
-    const int j = blockIdx.y;
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= (int64_t)D * nseg) return;
-    int c, s;
-    if (sym_stride == 1) { c = (int)(t / nseg); s = (int)(t - (int64_t)c * nseg); }
-    else { s = (int)(t / D); c = (int)(t - (int64_t)s * D); }
-    const int64_t g = (int64_t)c * nseg + s;
-    const int64_t i0 = (int64_t)s * S;
-    const int n = (int)min((int64_t)S, N - i0);
-    const uint64_t off = J.seg_off[j][g], in_bytes = J.in_bytes[j];
-    const uint32_t nb = J.seg_bytes[j][g];
-    int32_t *Q = J.Q[j];
-    if ((off & 3) || off > in_bytes || (((uint64_t)nb + 3u) & ~(uint64_t)3) > in_bytes - off) {
+    const int j = seg_frame<K>();
+    SegLane ln;
+    if (!ln.init(N, D, S, nseg, sym_stride != 1)) return;
+    const uint64_t off = J.seg_off[j][ln.g], in_bytes = J.in_bytes[j];
+    const uint32_t nb = J.seg_bytes[j][ln.g];
+    const int64_t at = ln.at(sym_stride, chan_stride);
+    int32_t *seq = J.Q[j] + at;
+    if (!seg_entry_ok(off, nb, in_bytes)) {
         if (bad) atomicOr(bad, 1u << j);
-        zero_segment(Q + (int64_t)c * chan_stride + i0 * sym_stride, n, sym_stride);
+        zero_segment(seq, ln.n, sym_stride);
         return;
     }
-    const bool aligned = sym_stride == 1 && ((((uintptr_t)Q) & 15) == 0) && ((chan_stride & 3) == 0) && ((S & 3) == 0);
+    const bool aligned = seg_aligned16(J.Q[j], sym_stride, chan_stride, S);
     const uint64_t o = nb ? off : 0;
-    if (sym_stride != 1 && (sync_rows || J.expect[j])) {
-        const int64_t at = (int64_t)c * chan_stride + i0 * sym_stride;
-        const int32_t *ex = J.expect[j] ? J.expect[j] + at : nullptr;
-        bool differs;
-        if (lds_in) differs = decode_segment_sync<2>((const uint32_t *)(J.in[j] + o), nb, n, flag_signed, Q + at, sym_stride, s_col, 0, ex);
-        else differs = decode_segment_sync<0>((const uint32_t *)(J.in[j] + o), nb, n, flag_signed, Q + at, sym_stride, nullptr, 0, ex);
-        if (__ballot(differs) && (threadIdx.x & 63) == 0 && bad) atomicOr(bad, 1u << (16 + j));
-    } else if (aligned && out_mode == OUT_LDS && (((uintptr_t)J.in[j]) & 31) == 0 && lds_in)
-        decode_segment<OUT_LDS, true>((const uint32_t *)(J.in[j] + o), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0, 1, s_col, s_in, (int64_t)((in_bytes - o) >> 2));
-    else if (aligned && out_mode == OUT_LDS) decode_segment<OUT_LDS>((const uint32_t *)(J.in[j] + o), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0, 1, s_col);
-    else decode_segment<OUT_WORD>((const uint32_t *)(J.in[j] + (nb ? off : 0)), nb, n, flag_signed, Q + (int64_t)c * chan_stride + i0 * sym_stride, sym_stride);
+    const uint32_t *in32 = (const uint32_t *)(J.in[j] + o);
+    if constexpr (K > 1) {
+        __shared__ int32_t s_in[8 * 64];
+        if (sym_stride != 1 && (sync_rows || J.expect[j])) {
+            const int32_t *ex = J.expect[j] ? J.expect[j] + at : nullptr;
+            const bool differs = decode_segment_sync<2>(in32, nb, ln.n, flag_signed, seq, sym_stride, s_col, 0, ex);
+            if (__ballot(differs) && (threadIdx.x & 63) == 0 && bad) atomicOr(bad, 1u << (16 + j));
+            return;
+        }
+        if (aligned && out_mode == OUT_LDS && (((uintptr_t)J.in[j]) & 31) == 0) {             // (the LDSIN reader fetches aligned 32-byte pieces)
+            decode_segment<OUT_LDS, true>(in32, nb, ln.n, flag_signed, seq, 1, s_col, s_in, (int64_t)((in_bytes - o) >> 2));
+            return;
+        }
+    } else if (sym_stride != 1 && sync_rows) {
+        decode_segment_sync<2>(in32, nb, ln.n, flag_signed, seq, sym_stride, s_col);
+        return;
+    }
+    if (aligned && out_mode == OUT_LDS) decode_segment<OUT_LDS>(in32, nb, ln.n, flag_signed, seq, 1, s_col);
+    else decode_segment<OUT_WORD>(in32, nb, ln.n, flag_signed, seq, sym_stride);
 }
 
 }  // namespace rlgr_seg
@@ -780,6 +654,69 @@ int seg_shape(const char *fn, int64_t N, int D, int seg_len, int64_t *nseg, int6
     return RAHT_OK;
 }
 
+// the kernels' view of k <= K frames (the entries behind k repeat frame 0: no kernel reads them)
+template <typename OffT, int K>
+rlgr_seg::SegEncJobs<OffT, K> enc_jobs(int k, const int32_t *const *Q, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap)
+{
+    rlgr_seg::SegEncJobs<OffT, K> J;
+    for (int j = 0; j < K; ++j) {
+        const int q = j < k ? j : 0;
+        J.Q[j] = Q[q]; J.seg_bytes[j] = seg_bytes[q]; J.seg_off[j] = seg_off[q]; J.out[j] = out[q]; J.cap[j] = (uint64_t)cap[q];
+    }
+    return J;
+}
+
+// a slot: what the raw integers of a segment would take, + 16; for the LDS-column output in whole 64-byte pieces (it needs
+// 16-byte aligned starts; 64: whole pieces). Fits: raht_rlgr_bound(seg_len) < 2^32.
+inline uint32_t slot_bytes(int seg_len, bool lds_out) { return lds_out ? (4u * (uint32_t)seg_len + 16u + 63u) & ~63u : 4u * (uint32_t)seg_len + 16u; }
+
+// The slots pass over the k frames of J: every segment into its slot, the padded sizes, one offset scan per frame, the compaction
+// (which closes the frames' tables), the flag words back (synchronises: the scratch may go back to the pool).
+//   RAHT_OK              total_bytes[] are set and the containers written
+//   RAHT_ERR_NOMEM       total_bytes[] are set and some container is too small (the text names the frame when name_frame)
+//   RAHT_ERR_UNSUPPORTED a segment outgrew its slot (incompressible data), or there is no scratch for k sets of slots: nothing
+//                        useful was written and the caller runs the two exact passes
+template <typename OffT, int K>
+int seg_encode_slots(const char *fn, bool name_frame, int k, const rlgr_seg::SegEncJobs<OffT, K> &J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride,
+                     int seg_len, int64_t nseg, int64_t G, int flag_signed, int64_t *total_bytes, hipStream_t s)
+{
+    constexpr int FW = SegFlags<OffT>::WORDS;
+    const bool lds_out = rlgr_seg::encode_lds_out((int64_t)k * G);
+    const uint32_t slot = slot_bytes(seg_len, lds_out);
+    const size_t npad = ((size_t)k * (size_t)G + 1) & ~(size_t)1;           // (the flag words behind it stay 8-byte aligned)
+    Scratch tmp(sizeof(uint32_t) * (npad + FW * (size_t)k), s);
+    Scratch slots((size_t)k * (size_t)G * slot, s);
+    if (!tmp.ok() || !slots.ok()) { (void)hipGetLastError(); return RAHT_ERR_UNSUPPORTED; }
+    uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + npad;
+    RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW * (size_t)k, s));
+    const dim3 lanes((unsigned)ceil_div(G, 64), (unsigned)k);
+    if (lds_out)
+        hipLaunchKernelGGL((rlgr_seg::seg_encode_slots_kernel<OffT, K, true>), lanes, dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
+                           slots.as<uint8_t>(), slot, flags);
+    else
+        hipLaunchKernelGGL((rlgr_seg::seg_encode_slots_kernel<OffT, K, false>), lanes, dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
+                           slots.as<uint8_t>(), slot, flags);
+    hipLaunchKernelGGL((rlgr_seg::seg_pad_kernel<OffT, K>), dim3((unsigned)ceil_div(G, 256), (unsigned)k), dim3(256), 0, s, J, G, padded);
+    for (int j = 0; j < k; ++j) RAHT_RET(scan_offsets<OffT>(padded + (size_t)j * (size_t)G, J.seg_off[j], G, SegFlags<OffT>::total(flags, j), s));
+    hipLaunchKernelGGL((rlgr_seg::seg_compact_kernel<OffT, K>), dim3((unsigned)ceil_div(G * 64, 256), (unsigned)k), dim3(256), 0, s, J, (const uint8_t *)slots.as<uint8_t>(), slot, G, flags);
+    RAHT_HIP_CHECK(hipGetLastError());
+    uint32_t back[FW * K] = {0};
+    RAHT_RET(read_back_u32(back, flags, FW * k, nullptr, nullptr, 0, s));
+    for (int j = 0; j < k; ++j)
+        if (back[FW * j] & 1u) return RAHT_ERR_UNSUPPORTED;
+    int rc = RAHT_OK;
+    for (int j = 0; j < k; ++j) {
+        const uint64_t total = total_of<OffT>(back, j);
+        total_bytes[j] = (int64_t)total;
+        if ((back[FW * j] & 2u) || total > J.cap[j]) {
+            if (name_frame) set_error("%s: frame %d needs %llu bytes, cap = %lld", fn, j, (unsigned long long)total, (long long)J.cap[j]);
+            else set_error("%s: %llu bytes needed, cap = %lld", fn, (unsigned long long)total, (long long)J.cap[j]);
+            rc = RAHT_ERR_NOMEM;
+        }
+    }
+    return rc;
+}
+
 template <typename OffT>
 int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
                     uint32_t *seg_bytes, OffT *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
@@ -796,6 +733,13 @@ int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t 
     hipStream_t s = (hipStream_t)stream;
     constexpr int FW = SegFlags<OffT>::WORDS;
     return guarded(fn, [&]() -> int {
+        const rlgr_seg::SegEncJobs<OffT, 1> J = enc_jobs<OffT, 1>(1, &Q, &seg_bytes, &seg_off, &out, &cap);
+        // ONE encoding pass into fixed slots + a compaction, when a scratch buffer of the raw size is to be had; the two exact
+        // passes (sizes, then streams) otherwise, and whenever a segment outgrows its slot
+        if ((uint64_t)G * slot_bytes(seg_len, rlgr_seg::encode_lds_out(G)) < ((uint64_t)1 << 33)) {
+            const int rc = seg_encode_slots<OffT, 1>(fn, false, 1, J, N, D, sym_stride, chan_stride, seg_len, nseg, G, flag_signed, total_bytes, s);
+            if (rc != RAHT_ERR_UNSUPPORTED) return rc;
+        }
         const size_t npad = ((size_t)G + 1) & ~(size_t)1;                   // (the flag words behind it stay 8-byte aligned)
         Scratch tmp(sizeof(uint32_t) * (npad + FW), s);
         if (!tmp.ok()) return RAHT_ERR_NOMEM;
@@ -803,37 +747,9 @@ int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t 
         OffT *dtotal = SegFlags<OffT>::total(flags, 0);
         RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW, s));
         const unsigned gb = (unsigned)ceil_div(G, 64);
-        // ONE encoding pass into fixed slots + a compaction, when a scratch buffer of the raw size is to be had; the two exact
-        // passes (sizes, then streams) otherwise, and whenever a segment outgrows its slot
-        static const bool two_pass_only = getenv("RAHT_RLGR_TWO_PASS") != nullptr;      // A/B knob
-        const uint32_t slot = 4u * (uint32_t)seg_len + 16u;                             // (fits: raht_rlgr_bound(seg_len) < 2^32)
-        if (!two_pass_only && (uint64_t)G * slot < ((uint64_t)1 << 33)) {
-            Scratch slots((size_t)G * slot, s);
-            if (slots.ok()) {
-                hipLaunchKernelGGL(rlgr_seg::seg_encode_slots_kernel, dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
-                                   seg_bytes, slots.as<uint8_t>(), slot, flags);
-                hipLaunchKernelGGL(rlgr_seg::seg_pad_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, seg_bytes, G, padded);
-                RAHT_RET(scan_offsets<OffT>(padded, seg_off, G, dtotal, s));
-                RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, dtotal, sizeof(OffT), hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(rlgr_seg::seg_compact_kernel<OffT>, dim3((unsigned)ceil_div(G * 64, 256)), dim3(256), 0, s, slots.as<uint8_t>(), slot,
-                                   (const uint32_t *)seg_bytes, (const OffT *)seg_off, G, out, (uint64_t)cap, flags);
-                RAHT_HIP_CHECK(hipGetLastError());
-                uint32_t back[FW] = {0};
-                RAHT_RET(read_back_u32(back, flags, FW, nullptr, nullptr, 0, s));    // (synchronises: the scratch may go back to the pool)
-                if (!(back[0] & 1u)) {
-                    const uint64_t total = total_of<OffT>(back, 0);
-                    *total_bytes = (int64_t)total;
-                    if ((back[0] & 2u) || (int64_t)total > cap) { set_error("%s: %llu bytes needed, cap = %lld", fn, (unsigned long long)total, (long long)cap); return RAHT_ERR_NOMEM; }
-                    return RAHT_OK;
-                }
-                RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW, s));                  // a segment outgrew its slot: the exact passes
-            } else {
-                (void)hipGetLastError();
-            }
-        }
         hipLaunchKernelGGL((rlgr_seg::seg_encode_kernel<false, OffT>), dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
                            seg_bytes, (const OffT *)nullptr, (uint8_t *)nullptr, (uint64_t)0, flags);
-        hipLaunchKernelGGL(rlgr_seg::seg_pad_kernel, dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, seg_bytes, G, padded);
+        hipLaunchKernelGGL((rlgr_seg::seg_pad_kernel<OffT, 1>), dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, J, G, padded);
         RAHT_RET(scan_offsets<OffT>(padded, seg_off, G, dtotal, s));
         RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, dtotal, sizeof(OffT), hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL((rlgr_seg::seg_encode_kernel<true, OffT>), dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
@@ -848,6 +764,24 @@ int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t 
     });
 }
 
+// one launch for k <= K frames whose arguments have been checked
+template <typename OffT, int K>
+int seg_decode_launch(int k, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes, int64_t N, int D,
+                      int seg_len, int64_t nseg, int64_t G, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
+                      int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
+{
+    rlgr_seg::SegDecJobs<OffT, K> J;
+    for (int j = 0; j < K; ++j) {
+        const int q = j < k ? j : 0;
+        J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
+        J.expect[j] = expect ? expect[q] : nullptr;
+    }
+    hipLaunchKernelGGL((rlgr_seg::seg_decode_kernel<OffT, K>), dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, (hipStream_t)stream, J, N, D, seg_len, (int)nseg,
+                       flag_signed, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode((int64_t)k * G), (int)rlgr_seg::decode_sync_rows());
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
 template <typename OffT>
 int seg_decode_impl(const char *fn, const uint8_t *in, int64_t in_bytes, const OffT *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
                     int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
@@ -859,10 +793,7 @@ int seg_decode_impl(const char *fn, const uint8_t *in, int64_t in_bytes, const O
     }
     const int64_t nseg = (N - 1) / seg_len + 1, G = nseg < ((int64_t)1 << 31) ? nseg * D : (int64_t)1 << 31;
     if (G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    hipLaunchKernelGGL(rlgr_seg::seg_decode_kernel<OffT>, dim3((unsigned)ceil_div(G, 64)), dim3(64), 0, (hipStream_t)stream, in, (uint64_t)in_bytes, seg_off, seg_bytes, N, D,
-                       seg_len, (int)nseg, flag_signed, Q, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode(G), rlgr_seg::decode_sync_rows() ? (rlgr_seg::decode_lds_in() ? 2 : 1) : 0);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return seg_decode_launch<OffT, 1>(1, &in, &in_bytes, &seg_off, &seg_bytes, N, D, seg_len, nseg, G, flag_signed, &Q, nullptr, sym_stride, chan_stride, bad_dev, stream);
 }
 
 // fn: the batch entry point's name; fn1: the one-frame entry point of the same width (the frame-by-frame fallback reports as it)
@@ -884,58 +815,21 @@ int seg_encode_batch_impl(const char *fn, const char *fn1, int k, const int32_t 
         if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
     int64_t nseg, G;
     RAHT_RET(seg_shape<OffT>(fn, N, D, seg_len, &nseg, &G));
-    hipStream_t s = (hipStream_t)stream;
-    auto one_by_one = [&]() -> int {
-        int rc_all = RAHT_OK;
-        for (int j = 0; j < k; ++j) {
-            const int rc = seg_encode_impl<OffT>(fn1, Q[j], N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j], stream);
-            if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
-            if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
-        }
-        return rc_all;
-    };
-    static const bool no_batch = getenv("RAHT_RLGR_NO_BATCH") != nullptr;          // A/B knob
-    if (k == 1 || no_batch) return one_by_one();
-    // slots of whole 64-byte pieces (16-byte aligned starts are what the LDS-column output needs; 64: whole pieces)
-    const uint32_t slot = (4u * (uint32_t)seg_len + 16u + 63u) & ~63u;
-    static const char *enc_out = getenv("RAHT_RLGR_ENCODE_OUT");                  // A/B knob: word | lds
-    const int lds_out = rlgr_seg::g_encode_out >= 0 ? (rlgr_seg::g_encode_out == rlgr_seg::OUT_LDS)
-                                                    : enc_out ? (enc_out[0] == 'l') : ((int64_t)k * G >= 200000);
-    constexpr int FW = SegFlags<OffT>::WORDS;
-    int rc = guarded(fn, [&]() -> int {
-        const size_t npad = ((size_t)k * (size_t)G + 1) & ~(size_t)1;           // (the flag words behind it stay 8-byte aligned)
-        Scratch tmp(sizeof(uint32_t) * (npad + FW * (size_t)k), s);
-        Scratch slots((size_t)k * (size_t)G * slot, s);
-        if (!tmp.ok() || !slots.ok()) { (void)hipGetLastError(); return RAHT_ERR_UNSUPPORTED; }      // no room for k sets of slots: frame by frame
-        uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + npad;
-        RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW * (size_t)k, s));
-        rlgr_seg::SegEncJobs<OffT> J;
-        for (int j = 0; j < RAHT_RLGR_BATCH_MAX; ++j) {
-            const int q = j < k ? j : 0;
-            J.Q[j] = Q[q]; J.seg_bytes[j] = seg_bytes[q]; J.seg_off[j] = seg_off[q]; J.out[j] = out[q]; J.cap[j] = (uint64_t)cap[q];
-        }
-        hipLaunchKernelGGL(rlgr_seg::seg_encode_slots_batch_kernel<OffT>, dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len,
-                           (int)nseg, flag_signed, slots.as<uint8_t>(), slot, flags, lds_out);
-        hipLaunchKernelGGL(rlgr_seg::seg_pad_batch_kernel<OffT>, dim3((unsigned)ceil_div(G, 256), (unsigned)k), dim3(256), 0, s, J, G, padded);
-        for (int j = 0; j < k; ++j) RAHT_RET(scan_offsets<OffT>(padded + (size_t)j * (size_t)G, seg_off[j], G, SegFlags<OffT>::total(flags, j), s));
-        hipLaunchKernelGGL(rlgr_seg::seg_compact_batch_kernel<OffT>, dim3((unsigned)ceil_div(G * 64, 256), (unsigned)k), dim3(256), 0, s, J, (const uint8_t *)slots.as<uint8_t>(), slot, G, flags);
-        RAHT_HIP_CHECK(hipGetLastError());
-        uint32_t back[FW * RAHT_RLGR_BATCH_MAX] = {0};
-        RAHT_RET(read_back_u32(back, flags, FW * k, nullptr, nullptr, 0, s));       // (synchronises: the scratch may go back to the pool)
-        int rc2 = RAHT_OK;
-        for (int j = 0; j < k; ++j) {
-            if (back[FW * j] & 1u) return RAHT_ERR_UNSUPPORTED;                       // a segment outgrew its slot (incompressible data): the exact passes
-            const uint64_t total = total_of<OffT>(back, j);
-            total_bytes[j] = (int64_t)total;
-            if ((back[FW * j] & 2u) || (int64_t)total > cap[j]) {
-                set_error("%s: frame %d needs %llu bytes, cap = %lld", fn, j, (unsigned long long)total, (long long)cap[j]);
-                rc2 = RAHT_ERR_NOMEM;
-            }
-        }
-        return rc2;
-    });
-    if (rc == RAHT_ERR_UNSUPPORTED) return one_by_one();
-    return rc;
+    // (k = 1 goes the one-frame way as well: its checks and its texts)
+    int rc = RAHT_ERR_UNSUPPORTED;
+    if (k > 1)
+        rc = guarded(fn, [&]() -> int {
+            return seg_encode_slots<OffT, RAHT_RLGR_BATCH_MAX>(fn, true, k, enc_jobs<OffT, RAHT_RLGR_BATCH_MAX>(k, Q, seg_bytes, seg_off, out, cap), N, D, sym_stride, chan_stride, seg_len, nseg, G, flag_signed,
+                                          total_bytes, (hipStream_t)stream);
+        });
+    if (rc != RAHT_ERR_UNSUPPORTED) return rc;
+    int rc_all = RAHT_OK;                                                   // frame by frame
+    for (int j = 0; j < k; ++j) {
+        rc = seg_encode_impl<OffT>(fn1, Q[j], N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j], stream);
+        if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
+        if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
+    }
+    return rc_all;
 }
 
 template <typename OffT>
@@ -955,16 +849,7 @@ int seg_decode_batch_impl(const char *fn, int k, const uint8_t *const *in, const
         }
     const int64_t nseg = (N - 1) / seg_len + 1, G = nseg < ((int64_t)1 << 31) ? nseg * D : (int64_t)1 << 31;
     if (G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    rlgr_seg::SegDecJobs<OffT> J;
-    for (int j = 0; j < RAHT_RLGR_BATCH_MAX; ++j) {
-        const int q = j < k ? j : 0;
-        J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
-        J.expect[j] = expect ? expect[q] : nullptr;
-    }
-    hipLaunchKernelGGL(rlgr_seg::seg_decode_batch_kernel<OffT>, dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, (hipStream_t)stream, J, N, D, seg_len, (int)nseg,
-                       flag_signed, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode((int64_t)k * G), rlgr_seg::decode_lds_in(), rlgr_seg::decode_sync_rows());
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return seg_decode_launch<OffT, RAHT_RLGR_BATCH_MAX>(k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, nseg, G, flag_signed, Q, expect, sym_stride, chan_stride, bad_dev, stream);
 }
 
 }  // namespace
@@ -1040,7 +925,7 @@ int raht_debug_rlgr_decode_out(int mode)
 {
     const int prev = rlgr_seg::g_decode_out;
     if (mode == 3 || mode == 4) { rlgr_seg::g_decode_sync = (mode == 3); return prev; }     // row-major output: symbol-synchronous decoder on / off
-    rlgr_seg::g_decode_out = (mode >= 0 && mode <= 2) ? mode : -1;
+    rlgr_seg::g_decode_out = (mode == rlgr_seg::OUT_WORD || mode == rlgr_seg::OUT_LDS) ? mode : -1;
     if (mode < 0) rlgr_seg::g_decode_sync = -1;
     return prev;
 }
@@ -1048,7 +933,7 @@ int raht_debug_rlgr_decode_out(int mode)
 int raht_debug_rlgr_encode_out(int mode)
 {
     const int prev = rlgr_seg::g_encode_out;
-    rlgr_seg::g_encode_out = (mode == 0 || mode == 2) ? mode : -1;
+    rlgr_seg::g_encode_out = (mode == rlgr_seg::OUT_WORD || mode == rlgr_seg::OUT_LDS) ? mode : -1;
     return prev;
 }
 

@@ -11,7 +11,8 @@ pytestmark = pytest.mark.gpu
 def _decoder_output_mode(request):
     """every test with each of the ways the decoders' symbols leave the lanes (raht_debug_rlgr_decode_out): these frames are far
     too small for the default to pick the LDS columns by itself. rows_per_lane: row-major output from the per-lane decoder with
-    strided stores instead of the symbol-synchronous one (the default for that layout)"""
+    strided stores instead of the symbol-synchronous one (the default for that layout). out_vec: the value 1 -- the 16-byte
+    register groups it once selected are gone and it restores the default, like any value without a meaning"""
     from raht_3dgs_codec_amd import _lib
     prev = _lib.lib().raht_debug_rlgr_decode_out(request.param)
     prev_e = _lib.lib().raht_debug_rlgr_encode_out(request.param)          # (the batched encoder: words / LDS columns)
@@ -308,3 +309,40 @@ def test_odd_shapes_in_both_layouts(N, D, seg_len):
         assert all(torch.equal(o, Q if rm else Q.t()) for o, Q in zip(outs, Qs))
     rlgr.SegmentedCoder.decode_batch(coders, row_major=True, expect=Qs)
     assert rlgr.SegmentedCoder.roundtrip_failed(coders) == []
+
+
+def test_one_frame_decode_reads_the_same_symbols_from_any_payload_alignment():
+    """channel-major frames, LDS columns out: in a batch the payload's words come through LDS in aligned 32-byte pieces when the
+    payload starts on a 32-byte boundary and one by one when it does not (here: 4 bytes further); a frame on its own reads them one
+    by one. The same symbols every way: the one-frame entry point at both alignments, and one batch launch with a frame of each."""
+    import ctypes as C
+    import torch
+    from raht_3dgs_codec_amd import _lib, rlgr
+    rng = np.random.default_rng(17)
+    N, D, S = 5000, 3, 64
+    Qh = np.stack([np.rint(rng.laplace(0, b, size=N)) for b in (0.3, 30.0, 2000.0)]).astype(np.int32)    # streams of a few bytes .. several pieces
+    Q = torch.from_numpy(Qh).cuda()
+    sc = rlgr.SegmentedCoder(N, D, S)
+    total = sc.encode(Q)
+    assert total % 4 == 0
+    L = _lib.lib()
+    bufs, outs = [], []
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for shift in (0, 4):
+        buf = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
+        assert buf.data_ptr() % 32 == 0
+        buf[shift: shift + total] = sc.out[:total]
+        out = torch.full((D, N), -7, dtype=torch.int32, device="cuda")
+        rc = L.raht_rlgr_seg_decode_strided(C.c_void_p(buf.data_ptr() + shift), total, C.c_void_p(sc.seg_off.data_ptr()), C.c_void_p(sc.seg_bytes.data_ptr()),
+                                            N, D, S, 1, C.c_void_p(out.data_ptr()), 1, N, C.c_void_p(bad.data_ptr()), None)
+        assert rc == 0, L.raht_last_error()
+        assert torch.equal(out, Q), shift
+        assert int(bad.item()) == 0, shift
+        bufs.append(buf)
+        outs.append(out.fill_(-7))
+    VP, I64 = C.c_void_p * 2, C.c_int64 * 2
+    rc = L.raht_rlgr_seg_decode_batch(2, VP(bufs[0].data_ptr(), bufs[1].data_ptr() + 4), I64(total, total), VP(*[sc.seg_off.data_ptr()] * 2),
+                                      VP(*[sc.seg_bytes.data_ptr()] * 2), N, D, S, 1, VP(*[o.data_ptr() for o in outs]), 1, N, C.c_void_p(bad.data_ptr()), None)
+    assert rc == 0, L.raht_last_error()
+    assert torch.equal(outs[0], Q) and torch.equal(outs[1], Q)
+    assert int(bad.item()) == 0

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 GB = 1 << 30
 
 
-@pytest.fixture(params=[-1, 0, 1, 2, 4], ids=["out_auto", "out_word", "out_vec", "out_lds", "rows_per_lane"])
+@pytest.fixture(params=[-1, 0, 2, 4], ids=["out_auto", "out_word", "out_lds", "rows_per_lane"])
 def decoder_output_mode(request):
     """each of the ways the decoders' symbols leave the lanes (raht_debug_rlgr_decode_out), and the batched encoder's words /
     LDS columns: small frames never pick the LDS columns by themselves"""
