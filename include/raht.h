@@ -298,7 +298,10 @@ int raht_plan_mixed_stats(raht_plan *plan, int D, int n_wide, int *tile_rows, in
  * single-scene entry points (same kernels, same tiles: tests/test_gpu_parity.py::test_batch_*). Any n >= 1 (launches carry
  * up to 8 scenes each); float32 tile engine -- scenes that need the level engine (D < 4, strides > 2^18, pathological key
  * patterns) or a row map run through their single-scene entry point inside the same call. Plans must be distinct objects
- * (a plan owns its workspaces) on the current device. Arrays of pointers / strides are HOST arrays. */
+ * (a plan owns its workspaces) on the current device. Arrays of pointers / strides are HOST arrays. Nothing of the tile
+ * engine is launched unless the arguments of every (scene, stage) are there. A plan with stage-0 events set
+ * (raht_plan_set_stage0_events) stays in the batch launches, and these four calls do NOT record its events: a batched launch
+ * is not one scene's stage 0. */
 int raht_fwd_batch(int n, raht_plan *const *plans, const float *const *C, const int64_t *ldc, int D,
                    float *const *T, const int64_t *ldt, raht_stream_t stream);
 int raht_inv_batch(int n, raht_plan *const *plans, const float *const *T, const int64_t *ldt, int D,
@@ -359,7 +362,10 @@ int raht_plan_set_concurrent_directions(raht_plan *plan, int on);
 /* Profiling aid: HIP events (hipEvent_t, created by the caller with timing enabled) recorded on the
  * launch stream immediately before and after the STAGE-0 kernel of every following transform of this
  * plan, so that the dominant kernel can be timed inside a real step (hipEventElapsedTime after the
- * stream has been synchronised). NULL, NULL switches it off. */
+ * stream has been synchronised). Stage 0 is the first launch of a forward and the last of an inverse,
+ * a tile stage or, for a tree of one launch, the top stage; every single-scene transform entry of the
+ * tile engines records the pair (tests/test_gpu_stage0_events.py), the level engine and the float32
+ * batch entries do not. NULL, NULL switches it off. */
 int raht_plan_set_stage0_events(raht_plan *plan, void *ev_before, void *ev_after);
 
 /* Profiling aid: enqueue ONE stage of the float32 tile schedule (stage 0 is the HBM-heavy launch).

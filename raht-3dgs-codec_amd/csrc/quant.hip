@@ -182,13 +182,8 @@ __global__ __launch_bounds__(256) void rows_f64_kernel(const void *__restrict__ 
 
 static int fill_steps64(StepTable64 &t, const double *steps, int n_steps, int D)
 {
-    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("quant: n_steps must be 1 or D"); return RAHT_ERR_INVALID; }
-    if (n_steps > MAX_STEP_CH) { set_error("quant: per-channel steps support D <= %d", MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
-    t.n = n_steps;
-    for (int c = 0; c < n_steps; ++c) {
-        if (!(steps[c] > 0.0)) { set_error("quant: step[%d] must be > 0", c); return RAHT_ERR_INVALID; }
-        t.v[c] = steps[c];
-    }
+    RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
+    fill_step_table(t, steps, n_steps);
     return RAHT_OK;
 }
 
@@ -232,10 +227,7 @@ __global__ __launch_bounds__(256) void transpose_i32_kernel(const int32_t *__res
 
 static int fill_steps(StepTable &t, const float *steps, int n_steps, int D)
 {
-    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("quant: n_steps must be 1 or D"); return RAHT_ERR_INVALID; }
-    if (n_steps > MAX_STEP_CH) { set_error("quant: per-channel steps support D <= %d", MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
-    for (int c = 0; c < n_steps; ++c)
-        if (!(steps[c] > 0.0f)) { set_error("quant: step[%d] must be > 0", c); return RAHT_ERR_INVALID; }
+    RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
     fill_step_table(t, steps, n_steps);
     return RAHT_OK;
 }

@@ -59,6 +59,23 @@ static inline int guarded(const char *what, F &&body) noexcept
     }
 }
 
+// THE rule of a table of quantization steps: one step or one per channel, at most MAX_STEP_CH of them, every step > 0
+// (also_as_float32: after rounding to float32 too -- the mixed kernels quantize the narrow channels with the float32 steps).
+// `what`: the entry point, in front of the message.
+constexpr int MAX_STEP_CH = 256;
+template <typename S>
+static inline int check_quant_steps(const char *what, const S *steps, int n_steps, int D, bool also_as_float32 = false)
+{
+    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("%s: n_steps must be 1 or D", what); return RAHT_ERR_INVALID; }
+    if (n_steps > MAX_STEP_CH) { set_error("%s: per-channel steps support D <= %d", what, MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
+    for (int c = 0; c < n_steps; ++c)
+        if (!(steps[c] > (S)0) || (also_as_float32 && !((float)steps[c] > 0.0f))) {
+            set_error("%s: step[%d] must be > 0%s", what, c, also_as_float32 ? " (also as float32)" : "");
+            return RAHT_ERR_INVALID;
+        }
+    return RAHT_OK;
+}
+
 // ---- devices -------------------------------------------------------------------------------------
 // One process per GPU is the intended use, but nothing below assumes it: every piece of cached device
 // state (block cache, scratch pool, kernel attributes, CU counts) is keyed by the HIP device ordinal, a

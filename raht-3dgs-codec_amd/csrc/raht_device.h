@@ -5,8 +5,7 @@
 
 namespace raht {
 
-constexpr int MAX_STEP_CH = 256;
-struct StepTable {
+struct StepTable {                 // (MAX_STEP_CH: raht_common.h)
     int n;                         // 0 = no quantization, 1 = one step, D = per channel
     int fast_div;                  // every step within [2^-100, 2^100]: the forward may divide without range scaling
     float v[MAX_STEP_CH];

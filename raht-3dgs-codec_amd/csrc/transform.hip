@@ -24,6 +24,7 @@
 #include "raht_common.h"
 #include "raht_device.h"
 #include "tile_engine.h"
+#include "tile_host.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -825,15 +826,14 @@ int launch_sq_final(const double *part, int64_t n_tiles, int D, int ncv, double 
     return RAHT_OK;
 }
 
-// Several scenes, one launch (raht_*_batch): the same stage of up to TILE_BATCH_MAX scenes. first_tile[s] = number of tiles of the
+// Several scenes, one launch (raht_*_batch): the same stage of up to BATCH_MAX scenes. first_tile[s] = number of tiles of the
 // scenes before s; a workgroup finds its scene with a handful of scalar compares and runs ONE tile of it. A frame of ~1 M
 // Gaussians fills the chip's 768 workgroup slots two and a half times and then waits ~20 us for its tail stages (a third of
 // its step); batched, the partial rounds of different scenes fill each other and ALL tails are one launch per stage.
-constexpr int TILE_BATCH_MAX = 8;
 template <typename T>
 struct TileBatch {
-    TileArgs<T> a[TILE_BATCH_MAX];
-    uint32_t first_tile[TILE_BATCH_MAX + 1];
+    TileArgs<T> a[BATCH_MAX];
+    uint32_t first_tile[BATCH_MAX + 1];
     int n;
 };
 
@@ -843,7 +843,7 @@ __global__ __launch_bounds__(TILE_THREADS, (sizeof(T) == 4 ? 6 : 4)) void tile_k
 {
     int s = 0;
 #pragma unroll
-    for (int q = 1; q < TILE_BATCH_MAX; ++q) s += (q < B.n && blockIdx.x >= B.first_tile[q]) ? 1 : 0;
+    for (int q = 1; q < BATCH_MAX; ++q) s += (q < B.n && blockIdx.x >= B.first_tile[q]) ? 1 : 0;
     const int64_t t = (int64_t)(blockIdx.x - B.first_tile[s]);
     tile_body<T, INV, IDENT, QM, SLOTS>(B.a[s], ST, t, (int64_t)1 << 40, (int)blockIdx.y);
 }
@@ -1086,7 +1086,7 @@ __global__ __launch_bounds__(TOP_THREADS) void top_kernel_multi(const TopArgs<fl
 
 // the top stages of several scenes in one launch (raht_*_batch): blockIdx.y = scene
 template <typename T>
-struct TopBatch { TopArgs<T> a[TILE_BATCH_MAX]; };
+struct TopBatch { TopArgs<T> a[BATCH_MAX]; };
 
 template <typename T, bool INV, bool QM>
 __global__ __launch_bounds__(TOP_THREADS) void top_kernel_batch(const TopBatch<T> B,
@@ -1123,10 +1123,13 @@ struct XformIO {
     T *dst = nullptr; int64_t ld_dst = 0;           // fwd: T (unless q)  inv: C
     int32_t *Q = nullptr; int64_t ldq = 0;          // fused quantization (fwd out / inv in)
     const typename StepsFor<T>::elem *steps = nullptr; int n_steps = 0;
+    const MultiQ *multi = nullptr;                  // forward: raht_fwd_quant_multi's steps and matrices (Q = its first matrix)
+    const T *ref = nullptr; int64_t ld_ref = 0;     // inverse stage 0, raht_dequant_inv_sqdiff: the reference rows ...
+    double *sq_part = nullptr;                      // ... and the per-tile partial sums (dst may then be NULL)
 };
 
-// ---- host side of the tile / top launches: "prepare" fills and validates the kernel arguments of one (scene, stage),
-// "launch" enqueues one scene's stage, "launch_*_batch" the same stage of several scenes in one launch ----
+// ---- host side of the tile / top launches: prepare_stage fills and validates the kernel arguments of one (scene, stage),
+// launch_prepared enqueues one scene's stage, launch_*_batch the same stage of several scenes in one launch ----
 struct TileGeom {
     int64_t n_tiles = 0;
     unsigned nchunks = 0;
@@ -1135,138 +1138,73 @@ struct TileGeom {
     bool same_shape(const TileGeom &o) const { return nchunks == o.nchunks && lds == o.lds && one == o.one && ident == o.ident; }
 };
 
-template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-static int tile_kernel_attr()
-{
-    // > 64 KiB of dynamic LDS must be allowed per function AND per device
-    static PerDeviceOnce attr, attr_b;
-    if (attr.first(current_device()))
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel<T, INV, IDENT, QM, SLOTS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (attr_b.first(current_device()))
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_batch<T, INV, IDENT, QM, SLOTS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return RAHT_OK;
-}
+// What one (scene, stage, direction) launches: the kernel arguments, filled and validated by prepare_stage, and the launch shape
+// (a top stage uses G.lds only). The single-scene calls launch it as it is (launch_prepared); the batch entries collect stages of
+// equal shape into one launch (run_batch).
+template <typename T>
+struct StageLaunch {
+    bool is_top = false;
+    TopArgs<T> P;                                   // top stage
+    TileArgs<T> A;                                  // tile stage
+    TileGeom G;
+};
 
-template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-static int launch_tile_one(const TileArgs<T> &A, const XformIO<T> &io, dim3 grid, size_t lds, hipStream_t s)
+// the kernels' step-table argument
+template <typename T, bool QM>
+static auto steps_arg(const XformIO<T> &io)
 {
-    RAHT_RET((tile_kernel_attr<T, INV, IDENT, QM, SLOTS>()));
     if constexpr (QM) {
         typename StepsFor<T>::type st;
         fill_step_table(st, io.steps, io.n_steps);
-        hipLaunchKernelGGL((tile_kernel<T, INV, IDENT, true, SLOTS>), grid, dim3(TILE_THREADS), lds, s, A, st);
+        return st;
     } else {
-        NoSteps ns{0, 0};
-        hipLaunchKernelGGL((tile_kernel<T, INV, IDENT, false, SLOTS>), grid, dim3(TILE_THREADS), lds, s, A, ns);
+        return NoSteps{0, 0};
     }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
-}
-
-template <typename T, bool INV, bool IDENT, bool QM, int SLOTS>
-static int launch_tile_batch_one(const TileBatch<T> &B, const XformIO<T> &io, dim3 grid, size_t lds, hipStream_t s)
-{
-    RAHT_RET((tile_kernel_attr<T, INV, IDENT, QM, SLOTS>()));
-    if constexpr (QM) {
-        typename StepsFor<T>::type st;
-        fill_step_table(st, io.steps, io.n_steps);
-        hipLaunchKernelGGL((tile_kernel_batch<T, INV, IDENT, true, SLOTS>), grid, dim3(TILE_THREADS), lds, s, B, st);
-    } else {
-        NoSteps ns{0, 0};
-        hipLaunchKernelGGL((tile_kernel_batch<T, INV, IDENT, false, SLOTS>), grid, dim3(TILE_THREADS), lds, s, B, ns);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
 }
 
 template <typename T, bool INV, bool QM>
-static int prepare_top_stage(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, TopArgs<T> &A, size_t &lds)
+static int prepare_stage(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, int Dc0, int dbg, StageLaunch<T> &L)
 {
     const Stage &st = sc.stages[(size_t)k];
+    const int K = (int)sc.stages.size();
     T *ws_k = (k >= 1) ? (T *)stage_ws(st, INV) : nullptr;
-    A.in = nullptr; A.ld_in = 0; A.out = nullptr; A.ld_out = 0;
-    if (!INV) { A.in = (k == 0) ? io.src : ws_k; A.ld_in = (k == 0) ? io.ld_src : D; A.fin = io.dst; A.ld_fin = io.ld_dst; }
-    else { A.fin = const_cast<T *>(io.src); A.ld_fin = io.ld_src; A.out = (k == 0) ? io.dst : ws_k; A.ld_out = (k == 0) ? io.ld_dst : D; }
-    A.Q = io.Q; A.ldq = io.ldq;
-    A.rows = st.rows;
-    A.io_mapped = 0;
-    if (p->row_map) {                                      // only single-stage plans carry a row map (run_transform checks)
-        if (k != 0 || st.rows || QM) { set_error("row-mapped plans run as ONE top stage without fused quantization"); return RAHT_ERR_UNSUPPORTED; }
-        A.rows = p->row_map;
-        A.io_mapped = 1;
+    constexpr bool F32Q = QM && std::is_same<T, float>::value;
+    if ((io.multi && !(F32Q && !INV)) || (io.sq_part && !(F32Q && INV))) {
+        set_error("tile stage %d: the multi-step / comparing kernels are float32, fused, forward / inverse only", k);
+        return RAHT_ERR_INVALID;
     }
-    A.e_pos = st.rows ? st.e_pos : p->inv_order;
-    A.pj = st.t_pj;
-    if constexpr (sizeof(T) == 4) A.ab = (const T *)st.t_ab32; else A.ab = (const T *)st.t_ab64;
-    A.root_rank = st.t_root;
-    A.root_buf = (T *)p->root_buf;
-    A.n = (int)st.n_entries; A.n_merges = (int)st.n_merges; A.D = D;
-    A.lev = st.t_lev; A.nlev = st.t_nlev; A.nbig = st.t_nbig; A.small_start = st.t_small_start;
-    const size_t n_small = st.n_merges - st.t_small_start;
-    lds = (size_t)st.n_entries * 16 + ((n_small + 3) & ~(size_t)3) * 4 + n_small * 2 * sizeof(T);   // + 512 B static
-    static PerDeviceOnce attr;
-    if (attr.first(current_device())) {
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel<T, INV, QM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_batch<T, INV, QM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+    L.is_top = st.is_top;
+    if (st.is_top) {
+        TopArgs<T> &A = L.P;
+        A.in = nullptr; A.ld_in = 0; A.out = nullptr; A.ld_out = 0;
+        if (!INV) { A.in = (k == 0) ? io.src : ws_k; A.ld_in = (k == 0) ? io.ld_src : D; A.fin = io.dst; A.ld_fin = io.ld_dst; }
+        else { A.fin = const_cast<T *>(io.src); A.ld_fin = io.ld_src; A.out = (k == 0) ? io.dst : ws_k; A.ld_out = (k == 0) ? io.ld_dst : D; }
+        A.Q = io.Q; A.ldq = io.ldq;
+        A.rows = st.rows;
+        A.io_mapped = 0;
+        if (p->row_map) {                                      // only single-stage plans carry a row map (run_transform checks)
+            if (k != 0 || st.rows || QM) { set_error("row-mapped plans run as ONE top stage without fused quantization"); return RAHT_ERR_UNSUPPORTED; }
+            A.rows = p->row_map;
+            A.io_mapped = 1;
+        }
+        A.e_pos = st.rows ? st.e_pos : p->inv_order;
+        A.pj = st.t_pj;
+        if constexpr (sizeof(T) == 4) A.ab = (const T *)st.t_ab32; else A.ab = (const T *)st.t_ab64;
+        A.root_rank = st.t_root;
+        A.root_buf = (T *)p->root_buf;
+        A.n = (int)st.n_entries; A.n_merges = (int)st.n_merges; A.D = D;
+        A.lev = st.t_lev; A.nlev = st.t_nlev; A.nbig = st.t_nbig; A.small_start = st.t_small_start;
+        const size_t n_small = st.n_merges - st.t_small_start;
+        L.G.lds = (size_t)st.n_entries * 16 + ((n_small + 3) & ~(size_t)3) * 4 + n_small * 2 * sizeof(T);   // + 512 B static
+        return RAHT_OK;
     }
-    return RAHT_OK;
-}
-
-template <typename T, bool INV, bool QM>
-static int launch_top_stage(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, hipStream_t s)
-{
-    constexpr int VN = 16 / (int)sizeof(T);
-    TopArgs<T> A;
-    size_t lds = 0;
-    RAHT_RET((prepare_top_stage<T, INV, QM>(p, sc, k, io, D, A, lds)));
-    const dim3 grid((unsigned)((D + VN - 1) / VN));
-    if constexpr (QM) {
-        typename StepsFor<T>::type stp;
-        fill_step_table(stp, io.steps, io.n_steps);
-        hipLaunchKernelGGL((top_kernel<T, INV, true>), grid, dim3(TOP_THREADS), lds, s, A, stp);
-    } else {
-        NoSteps ns{0, 0};
-        hipLaunchKernelGGL((top_kernel<T, INV, false>), grid, dim3(TOP_THREADS), lds, s, A, ns);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
-}
-
-// the top stages of scenes idx[0..m): one launch, blockIdx.y = scene (io.steps: the batch shares one step table)
-template <typename T, bool INV, bool QM>
-static int launch_top_batch(int m, const TopArgs<T> *As, const size_t *ldss, const XformIO<T> &io, int D, hipStream_t s)
-{
-    constexpr int VN = 16 / (int)sizeof(T);
-    TopBatch<T> B;
-    size_t lds = 0;
-    for (int i = 0; i < m; ++i) { B.a[i] = As[i]; lds = std::max(lds, ldss[i]); }
-    for (int i = m; i < TILE_BATCH_MAX; ++i) B.a[i] = As[0];
-    const dim3 grid((unsigned)((D + VN - 1) / VN), (unsigned)m);
-    if constexpr (QM) {
-        typename StepsFor<T>::type stp;
-        fill_step_table(stp, io.steps, io.n_steps);
-        hipLaunchKernelGGL((top_kernel_batch<T, INV, true>), grid, dim3(TOP_THREADS), lds, s, B, stp);
-    } else {
-        NoSteps ns{0, 0};
-        hipLaunchKernelGGL((top_kernel_batch<T, INV, false>), grid, dim3(TOP_THREADS), lds, s, B, ns);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
-}
-
-template <typename T, bool INV, bool QM>
-static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, int Dc0, int dbg,
-                              TileArgs<T> &A, TileGeom &G)
-{
-    const Stage &st = sc.stages[(size_t)k];
+    TileArgs<T> &A = L.A;
+    TileGeom &G = L.G;
     int Dc = Dc0;
     if (k >= 1) {                                    // later stages: large tiles, channel chunks
         int r1 = 0, rf = 0;
         pick_tail_geometry(p, (int)sizeof(T), D, sc.tile_rows, &r1, &Dc, &rf);
     }
-    const int K = (int)sc.stages.size();
     A.rows = st.rows; A.surv_off = st.surv_off; A.n_entries = st.n_entries; A.N = p->N; A.R = st.tile_rows;
     A.D = D; A.Dc = Dc;
     constexpr int VN = 16 / (int)sizeof(T);
@@ -1283,7 +1221,6 @@ static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, con
     A.dbg = dbg; A.nwide = 0; A.ref = nullptr; A.ld_ref = 0; A.sq_part = nullptr;
     A.ld_ws = D;
     A.wsn = (k + 1 < K) ? (T *)stage_ws(sc.stages[(size_t)k + 1], INV) : nullptr;
-    T *ws_k = (k >= 1) ? (T *)stage_ws(st, INV) : nullptr;
     if (!INV) {
         A.in = (k == 0) ? io.src : ws_k; A.ld_in = (k == 0) ? io.ld_src : D;
         A.fin = io.dst; A.ld_fin = io.ld_dst;
@@ -1293,6 +1230,7 @@ static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, con
         A.fin = const_cast<T *>(io.src); A.ld_fin = io.ld_src;
         A.out = (k == 0) ? io.dst : ws_k; A.ld_out = (k == 0) ? io.ld_dst : D;
     }
+    const bool sq = k == 0 && io.sq_part;                 // the comparing stage 0 (raht_dequant_inv_sqdiff): dst may be NULL
     // Every pointer the kernel will dereference for THIS (direction, stage) must be there before it is
     // launched: a tile kernel handed a null workspace reads address 0 and the process dies in ROCr's
     // fault handler at the next synchronisation (the round-1 abort). In particular the LAST
@@ -1304,7 +1242,8 @@ static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, con
         else if (k >= 1 && !ws_k) bad = "stage workspace";
         else if (QM && (!A.Q || !A.inv_order)) bad = "Q / inv_order";
         else if (!INV && (!A.in || (!QM && !A.fin))) bad = "forward input / output";
-        else if (INV && (!A.out || (!QM && !A.fin))) bad = "inverse input / output";
+        else if (INV && ((!A.out && !sq) || (!QM && !A.fin))) bad = "inverse input / output";
+        else if (sq && !io.ref) bad = "sqdiff reference rows";
         else if (st.tile_rows < 1 || (int64_t)st.tile_rows * std::max<int64_t>(std::max(A.ld_in, A.ld_out), A.ld_fin) * (int64_t)sizeof(T) >= ((int64_t)1 << 32)) bad = "tile geometry (32-bit row offsets)";
         if (bad) { set_error("tile stage %d (%s): missing %s", k, INV ? "inverse" : "forward", bad); return RAHT_ERR_INVALID; }
     }
@@ -1317,63 +1256,92 @@ static int prepare_tile_stage(const raht_plan *p, const Schedule &sc, int k, con
     G.n_tiles = st.n_tiles;                               // one tile per workgroup
     G.one = st.tile_rows <= TILE_THREADS;
     G.ident = st.rows == nullptr;
+    if (sq) {
+        // one chunk holds the whole row, and the tile's LDS block has room for every wave's partial sums
+        if (G.nchunks != 1 || !G.ident || (size_t)(TILE_THREADS / 64) * (size_t)(((D + 3) / 4) * 4) * 8 > G.lds) {
+            set_error("raht_dequant_inv_sqdiff: unexpected stage-0 geometry");
+            return RAHT_ERR_INVALID;
+        }
+        if (!A.out) A.ld_out = 0;
+        A.ref = io.ref; A.ld_ref = io.ld_ref; A.sq_part = io.sq_part;
+    }
     return RAHT_OK;
 }
 
+// one prepared stage of ONE scene: the plain kernel, the forward multi-step one (io.multi) or the inverse's comparing stage 0
+// (L.A.sq_part); prepare_stage has checked that the direction and type have that kernel. `events`: stage 0 of a real transform is
+// bracketed by the plan's profiling events (raht_plan_set_stage0_events) -- the only place of this file that records them.
 template <typename T, bool INV, bool QM>
-static int launch_stage_impl(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, int Dc0,
-                             hipStream_t s, int dbg);
-
-template <typename T, bool INV, bool QM>
-static int launch_tile_stage(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, int Dc0,
-                             hipStream_t s, int dbg = 0)
+static int launch_prepared(const raht_plan *p, int k, const StageLaunch<T> &L, const XformIO<T> &io, bool events, hipStream_t s)
 {
-    if (k == 0 && p->ev_before && dbg == 0) {          // profiling: bracket the stage-0 launch of a real transform
-        RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
-        const int rc = launch_stage_impl<T, INV, QM>(p, sc, k, io, D, Dc0, s, dbg);
-        RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
-        return rc;
-    }
-    return launch_stage_impl<T, INV, QM>(p, sc, k, io, D, Dc0, s, dbg);
+    constexpr bool F32Q = QM && std::is_same<T, float>::value;     // the multi / sq kernels: float32, fused quantization
+    const auto st = steps_arg<T, QM>(io);
+    auto launch = [&]() -> int {
+        if (L.is_top) {
+            constexpr int VN = 16 / (int)sizeof(T);
+            const dim3 grid((unsigned)((L.P.D + VN - 1) / VN)), block(TOP_THREADS);
+            if constexpr (F32Q && !INV) { if (io.multi) return launch_lds<top_kernel_multi>(grid, block, L.G.lds, TOP_LDS_LIMIT, s, L.P, st, *io.multi); }
+            return launch_lds<top_kernel<T, INV, QM>>(grid, block, L.G.lds, TOP_LDS_LIMIT, s, L.P, st);
+        }
+        const TileGeom &G = L.G;
+        const dim3 grid((unsigned)G.n_tiles, G.nchunks), block(TILE_THREADS);
+        return by_ident_slots(G.ident, G.one, [&](auto ident, auto slots) -> int {
+            constexpr bool IDENT = decltype(ident)::value;
+            constexpr int SLOTS = decltype(slots)::value;
+            if constexpr (F32Q && !INV) { if (io.multi) return launch_lds<tile_kernel_multi<IDENT, SLOTS>>(grid, block, G.lds, TILE_LDS_LIMIT, s, L.A, st, *io.multi); }
+            if constexpr (F32Q && INV && IDENT) { if (L.A.sq_part) return launch_lds<tile_kernel_sq<SLOTS>>(grid, block, G.lds, TILE_LDS_LIMIT, s, L.A, st); }
+            return launch_lds<tile_kernel<T, INV, IDENT, QM, SLOTS>>(grid, block, G.lds, TILE_LDS_LIMIT, s, L.A, st);
+        });
+    };
+    if (!(events && k == 0 && p->ev_before)) return launch();
+    RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
+    const int rc = launch();
+    RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
+    return rc;
 }
 
+// stage k of one scene: prepared on the stack, then launched. dbg != 0 (raht_debug_run_stage's ablations): no events.
 template <typename T, bool INV, bool QM>
-static int launch_stage_impl(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, int Dc0,
-                             hipStream_t s, int dbg)
+static int launch_stage(const raht_plan *p, const Schedule &sc, int k, const XformIO<T> &io, int D, int Dc0, hipStream_t s, int dbg = 0)
 {
-    const Stage &st = sc.stages[(size_t)k];
-    if (st.is_top) return launch_top_stage<T, INV, QM>(p, sc, k, io, D, s);
-    TileArgs<T> A;
-    TileGeom G;
-    RAHT_RET((prepare_tile_stage<T, INV, QM>(p, sc, k, io, D, Dc0, dbg, A, G)));
-    const dim3 grid((unsigned)G.n_tiles, G.nchunks);
-    if (G.ident)
-        return G.one ? launch_tile_one<T, INV, true, QM, 1>(A, io, grid, G.lds, s)
-                     : launch_tile_one<T, INV, true, QM, 2>(A, io, grid, G.lds, s);
-    return G.one ? launch_tile_one<T, INV, false, QM, 1>(A, io, grid, G.lds, s)
-                 : launch_tile_one<T, INV, false, QM, 2>(A, io, grid, G.lds, s);
+    StageLaunch<T> L;
+    RAHT_RET((prepare_stage<T, INV, QM>(p, sc, k, io, D, Dc0, dbg, L)));
+    return launch_prepared<T, INV, QM>(p, k, L, io, dbg == 0, s);
 }
 
-// the same tile stage of m <= TILE_BATCH_MAX scenes (equal launch shape) in one launch, one tile per workgroup
+// the same tile stage of m <= BATCH_MAX scenes (equal launch shape) in one launch, one tile per workgroup (io.steps: the batch
+// shares one step table)
 template <typename T, bool INV, bool QM>
-static int launch_tile_batch(int m, const TileArgs<T> *As, const TileGeom *Gs, const XformIO<T> &io, hipStream_t s)
+static int launch_tile_batch(int m, const StageLaunch<T> *const *Ls, const XformIO<T> &io, hipStream_t s)
 {
     TileBatch<T> B;
     B.n = m;
     uint32_t tot = 0;
-    for (int i = 0; i < TILE_BATCH_MAX; ++i) {
-        B.a[i] = As[i < m ? i : 0];
+    for (int i = 0; i < BATCH_MAX; ++i) {
+        B.a[i] = Ls[i < m ? i : 0]->A;
         B.first_tile[i] = tot;
-        if (i < m) tot += (uint32_t)Gs[i].n_tiles;
+        if (i < m) tot += (uint32_t)Ls[i]->G.n_tiles;
     }
-    B.first_tile[TILE_BATCH_MAX] = tot;
-    const TileGeom &G = Gs[0];
-    const dim3 grid(tot, G.nchunks);
-    if (G.ident)
-        return G.one ? launch_tile_batch_one<T, INV, true, QM, 1>(B, io, grid, G.lds, s)
-                     : launch_tile_batch_one<T, INV, true, QM, 2>(B, io, grid, G.lds, s);
-    return G.one ? launch_tile_batch_one<T, INV, false, QM, 1>(B, io, grid, G.lds, s)
-                 : launch_tile_batch_one<T, INV, false, QM, 2>(B, io, grid, G.lds, s);
+    B.first_tile[BATCH_MAX] = tot;
+    const TileGeom &G = Ls[0]->G;
+    const auto st = steps_arg<T, QM>(io);
+    return by_ident_slots(G.ident, G.one, [&](auto ident, auto slots) -> int {
+        return launch_lds<tile_kernel_batch<T, INV, decltype(ident)::value, QM, decltype(slots)::value>>(
+            dim3(tot, G.nchunks), dim3(TILE_THREADS), G.lds, TILE_LDS_LIMIT, s, B, st);
+    });
+}
+
+// the top stages of m scenes: one launch, blockIdx.y = scene; the dynamic LDS block is the largest scene's
+template <typename T, bool INV, bool QM>
+static int launch_top_batch(int m, const StageLaunch<T> *const *Ls, const XformIO<T> &io, hipStream_t s)
+{
+    constexpr int VN = 16 / (int)sizeof(T);
+    TopBatch<T> B;
+    size_t lds = 0;
+    for (int i = 0; i < BATCH_MAX; ++i) B.a[i] = Ls[i < m ? i : 0]->P;
+    for (int i = 0; i < m; ++i) lds = std::max(lds, Ls[i]->G.lds);
+    const dim3 grid((unsigned)((B.a[0].D + VN - 1) / VN), (unsigned)m);
+    return launch_lds<top_kernel_batch<T, INV, QM>>(grid, dim3(TOP_THREADS), lds, TOP_LDS_LIMIT, s, B, steps_arg<T, QM>(io));
 }
 
 template <typename T>
@@ -1468,7 +1436,7 @@ static int run_transform(const raht_plan *cp, const T *src, int64_t ld_src, int 
         XformIO<T> io;
         io.src = src; io.ld_src = ld_src; io.dst = dst; io.ld_dst = ld_dst;
         const int K = (int)sc->stages.size();
-        for (int q = 0; q < K && rc == RAHT_OK; ++q) rc = launch_tile_stage<T, INV, false>(p, *sc, INV ? K - 1 - q : q, io, D, Dc, s);
+        for (int q = 0; q < K && rc == RAHT_OK; ++q) rc = launch_stage<T, INV, false>(p, *sc, INV ? K - 1 - q : q, io, D, Dc, s);
     }
     if (rc == RAHT_OK && w && p->row_map) { set_error("node weights are not available from a row-mapped plan"); return RAHT_ERR_UNSUPPORTED; }
     if (rc == RAHT_OK && w) {
@@ -1477,16 +1445,6 @@ static int run_transform(const raht_plan *cp, const T *src, int64_t ld_src, int 
         RAHT_HIP_CHECK(hipGetLastError());
     }
     return rc;
-}
-
-template <typename S>
-static int check_steps(const S *steps, int n_steps, int D)
-{
-    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("quant: n_steps must be 1 or D"); return RAHT_ERR_INVALID; }
-    if (n_steps > MAX_STEP_CH) { set_error("quant: per-channel steps support D <= %d", MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
-    for (int c = 0; c < n_steps; ++c)
-        if (!(steps[c] > (S)0)) { set_error("quant: step[%d] must be > 0", c); return RAHT_ERR_INVALID; }
-    return RAHT_OK;
 }
 
 // the two-pass entry points (quant.hip), by element type: what the fused entry points fall back to
@@ -1510,7 +1468,7 @@ static int fwd_quant_impl(const raht_plan *cp, const T *C, int64_t ldc, int D, c
     if (!p || !C || !Q || D < 1 || ldc < D || ldq < D) { set_error("raht_fwd_quant: bad argument"); return RAHT_ERR_INVALID; }
     RAHT_RET(check_plan_device(p, "raht_fwd_quant"));
     if (p->row_map) { set_error("raht_fwd_quant: not available for a row-mapped plan"); return RAHT_ERR_UNSUPPORTED; }
-    RAHT_RET(check_steps(steps, n_steps, D));
+    RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
     Schedule *sc = nullptr;
     int Dc = 0;
     RAHT_RET(tile_setup<T>(p, D, std::max(ldc, ldq), s, &sc, &Dc));
@@ -1525,7 +1483,7 @@ static int fwd_quant_impl(const raht_plan *cp, const T *C, int64_t ldc, int D, c
     XformIO<T> io;
     io.src = C; io.ld_src = ldc; io.Q = Q; io.ldq = ldq; io.steps = steps; io.n_steps = n_steps;
     const int K = (int)sc->stages.size();
-    for (int k = 0; k < K; ++k) RAHT_RET((launch_tile_stage<T, false, true>(p, *sc, k, io, D, Dc, s)));
+    for (int k = 0; k < K; ++k) RAHT_RET((launch_stage<T, false, true>(p, *sc, k, io, D, Dc, s)));
     return RAHT_OK;
 }
 
@@ -1539,7 +1497,7 @@ static int dequant_inv_impl(const raht_plan *cp, const int32_t *Q, int64_t ldq, 
     if (!p || !C || !Q || D < 1 || ldc < D || ldq < D) { set_error("raht_dequant_inv: bad argument"); return RAHT_ERR_INVALID; }
     RAHT_RET(check_plan_device(p, "raht_dequant_inv"));
     if (p->row_map) { set_error("raht_dequant_inv: not available for a row-mapped plan"); return RAHT_ERR_UNSUPPORTED; }
-    RAHT_RET(check_steps(steps, n_steps, D));
+    RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
     Schedule *sc = nullptr;
     int Dc = 0;
     RAHT_RET(tile_setup<T>(p, D, std::max(ldc, ldq), s, &sc, &Dc));
@@ -1552,7 +1510,7 @@ static int dequant_inv_impl(const raht_plan *cp, const int32_t *Q, int64_t ldq, 
     XformIO<T> io;
     io.dst = C; io.ld_dst = ldc; io.Q = const_cast<int32_t *>(Q); io.ldq = ldq; io.steps = steps; io.n_steps = n_steps;
     const int K = (int)sc->stages.size();
-    for (int k = K - 1; k >= 0; --k) RAHT_RET((launch_tile_stage<T, true, true>(p, *sc, k, io, D, Dc, s)));
+    for (int k = K - 1; k >= 0; --k) RAHT_RET((launch_stage<T, true, true>(p, *sc, k, io, D, Dc, s)));
     return RAHT_OK;
 }
 
@@ -1587,38 +1545,9 @@ static int fwd_quant_multi_impl(const raht_plan *cp, const float *C, int64_t ldc
             if (!(M.step[i] >= 0x1p-100f && M.step[i] <= 0x1p100f)) M.fast_div = 0;
         }
         XformIO<float> io;
-        io.src = C; io.ld_src = ldc; io.Q = M.Q[0]; io.ldq = ldq; io.steps = &steps[k0]; io.n_steps = 1;
-        StepTable st;
-        fill_step_table(st, io.steps, 1);
+        io.src = C; io.ld_src = ldc; io.Q = M.Q[0]; io.ldq = ldq; io.steps = &steps[k0]; io.n_steps = 1; io.multi = &M;
         const int K = (int)sc->stages.size();
-        for (int kk = 0; kk < K; ++kk) {
-            const Stage &stg = sc->stages[(size_t)kk];
-            if (stg.is_top) {
-                TopArgs<float> A;
-                size_t lds = 0;
-                RAHT_RET((prepare_top_stage<float, false, true>(p, *sc, kk, io, D, A, lds)));
-                static PerDeviceOnce attr;
-                if (attr.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-                hipLaunchKernelGGL(top_kernel_multi, dim3((unsigned)((D + 3) / 4)), dim3(TOP_THREADS), lds, s, A, st, M);
-            } else {
-                TileArgs<float> A;
-                TileGeom G;
-                RAHT_RET((prepare_tile_stage<float, false, true>(p, *sc, kk, io, D, Dc, 0, A, G)));
-                const dim3 grid((unsigned)G.n_tiles, G.nchunks);
-                static PerDeviceOnce a11, a12, a01, a02;
-                if (kk == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
-                if (G.ident && G.one) { if (a11.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                                        hipLaunchKernelGGL((tile_kernel_multi<true, 1>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
-                else if (G.ident) { if (a12.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                                    hipLaunchKernelGGL((tile_kernel_multi<true, 2>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
-                else if (G.one) { if (a01.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                                  hipLaunchKernelGGL((tile_kernel_multi<false, 1>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
-                else { if (a02.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_multi<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                       hipLaunchKernelGGL((tile_kernel_multi<false, 2>), grid, dim3(TILE_THREADS), G.lds, s, A, st, M); }
-                if (kk == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
-            }
-            RAHT_HIP_CHECK(hipGetLastError());
-        }
+        for (int kk = 0; kk < K; ++kk) RAHT_RET((launch_stage<float, false, true>(p, *sc, kk, io, D, Dc, s)));
     }
     return RAHT_OK;
 }
@@ -1635,7 +1564,7 @@ static int dequant_inv_sqdiff_impl(const raht_plan *cp, const int32_t *Q, int64_
     if (!p || !Q || !Cref || !sq || D < 1 || ldq < D || ldref < D || (Crec && ldc < D)) { set_error("raht_dequant_inv_sqdiff: bad argument"); return RAHT_ERR_INVALID; }
     RAHT_RET(check_plan_device(p, "raht_dequant_inv_sqdiff"));
     if (p->row_map) { set_error("raht_dequant_inv_sqdiff: not available for a row-mapped plan"); return RAHT_ERR_UNSUPPORTED; }
-    RAHT_RET(check_steps(steps, n_steps, D));
+    RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
     Schedule *sc = nullptr;
     int Dc = 0;
     RAHT_RET(tile_setup<float>(p, D, std::max(std::max(ldref, ldq), Crec ? ldc : (int64_t)D), s, &sc, &Dc));
@@ -1649,125 +1578,72 @@ static int dequant_inv_sqdiff_impl(const raht_plan *cp, const int32_t *Q, int64_
         RAHT_RET(dequant_inv_impl<float>(p, Q, ldq, D, steps, n_steps, out, ldo, stream));
         return raht_sqdiff_columns(Cref, ldref, out, ldo, p->N, D, RAHT_F32, sq, stream);
     }
+    // stage 0 is the comparing kernel: it leaves ncv partial sums per tile
+    const int ncv = ((D + 3) / 4) * 4;
+    const int64_t n_tiles = sc->stages[0].n_tiles;
+    Scratch part(sizeof(double) * (size_t)n_tiles * (size_t)ncv, s);
+    if (!part.ok()) return RAHT_ERR_NOMEM;
     XformIO<float> io;
     io.dst = Crec; io.ld_dst = Crec ? ldc : D; io.Q = const_cast<int32_t *>(Q); io.ldq = ldq; io.steps = steps; io.n_steps = n_steps;
+    io.ref = Cref; io.ld_ref = ldref; io.sq_part = part.as<double>();
     const int K = (int)sc->stages.size();
-    for (int k = K - 1; k >= 1; --k) RAHT_RET((launch_tile_stage<float, true, true>(p, *sc, k, io, D, Dc, s)));
-    // stage 0: the comparing kernel
-    TileArgs<float> A;
-    TileGeom G;
-    XformIO<float> io0 = io;
-    if (!Crec) io0.dst = const_cast<float *>(Cref);            // (only so that the argument check sees an output; overridden below)
-    RAHT_RET((prepare_tile_stage<float, true, true>(p, *sc, 0, io0, D, Dc, 0, A, G)));
-    const int ncv = ((D + 3) / 4) * 4;
-    Scratch part(sizeof(double) * (size_t)G.n_tiles * (size_t)ncv, s);
-    if (!part.ok()) return RAHT_ERR_NOMEM;
-    A.out = Crec; A.ld_out = Crec ? ldc : 0;
-    A.ref = Cref; A.ld_ref = ldref; A.sq_part = part.as<double>();
-    if (G.nchunks != 1 || !G.ident || (size_t)(TILE_THREADS / 64) * (size_t)ncv * 8 > G.lds) {
-        set_error("raht_dequant_inv_sqdiff: unexpected stage-0 geometry");
-        return RAHT_ERR_INVALID;
-    }
-    StepTable st;
-    fill_step_table(st, steps, n_steps);
-    static PerDeviceOnce attr1, attr2;
-    if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
-    if (G.one) {
-        if (attr1.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_sq<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((tile_kernel_sq<1>), dim3((unsigned)G.n_tiles), dim3(TILE_THREADS), G.lds, s, A, st);
-    } else {
-        if (attr2.first(current_device())) RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_sq<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((tile_kernel_sq<2>), dim3((unsigned)G.n_tiles), dim3(TILE_THREADS), G.lds, s, A, st);
-    }
-    if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
-    hipLaunchKernelGGL(sq_final_kernel, dim3((unsigned)D), dim3(256), 0, s, part.as<double>(), G.n_tiles, D, ncv, sq);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    for (int k = K - 1; k >= 0; --k) RAHT_RET((launch_stage<float, true, true>(p, *sc, k, io, D, Dc, s)));
+    return launch_sq_final(part.as<double>(), n_tiles, D, ncv, sq, s);
 }
 
 // ---- several scenes, one set of launches (raht_*_batch) ----------------------------------------------
-// Round r of the forward direction runs stage r of every scene that has one (inverse: the stages from the top of the
-// deepest schedule downwards, a scene joining when its own top stage comes up); within a round the tile stages of equal
-// launch shape go out TILE_BATCH_MAX scenes per launch, the top stages likewise with blockIdx.y = scene. Scenes without a
-// tile schedule run through the single-scene path.
+// The rounds and groups are group_batch_rounds' (tile_host.h); tile stages share a launch when their launch shapes are equal, the
+// top stages of a round always do (blockIdx.y = scene). Scenes without a tile schedule run through the single-scene path. Nothing
+// is launched unless the arguments of every (scene, stage) are there. The plans' stage-0 events are not recorded here.
 template <typename T, bool INV, bool QM>
 static int run_batch(int n, raht_plan *const *plans, const XformIO<T> *ios, int D, hipStream_t s, const char *what)
 {
     if (n < 1 || !plans || !ios) { set_error("%s: bad argument", what); return RAHT_ERR_INVALID; }
-    std::vector<Schedule *> scs((size_t)n, nullptr);
-    std::vector<int> Dcs((size_t)n, 0);
-    int maxK = 0;
+    RAHT_RET(check_batch_plans(what, n, plans));
+    struct Scene { Schedule *sc = nullptr; int Dc = 0, K = 0; size_t first = 0; };
+    std::vector<Scene> scn((size_t)n);
+    size_t total = 0;
     for (int i = 0; i < n; ++i) {
         raht_plan *p = plans[i];
         const XformIO<T> &io = ios[i];
-        if (!p) { set_error("%s: NULL plan (scene %d)", what, i); return RAHT_ERR_INVALID; }
-        for (int j = 0; j < i; ++j) if (plans[j] == p) { set_error("%s: scenes %d and %d share a plan (a plan owns its workspaces)", what, j, i); return RAHT_ERR_INVALID; }
+        Scene &S = scn[(size_t)i];
         RAHT_RET(check_plan_device(p, what));
         const int64_t ld_a = INV ? (QM ? io.ldq : io.ld_src) : io.ld_src, ld_b = INV ? io.ld_dst : (QM ? io.ldq : io.ld_dst);
         const void *pa = INV ? (QM ? (const void *)io.Q : (const void *)io.src) : (const void *)io.src;
         const void *pb = INV ? (const void *)io.dst : (QM ? (const void *)io.Q : (const void *)io.dst);
         if (!pa || !pb || D < 1 || ld_a < D || ld_b < D) { set_error("%s: bad matrix argument (scene %d)", what, i); return RAHT_ERR_INVALID; }
-        if (p->row_map) continue;                              // single-scene path (one mapped top stage)
-        RAHT_RET(tile_setup<T>(p, D, std::max(ld_a, ld_b), s, &scs[(size_t)i], &Dcs[(size_t)i]));
-        if (scs[(size_t)i]) maxK = std::max(maxK, (int)scs[(size_t)i]->stages.size());
+        if (!p->row_map) RAHT_RET(tile_setup<T>(p, D, std::max(ld_a, ld_b), s, &S.sc, &S.Dc));      // row-mapped: single-scene path (one mapped top stage)
+        S.K = S.sc ? (int)S.sc->stages.size() : 0;
+        S.first = total;
+        total += (size_t)S.K;
     }
-    // scenes outside the tile engine: their own entry point, in place in the stream
-    for (int i = 0; i < n; ++i) {
-        if (scs[(size_t)i]) continue;
+    std::vector<StageLaunch<T>> prep(total);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < scn[(size_t)i].K; ++k)
+            RAHT_RET((prepare_stage<T, INV, QM>(plans[i], *scn[(size_t)i].sc, k, ios[i], D, scn[(size_t)i].Dc, 0, prep[scn[(size_t)i].first + (size_t)k])));
+    auto stage_of = [&](int i, int k) -> const StageLaunch<T> & { return prep[scn[(size_t)i].first + (size_t)k]; };
+    auto single = [&](int i) -> int {          // scenes outside the tile engine: their own entry point, in place in the stream
         const XformIO<T> &io = ios[i];
-        int rc;
-        if constexpr (QM && !INV) rc = fwd_quant_impl<T>(plans[i], io.src, io.ld_src, D, io.steps, io.n_steps, io.Q, io.ldq, (raht_stream_t)s);
-        else if constexpr (QM && INV) rc = dequant_inv_impl<T>(plans[i], io.Q, io.ldq, D, io.steps, io.n_steps, io.dst, io.ld_dst, (raht_stream_t)s);
-        else rc = run_transform<T, INV>(plans[i], io.src, io.ld_src, D, io.dst, io.ld_dst, nullptr, s);
-        RAHT_RET(rc);
-    }
-    for (int r = 0; r < maxK; ++r) {
-        int idx_tile[TILE_BATCH_MAX], idx_top[TILE_BATCH_MAX], n_tile = 0, n_top = 0;
-        TileArgs<T> At[TILE_BATCH_MAX];
-        TileGeom Gt[TILE_BATCH_MAX];
-        TopArgs<T> Ap[TILE_BATCH_MAX];
-        size_t Lp[TILE_BATCH_MAX];
-        auto flush_tile = [&]() -> int {
-            if (n_tile == 0) return RAHT_OK;
-            int rc;
-            if (n_tile == 1) {
-                const int i = idx_tile[0];
-                rc = launch_stage_impl<T, INV, QM>(plans[i], *scs[(size_t)i], INV ? maxK - 1 - r : r, ios[i], D, Dcs[(size_t)i], s, 0);
-            } else {
-                rc = launch_tile_batch<T, INV, QM>(n_tile, At, Gt, ios[idx_tile[0]], s);
-            }
-            n_tile = 0;
-            return rc;
-        };
-        auto flush_top = [&]() -> int {
-            if (n_top == 0) return RAHT_OK;
-            const int rc = launch_top_batch<T, INV, QM>(n_top, Ap, Lp, ios[idx_top[0]], D, s);
-            n_top = 0;
-            return rc;
-        };
-        for (int i = 0; i < n; ++i) {
-            Schedule *sc = scs[(size_t)i];
-            if (!sc) continue;
-            const int K = (int)sc->stages.size();
-            const int k = INV ? maxK - 1 - r : r;
-            if (k < 0 || k >= K) continue;
-            if (sc->stages[(size_t)k].is_top) {
-                RAHT_RET((prepare_top_stage<T, INV, QM>(plans[i], *sc, k, ios[i], D, Ap[n_top], Lp[n_top])));
-                idx_top[n_top++] = i;
-                if (n_top == TILE_BATCH_MAX) RAHT_RET(flush_top());
-            } else {
-                TileArgs<T> A;
-                TileGeom G;
-                RAHT_RET((prepare_tile_stage<T, INV, QM>(plans[i], *sc, k, ios[i], D, Dcs[(size_t)i], 0, A, G)));
-                if (n_tile > 0 && !G.same_shape(Gt[0])) RAHT_RET(flush_tile());     // another launch shape: its own launch
-                At[n_tile] = A; Gt[n_tile] = G; idx_tile[n_tile++] = i;
-                if (n_tile == TILE_BATCH_MAX) RAHT_RET(flush_tile());
-            }
-        }
-        RAHT_RET(flush_tile());
-        RAHT_RET(flush_top());
-    }
-    return RAHT_OK;
+        if constexpr (QM && !INV) return fwd_quant_impl<T>(plans[i], io.src, io.ld_src, D, io.steps, io.n_steps, io.Q, io.ldq, (raht_stream_t)s);
+        else if constexpr (QM && INV) return dequant_inv_impl<T>(plans[i], io.Q, io.ldq, D, io.steps, io.n_steps, io.dst, io.ld_dst, (raht_stream_t)s);
+        else return run_transform<T, INV>(plans[i], io.src, io.ld_src, D, io.dst, io.ld_dst, nullptr, s);
+    };
+    auto tile = [&](int m, const int *idx, int k) -> int {
+        if (m == 1) return launch_prepared<T, INV, QM>(plans[idx[0]], k, stage_of(idx[0], k), ios[idx[0]], false, s);
+        const StageLaunch<T> *Ls[BATCH_MAX];
+        for (int q = 0; q < m; ++q) Ls[q] = &stage_of(idx[q], k);
+        return launch_tile_batch<T, INV, QM>(m, Ls, ios[idx[0]], s);
+    };
+    auto top = [&](int m, const int *idx, int k) -> int {
+        const StageLaunch<T> *Ls[BATCH_MAX];
+        for (int q = 0; q < m; ++q) Ls[q] = &stage_of(idx[q], k);
+        return launch_top_batch<T, INV, QM>(m, Ls, ios[idx[0]], s);
+    };
+    BatchCounts cnt;
+    return group_batch_rounds<INV>(n, [&](int i) { return scn[(size_t)i].K; },
+                                   [&](int i, int k) { return stage_of(i, k).is_top; },
+                                   [&](int i, int j, int k) { return stage_of(i, k).G.same_shape(stage_of(j, k).G); },
+                                   [](int, int, int) { return true; }, cnt, single, tile, top);
 }
 
 }  // namespace raht
@@ -1888,16 +1764,16 @@ static int debug_run_stage_impl(const raht_plan *cp, int inverse, int stage, con
     XformIO<float> io;
     if (!Q) {
         io.src = mat; io.ld_src = ld_mat; io.dst = mat2; io.ld_dst = ld_mat2;
-        if (inverse) return launch_tile_stage<float, true, false>(p, *sc, stage, io, D, Dc, s, ablate);
-        return launch_tile_stage<float, false, false>(p, *sc, stage, io, D, Dc, s, ablate);
+        if (inverse) return launch_stage<float, true, false>(p, *sc, stage, io, D, Dc, s, ablate);
+        return launch_stage<float, false, false>(p, *sc, stage, io, D, Dc, s, ablate);
     }
     io.Q = Q; io.ldq = ldq; io.steps = &step; io.n_steps = 1;
     if (inverse) {
         io.dst = mat2; io.ld_dst = ld_mat2;
-        return launch_tile_stage<float, true, true>(p, *sc, stage, io, D, Dc, s, ablate);
+        return launch_stage<float, true, true>(p, *sc, stage, io, D, Dc, s, ablate);
     }
     io.src = mat; io.ld_src = ld_mat;
-    return launch_tile_stage<float, false, true>(p, *sc, stage, io, D, Dc, s, ablate);
+    return launch_stage<float, false, true>(p, *sc, stage, io, D, Dc, s, ablate);
 }
 
 
@@ -1928,7 +1804,7 @@ int raht_fwd_quant_batch(int n, raht_plan *const *plans, const float *const *C, 
 {
     return guarded("raht_fwd_quant_batch", [&]() -> int {
         if (n < 1 || !plans || !C || !ldc || !Q || !ldq) { set_error("raht_fwd_quant_batch: bad argument"); return RAHT_ERR_INVALID; }
-        RAHT_RET(check_steps(steps, n_steps, D));
+        RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
         std::vector<XformIO<float>> ios((size_t)n);
         for (int i = 0; i < n; ++i) {
             XformIO<float> &io = ios[(size_t)i];
@@ -1943,7 +1819,7 @@ int raht_dequant_inv_batch(int n, raht_plan *const *plans, const int32_t *const 
 {
     return guarded("raht_dequant_inv_batch", [&]() -> int {
         if (n < 1 || !plans || !C || !ldc || !Q || !ldq) { set_error("raht_dequant_inv_batch: bad argument"); return RAHT_ERR_INVALID; }
-        RAHT_RET(check_steps(steps, n_steps, D));
+        RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
         std::vector<XformIO<float>> ios((size_t)n);
         for (int i = 0; i < n; ++i) {
             XformIO<float> &io = ios[(size_t)i];

@@ -24,6 +24,7 @@
 #include "raht_common.h"
 #include "raht_device.h"
 #include "tile_engine.h"
+#include "tile_host.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -696,15 +697,14 @@ __global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_sq(const TileArg
     tile_body_mx<true, true, SLOTS, false, false, true>(A, P, ST, (int64_t)blockIdx.x);
 }
 
-// Several scenes, one launch (raht_fwd_quant_mixed_batch / raht_dequant_inv_mixed_batch): the same stage of up to MX_BATCH_MAX
+// Several scenes, one launch (raht_fwd_quant_mixed_batch / raht_dequant_inv_mixed_batch): the same stage of up to BATCH_MAX
 // scenes, as tile_kernel_batch does for the float32 engine (transform.hip). first_tile[q] = number of tiles of the scenes before q;
 // a workgroup finds its scene with scalar compares on blockIdx.x and runs ONE tile of it through tile_body_mx, reading that
 // scene's arguments where they lie in the kernarg segment (a scalar offset, no private copy of the struct).
-constexpr int MX_BATCH_MAX = 8;
 struct TileBatchMX {
-    TileArgs<float> a[MX_BATCH_MAX];
-    MxPtrs p[MX_BATCH_MAX];
-    uint32_t first_tile[MX_BATCH_MAX + 1];
+    TileArgs<float> a[BATCH_MAX];
+    MxPtrs p[BATCH_MAX];
+    uint32_t first_tile[BATCH_MAX + 1];
     int n;
 };
 static_assert(sizeof(TileBatchMX) + sizeof(StepTableMX) <= 4096, "tile_kernel_mx_batch: arguments exceed the 4 KB kernarg segment");
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(MX_THREADS, 6) void tile_kernel_mx_batch(const Tile
 {
     int s = 0;
 #pragma unroll
-    for (int q = 1; q < MX_BATCH_MAX; ++q) s += (q < B.n && blockIdx.x >= B.first_tile[q]) ? 1 : 0;
+    for (int q = 1; q < BATCH_MAX; ++q) s += (q < B.n && blockIdx.x >= B.first_tile[q]) ? 1 : 0;
     tile_body_mx<INV, IDENT, SLOTS, false>(B.a[s], B.p[s], ST, (int64_t)(blockIdx.x - B.first_tile[s]));
 }
 
@@ -959,7 +959,7 @@ __global__ __launch_bounds__(MX_TOP_THREADS) void top_kernel_mx_roots(const TopA
 }
 
 // the top stages of several scenes in one launch (the mixed batch entries): blockIdx.y = scene, blockIdx.x = chunk place
-struct TopBatchMX { TopArgsMX a[MX_BATCH_MAX]; };
+struct TopBatchMX { TopArgsMX a[BATCH_MAX]; };
 static_assert(sizeof(TopBatchMX) + sizeof(StepTableMX) <= 4096, "top_kernel_mx_batch: arguments exceed the 4 KB kernarg segment");
 
 template <bool INV>
@@ -1042,38 +1042,28 @@ static void fill_steps_mx(StepTableMX &t, const double *steps, int n_steps, int 
 // inverse's comparing stage 0
 enum { MX_PLAIN = 0, MX_MULTI = 1, MX_SQ = 2 };
 
-template <bool INV, bool IDENT, int SLOTS, bool ROOTS, int KIND>
-static int launch_tile_mx_one(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, const MxMultiQ *M, unsigned n_tiles,
-                              size_t lds, hipStream_t s)
+// one tile stage of one scene: the kernel for (KIND, ROOTS, stage 0 or later, one or two rows per thread)
+template <bool INV, bool ROOTS, int KIND>
+static int launch_tile_mx(bool ident, const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, const MxMultiQ *M, unsigned n_tiles,
+                          size_t lds, hipStream_t s)
 {
-    static PerDeviceOnce attr;
-    if constexpr (KIND == MX_MULTI) {
-        static_assert(!INV && !ROOTS, "multi: forward, no root buffers");
-        if (attr.first(current_device()))
-            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx_multi<IDENT, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((tile_kernel_mx_multi<IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st, *M);
-    } else if constexpr (KIND == MX_SQ) {
-        static_assert(INV && IDENT && !ROOTS, "sqdiff: inverse stage 0, no root buffers");
-        if (attr.first(current_device()))
-            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx_sq<SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((tile_kernel_mx_sq<SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
-    } else {
-        const void *fn = ROOTS ? (const void *)tile_kernel_mx_roots<INV, IDENT, SLOTS> : (const void *)tile_kernel_mx<INV, IDENT, SLOTS>;
-        if (attr.first(current_device()))
-            RAHT_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if constexpr (ROOTS) hipLaunchKernelGGL((tile_kernel_mx_roots<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
-        else hipLaunchKernelGGL((tile_kernel_mx<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, A, P, st);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
-}
-
-template <bool INV, bool IDENT, bool ROOTS, int KIND>
-static int launch_tile_mx_slots(const TileArgs<float> &A, const MxPtrs &P, const StepTableMX &st, const MxMultiQ *M, unsigned n_tiles,
-                                size_t lds, hipStream_t s)
-{
-    return A.R <= MX_THREADS ? launch_tile_mx_one<INV, IDENT, 1, ROOTS, KIND>(A, P, st, M, n_tiles, lds, s)
-                             : launch_tile_mx_one<INV, IDENT, 2, ROOTS, KIND>(A, P, st, M, n_tiles, lds, s);
+    const dim3 grid(n_tiles), block(MX_THREADS);
+    return by_ident_slots(ident, A.R <= MX_THREADS, [&](auto id, auto slots) -> int {
+        constexpr bool IDENT = decltype(id)::value;
+        constexpr int SLOTS = decltype(slots)::value;
+        if constexpr (KIND == MX_MULTI) {
+            static_assert(!INV && !ROOTS, "multi: forward, no root buffers");
+            return launch_lds<tile_kernel_mx_multi<IDENT, SLOTS>>(grid, block, lds, TILE_LDS_LIMIT, s, A, P, st, *M);
+        } else if constexpr (KIND == MX_SQ) {
+            static_assert(INV && !ROOTS, "sqdiff: inverse stage 0, no root buffers");
+            if constexpr (IDENT) return launch_lds<tile_kernel_mx_sq<SLOTS>>(grid, block, lds, TILE_LDS_LIMIT, s, A, P, st);
+            else { set_error("mixed sqdiff: stage 0 only"); return RAHT_ERR_INVALID; }
+        } else if constexpr (ROOTS) {
+            return launch_lds<tile_kernel_mx_roots<INV, IDENT, SLOTS>>(grid, block, lds, TILE_LDS_LIMIT, s, A, P, st);
+        } else {
+            return launch_lds<tile_kernel_mx<INV, IDENT, SLOTS>>(grid, block, lds, TILE_LDS_LIMIT, s, A, P, st);
+        }
+    });
 }
 
 struct MxIO {
@@ -1172,53 +1162,28 @@ static int prepare_stage_mx(const raht_plan *p, const Schedule &sc, int k, const
     return RAHT_OK;
 }
 
-// one prepared stage of ONE scene: the launch of the single-scene calls
+// one prepared stage of ONE scene: the launch of the single-scene calls. Stage 0 of a transform, tile or top, is bracketed by the
+// plan's profiling events (raht_plan_set_stage0_events) -- the only place of this file that records them.
 template <bool INV>
 static int launch_prepared_mx(const raht_plan *p, int k, const MxIO &io, const MxStageLaunch &L, const MxGeom &g,
                               const StepTableMX &stp, hipStream_t s)
 {
-    if (L.is_top) {
-        const TopArgsMX &A = L.T;
-        const size_t lds = L.lds;
-        static PerDeviceOnce attr;
-        if (attr.first(current_device())) {
-            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_roots<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+    auto launch = [&]() -> int {
+        if (L.is_top) {
+            const dim3 grid((unsigned)g.NCp), block(MX_TOP_THREADS);
+            if constexpr (!INV) { if (io.multi) return launch_lds<top_kernel_mx_multi>(grid, block, L.lds, TOP_LDS_LIMIT, s, L.T, stp, *io.multi); }
+            if (L.T.root_f) return launch_lds<top_kernel_mx_roots<INV>>(grid, block, L.lds, TOP_LDS_LIMIT, s, L.T, stp);
+            return launch_lds<top_kernel_mx<INV>>(grid, block, L.lds, TOP_LDS_LIMIT, s, L.T, stp);
         }
-        if (!INV && io.multi) {
-            static PerDeviceOnce attr_m;
-            if (attr_m.first(current_device()))
-                RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-            hipLaunchKernelGGL(top_kernel_mx_multi, dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp, *io.multi);
-        }
-        else if (A.root_f) hipLaunchKernelGGL((top_kernel_mx_roots<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
-        else hipLaunchKernelGGL((top_kernel_mx<INV>), dim3((unsigned)g.NCp), dim3(MX_TOP_THREADS), lds, s, A, stp);
-        RAHT_HIP_CHECK(hipGetLastError());
-        return RAHT_OK;
-    }
-    const TileArgs<float> &A = L.A;
-    const MxPtrs &P = L.P;
-    const size_t lds = L.lds;
-    const unsigned nt = L.n_tiles;
-    if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
-    int rc;
-    if constexpr (!INV) {
-        if (io.multi) {
-            rc = k == 0 ? launch_tile_mx_slots<false, true, false, MX_MULTI>(A, P, stp, io.multi, nt, lds, s)
-                        : launch_tile_mx_slots<false, false, false, MX_MULTI>(A, P, stp, io.multi, nt, lds, s);
-            if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
-            return rc;
-        }
-    } else {
-        if (k == 0 && io.sq_part) {
-            rc = launch_tile_mx_slots<true, true, false, MX_SQ>(A, P, stp, nullptr, nt, lds, s);
-            if (p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
-            return rc;
-        }
-    }
-    if (k == 0) rc = A.root_buf ? launch_tile_mx_slots<INV, true, true, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s) : launch_tile_mx_slots<INV, true, false, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s);
-    else rc = A.root_buf ? launch_tile_mx_slots<INV, false, true, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s) : launch_tile_mx_slots<INV, false, false, MX_PLAIN>(A, P, stp, nullptr, nt, lds, s);
-    if (k == 0 && p->ev_before) RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
+        if constexpr (!INV) { if (io.multi) return launch_tile_mx<false, false, MX_MULTI>(k == 0, L.A, L.P, stp, io.multi, L.n_tiles, L.lds, s); }
+        if constexpr (INV) { if (k == 0 && io.sq_part) return launch_tile_mx<true, false, MX_SQ>(true, L.A, L.P, stp, nullptr, L.n_tiles, L.lds, s); }
+        return L.A.root_buf ? launch_tile_mx<INV, true, MX_PLAIN>(k == 0, L.A, L.P, stp, nullptr, L.n_tiles, L.lds, s)
+                            : launch_tile_mx<INV, false, MX_PLAIN>(k == 0, L.A, L.P, stp, nullptr, L.n_tiles, L.lds, s);
+    };
+    if (!(k == 0 && p->ev_before)) return launch();
+    RAHT_HIP_CHECK(hipEventRecord(p->ev_before, s));
+    const int rc = launch();
+    RAHT_HIP_CHECK(hipEventRecord(p->ev_after, s));
     return rc;
 }
 
@@ -1237,10 +1202,7 @@ static int mx_check_args(const raht_plan *p, const void *a, const void *b, int D
     if (!p || !a || !b || D < 1 || lda < D || ldb < D) { set_error("%s: bad argument", what); return RAHT_ERR_INVALID; }
     RAHT_RET(check_plan_device(p, what));
     if (n_wide < 1 || n_wide > MX_MAX_WIDE || n_wide > D) { set_error("%s: n_wide must be 1..%d (and <= D)", what, MX_MAX_WIDE); return RAHT_ERR_INVALID; }
-    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("%s: n_steps must be 1 or D", what); return RAHT_ERR_INVALID; }
-    if (n_steps > MAX_STEP_CH) { set_error("%s: per-channel steps support D <= %d", what, MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
-    for (int c = 0; c < n_steps; ++c)
-        if (!(steps[c] > 0.0) || !((float)steps[c] > 0.0f)) { set_error("%s: step[%d] must be > 0 (also as float32)", what, c); return RAHT_ERR_INVALID; }
+    RAHT_RET(check_quant_steps(what, steps, n_steps, D, true));
     if (p->row_map) { set_error("%s: not available for row-mapped plans", what); return RAHT_ERR_UNSUPPORTED; }
     // root buffers: both (float n_roots x D, float64 n_roots x n_wide) or neither; a truncated plan's roots need them
     if ((p->root_buf == nullptr) != (p->root_buf_w == nullptr)) {
@@ -1435,7 +1397,7 @@ static int dequant_inv_mixed_sqdiff_impl(const raht_plan *cp, const int32_t *Q, 
 
 // ---- several scenes, one set of launches (raht_fwd_quant_mixed_batch / raht_dequant_inv_mixed_batch) ---------------------------
 // Round r of the forward direction carries stage r of every scene that has one; the inverse walks the rounds backwards from the
-// deepest schedule. Within a round the tile stages of equal launch shape go out up to MX_BATCH_MAX scenes per launch
+// deepest schedule. Within a round the tile stages of equal launch shape go out up to BATCH_MAX scenes per launch
 // (tile_kernel_mx_batch), the top stages likewise (top_kernel_mx_batch, blockIdx.y = scene); a group of one is the single-scene
 // launch. Scenes the batch kernels do not cover run through the single-scene entry, in place in the stream.
 struct MxScene {
@@ -1444,7 +1406,6 @@ struct MxScene {
     MxGeom g;
     MxIO io;
 };
-struct MxBatchCounts { int tile = 0, top = 0, single = 0; };
 
 // the batch kernels cover: a mixed tile schedule, no root buffers (a truncated plan always has them here: mx_check_args), no
 // stage-0 events (they bracket ONE scene's stage-0 launch)
@@ -1464,69 +1425,18 @@ static MxShape mx_tile_shape(const Stage &st, int k, const MxGeom &g)
     return MxShape{k == 0, st.tile_rows <= MX_THREADS ? 1 : 2, tile_lds_bytes_mx(st.tile_rows, g.Dp / 4, g.nwide), g.nwide, g.NCp, g.Dp, g.lg};
 }
 
-// THE grouping of a batch: calls single(i) for every scene outside the batch kernels, then, round by round, tile(m, idx, k) /
-// top(m, idx, k) for every launch (stage k of the m scenes idx[0..m)), and counts what it called. The runner passes callbacks
-// that launch, raht_mixed_batch_stats callbacks that do nothing.
+// group_batch_rounds (tile_host.h) over mixed scenes: the tile stages of a launch agree in MxShape, the top stages in the row layout
 template <bool INV, typename FS, typename FT, typename FP>
-static int group_batch_mx(int n, const MxScene *scn, MxBatchCounts &cnt, FS &&single, FT &&tile, FP &&top)
+static int group_mx_scenes(int n, const MxScene *scn, BatchCounts &cnt, FS &&single, FT &&tile, FP &&top)
 {
-    int maxK = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!scn[i].sc) { ++cnt.single; RAHT_RET(single(i)); }
-        else maxK = std::max(maxK, (int)scn[i].sc->stages.size());
-    }
-    for (int r = 0; r < maxK; ++r) {
-        const int k = INV ? maxK - 1 - r : r;
-        int idx_tile[MX_BATCH_MAX], idx_top[MX_BATCH_MAX], n_tile = 0, n_top = 0;
-        MxShape shape{};
-        auto flush_tile = [&]() -> int {
-            if (n_tile == 0) return RAHT_OK;
-            const int m = n_tile;
-            n_tile = 0;
-            ++cnt.tile;
-            return tile(m, idx_tile, k);
-        };
-        auto flush_top = [&]() -> int {
-            if (n_top == 0) return RAHT_OK;
-            const int m = n_top;
-            n_top = 0;
-            ++cnt.top;
-            return top(m, idx_top, k);
-        };
-        for (int i = 0; i < n; ++i) {
-            const Schedule *sc = scn[i].sc;
-            if (!sc || k >= (int)sc->stages.size()) continue;
-            const Stage &st = sc->stages[(size_t)k];
-            if (st.is_top) {
-                if (n_top > 0 && !(scn[i].g.NCp == scn[idx_top[0]].g.NCp && scn[i].g.Dp == scn[idx_top[0]].g.Dp)) RAHT_RET(flush_top());
-                idx_top[n_top++] = i;
-                if (n_top == MX_BATCH_MAX) RAHT_RET(flush_top());
-            } else {
-                const MxShape sh = mx_tile_shape(st, k, scn[i].g);
-                if (n_tile > 0 && !(sh == shape)) RAHT_RET(flush_tile());          // another launch shape: its own launch
-                shape = sh;
-                idx_tile[n_tile++] = i;
-                if (n_tile == MX_BATCH_MAX) RAHT_RET(flush_tile());
-            }
-        }
-        RAHT_RET(flush_tile());
-        RAHT_RET(flush_top());
-    }
-    return RAHT_OK;
+    return group_batch_rounds<INV>(n, [&](int i) { return scn[i].sc ? (int)scn[i].sc->stages.size() : 0; },
+                                   [&](int i, int k) { return scn[i].sc->stages[(size_t)k].is_top; },
+                                   [&](int i, int j, int k) { return mx_tile_shape(scn[i].sc->stages[(size_t)k], k, scn[i].g) == mx_tile_shape(scn[j].sc->stages[(size_t)k], k, scn[j].g); },
+                                   [&](int i, int j, int) { return scn[i].g.NCp == scn[j].g.NCp && scn[i].g.Dp == scn[j].g.Dp; },
+                                   cnt, single, tile, top);
 }
 
-template <bool INV, bool IDENT, int SLOTS>
-static int launch_tile_batch_mx_one(const TileBatchMX &B, const StepTableMX &stp, unsigned n_tiles, size_t lds, hipStream_t s)
-{
-    static PerDeviceOnce attr;
-    if (attr.first(current_device()))
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)tile_kernel_mx_batch<INV, IDENT, SLOTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((tile_kernel_mx_batch<INV, IDENT, SLOTS>), dim3(n_tiles), dim3(MX_THREADS), lds, s, B, stp);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
-}
-
-// the same tile stage of m <= MX_BATCH_MAX scenes (equal launch shape) in one launch, one tile per workgroup. (Tile counts: a
+// the same tile stage of m <= BATCH_MAX scenes (equal launch shape) in one launch, one tile per workgroup. (Tile counts: a
 // plan's rows are indexed with 32 bits and a tile holds >= 64 of them, so eight scenes stay far below 2^32 tiles.)
 template <bool INV>
 static int launch_tile_batch_mx(int m, const MxStageLaunch *const *Ls, bool ident, const StepTableMX &stp, hipStream_t s)
@@ -1534,17 +1444,16 @@ static int launch_tile_batch_mx(int m, const MxStageLaunch *const *Ls, bool iden
     TileBatchMX B;
     B.n = m;
     uint32_t tot = 0;
-    for (int i = 0; i < MX_BATCH_MAX; ++i) {
+    for (int i = 0; i < BATCH_MAX; ++i) {
         B.a[i] = Ls[i < m ? i : 0]->A;
         B.p[i] = Ls[i < m ? i : 0]->P;
         B.first_tile[i] = tot;
         if (i < m) tot += Ls[i]->n_tiles;
     }
-    B.first_tile[MX_BATCH_MAX] = tot;
-    const size_t lds = Ls[0]->lds;
-    const bool one = Ls[0]->A.R <= MX_THREADS;
-    if (ident) return one ? launch_tile_batch_mx_one<INV, true, 1>(B, stp, tot, lds, s) : launch_tile_batch_mx_one<INV, true, 2>(B, stp, tot, lds, s);
-    return one ? launch_tile_batch_mx_one<INV, false, 1>(B, stp, tot, lds, s) : launch_tile_batch_mx_one<INV, false, 2>(B, stp, tot, lds, s);
+    B.first_tile[BATCH_MAX] = tot;
+    return by_ident_slots(ident, Ls[0]->A.R <= MX_THREADS, [&](auto id, auto slots) -> int {
+        return launch_lds<tile_kernel_mx_batch<INV, decltype(id)::value, decltype(slots)::value>>(dim3(tot), dim3(MX_THREADS), Ls[0]->lds, TILE_LDS_LIMIT, s, B, stp);
+    });
 }
 
 // the top stages of m scenes: one launch, blockIdx.y = scene; the dynamic LDS block is the largest scene's
@@ -1553,14 +1462,9 @@ static int launch_top_batch_mx(int m, const MxStageLaunch *const *Ls, int NCp, c
 {
     TopBatchMX B;
     size_t lds = 0;
-    for (int i = 0; i < MX_BATCH_MAX; ++i) B.a[i] = Ls[i < m ? i : 0]->T;
+    for (int i = 0; i < BATCH_MAX; ++i) B.a[i] = Ls[i < m ? i : 0]->T;
     for (int i = 0; i < m; ++i) lds = std::max(lds, Ls[i]->lds);
-    static PerDeviceOnce attr;
-    if (attr.first(current_device()))
-        RAHT_HIP_CHECK(hipFuncSetAttribute((const void *)top_kernel_mx_batch<INV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    hipLaunchKernelGGL((top_kernel_mx_batch<INV>), dim3((unsigned)NCp, (unsigned)m), dim3(MX_TOP_THREADS), lds, s, B, stp);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return launch_lds<top_kernel_mx_batch<INV>>(dim3((unsigned)NCp, (unsigned)m), dim3(MX_TOP_THREADS), lds, TOP_LDS_LIMIT, s, B, stp);
 }
 
 // Everything that can be judged from the arguments alone, before any plan is dereferenced and before any HIP call (a / b: the
@@ -1570,16 +1474,10 @@ static int mx_batch_check_args(const char *what, int n, raht_plan *const *plans,
 {
     if (n < 1 || !plans || !a || !lda || !b || !ldb || D < 1) { set_error("%s: bad argument (n >= 1, D >= 1, the arrays of plans, matrices and strides must be set)", what); return RAHT_ERR_INVALID; }
     if (n_wide < 1 || n_wide > MX_MAX_WIDE || n_wide > D) { set_error("%s: n_wide must be 1..%d (and <= D)", what, MX_MAX_WIDE); return RAHT_ERR_INVALID; }
-    if (!steps || !(n_steps == 1 || n_steps == D)) { set_error("%s: n_steps must be 1 or D", what); return RAHT_ERR_INVALID; }
-    if (n_steps > MAX_STEP_CH) { set_error("%s: per-channel steps support D <= %d", what, MAX_STEP_CH); return RAHT_ERR_UNSUPPORTED; }
-    for (int c = 0; c < n_steps; ++c)
-        if (!(steps[c] > 0.0) || !((float)steps[c] > 0.0f)) { set_error("%s: step[%d] must be > 0 (also as float32)", what, c); return RAHT_ERR_INVALID; }
-    for (int i = 0; i < n; ++i) {
-        if (!plans[i]) { set_error("%s: NULL plan (scene %d)", what, i); return RAHT_ERR_INVALID; }
+    RAHT_RET(check_quant_steps(what, steps, n_steps, D, true));
+    RAHT_RET(check_batch_plans(what, n, plans));
+    for (int i = 0; i < n; ++i)
         if (!a[i] || !b[i] || lda[i] < D || ldb[i] < D) { set_error("%s: bad matrix argument (scene %d: NULL pointer or row stride < D)", what, i); return RAHT_ERR_INVALID; }
-        for (int j = 0; j < i; ++j)
-            if (plans[j] == plans[i]) { set_error("%s: scenes %d and %d share a plan (a plan owns its workspaces)", what, j, i); return RAHT_ERR_INVALID; }
-    }
     return RAHT_OK;
 }
 
@@ -1638,18 +1536,18 @@ static int run_batch_mx(const char *what, int n, raht_plan *const *plans, const 
     };
     auto tile = [&](int m, const int *idx, int k) -> int {
         if (m == 1) return launch_prepared_mx<INV>(scn[(size_t)idx[0]].p, k, scn[(size_t)idx[0]].io, stage_of(idx[0], k), scn[(size_t)idx[0]].g, stp, s);
-        const MxStageLaunch *Ls[MX_BATCH_MAX];
+        const MxStageLaunch *Ls[BATCH_MAX];
         for (int q = 0; q < m; ++q) Ls[q] = &stage_of(idx[q], k);
         return launch_tile_batch_mx<INV>(m, Ls, k == 0, stp, s);
     };
     auto top = [&](int m, const int *idx, int k) -> int {
         if (m == 1) return launch_prepared_mx<INV>(scn[(size_t)idx[0]].p, k, scn[(size_t)idx[0]].io, stage_of(idx[0], k), scn[(size_t)idx[0]].g, stp, s);
-        const MxStageLaunch *Ls[MX_BATCH_MAX];
+        const MxStageLaunch *Ls[BATCH_MAX];
         for (int q = 0; q < m; ++q) Ls[q] = &stage_of(idx[q], k);
         return launch_top_batch_mx<INV>(m, Ls, scn[(size_t)idx[0]].g.NCp, stp, s);
     };
-    MxBatchCounts cnt;
-    return group_batch_mx<INV>(n, scn.data(), cnt, single, tile, top);
+    BatchCounts cnt;
+    return group_mx_scenes<INV>(n, scn.data(), cnt, single, tile, top);
 }
 
 // the dry run of the grouping: schedules and tile programs may be built, no transform kernel is launched
@@ -1661,11 +1559,7 @@ static int mixed_batch_stats_impl(int n, raht_plan *const *plans, int D, int n_w
         set_error("%s: bad argument", what);
         return RAHT_ERR_INVALID;
     }
-    for (int i = 0; i < n; ++i) {
-        if (!plans[i]) { set_error("%s: NULL plan (scene %d)", what, i); return RAHT_ERR_INVALID; }
-        for (int j = 0; j < i; ++j)
-            if (plans[j] == plans[i]) { set_error("%s: scenes %d and %d share a plan", what, j, i); return RAHT_ERR_INVALID; }
-    }
+    RAHT_RET(check_batch_plans(what, n, plans));
     std::vector<MxScene> scn((size_t)n);
     for (int i = 0; i < n; ++i) {
         MxScene &S = scn[(size_t)i];
@@ -1676,11 +1570,11 @@ static int mixed_batch_stats_impl(int n, raht_plan *const *plans, int D, int n_w
         RAHT_RET(mx_setup(S.p, D, n_wide, D, nullptr, &sc, S.g));
         S.sc = mx_batchable(S.p, sc) ? sc : nullptr;
     }
-    MxBatchCounts cnt;
+    BatchCounts cnt;
     auto none1 = [](int) { return (int)RAHT_OK; };
     auto none3 = [](int, const int *, int) { return (int)RAHT_OK; };
-    if (inverse) RAHT_RET((group_batch_mx<true>(n, scn.data(), cnt, none1, none3, none3)));
-    else RAHT_RET((group_batch_mx<false>(n, scn.data(), cnt, none1, none3, none3)));
+    if (inverse) RAHT_RET((group_mx_scenes<true>(n, scn.data(), cnt, none1, none3, none3)));
+    else RAHT_RET((group_mx_scenes<false>(n, scn.data(), cnt, none1, none3, none3)));
     *tile_launches = cnt.tile; *top_launches = cnt.top; *single_scene_calls = cnt.single;
     return RAHT_OK;
 }
