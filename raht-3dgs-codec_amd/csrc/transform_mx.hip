@@ -132,12 +132,22 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
         sp = fl;
         goff = min(fl * 4, Df - 4);
     };
-    float my_step[4], my_rcp[4];
-    auto load_steps = [&](int place) {
-        const int g0 = min(place * 4, Df - 4);
+    // The float32 steps of this lane's four channels. One step for all channels (ST.f.n == 1, the usual call) is a scalar kernel
+    // argument: use_steps reads it where it is needed. A per-channel table is indexed by lane, i.e. fetched from the kernarg
+    // segment with vector loads: fetch_steps issues them at kernel start, next to the program fetch (a round trip to memory every
+    // tile sits through anyway), NOT behind the barrier in front of the first use, where all eight waves would sit through one
+    // more. (Issued whatever ST.f.n is -- a single step's lanes all read the table's first 16 bytes, unused: a branch around
+    // the loads ends in register copies where the paths join, and the compiler waits for the loads in front of those.)
+    float my_step[4], my_rcp[4], tab_step[4];
+    auto fetch_steps = [&](int place) {
+        const int g0 = ST.f.n == 1 ? 0 : min(place * 4, Df - 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tab_step[i] = ST.f.v[g0 + i];
+    };
+    auto use_steps = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            my_step[i] = ST.f.v[ST.f.n == 1 ? 0 : g0 + i];
+            my_step[i] = ST.f.n == 1 ? ST.f.v[0] : tab_step[i];
             my_rcp[i] = refined_rcp(my_step[i]);
         }
     };
@@ -149,6 +159,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
     const int64_t e0 = tile_id * R;
     const int nt = (int)min((int64_t)R, A.n_entries - e0);
     MX_STAMP(0);
+    if constexpr (!MULTI) fetch_steps(fl);                 // (MULTI: one scalar step per output matrix, MxMultiQ)
 
     // ---- P0a. the tile's program (plan.hip: tile_program_kernel; raht_common.h: Stage::prog), fetched first: every butterfly,
     // survivor and destination of this tile, resolved once per schedule. Each wave reads the height offsets into its lanes
@@ -156,7 +167,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
     const uint32_t *pg = P.prog + (uint64_t)tile_id * P.prog_stride;
     const int end_v = ((const uint16_t *)pg)[lane];
     const int endm_v = lane ? ((const uint16_t *)pg)[lane - 1] : 0;
-    const uint32_t surv_raw = A.surv_off ? A.surv_off[tile_id + (tid0 & 1)] : 0u;   // (lane-dependent: see TileMeta::surv_raw)
+    uint32_t surv_raw = A.surv_off ? A.surv_off[tile_id + (tid0 & 1)] : 0u;   // (lane-dependent: see TileMeta::surv_raw)
     uint32_t m_rw[SLOTS], m_rec[SLOTS];
     W16 m_ab[SLOTS];
 #pragma unroll
@@ -169,6 +180,12 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             if (!P.prog_compact) m_ab[s] = ((const W16 *)(pg + P.prog_ab))[j];
         }
     }
+    // behind wait_landed(): what the compiler's own early loads fetched is there as well, and it is told so here -- else it waits for
+    // them where they are first used, in the write-back, with a vmcnt(0) that also sits out the survivor stores just issued
+    auto early_loads_landed = [&]() {
+        asm volatile("" : "+v"(surv_raw));
+        if constexpr (!MULTI) asm volatile("" : "+v"(tab_step[0]), "+v"(tab_step[1]), "+v"(tab_step[2]), "+v"(tab_step[3]));
+    };
     // (a row is finalised in this tile when it merges here, or when this is the last stage and its low-pass row goes to Q)
     auto fin_of = [&](uint32_t rw) { return (rw >> 31) != 0 || (A.last_stage && !ROOTS); };
     auto write_dst = [&]() {
@@ -251,12 +268,14 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             load_linear(ftile, nt * NF, A.in + e0 * (int64_t)Fp);
             load_linear((const float *)wd, (nt * nwide + 1) >> 1, (const float *)(P.in_w + e0 * (int64_t)nwide));      // (16-byte chunks: may read one double past the tile's rows -- the next tile's, or the array's slack)
         }
+        MX_STAMP(9);
         const uint32_t n_merged = (uint32_t)__builtin_amdgcn_readlane(end_v, 63);
         write_dst();
         write_survivors(n_merged);
         write_records(n_merged);
         MX_STAMP(1);
         wait_landed();                                                     // this wave's rows are in LDS
+        early_loads_landed();
         sync_lds();                                                        // sync #1: every wave's rows, the records
         MX_STAMP(2);
         if constexpr (IDENT) {
@@ -310,9 +329,10 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
         }
         MX_STAMP(3);
         wait_landed();                                                     // this wave's Q rows are in LDS
+        early_loads_landed();
         sync_lds();                                                        // sync #2: every row, every record
         MX_STAMP(4);
-        load_steps(fl);
+        use_steps();
         // the wide channels of the rows finalised here, from the raw integers that arrived with them (one ROW per thread)
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s) {
@@ -613,6 +633,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             // (a) the wide channels: one ROW per thread -- the IEEE double division is ~40 instructions a channel, so it runs on
             //     whole waves of rows -- and the integers go back into the row's first wide place (a row finalised here is nobody's
             //     survivor)
+            MX_STAMP(10);
 #pragma unroll
             for (int s = 0; s < SLOTS; ++s) {
                 const int j = tid0 + s * nthreads;
@@ -632,7 +653,11 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
             // (b) ONE store instruction per row group writes whole rows of Q: the float lanes their quantized chunks, the head lane the
             //     row's first 16 bytes = the wide integers and, behind them, the first 4 - n_wide float channels quantized once more
             //     (same values as their own lane's). See the inverse's write-back for why.
-            load_steps(sp);
+            use_steps();                                           // (sp == fl: the places fetch_steps fetched)
+#ifdef RAHT_PHASE_CLOCKS
+            asm volatile("" :: "v"(my_step[0]), "v"(my_rcp[3]));
+#endif
+            MX_STAMP(11);
             auto store_final = [&](auto fast_div) {
                 if (rowlane) for (int it = wid; (it << lr) < nt; it += 2 * nwv) {
                     int jc[2]; V16 x[2]; I16 qi[2] = {}; uint32_t dv[2];

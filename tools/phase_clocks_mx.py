@@ -58,3 +58,10 @@ for inverse in (0, 1):
     if inverse:
         buf[:, 7] = buf[:, 6]
     show(f"mixed fused {'inverse' if inverse else 'forward'} stage 0", buf, names_mx, 8)
+    if not inverse:
+        # the forward's three waits, each between two stamps of its own (slots 9 - 11; thread 0's view, i.e. wave 0's)
+        t = buf[1024:].astype(np.int64)
+        for nm, a, b in [("rows issued -> program landed, records decoded", 9, 1), ("rows issued -> sync 1", 9, 2),
+                         ("pass (a): wide divisions", 10, 7), ("barrier behind pass (a) -> first store", 7, 11)]:
+            d = t[:, b] - t[:, a]
+            print(f"    {nm:48s} {np.median(d):8.0f}  (p10 {np.percentile(d, 10):.0f}, p90 {np.percentile(d, 90):.0f})")
