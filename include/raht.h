@@ -705,6 +705,15 @@ int raht_debug_rlgr_decode_out(int mode);
  * -1 = by the lanes in flight, 0 = one 4-byte store per word, 2 = LDS columns, 64-byte pieces (9 steps of a 3 M x 56 frame:
  * 0.79 -> 0.71 ms per step). */
 int raht_debug_rlgr_encode_out(int mode);
+/* Tile stages whose butterfly heights one launch computes while a schedule is built (default 8, the most a launch holds): a
+ * smaller n makes ordinary schedules walk the several-launches path that only very deep ones reach. n = 0 or out of [1, 8]
+ * restores the default. While a non-default value is set, the heights are launched behind the schedule builder's read-back
+ * instead of in front of it. Same schedules, same transforms; a testing hook, process-wide. Returns the previous value. */
+int raht_debug_height_stages_per_launch(int n);
+/* Device blocks of the library's block cache that are handed out and not yet given back (plan arrays, schedules, workspaces
+ * of every live plan, on every device). Scratch-pool blocks and borrowed key arrays are not counted. A testing hook: after a plan
+ * is destroyed, or a constructor has failed, the count is what it was before. */
+int64_t raht_debug_live_blocks(void);
 
 /* out[c] = sum over rows of (A[i, c] - B[i, c])^2, DEVICE double[D]: what the drivers' five PSNR columns are made of
  * (python/encode_3dgs.py:298-310: torch.mean((C - C_rec) ** 2) over all / quats / scales / opacity / colour columns -- each a

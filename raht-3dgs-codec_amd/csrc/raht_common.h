@@ -11,6 +11,8 @@
 #include <exception>
 #include <functional>
 #include <new>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "raht.h"
@@ -142,6 +144,44 @@ hipError_t dev_malloc(void **p, size_t bytes);
 template <typename T> inline hipError_t dev_malloc(T **p, size_t bytes) { return dev_malloc((void **)p, bytes); }
 void dev_free(void *p);
 
+// THE owner of one dev_malloc block: whoever holds the DevBuf owns the block, and nothing else frees it. Move-only; converts to
+// T* so that readers use it like the pointer it replaces. borrow() holds a pointer WITHOUT owning it (the caller's key array of
+// raht_plan_create_from_keys_borrowed): never freed here. The destructor (and reset) calls dev_free and nothing else -- it does
+// NOT synchronise: the block may be handed out again at once, so whoever drops a DevBuf that enqueued work may still use first
+// waits for that work, and the argument why a release is safe stays at the site of the release.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), owned_(o.owned_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p_ = o.p_; owned_ = o.owned_; o.p_ = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    // `count` elements (bytes for DevBuf<void>); whatever was held is dropped first
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        owned_ = true;
+        return dev_malloc((void **)&p_, count * sizeof(typename std::conditional<std::is_void<T>::value, char, T>::type));
+    }
+    void borrow(T *p) { reset(); p_ = p; owned_ = false; }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    void reset() { if (p_ && owned_) dev_free(p_); p_ = nullptr; }
+    T *release() { T *q = p_; p_ = nullptr; return q; }
+private:
+    T *p_ = nullptr;
+    bool owned_ = true;
+};
+// a hipEvent_t destroyed with its holder (Schedule::ready)
+struct OwnedEvent {
+    hipEvent_t ev = nullptr;
+    OwnedEvent() = default;
+    OwnedEvent(OwnedEvent &&o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    OwnedEvent &operator=(OwnedEvent &&o) noexcept { std::swap(ev, o.ev); return *this; }
+    ~OwnedEvent() { if (ev) (void)hipEventDestroy(ev); }
+    operator hipEvent_t() const { return ev; }
+};
+
 // ---- device primitives (scan_sort.hip) ---------------------------------------------------------
 // Exclusive prefix sum of n uint32 values, in place allowed (out may equal in). `total` (device
 // uint32*, may be NULL) receives the sum. Allocates its own small workspace (plan/voxelize time
@@ -179,6 +219,7 @@ int bucket_sort_u8(const uint8_t *bucket, uint32_t *perm_out, int64_t n, int bit
 // pageable hipMemcpyAsync + hipStreamSynchronize (tools/native/probe_readback.hip). Returns once the
 // words (and therefore all earlier work on `s`) are complete. `behind` (may be empty) is called once the read-back has been
 // enqueued and before the host starts waiting: work it enqueues on `s` runs while the host waits and is NOT waited for.
+// `behind` runs under the mailbox lock: it must not itself reach read_back_u32 (directly or through a helper that reads back).
 int read_back_u32(uint32_t *dst_a, const uint32_t *dev_a, int na, uint32_t *dst_b, const uint32_t *dev_b, int nb,
                   hipStream_t s, const std::function<void()> &behind = std::function<void()>());
 
@@ -193,43 +234,61 @@ int compact_u32(const uint32_t *in, const uint32_t *flag, uint32_t *out, int64_t
 int run_starts_u64(const uint64_t *keys_sorted, int64_t n, uint32_t *starts, int64_t *starts64, uint64_t *run_keys,
                    uint32_t *count_dev, hipStream_t s);
 
-// ---- plan (plan.hip) ---------------------------------------------------------------------------
+// Profiling build only (-DRAHT_PHASE_CLOCKS, tools/phase_clocks_plan.py): thread 0 of a plan-build workgroup stamps the shader
+// clock at its phase boundaries. [0] level_extent blocks (plan.hip), [1] tile_heights tiles, [2] sched_tail (one workgroup; schedule.hip). One copy of the
+// stamps per translation unit: each file reads back its own (raht_debug_read_phase_clocks_plan).
+#ifdef RAHT_PHASE_CLOCKS
+constexpr int PL_CLK_BLOCKS = 4096, PL_CLK_SLOTS = 12;
+static __device__ unsigned long long g_phase_clk_plan[3][PL_CLK_BLOCKS][PL_CLK_SLOTS];
+#define PL_STAMP(which, blk, k) do { if (threadIdx.x == 0 && (blk) < PL_CLK_BLOCKS) g_phase_clk_plan[which][blk][k] = __builtin_readcyclecounter(); } while (0)
+#define PL_NOTE_LEVELS(blk, n) do { if (threadIdx.x == 0 && (blk) < PL_CLK_BLOCKS) g_phase_clk_plan[1][blk][PL_CLK_SLOTS - 1] = (unsigned long long)(n); } while (0)
+#define PL_SLOT_DECL int pl_slot = 0
+#define PL_STAMP_NEXT() do { if (pl_slot < 8) { PL_STAMP(2, 0, pl_slot); ++pl_slot; } } while (0)
+int read_phase_clocks_sched(unsigned long long *dst, int which, int n_blocks);
+#else
+#define PL_STAMP(which, blk, k) do { } while (0)
+#define PL_NOTE_LEVELS(blk, n) do { } while (0)
+#define PL_SLOT_DECL do { } while (0)
+#define PL_STAMP_NEXT() do { } while (0)
+#endif
+
+// ---- plan (plan.hip) and tile schedule (schedule.hip) ---------------------------------------------------------------------------
 constexpr int RAHT_TOP_MAX_ROWS = 8192;   // entries the TOP stage can hold (16 bytes each in LDS)
 
 struct Stage {
     int64_t n_entries = 0;   // active rows entering this stage
     int64_t n_tiles = 0;
-    uint32_t *rows = nullptr;      // device; nullptr for stage 0 (identity)
-    uint32_t *surv_off = nullptr;  // device uint32[n_tiles + 1]: index (in the NEXT stage's entry
+    DevBuf<uint32_t> rows;         // device; nullptr for stage 0 (identity)
+    DevBuf<uint32_t> surv_off;     // device uint32[n_tiles + 1]: index (in the NEXT stage's entry
                                    // list) of the first survivor of every tile; nullptr on the last stage
-    void *ws = nullptr;            // device workspace holding this stage's entries (stages >= 1)
+    DevBuf<void> ws;               // device workspace holding this stage's entries (stages >= 1)
     size_t ws_inv_off = 0;         // byte offset of the INVERSE direction's own copy of the workspace inside `ws` (0: both directions
                                    // share one -- the default; raht_plan_set_concurrent_directions gives each its own)
     int tile_rows = 0;             // rows per tile of THIS stage
     // entry-ordered copies of the plan metadata (stages >= 1): one contiguous, single-latency load
     // per tile instead of rows[] -> wl/wr/lvl/inv_order[row] chains. nullptr on stage 0 (entry = row).
-    int32_t *e_wl = nullptr, *e_wr = nullptr;
-    uint8_t *e_lvl = nullptr;
-    uint32_t *e_pos = nullptr;
+    DevBuf<int32_t> e_wl, e_wr;
+    DevBuf<uint8_t> e_lvl;
+    DevBuf<uint32_t> e_pos;
     // tile stages (stage 0 included): HEIGHT of every entry's butterfly inside its tile's merge tree (1 = both children are
     // single entries; 0 = the entry survives the tile). The tile kernels run their butterfly rounds by height, not by
     // binary level: a butterfly's height is 1 + the larger height of its two children, so rounds by ascending height
     // respect every dependency, butterflies of one height are independent, and a tile needs as many rounds as its tree
     // is high (9.3 on average at 184 rows) instead of one per binary level present (13.9). Heights are < 64: levels
     // strictly increase along a dependency chain.
-    uint8_t *e_ht = nullptr;
+    DevBuf<uint8_t> e_ht;
     // TOP stage (the last one, when at most `top_rows` entries are left): ONE launch of top_kernel
     // finishes the tree. A workgroup per 16-byte channel chunk keeps all entries in LDS and walks
     // the butterflies level by level from this precomputed list, sorted by level:
     bool is_top = false;
     uint32_t n_merges = 0;
-    uint32_t *t_pj = nullptr;      // device [n_merges]: partner entry | own entry << 16
-    float *t_ab32 = nullptr;       // device [2 * n_merges]: a, b as the float32 transform uses them
-    double *t_ab64 = nullptr;      // device [2 * n_merges]: a, b in float64
-    uint32_t *t_root = nullptr;    // device [n_entries]: rank among the roots (root buffer row), ~0u = not a root
+    DevBuf<uint32_t> t_pj;         // device [n_merges]: partner entry | own entry << 16
+    DevBuf<float> t_ab32;         // device [2 * n_merges]: a, b as the float32 transform uses them
+    DevBuf<double> t_ab64;        // device [2 * n_merges]: a, b in float64
+    DevBuf<uint32_t> t_root;       // device [n_entries]: rank among the roots (root buffer row), ~0u = not a root
     uint32_t t_loff[65] = {0};     // host: first merge of every binary level (t_loff[63] = n_merges)
     uint32_t t_lev_host[2 * 64] = {0};
-    uint32_t *t_lev = nullptr;     // device [2 * t_nlev]: (first, end) butterfly of every NON-EMPTY level, ascending
+    DevBuf<uint32_t> t_lev;        // device [2 * t_nlev]: (first, end) butterfly of every NON-EMPTY level, ascending
     int t_nlev = 0;
     int t_nbig = 0;                // the first t_nbig of them run on the whole workgroup (a barrier each); the rest
                                    // hold <= 64 butterflies each and are chained by ONE wave without barriers
@@ -242,7 +301,7 @@ struct Stage {
     //                        compact (stage 0 of an unweighted plan): j | l << 10 | r << 20 (left / right extent; p = j - l)
     //                        full (all other tile stages): p | j << 16
     //   words [prog_ab, +4R) full programs only: a, b of record k in float64
-    uint32_t *prog = nullptr;
+    DevBuf<uint32_t> prog;
     uint32_t prog_stride = 0;      // words per tile (a multiple of 4)
     uint32_t prog_ab = 0;          // word offset of the a, b pairs inside a tile's program
     bool prog_compact = false;
@@ -258,9 +317,12 @@ struct Schedule {
     bool ws_split = false;     // the workspaces currently allocated hold one copy per direction
     // recorded on `ready_on` behind the last kernel that writes schedule-derived arrays (heights, tile programs); get_schedule
     // makes a caller on another stream wait for it (raht.h: raht_plan_set_concurrent_directions)
-    hipEvent_t ready = nullptr;
+    OwnedEvent ready;
     hipStream_t ready_on = nullptr;
 };
+// A schedule owns every block of its stages and its event; they go back to the cache when the schedule is dropped (free_schedule,
+// raht_plan_destroy), behind a device synchronisation made THERE.
+static_assert(!std::is_copy_constructible<Stage>::value && !std::is_copy_constructible<Schedule>::value, "stages and schedules own device memory: moved, never copied");
 
 }  // namespace raht
 
@@ -269,22 +331,20 @@ struct raht_plan {
     int64_t N = 0;
     int nbits = 0;
     int max_level = -1;          // highest binary level with a pair (-1 when N == 1)
-    uint64_t *keys = nullptr;    // device, sorted Morton keys
-    bool keys_borrowed = false;  // keys is the CALLER's array (raht_plan_create_from_keys_borrowed): never freed here
-    uint8_t *lvl = nullptr;      // device, 255 for row 0
-    int32_t *wl = nullptr;       // device
-    int32_t *wr = nullptr;       // device
-    int64_t *wsum = nullptr;     // device int64[N+1] prefix of leaf weights, or nullptr (all ones)
-    uint32_t *order = nullptr;   // device, order_RAGFT
-    uint32_t *inv_order = nullptr;  // device, inverse permutation: inv_order[order[k]] = k
-    uint32_t *level_rows = nullptr;          // device, rows 1..N-1 stably sorted by lvl (LEVEL engine only: ensure_level_rows)
+    raht::DevBuf<uint64_t> keys; // device, sorted Morton keys (borrowed: the CALLER's array, raht_plan_create_from_keys_borrowed)
+    raht::DevBuf<uint8_t> lvl;   // device, 255 for row 0
+    raht::DevBuf<int32_t> wl, wr;   // device
+    raht::DevBuf<int64_t> wsum;  // device int64[N+1] prefix of leaf weights, or nullptr (all ones)
+    raht::DevBuf<uint32_t> order;   // device, order_RAGFT
+    raht::DevBuf<uint32_t> inv_order;  // device, inverse permutation: inv_order[order[k]] = k
+    raht::DevBuf<uint32_t> level_rows;       // device, rows 1..N-1 stably sorted by lvl (LEVEL engine only: ensure_level_rows)
     uint32_t level_off[RAHT_MAX_LEVELS + 1]; // host, start of every level inside level_rows
     int top_level = 64;          // butterflies at binary levels >= top_level are NOT performed
     int64_t n_roots = 1;         // row 0 plus every row whose level is >= top_level
-    uint32_t *root_rows = nullptr;   // device, ascending
+    raht::DevBuf<uint32_t> root_rows;   // device, ascending
     void *root_buf = nullptr;    // caller-owned device buffer (n_roots x D), see raht_plan_set_root_buffer
     double *root_buf_w = nullptr;    // caller-owned device buffer (n_roots x n_wide) of the mixed kernels' wide columns (raht_plan_set_root_buffer_wide)
-    uint32_t *row_map = nullptr; // device [N] or nullptr: plan row i lives in matrix row row_map[i] (raht_plan_set_row_map)
+    raht::DevBuf<uint32_t> row_map; // device [N] or nullptr: plan row i lives in matrix row row_map[i] (raht_plan_set_row_map)
     int64_t map_rows = 0;        // rows of the mapped matrices
     int engine = RAHT_ENGINE_TILE;
     int tile_rows_override = 0;
@@ -332,7 +392,17 @@ int build_tile_programs(raht_plan *plan, Schedule *sc, hipStream_t s);
 // first use / growth only).
 int ensure_workspace(Schedule *sc, size_t row_bytes, bool split = false);
 // stage workspace as a direction sees it
-static inline void *stage_ws(const Stage &st, bool inverse) { return st.ws ? (void *)((char *)st.ws + (inverse ? st.ws_inv_off : 0)) : nullptr; }
+static inline void *stage_ws(const Stage &st, bool inverse) { return st.ws ? (void *)((char *)st.ws.get() + (inverse ? st.ws_inv_off : 0)) : nullptr; }
+// Drops the stages of `sc` (and their blocks) once nothing enqueued can still use them: synchronises the device if it holds any.
+void free_schedule(Schedule &sc);
+// The arrays stage k of a schedule reads: entry-ordered copies for a stage with a row list, the plan's own for stage 0
+// (entry = row). ht: the stage's butterfly heights.
+struct StageArrays { const uint32_t *rows; const int32_t *wl, *wr; const uint8_t *lvl; const uint32_t *pos; uint8_t *ht; };
+static inline StageArrays stage_arrays(const raht_plan *p, const Stage &st)
+{
+    if (st.rows) return {st.rows, st.e_wl, st.e_wr, st.e_lvl, st.e_pos, st.e_ht};
+    return {nullptr, p->wl, p->wr, p->lvl, p->inv_order, st.e_ht};
+}
 // Rows per LDS tile for an element size / channel count (0 = does not fit).
 int pick_tile_rows(const raht_plan *plan, int elem_size, int chunk_channels);
 int pick_chunk_channels(int elem_size, int D);

@@ -32,7 +32,7 @@ template <typename E> struct __attribute__((packed, aligned(sizeof(E)))) MemChun
 // values. That keeps every load and store a plain, unpredicated 16-byte access (a load inside a
 // divergent branch costs an exec-mask region with its own s_waitcnt, i.e. one serialised HBM round
 // trip per chunk; masks and shifts cost VALU issue slots, which is what bounds this kernel). The host
-// only runs the tile kernel on channel chunks of at least VN channels (plan.hip: fit_chunk_channels).
+// only runs the tile kernel on channel chunks of at least VN channels (schedule.hip: fit_chunk_channels).
 // STREAM = true marks the once-touched matrices (C, T, Q): nontemporal loads / stores (`nt`), measured
 // +1.5 % on the fused cfg3 step when applied to both directions of the big streams (loads alone: -3 %).
 // Workspace rows, which the next stage re-reads from L2, keep the default policy.

@@ -155,6 +155,13 @@ void dev_free(void *p)
     (void)hipFree(p);
 }
 
+extern "C" int64_t raht_debug_live_blocks(void)
+{
+    DevCache &c = dev_cache();
+    std::lock_guard<std::mutex> g(c.mu);
+    return (int64_t)c.live.size();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Exclusive scan (3 kernels, recursive on the block sums).
 // ------------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@
 //    and writes the run back once. Rows whose subtree crosses the run boundary (4.3 % at R = 184)
 //    are the entries of the next, ~20x smaller stage. HBM traffic ~1.05x the ideal (read C once,
 //    write T once). Stage membership is a pure function of the plan, so it is precomputed
-//    (plan.hip). Every data-touching phase works on 16-byte row chunks (raht_device.h).
+//    (schedule.hip). Every data-touching phase works on 16-byte row chunks (raht_device.h).
 //
 //  * TOP stage: once <= 4096 entries are left, one launch of top_kernel finishes the tree from
 //    butterflies resolved at schedule time.
@@ -854,7 +854,7 @@ __global__ __launch_bounds__(TILE_THREADS, (sizeof(T) == 4 ? 6 : 4)) void tile_k
 // The top of the tree is a handful of butterflies per level over a few thousand rows: as tile
 // stages it was two or three launches of ~15-20 us each, all of it latency (launch, metadata round
 // trip, merge resolution, ~20 barrier-separated rounds per tile). Here the butterflies are resolved
-// once per schedule (plan.hip: build_top_stage; partner entry, a, b, sorted by level), a workgroup
+// once per schedule (schedule.hip: build_top_stage; partner entry, a, b, sorted by level), a workgroup
 // owns ONE 16-byte channel chunk of ALL entries (LDS: 16 bytes per entry), every thread keeps its
 // <= 8 butterfly records in registers, and the levels are walked with one barrier each.
 // ------------------------------------------------------------------------------------------------
@@ -1187,7 +1187,7 @@ static int prepare_stage(const raht_plan *p, const Schedule &sc, int k, const Xf
             A.rows = p->row_map;
             A.io_mapped = 1;
         }
-        A.e_pos = st.rows ? st.e_pos : p->inv_order;
+        A.e_pos = stage_arrays(p, st).pos;
         A.pj = st.t_pj;
         if constexpr (sizeof(T) == 4) A.ab = (const T *)st.t_ab32; else A.ab = (const T *)st.t_ab64;
         A.root_rank = st.t_root;
@@ -1213,9 +1213,8 @@ static int prepare_stage(const raht_plan *p, const Schedule &sc, int k, const Xf
     while ((1 << A.lg) < A.Dp / VN) ++A.lg;               // lanes per row: power of two >= chunks per row (Dc <= 64)
     A.last_stage = (k == K - 1) ? 1 : 0;
     A.wsum = p->wsum;
-    if (st.rows) { A.lvl = st.e_lvl; A.wl = st.e_wl; A.wr = st.e_wr; A.inv_order = st.e_pos; }
-    else { A.lvl = p->lvl; A.wl = p->wl; A.wr = p->wr; A.inv_order = p->inv_order; }
-    A.ht = st.e_ht;
+    const StageArrays a = stage_arrays(p, st);
+    A.lvl = a.lvl; A.wl = a.wl; A.wr = a.wr; A.inv_order = a.pos; A.ht = a.ht;
     A.Q = io.Q; A.ldq = io.ldq;
     A.top_level = p->top_level; A.root_buf = (T *)p->root_buf;
     A.dbg = dbg; A.nwide = 0; A.ref = nullptr; A.ld_ref = 0; A.sq_part = nullptr;
@@ -1411,7 +1410,7 @@ static int tile_setup(raht_plan *p, int D, int64_t max_ld, hipStream_t s, Schedu
     pick_tail_geometry(p, (int)sizeof(T), D, R, &R1, &Dc1, &Rf);
     if (p->row_map) Rf = RAHT_TOP_MAX_ROWS;           // ONE top stage (the only kernel that addresses rows through the map)
     RAHT_RET(get_schedule(p, R, R1, Rf, s, &sc));
-    if (!sc->valid) return RAHT_OK;                   // pathological key pattern, see plan.hip
+    if (!sc->valid) return RAHT_OK;                   // pathological key pattern, see schedule.hip
     RAHT_RET(ensure_workspace(sc, (size_t)D * sizeof(T), p->split_ws));
     *sc_out = sc;
     *Dc_out = Dc;

@@ -161,7 +161,7 @@ __device__ __forceinline__ void tile_body_mx(const TileArgs<float> &A, const MxP
     MX_STAMP(0);
     if constexpr (!MULTI) fetch_steps(fl);                 // (MULTI: one scalar step per output matrix, MxMultiQ)
 
-    // ---- P0a. the tile's program (plan.hip: tile_program_kernel; raht_common.h: Stage::prog), fetched first: every butterfly,
+    // ---- P0a. the tile's program (schedule.hip: tile_program_kernel; raht_common.h: Stage::prog), fetched first: every butterfly,
     // survivor and destination of this tile, resolved once per schedule. Each wave reads the height offsets into its lanes
     // (lane h: butterflies of height <= h), each thread the words of its slots.
     const uint32_t *pg = P.prog + (uint64_t)tile_id * P.prog_stride;
@@ -1129,7 +1129,7 @@ static int prepare_stage_mx(const raht_plan *p, const Schedule &sc, int k, const
         if (!INV) { if (k == 0) { A.in_rows = io.C_in; A.ld_in = io.ldc; } else { A.in_img = ws_k; A.in_img_w = ws_k_w; } }
         else { if (k == 0) { A.out_rows = io.C_out; A.ld_out = io.ldc; } else { A.out_img = ws_k; A.out_img_w = ws_k_w; } }
         A.Q = io.Q; A.ldq = io.ldq;
-        A.e_pos = st.rows ? st.e_pos : p->inv_order;
+        A.e_pos = stage_arrays(p, st).pos;
         A.root_rank = st.t_root;
         A.root_f = (float *)p->root_buf; A.root_w = p->root_buf_w;      // (mx_check_args: both or neither)
         A.pj = st.t_pj; A.ab32 = st.t_ab32; A.ab64 = st.t_ab64;
@@ -1147,9 +1147,8 @@ static int prepare_stage_mx(const raht_plan *p, const Schedule &sc, int k, const
     A.D = D; A.Dc = D; A.Dp = g.Dp; A.lg = g.lg; A.nwide = g.nwide;
     A.last_stage = (k == K - 1) ? 1 : 0;
     A.wsum = p->wsum;
-    if (st.rows) { A.lvl = st.e_lvl; A.wl = st.e_wl; A.wr = st.e_wr; A.inv_order = st.e_pos; }
-    else { A.lvl = p->lvl; A.wl = p->wl; A.wr = p->wr; A.inv_order = p->inv_order; }
-    A.ht = st.e_ht;
+    const StageArrays a = stage_arrays(p, st);
+    A.lvl = a.lvl; A.wl = a.wl; A.wr = a.wr; A.inv_order = a.pos; A.ht = a.ht;
     A.Q = io.Q; A.ldq = io.ldq;
     A.top_level = p->top_level; A.root_buf = A.last_stage ? (float *)p->root_buf : nullptr; A.dbg = 0; A.ref = nullptr; A.ld_ref = 0; A.sq_part = nullptr;
     A.ld_ws = g.Dp; A.wsn = ws_n;

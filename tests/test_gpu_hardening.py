@@ -118,7 +118,7 @@ def test_abandoned_tile_schedule_falls_back_to_the_level_engine(rt, oracle):
 # ------------------------------------------------- the device-driven schedule chain and its exits
 @pytest.mark.parametrize("case", ["half_roots", "early_top", "many_small_stages"])
 def test_schedule_chain_exits(rt, case):
-    """The schedule is built by a chain of launches that never returns to the host (plan.hip: build_schedule_fast):
+    """The schedule is built by a chain of launches that never returns to the host (schedule.hip: build_schedule_fast):
     multi-workgroup stages, then ONE launch for every small stage and the top stage. Its exits must all end in a
     correct transform:
     * half_roots: a tree truncated so that half the rows are roots -- stage 0 keeps more entries than the buffer of
@@ -165,8 +165,8 @@ def test_schedule_chain_exits(rt, case):
     assert (R - Cd).abs().max().item() <= 1e-11 * Cd.abs().max().item()
 
 
-def test_deep_schedules_take_several_height_launches(rt, monkeypatch):
-    """The butterfly heights of a schedule's tile stages come from one launch per 8 stages (plan.hip: launch_stage_heights);
+def test_deep_schedules_take_several_height_launches(rt):
+    """The butterfly heights of a schedule's tile stages come from one launch per 8 stages (schedule.hip: launch_stage_heights);
     schedules with more tile stages (deep / unbalanced key sets, small tail tiles) used to be refused, failing every transform
     of the plan. Here the per-launch group is cut to 2 so that an ordinary four-stage schedule walks the several-launches
     path: same heights, hence bit-identical transforms."""
@@ -179,14 +179,18 @@ def test_deep_schedules_take_several_height_launches(rt, monkeypatch):
     p0.set_engine("tile", 64, 64, 0, 64)
     T0 = p0.forward(C, want_w=False)
     Q0 = p0.forward_quant(C, 0.02)
-    monkeypatch.setenv("RAHT_HEIGHT_STAGES_PER_LAUNCH", "2")
-    p1 = rt.RahtPlan.from_keys(keys, nbits)
-    p1.set_engine("tile", 64, 64, 0, 64)
-    st = p1.stage_stats(4, D)
-    assert st["valid"] and len(st["rows_per_stage"]) >= 4
-    assert torch.equal(p1.forward(C, want_w=False), T0)
-    assert torch.equal(p1.forward_quant(C, 0.02), Q0)
-    assert torch.equal(p1.dequant_inverse(Q0, 0.02), p0.dequant_inverse(Q0, 0.02))
+    from raht_3dgs_codec_amd import _lib
+    prev = _lib.lib().raht_debug_height_stages_per_launch(2)
+    try:
+        p1 = rt.RahtPlan.from_keys(keys, nbits)
+        p1.set_engine("tile", 64, 64, 0, 64)
+        st = p1.stage_stats(4, D)
+        assert st["valid"] and len(st["rows_per_stage"]) >= 4
+        assert torch.equal(p1.forward(C, want_w=False), T0)
+        assert torch.equal(p1.forward_quant(C, 0.02), Q0)
+        assert torch.equal(p1.dequant_inverse(Q0, 0.02), p0.dequant_inverse(Q0, 0.02))
+    finally:
+        _lib.lib().raht_debug_height_stages_per_launch(prev)
 
 
 # ----------------------------------------------------------- several schedules alive on one plan

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 D, NW = 59, 3
 STEP = 0.01
 STEPS3 = [0.01, 0.02, 0.05]
-TOP_ROWS_DEFAULT = 1536              # csrc/plan.hip pick_tail_geometry: a stage of at most this many entries is a top stage
+TOP_ROWS_DEFAULT = 1536              # csrc/schedule.hip pick_tail_geometry: a stage of at most this many entries is a top stage
 SCENES = {"A": (20000, 10), "B": (300, 6)}
 
 
@@ -64,7 +64,7 @@ def scenes(rt):
             assert all(len(r) >= 2 for r in rows), rows
         else:
             # exactly one stage, a top stage. Mixed: asserted directly, the grouping counts one top launch and no tile launch.
-            # float32 / float64: INFERRED from one stage of N <= 1536 rows, plan.hip's default limit of a top stage (no entry
+            # float32 / float64: INFERRED from one stage of N <= 1536 rows, schedule.hip's default limit of a top stage (no entry
             # point reports is_top; should that default ever drop below N, this assertion keeps passing and means less)
             assert p.N <= TOP_ROWS_DEFAULT and all(r == [p.N] for r in rows), rows
             assert ops.mixed_batch_stats([p], D, NW) == {"tile_launches": 0, "top_launches": 1, "single_scene_calls": 0}

@@ -1,4 +1,4 @@
-"""Tile programs (csrc/plan.hip: tile_program_kernel; raht_common.h: Stage::prog): the mixed-precision tile kernels replay every
+"""Tile programs (csrc/schedule.hip: tile_program_kernel; raht_common.h: Stage::prog): the mixed-precision tile kernels replay every
 tile's butterflies, survivors and destinations from a program built once per schedule instead of resolving them per call.
 
 Bar: bit-identical to raht_fwd_quant_f64 / raht_dequant_inv_f64 on the wide columns and to raht_fwd_quant / raht_dequant_inv on

@@ -75,10 +75,10 @@ def test_plan_kernels_save_and_restore_m0_around_their_writelanes(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-@pytest.mark.parametrize("tu", ["rlgr_seg.hip", "plan.hip"])
+@pytest.mark.parametrize("tu", ["rlgr_seg.hip", "plan.hip", "schedule.hip"])
 def test_coder_and_plan_kernels_do_not_spill(tu):
     """the segmented coder's kernels must keep 7-8 waves per SIMD (that is where their batched speed comes from): no scratch, at most
-    72 VGPRs; the plan kernels: no scratch"""
+    72 VGPRs; the plan and schedule kernels: no scratch"""
     r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-fno-fast-math",
                         "-ffp-contract=on", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, tu), "-o", os.devnull],
                        capture_output=True, text=True, timeout=900)
