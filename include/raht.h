@@ -767,6 +767,37 @@ int raht_octree_bytes(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_o
                       raht_stream_t stream);
 int raht_demorton(const uint64_t *keys, int64_t N, int J, int64_t *V, raht_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Regions of a frame (csrc/region.hip): where the rows of a run of octree cells lie in the frame's coded order, so that a decoder
+ * can rebuild them from the segments that hold them (python: bitstream.decode_region_bytes).
+ *
+ * Buckets: a row i >= 1 has bucket msb(key[i] ^ key[i-1]) / 3 (0 .. 20), row 0 has bucket 21 = RAHT_REGION_BUCKETS - 1. The coded
+ * order of a frame (order_RAGFT) is the stable sort of its rows by DESCENDING bucket. For the cells of octree depth d of a frame
+ * of depth J, top_level = 3 (J - d): the rows of the buckets >= J - d are the first rows of the occupied depth-d cells, and they
+ * are the first coded rows; in every bucket below, the rows [row_lo, row_hi) of a run of such cells are ONE run of coded rows.
+ * keys_sorted: N >= 1 strictly ascending keys below 2^nbits, 1 <= nbits <= 63 (what raht_plan_create_from_keys takes; not checked
+ * again here).
+ *   raht_region_layout   : table (DEVICE int64[3 * RAHT_REGION_BUCKETS]) = rows per bucket in the whole frame, in [0, row_lo) and
+ *                          in [row_lo, row_hi), from one pass over the keys. Enqueues only (a memset and one launch).
+ *   raht_region_cells    : the rows with i == 0 or msb(key[i] ^ key[i-1]) >= top_level, in row order: cell_keys[j] = key >>
+ *                          top_level (DEVICE uint64[n_cells]), cell_first[j] = the row (DEVICE int64[n_cells + 1], the last entry
+ *                          N). n_cells is the caller's expectation (the level count of a geometry header); every store is
+ *                          bounded by it, and a different count is RAHT_ERR_INVALID. SYNCHRONISES `stream` (it reads the count
+ *                          back). top_level: a multiple of 3 in [3, nbits - 3].
+ *   raht_region_assemble : dst (n_dst_rows x D int32, row stride ld_dst) from runs of rows of src (n_src_rows x D int32, row
+ *                          stride ld_src): runs (HOST int64[3 * n_runs], n_runs <= RAHT_REGION_BUCKETS) holds (src_row, dst_row,
+ *                          count) triples with ascending, disjoint destinations; they travel to the kernel by value. dst rows
+ *                          that no run covers are set to 0. One launch, enqueues only.
+ * RAHT_ERR_INVALID, with nothing enqueued: NULL pointers, N < 1, row_lo > row_hi or row_hi > N, nbits or top_level out of range,
+ * a run that leaves either matrix. */
+#define RAHT_REGION_BUCKETS 22
+int raht_region_layout(const uint64_t *keys_sorted, int64_t N, int nbits, int64_t row_lo, int64_t row_hi, int64_t *table,
+                       raht_stream_t stream);
+int raht_region_cells(const uint64_t *keys_sorted, int64_t N, int nbits, int top_level, int64_t n_cells, uint64_t *cell_keys,
+                      int64_t *cell_first, raht_stream_t stream);
+int raht_region_assemble(const int32_t *src, int64_t ld_src, int64_t n_src_rows, int32_t *dst, int64_t ld_dst, int64_t n_dst_rows, int D,
+                         const int64_t *runs, int n_runs, raht_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

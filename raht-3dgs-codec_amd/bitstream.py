@@ -1,6 +1,7 @@
 """A frame as self-contained bytes: geometry (geometry.OctreeCoder) + quantized RAHT coefficients (rlgr.SegmentedCoder) + the few
 numbers a decoder needs. ``decode_frame_bytes`` is handed nothing but the blob: it rebuilds the voxel keys, builds its own plan
-from them and runs the inverse kernels that match the encoder's.
+from them and runs the inverse kernels that match the encoder's. ``decode_region_bytes`` rebuilds the voxels of a run of octree
+cells from the geometry and the attribute segments those voxels depend on.
 
     RAHTF001 | int64 J, N, D, n_wide, n_steps | float64 steps[n_steps] | float64 vmin[3], width |
     int64 length + geometry section | int64 length + attribute container (SegmentedCoder.container())
@@ -209,3 +210,111 @@ def decode_frame_bytes(blob, device="cuda", max_voxels=None):
         if int(sc.bad.item()) != 0:
             raise ValueError("frame container: an attribute segment reaches outside its payload")
     return V, C_rec
+
+
+def region_runs(table, J, depth, n_roots):
+    """Where a region lies in the coded order of its frame, from the three bucket histograms of ``ops.region_layout`` (host
+    integers, (3, 22): whole frame, rows before the region, rows inside it) -> (n_top, runs). The first ``n_top`` coded rows are the
+    tree above ``depth`` (row 0 and every row of a bucket >= J - depth); ``runs`` holds one (coded row, row of the region's own coded
+    matrix, count) per finer bucket that has rows in the region, coarse to fine. The region's matrix starts with its ``n_roots``
+    root slots (one per occupied cell)."""
+    whole, before, inside = table
+    cut = int(J) - int(depth)
+    n_top = int(sum(whole[cut:]))
+    coded, dst, runs = n_top, int(n_roots), []
+    for beta in range(cut - 1, -1, -1):
+        if inside[beta]:
+            runs.append((coded + int(before[beta]), dst, int(inside[beta])))
+        coded += int(whole[beta])
+        dst += int(inside[beta])
+    return n_top, runs
+
+
+def region_segments(n_top, runs, seg_len):
+    """-> (seg_ids, compact): the ascending segment indices that hold the coded rows [0, n_top) and the runs, and the map from a
+    coded row inside them to its row of the matrix those segments decode to"""
+    S = int(seg_len)
+    spans = [(0, n_top)] + [(r, r + n) for r, _, n in runs]
+    ids = np.unique(np.concatenate([np.arange(lo // S, (hi - 1) // S + 1) for lo, hi in spans]))
+
+    def compact(row):
+        return int(np.searchsorted(ids, row // S)) * S + row % S
+    return ids, compact
+
+
+def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys=None):
+    """The voxels of the octree cells ``cells = (c0, c1)`` (Morton indices at ``depth``, 1 <= depth <= J - 1, 0 <= c0 < c1 <=
+    8^depth) of a frame, from the geometry and the attribute segments they depend on -> (V_int (n, 3) int64, C_rec (n, D) float32,
+    info): rows [a, b) of what ``decode_frame_bytes`` returns, up to the rounding of the tree above ``depth``, which the two
+    decoders compute in different launches. ``keys``: ``info["keys"]`` of an earlier call on the same frame; the geometry is then
+    not decoded again. info: rows (a, b), n_cells (occupied cells in the range), segments_decoded / segments_total (per channel),
+    byte_ranges ((offset, length) within ``blob``: everything outside them may be missing) and bytes_needed, geometry_decoded,
+    keys. No N x D matrix is allocated: the only full-length arrays are the keys and the cell search's flags.
+    ``ValueError`` for a corrupt frame or arguments outside the ranges above."""
+    import torch
+    from . import ops
+    h = parse_frame(blob, max_voxels)
+    J, N, D, n_wide, steps = h["J"], h["N"], h["D"], h["n_wide"], h["steps"]
+    try:
+        depth, (c0, c1) = int(depth), (int(c) for c in cells)
+    except (TypeError, ValueError):
+        raise ValueError("decode_region_bytes: depth is an integer, cells a pair of integers") from None
+    if not 1 <= depth <= J - 1:
+        raise ValueError(f"decode_region_bytes: depth must be 1 .. J - 1 = {J - 1}")
+    if not 0 <= c0 < c1 <= 8 ** depth:
+        raise ValueError(f"decode_region_bytes: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
+    dev = torch.device(device)
+    (go, gl), (ao, al) = h["geometry"], h["attributes"]
+    view = memoryview(blob)
+    n_d = OctreeCoder.parse(view[go: go + gl], max_voxels)["counts"][depth]
+    att = view[ao: ao + al]
+    _, _, S, _, _, _, pay = SegmentedCoder._parse(att, N * D)
+    nseg = (N + S - 1) // S
+    ranges = [(0, ao + pay)]                                              # frame header, geometry section, attribute header + table
+    if keys is not None:
+        if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dtype != torch.int64 or tuple(keys.shape) != (N,):
+            raise ValueError(f"decode_region_bytes: keys must be the ({N},) int64 CUDA tensor an earlier call returned")
+        keys = keys.contiguous()
+    tl = 3 * (J - depth)
+    with torch.cuda.device(dev):
+        decoded = keys is None
+        if decoded:
+            keys = OctreeCoder.decode(view[go: go + gl], dev, max_voxels)
+        try:
+            cell_keys, cell_first = ops.region_cells(keys, 3 * J, tl, n_d)
+        except ops.RahtError as e:
+            raise ValueError(f"decode_region_bytes: the keys are not this frame's ({e})") from None
+        j = torch.searchsorted(cell_keys, torch.tensor([c0, c1], dtype=torch.int64, device=dev))
+        j0, j1, a, b = torch.cat([j, cell_first[j]]).tolist()
+        info = dict(rows=(a, b), n_cells=j1 - j0, segments_decoded=0, segments_total=nseg, byte_ranges=ranges,
+                    bytes_needed=ranges[0][1], geometry_decoded=decoded, keys=keys)
+        if j0 == j1:
+            return (torch.empty((0, 3), dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev), info)
+        n_top, runs = region_runs(ops.region_layout(keys, 3 * J, a, b).tolist(), J, depth, j1 - j0)
+        if n_top != n_d:
+            raise ValueError("decode_region_bytes: the keys are not this frame's")
+        seg_ids, compact = region_segments(n_top, runs, S)
+        sc, att_ranges = SegmentedCoder.from_container_segments(att, seg_ids, dev, max_symbols=N * D)
+        Qc = sc.decode(row_major=True)
+        # the tree above `depth`: a weighted plan over the occupied cells; its inverse gives every cell's low-pass row
+        top = ops.RahtPlan.from_keys(cell_keys, 3 * depth, leaf_weights=cell_first[1:] - cell_first[:-1])
+        roots = top.dequant_inverse(Qc[:n_top], steps)[j0:j1]
+        # the region: a plan truncated at the cells over its own rows, its coded matrix put together from the decoded runs
+        plan = ops.RahtPlan.from_keys(keys[a:b], 3 * J, top_level=tl)
+        Qr = ops.region_assemble(Qc, [(compact(r), d, n) for r, d, n in runs], b - a)
+        if n_wide:
+            wide = top.dequant_inverse(Qc[:n_top, :n_wide], steps[:n_wide], dtype=torch.float64)[j0:j1]
+            C_rec = plan.dequant_inverse_mixed(Qr, steps, n_wide, roots=roots.contiguous(), roots_wide=wide.contiguous())
+        else:
+            C_rec = plan.dequant_inverse(Qr, steps, roots=roots.contiguous())
+        V = ops.demorton(keys[a:b], J)
+        if int(sc.bad.item()) != 0:
+            raise ValueError("frame container: an attribute segment reaches outside its payload")
+    ranges = [(0, ao)]                                                    # frame header, geometry section, the attributes' length word
+    for off, ln in att_ranges:                                            # the first: header + table (+ the slots that follow them)
+        if ranges[-1][0] + ranges[-1][1] == ao + off:
+            ranges[-1] = (ranges[-1][0], ranges[-1][1] + ln)
+        else:
+            ranges.append((ao + off, ln))
+    info.update(segments_decoded=len(seg_ids), byte_ranges=ranges, bytes_needed=sum(ln for _, ln in ranges))
+    return V, C_rec, info

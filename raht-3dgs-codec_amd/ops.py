@@ -946,6 +946,63 @@ def demorton(keys, J):
     return out
 
 
+REGION_BUCKETS = 22                                          # RAHT_REGION_BUCKETS
+
+
+def _region_keys(keys, what):
+    _need_cuda(keys, "keys")
+    if keys.dtype not in (torch.int64, torch.uint64) or keys.dim() != 1 or keys.shape[0] < 1:
+        raise ValueError(f"{what}: keys must be a non-empty 1-D int64/uint64 tensor")
+    return keys.contiguous()
+
+
+@torch.no_grad()
+def region_layout(keys_sorted, nbits, row_lo, row_hi):
+    """-> (3, 22) int64 device tensor: rows per bucket (a row's bucket: msb(key[i] ^ key[i-1]) / 3, row 0: 21) in the whole frame,
+    in [0, row_lo) and in [row_lo, row_hi) (raht_region_layout). Enqueued only."""
+    k = _region_keys(keys_sorted, "region_layout")
+    table = torch.empty((3, REGION_BUCKETS), dtype=torch.int64, device=k.device)
+    with torch.cuda.device(k.device):
+        check(_lib.lib().raht_region_layout(C.c_void_p(k.data_ptr()), k.shape[0], int(nbits), int(row_lo), int(row_hi),
+                                            C.c_void_p(table.data_ptr()), _stream()))
+    return table
+
+
+@torch.no_grad()
+def region_cells(keys_sorted, nbits, top_level, n_cells):
+    """The occupied cells of the octree level ``top_level / 3`` bits above the voxels -> (cell_keys (n_cells,) int64: key >>
+    top_level, cell_first (n_cells + 1,) int64: every cell's first row, then N) on the keys' device (raht_region_cells).
+    ``n_cells``: how many there must be (a geometry header's level count); ``RahtError`` when the keys hold another number.
+    Synchronises."""
+    k = _region_keys(keys_sorted, "region_cells")
+    n_cells = int(n_cells)
+    if n_cells < 1:
+        raise ValueError("region_cells: n_cells must be at least 1")
+    cell_keys = torch.empty(n_cells, dtype=torch.int64, device=k.device)
+    cell_first = torch.empty(n_cells + 1, dtype=torch.int64, device=k.device)
+    with torch.cuda.device(k.device):
+        check(_lib.lib().raht_region_cells(C.c_void_p(k.data_ptr()), k.shape[0], int(nbits), int(top_level), n_cells,
+                                           C.c_void_p(cell_keys.data_ptr()), C.c_void_p(cell_first.data_ptr()), _stream()))
+    return cell_keys, cell_first
+
+
+@torch.no_grad()
+def region_assemble(src, runs, n_dst_rows):
+    """-> (n_dst_rows, D) int32: the runs ``(src_row, dst_row, count)`` (at most 22, destinations ascending and disjoint) of rows of
+    the int32 matrix ``src``, every other row 0, in one launch (raht_region_assemble)."""
+    _need_cuda(src, "src")
+    if src.dtype != torch.int32 or src.dim() != 2 or src.stride(1) != 1 or src.shape[0] < 1:
+        raise ValueError("region_assemble: src must be a non-empty int32 matrix with contiguous rows")
+    D = int(src.shape[1])
+    dst = torch.empty((int(n_dst_rows), D), dtype=torch.int32, device=src.device)
+    flat = [int(x) for r in runs for x in r]
+    arr = (C.c_int64 * max(len(flat), 1))(*flat)
+    with torch.cuda.device(src.device):
+        check(_lib.lib().raht_region_assemble(C.c_void_p(src.data_ptr()), src.stride(0), src.shape[0], C.c_void_p(dst.data_ptr()), D,
+                                              int(n_dst_rows), D, arr, len(flat) // 3, _stream()))
+    return dst
+
+
 @torch.no_grad()
 def voxel_keys(PC, vmin, width, J):
     """Unsorted 3J-bit Morton keys (int64) of the points of PC (n, >= 3) float32 for a given bounding box: the

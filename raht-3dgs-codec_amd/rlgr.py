@@ -261,13 +261,11 @@ class SegmentedCoder:
         return hdr + lens.tobytes() + payload.tobytes()
 
     @classmethod
-    def from_container(cls, blob, device="cuda", max_symbols=None, wide=None):
-        """wide: as in the constructor; the default also takes the 64-bit table when the payload itself is 4 GiB or more.
-        max_symbols: refuse containers whose header announces more than this many symbols (N x D): decode() allocates
-        4 N D bytes for them, and the header comes off the wire."""
-        import torch
+    def _parse(cls, blob, max_symbols=None):
+        """The header and the WHOLE length table of a container, checked against the blob before anything is allocated from them
+        (pure host code) -> (N, D, seg_len, flag, total, lens int64 (G,), payload offset). ``ValueError`` when they do not add up."""
         m = len(cls.MAGIC)
-        if blob[:m] != cls.MAGIC:
+        if bytes(blob[:m]) != cls.MAGIC:
             raise ValueError("not a segmented RLGR container")
         if len(blob) < m + 40:
             raise ValueError("segmented RLGR container: truncated header")
@@ -280,20 +278,81 @@ class SegmentedCoder:
             raise ValueError("segmented RLGR container: shorter than its header says")
         if max_symbols is not None and N * D > int(max_symbols):
             raise ValueError(f"segmented RLGR container: {N} x {D} symbols, more than the caller allows ({max_symbols})")
+        lens = np.frombuffer(blob, np.uint32, G, m + 40).astype(np.int64)
+        if total % 4 or total > len(blob) - (m + 40 + 4 * G) or int(((lens + 3) // 4 * 4).sum()) != total:
+            raise ValueError("segmented RLGR container: inconsistent length table")
+        return N, D, S, flag, total, lens, m + 40 + 4 * G
+
+    def _upload(self, lens, payload):
+        """length table (int64 numpy) and padded payload (uint8 numpy) of a decoder -> the device"""
+        import torch
+        total = int(payload.shape[0])
+        off = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
+        self.seg_bytes.copy_(torch.from_numpy(lens.astype(np.int32)))
+        self.seg_off.copy_(torch.from_numpy(off.astype(np.int64) if self.wide else off.astype(np.int64).astype(np.int32)))
+        if total > self.cap:
+            self.cap, self.out = total, torch.empty(total, dtype=torch.uint8, device=self.device)
+        self.out[:total].copy_(torch.from_numpy(payload))
+        self.total = total
+
+    @classmethod
+    def from_container(cls, blob, device="cuda", max_symbols=None, wide=None):
+        """wide: as in the constructor; the default also takes the 64-bit table when the payload itself is 4 GiB or more.
+        max_symbols: refuse containers whose header announces more than this many symbols (N x D): decode() allocates
+        4 N D bytes for them, and the header comes off the wire."""
+        N, D, S, flag, total, lens, pay = cls._parse(blob, max_symbols)
         if wide is None and total >= 2 ** 32:
             wide = True
         sc = cls(N, D, S, flag, device, payload_cap=total, wide=wide)     # (the payload only: a decoder never needs the encoder's raw-size buffer)
-        lens = np.frombuffer(blob, np.uint32, sc.G, m + 40).astype(np.int64)
-        if total % 4 or total > len(blob) - (m + 40 + 4 * sc.G) or int(((lens + 3) // 4 * 4).sum()) != total:
-            raise ValueError("segmented RLGR container: inconsistent length table")
-        off = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
-        sc.seg_bytes.copy_(torch.from_numpy(lens.astype(np.int32)))
-        sc.seg_off.copy_(torch.from_numpy(off.astype(np.int64) if sc.wide else off.astype(np.int64).astype(np.int32)))
-        if total > sc.cap:
-            sc.cap, sc.out = total, torch.empty(total, dtype=torch.uint8, device=sc.device)
-        sc.out[:total].copy_(torch.from_numpy(np.frombuffer(blob, np.uint8, total, m + 40 + 4 * sc.G).copy()))
-        sc.total = total
+        sc._upload(lens, np.frombuffer(blob, np.uint8, total, pay).copy())
         return sc
+
+    @classmethod
+    def select_segments(cls, blob, seg_ids):
+        """The container of a few segments of every channel, cut out of a whole one (pure host code, no device).
+        seg_ids: ascending, distinct segment indices in 0 .. nseg - 1, the same for every channel. The header and the WHOLE length
+        table are checked as ``from_container`` checks them. -> ((N', lens', payload'), byte_ranges): the pseudo-frame whose
+        segment k of channel c is segment seg_ids[k] of channel c -- N' = (n_sel - 1) seg_len + symbols of the last selected
+        segment (the frame's last segment may be short), lens' int64 (D n_sel,), payload' uint8: their 4-byte slots, concatenated --
+        and the merged (offset, length) ranges of ``blob`` that were read: header + table, then one per channel and run of
+        consecutive segments."""
+        N, D, S, flag, total, lens, pay = cls._parse(blob)
+        nseg = (N + S - 1) // S
+        ids = np.asarray(seg_ids, dtype=np.int64).reshape(-1)
+        if ids.size < 1 or ids[0] < 0 or ids[-1] >= nseg or np.any(ids[1:] <= ids[:-1]):
+            raise ValueError(f"SegmentedCoder.select_segments: segment ids must be ascending, distinct and in 0 .. {nseg - 1}")
+        off = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
+        cut = np.nonzero(ids[1:] != ids[:-1] + 1)[0] + 1                   # runs of consecutive ids: [first[r], last[r]]
+        first, last = ids[np.concatenate([[0], cut])], ids[np.concatenate([cut - 1, [ids.size - 1]])]
+        view = np.frombuffer(blob, np.uint8, total, pay)
+        pieces, ranges = [], [(0, pay)]
+        for c in range(D):
+            for f, l in zip(first, last):
+                lo, hi = int(off[c * nseg + f]), int(off[c * nseg + l + 1])
+                pieces.append(view[lo:hi])
+                if hi > lo:
+                    if ranges[-1][0] + ranges[-1][1] == pay + lo:
+                        ranges[-1] = (ranges[-1][0], ranges[-1][1] + hi - lo)
+                    else:
+                        ranges.append((pay + lo, hi - lo))
+        n_last = N - (nseg - 1) * S if ids[-1] == nseg - 1 else S
+        lens_sel = lens.reshape(D, nseg)[:, ids].reshape(-1)
+        return ((ids.size - 1) * S + n_last, lens_sel, np.concatenate(pieces)), ranges
+
+    @classmethod
+    def from_container_segments(cls, blob, seg_ids, device="cuda", max_symbols=None):
+        """A decoder for the segments ``seg_ids`` of every channel only (``select_segments``): -> (coder, byte_ranges). The coder is
+        an ordinary ``SegmentedCoder(N', D, seg_len)`` that was handed nothing but those segments' lengths and bytes; its
+        ``decode(row_major=True)`` gives the (N', D) rows the selected segments cover, in segment order. ``max_symbols``: refuse
+        more than this many symbols (N' x D)."""
+        (Np, lens, payload), ranges = cls.select_segments(blob, seg_ids)
+        m = len(cls.MAGIC)
+        _, D, S, flag, _ = [int(x) for x in np.frombuffer(blob, np.int64, 5, m)]
+        if max_symbols is not None and Np * D > int(max_symbols):
+            raise ValueError(f"segmented RLGR container: {Np} x {D} symbols selected, more than the caller allows ({max_symbols})")
+        sc = cls(Np, D, S, flag, device, payload_cap=int(payload.shape[0]))
+        sc._upload(lens, payload)
+        return sc, ranges
 
     def decode(self, out=None, row_major=False):
         """-> (D, N) int32 CUDA tensor, or (N, D) with ``row_major=True`` (what dequant_inverse takes: no transpose behind the
