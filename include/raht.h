@@ -668,6 +668,26 @@ int raht_rlgr_seg_decode_batch64(int k, const uint8_t *const *in, const int64_t 
                                  int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride, int64_t chan_stride,
                                  uint32_t *bad_dev, raht_stream_t stream);
 
+/* k frames of k SHAPES in one set of launches -- the frames of a sequence: a different voxel count in every frame, D, seg_len and
+ * flag_signed shared. N[j], sym_stride[j], chan_stride[j]: HOST arrays of k entries; all frames channel-major or all row-major,
+ * each within the stride rules of raht_rlgr_seg_encode_strided. 32-bit offset tables only: a frame for which
+ * raht_rlgr_seg_offsets_width(N[j], D, seg_len) is not 32 is refused (RAHT_ERR_INVALID, the text names the frame) -- such a
+ * frame fills the chip alone. The contract is that of the same-shape batch, which is this launch with N[j] = N: every frame gets
+ * EXACTLY the bytes, seg_bytes, seg_off (its closing entry seg_off[D * nseg_j] included) and total_bytes[j] that
+ * raht_rlgr_seg_encode_strided leaves for it alone. The encoder synchronises and fills total_bytes[k] (RAHT_ERR_NOMEM: some
+ * cap[j] < total_bytes[j]); a segment that outgrows its slot sends the call to the exact passes, frame by frame. The decoder does
+ * not synchronise; it sets bit j of *bad_dev when a table entry of frame j reached outside in[j] (that segment decodes as zeros)
+ * and, with expect != NULL (row-major frames only, bad_dev required, no expect[j] NULL), bit 16 + j when frame j differs from
+ * expect[j]. */
+int raht_rlgr_seg_encode_ragged(int k, const int32_t *const *Q, const int64_t *N, int D, const int64_t *sym_stride,
+                                const int64_t *chan_stride, int seg_len, int flag_signed, uint32_t *const *seg_bytes,
+                                uint32_t *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
+                                raht_stream_t stream);
+int raht_rlgr_seg_decode_ragged(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint32_t *const *seg_off,
+                                const uint32_t *const *seg_bytes, const int64_t *N, int D, int seg_len, int flag_signed,
+                                int32_t *const *Q, const int32_t *const *expect, const int64_t *sym_stride,
+                                const int64_t *chan_stride, uint32_t *bad_dev, raht_stream_t stream);
+
 /* The SIZE of that container at k quantization steps, and the squared quantization error beside it, from ONE read of the
  * coefficients (csrc/rlgr_rate.hip): the rate-distortion curve of a frame without a quantized matrix, a slot buffer or a stream
  * being written. A lane walks one segment of one channel and advances up to RAHT_RLGR_RATE_MAX independent coder states, each

@@ -6,6 +6,12 @@ cells from the geometry and the attribute segments those voxels depend on (DESIG
     RAHTF001 | int64 J, N, D, n_wide, n_steps | float64 steps[n_steps] | float64 vmin[3], width |
     int64 length + geometry section | int64 length + attribute container (SegmentedCoder.container())
 
+A SEQUENCE of frames (a different voxel count in every frame) is a container OF such frames: every frame is an ordinary RAHTF001
+blob -- ``sequence_frame`` hands out its slice, and ``decode_frame_bytes`` / ``decode_region_bytes`` work on it -- coded and decoded
+with the transform and entropy stages of all frames in common launches:
+
+    RAHTS001 | int64 n_frames | int64 offset[n_frames + 1] (from the start of the blob) | the frames
+
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
 sides, as ``ops._steps`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
@@ -18,6 +24,8 @@ from .geometry import MAX_J, OctreeCoder
 from .rlgr import SegmentedCoder
 
 MAGIC = b"RAHTF001"
+SEQ_MAGIC = b"RAHTS001"
+MIN_FRAME_BYTES = len(MAGIC) + 40 + 8 * 5 + 2 * (8 + 48)      # header, one step + box, two sections of 48 bytes at least
 
 
 def _step_list(step, D):
@@ -60,13 +68,18 @@ def encode_frame_bytes(V_int, attributes, J, step, device="cuda", n_wide=0, seg_
     return _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att)
 
 
-def _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att):
+def _frame_parts(J, N, D, n_wide, steps, vmin, width, geo, att_parts):
+    """the pieces of a frame container, in order; att_parts: the attribute container, whole or in pieces"""
     box = [0.0, 0.0, 0.0] if vmin is None else [float(x) for x in vmin]
     if len(box) != 3:
         raise ValueError("encode_frame_bytes: vmin must have 3 entries")
     box.append(0.0 if width is None else float(width))
-    return (MAGIC + np.array([J, N, D, n_wide, len(steps)], np.int64).tobytes() + np.array(steps + box, np.float64).tobytes()
-            + np.array([len(geo)], np.int64).tobytes() + geo + np.array([len(att)], np.int64).tobytes() + att)
+    return [MAGIC + np.array([J, N, D, n_wide, len(steps)], np.int64).tobytes() + np.array(steps + box, np.float64).tobytes()
+            + np.array([len(geo)], np.int64).tobytes(), geo, np.array([sum(len(a) for a in att_parts)], np.int64).tobytes(), *att_parts]
+
+
+def _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att):
+    return b"".join(_frame_parts(J, N, D, n_wide, steps, vmin, width, geo, [att]))
 
 
 def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scale_range=(2 ** -10, 2 ** 10), rounds=3, n_wide=0,
@@ -318,3 +331,190 @@ def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys
             ranges.append((ao + off, ln))
     info.update(segments_decoded=len(seg_ids), byte_ranges=ranges, bytes_needed=sum(ln for _, ln in ranges))
     return V, C_rec, info
+
+
+def pack_sequence(frame_blobs):
+    """frames (bytes-like, each a RAHTF001 container) -> the sequence container (pure host code)"""
+    blobs = [bytes(b) for b in frame_blobs]
+    if not blobs:
+        raise ValueError("pack_sequence: a sequence has one frame at least")
+    if any(len(b) < MIN_FRAME_BYTES for b in blobs):
+        raise ValueError(f"pack_sequence: no frame container is shorter than {MIN_FRAME_BYTES} bytes")
+    return _pack_parts([[b] for b in blobs])
+
+
+def _pack_parts(frames):
+    """frames: every frame container as a list of its pieces -> the sequence container, every byte copied once"""
+    head = len(SEQ_MAGIC) + 8 * (len(frames) + 2)
+    off = head + np.concatenate([[0], np.cumsum([sum(len(p) for p in f) for f in frames], dtype=np.int64)]).astype(np.int64)
+    return b"".join([SEQ_MAGIC, np.array([len(frames)], np.int64).tobytes(), off.tobytes()] + [p for f in frames for p in f])
+
+
+def parse_sequence(blob, max_frames=None):
+    """The header of a sequence container, checked against the blob before anything is allocated from its numbers (pure host code)
+    -> offsets: a list of n_frames + 1 integers, frame i is blob[offsets[i]: offsets[i + 1]]. ``ValueError`` when it does not add up:
+    wrong magic, a truncated header, an implausible frame count (or more than ``max_frames``), offsets that do not ascend by at least
+    the smallest frame, a first offset that is not the header's size, a last one that is not the blob's length."""
+    m = len(SEQ_MAGIC)
+    if bytes(blob[:m]) != SEQ_MAGIC:
+        raise ValueError("not a RAHT sequence container")
+    if len(blob) < m + 8:
+        raise ValueError("sequence container: truncated header")
+    n = int(np.frombuffer(blob, np.int64, 1, m)[0])
+    if n < 1 or n > (len(blob) - m - 16) // (8 + MIN_FRAME_BYTES):      # (every frame costs its offset and its smallest container)
+        raise ValueError("sequence container: implausible frame count")
+    if max_frames is not None and n > int(max_frames):
+        raise ValueError(f"sequence container: {n} frames, more than the caller allows ({max_frames})")
+    head = m + 8 * (n + 2)
+    off = np.frombuffer(blob, np.int64, n + 1, m + 8)
+    if int(off[0]) != head or int(off[-1]) != len(blob) or bool(np.any(off[1:] - off[:-1] < MIN_FRAME_BYTES)) or bool(np.any(off < 0)):
+        raise ValueError("sequence container: the offset table does not match the blob")
+    return [int(x) for x in off]
+
+
+def sequence_frame(blob, i, offsets=None):
+    """frame i of a sequence container as a memoryview of its RAHTF001 container (no copy). ``offsets``: what ``parse_sequence``
+    returned for this blob (parsed here otherwise)."""
+    off = parse_sequence(blob) if offsets is None else offsets
+    i = int(i)
+    if not 0 <= i < len(off) - 1:
+        raise ValueError(f"sequence_frame: frame index outside 0 .. {len(off) - 2}")
+    return memoryview(blob)[off[i]: off[i + 1]]
+
+
+SEQ_CHUNK = SegmentedCoder.BATCH_MAX                                     # frames whose transform and entropy stages share launches
+
+
+def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None):
+    """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
+    container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
+    frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
+    when ``n_wide`` is set, ``forward_quant_batch`` otherwise) and their entropy stage in another
+    (``SegmentedCoder.encode_ragged`` on the row-major integers). Device memory: the quantized matrices and the coders' buffers
+    of a whole chunk are alive together, about 8 N D bytes per frame beside its attributes (12 frames of 1 M x 59: 5.7 GB)."""
+    import torch
+    from . import ops
+    dev = torch.device(device)
+    J = int(J)
+    if not frames:
+        raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
+    if not 1 <= J <= MAX_J:
+        raise ValueError("encode_sequence_bytes: J outside 1 .. 21")
+    VA = []
+    for i, (V_int, attributes) in enumerate(frames):
+        V = torch.as_tensor(V_int).to(dev, torch.int64)
+        A = torch.as_tensor(attributes).to(dev, torch.float32)
+        if V.dim() != 2 or V.shape[1] != 3 or A.dim() != 2 or A.shape[0] != V.shape[0] or V.shape[0] < 1:
+            raise ValueError(f"encode_sequence_bytes: frame {i}: expected (N, 3) coordinates and (N, D) attributes, N >= 1")
+        if VA and A.shape[1] != VA[0][1].shape[1]:
+            raise ValueError(f"encode_sequence_bytes: frame {i} has {A.shape[1]} attribute columns, frame 0 has {VA[0][1].shape[1]}")
+        VA.append((V, A))
+    D = int(VA[0][1].shape[1])
+    n_wide = int(n_wide)
+    if not 0 <= n_wide <= D:
+        raise ValueError("encode_sequence_bytes: n_wide outside 0 .. D")
+    steps = _step_list(step, D)
+    parts = []                                                               # (the pieces of every frame: joined once, at the end)
+    with torch.cuda.device(dev):
+        for lo in range(0, len(VA), SEQ_CHUNK):
+            chunk = VA[lo: lo + SEQ_CHUNK]
+            geos, plans = [], []
+            for V, _ in chunk:
+                keys = ops.get_morton_code(V, J)
+                geos.append(OctreeCoder.encode(keys, J, entropy=geometry))    # (also refuses rows that are not sorted and unique)
+                plans.append(ops.RahtPlan.from_keys(keys, 3 * J))
+            As = [A for _, A in chunk]
+            if len(chunk) == 1:
+                Qs = [plans[0].forward_quant_mixed(As[0], steps, n_wide) if n_wide else plans[0].forward_quant(As[0], steps)]
+            else:
+                Qs = ops.forward_quant_mixed_batch(plans, As, steps, n_wide) if n_wide else ops.forward_quant_batch(plans, As, steps)
+            coders = [SegmentedCoder(A.shape[0], D, seg_len, 1, dev) for A in As]
+            # alone: a frame that needs 64-bit offsets (it fills the chip by itself) and a frame of exactly D voxels, whose square Q
+            # encode_frame_bytes hands to a coder that reads a square matrix as (D, N) -- the same call here, for the same bytes
+            alone = [c.wide or c.N == c.D for c in coders]
+            for c, Q, a in zip(coders, Qs, alone):
+                if a:
+                    c.encode(Q)
+            rest = [(c, Q) for c, Q, a in zip(coders, Qs, alone) if not a]
+            if rest:
+                SegmentedCoder.encode_ragged([c for c, _ in rest], [Q for _, Q in rest], row_major=True)
+            for (V, A), geo, c in zip(chunk, geos, coders):
+                hdr, lens, payload = c.container_parts()
+                parts.append(_frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, [hdr, lens.tobytes(), payload.tobytes()]))
+    return _pack_parts(parts)
+
+
+def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max_frames=None):
+    """-> [(V_int (N_i, 3) int64, C_rec (N_i, D) float32)] for the frame indices ``frames`` (default: all, in order), each what
+    ``decode_frame_bytes(sequence_frame(blob, i))`` returns, bit for bit. The geometry is decoded frame by frame; consecutive chosen
+    frames with the same (D, seg_len, n_wide, steps) share one entropy launch (``SegmentedCoder.decode_ragged``) and one set of
+    inverse transform launches (a frame of exactly D voxels goes alone). ``max_voxels`` per frame and ``max_frames`` are checked
+    before anything is allocated from the numbers of the blob. ``ValueError`` for a corrupt container; a corrupt frame is named by
+    its index -- for a header or an attribute length table that does not add up before any device work, for a corrupt geometry
+    section or a segment outside its payload when that frame's group is decoded."""
+    import torch
+    from . import ops
+    off = parse_sequence(blob, max_frames)
+    n = len(off) - 1
+    if frames is None:
+        frames = range(n)
+    try:
+        idx = [int(i) for i in frames]
+    except (TypeError, ValueError):
+        raise ValueError("decode_sequence_bytes: frames is a list of frame indices") from None
+    if any(not 0 <= i < n for i in idx):
+        raise ValueError(f"decode_sequence_bytes: frame indices must be in 0 .. {n - 1}")
+    dev = torch.device(device)
+    view = memoryview(blob)
+    heads = []
+    for i in idx:
+        fb = view[off[i]: off[i + 1]]
+        try:
+            h = parse_frame(fb, max_voxels)
+            ao, al = h["attributes"]
+            S = SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[2]
+        except ValueError as e:
+            raise ValueError(f"sequence container: frame {i}: {e}") from None
+        # (a frame of exactly D voxels is a group of its own: decode_frame_bytes reads its square matrix as the encoder wrote it)
+        heads.append((i, fb, h, (h["D"], S, h["n_wide"], tuple(h["steps"])) + ((len(heads),) if h["N"] == h["D"] else ())))
+    out = []
+    with torch.cuda.device(dev):
+        lo = 0
+        while lo < len(heads):
+            hi = lo + 1
+            while hi < len(heads) and hi - lo < SEQ_CHUNK and heads[hi][3] == heads[lo][3]:
+                hi += 1
+            group = heads[lo:hi]
+            lo = hi
+            if len(group) == 1:
+                i, fb, _, _ = group[0]
+                try:
+                    out.append(decode_frame_bytes(fb, dev, max_voxels))
+                except ValueError as e:
+                    raise ValueError(f"sequence container: frame {i}: {e}") from None
+                continue
+            Vs, plans, coders = [], [], []
+            for i, fb, h, _ in group:
+                (go, gl), (ao, al) = h["geometry"], h["attributes"]
+                try:
+                    keys = OctreeCoder.decode(fb[go: go + gl], dev, max_voxels)
+                    coders.append(SegmentedCoder.from_container(fb[ao: ao + al], dev, max_symbols=h["N"] * h["D"]))
+                except ValueError as e:
+                    raise ValueError(f"sequence container: frame {i}: {e}") from None
+                Vs.append(ops.demorton(keys, h["J"]))
+                plans.append(ops.RahtPlan.from_keys(keys, 3 * h["J"]))
+            _, _, n_wide, steps = group[0][3][:4]
+            steps = list(steps)
+            if any(c.wide for c in coders):                              # (64-bit offsets: such a frame goes alone)
+                Qs = [c.decode(row_major=True) for c in coders]
+                bad = [j for j, c in enumerate(coders) if int(c.bad.item()) != 0]
+            else:
+                Qs = SegmentedCoder.decode_ragged(coders, row_major=True)
+                bad = None
+            Cs = ops.dequant_inverse_mixed_batch(plans, Qs, steps, n_wide) if n_wide else ops.dequant_inverse_batch(plans, Qs, steps)
+            if bad is None:
+                bad = SegmentedCoder.roundtrip_failed(coders)
+            if bad:
+                raise ValueError(f"sequence container: frame {group[bad[0]][0]}: frame container: an attribute segment reaches outside its payload")
+            out += list(zip(Vs, Cs))
+    return out

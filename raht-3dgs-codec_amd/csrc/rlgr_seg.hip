@@ -493,12 +493,16 @@ __device__ __forceinline__ void zero_segment(int32_t *__restrict__ seq, int n, i
     for (int i = 0; i < n; ++i, seq += sstr) *seq = 0;
 }
 
-// ---- k frames of ONE shape in one set of launches (blockIdx.y = frame) ----------------------------------------------
+// ---- k frames in one set of launches (blockIdx.y = frame) ------------------------------------------------------------
 // What bounds the coders is the number of independent lanes: one frame (3 M x 56 at 2048 symbols per segment) is 1.25 waves
 // per SIMD, and a wave that is alone on its SIMD waits out the latency of every one of its ~480 k dependent instructions.
 // The quantization steps of a frame (python/encode_3dgs.py:199-275: nine of them) are nine such frames of the same shape with
 // nothing between them: coded by ONE launch they fill every wave slot of the chip. Each frame keeps its own tables and
 // container. The one-frame entry points are k = 1 of the same kernels: the bytes of a frame cannot depend on its company.
+// The frames of a SEQUENCE (a different voxel count in every frame, D and seg_len shared) go the same way: the job tables below
+// are the only place where a kernel learns a frame's shape -- N, nseg and the strides are per frame, the grid is as wide as the
+// largest frame needs and a lane past the end of ITS frame leaves through SegLane::init, as the lanes of a last, partial
+// workgroup always did. The frames of one shape are the ragged launch with N[j] = N: there is no instantiation of their own.
 // K: the entries of the job table a kernel is built for. RAHT_RLGR_BATCH_MAX: a batch. 1: the one-frame entry points' own instantiation
 // -- no blockIdx.y, a table of one entry and, in the decoder, neither the comparison with expect[] nor the stream words' way
 // through LDS: a lone wave per SIMD pays for every instruction on its chain (measured with the batch instantiation on one 3 M x 56
@@ -507,12 +511,17 @@ template <typename OffT, int K>
 struct SegEncJobs {
     const int32_t *Q[K]; uint32_t *seg_bytes[K]; OffT *seg_off[K]; uint8_t *out[K];
     uint64_t cap[K];
+    int64_t N[K], sym_stride[K], chan_stride[K];
+    int64_t slot0[K];                            // the frame's first slot of the scratch (and entry of `padded`): G of the frames before it
+    int nseg[K];
 };
 template <typename OffT, int K>
 struct SegDecJobs {
     const uint8_t *in[K]; uint64_t in_bytes[K]; const OffT *seg_off[K]; const uint32_t *seg_bytes[K];
     int32_t *Q[K];
     const int32_t *expect[K];                    // (may be NULL) what Q[j] should become: compared inside the row-major decoder (K > 1)
+    int64_t N[K], sym_stride[K], chan_stride[K];
+    int nseg[K];
 };
 template <int K> __device__ __forceinline__ int seg_frame() { return K == 1 ? 0 : (int)blockIdx.y; }
 
@@ -521,8 +530,8 @@ template <int K> __device__ __forceinline__ int seg_frame() { return K == 1 ? 0 
 // falls back to the two exact passes. flags: SegFlags<OffT>::WORDS words per frame (overflow bits, container bytes).
 // LDSOUT: the streams' words leave through LDS columns (DevBitWriter; the host's choice: encode_lds_out).
 template <typename OffT, int K, bool LDSOUT>
-__global__ __launch_bounds__(64) void seg_encode_slots_kernel(const SegEncJobs<OffT, K> J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int S, int nseg,
-                                                              int flag_signed, uint8_t *__restrict__ slots, uint32_t slot, uint32_t *__restrict__ flags)
+__global__ __launch_bounds__(64) void seg_encode_slots_kernel(const SegEncJobs<OffT, K> J, int D, int S, int flag_signed, uint8_t *__restrict__ slots, uint32_t slot,
+                                                              uint32_t *__restrict__ flags)
 {
     uint32_t *col = nullptr;
     if constexpr (LDSOUT) {
@@ -530,11 +539,12 @@ __global__ __launch_bounds__(64) void seg_encode_slots_kernel(const SegEncJobs<O
         col = s_col;
     }
     const int j = seg_frame<K>();
+    const int64_t sym_stride = J.sym_stride[j], chan_stride = J.chan_stride[j];
     SegLane ln;
-    if (!ln.init(N, D, S, nseg, sym_stride != 1)) return;
+    if (!ln.init(J.N[j], D, S, J.nseg[j], sym_stride != 1)) return;
     const int32_t *Q = J.Q[j];
     const int32_t *seq = Q + ln.at(sym_stride, chan_stride);
-    uint32_t *o = (uint32_t *)(slots + ((size_t)j * (size_t)D * (size_t)nseg + (size_t)ln.g) * slot);
+    uint32_t *o = (uint32_t *)(slots + ((size_t)J.slot0[j] + (size_t)ln.g) * slot);
     const uint32_t nb = seg_aligned16(Q, sym_stride, chan_stride, S) ? encode_segment<true, true, LDSOUT>(seq, ln.n, flag_signed, o, slot, 1, col)
                                                                      : encode_segment<true, false, LDSOUT>(seq, ln.n, flag_signed, o, slot, sym_stride, col);
     J.seg_bytes[j][ln.g] = nb;
@@ -543,20 +553,21 @@ __global__ __launch_bounds__(64) void seg_encode_slots_kernel(const SegEncJobs<O
 
 // padded size of every segment (its place in the container): the input of the offset scan
 template <typename OffT, int K>
-__global__ void seg_pad_kernel(const SegEncJobs<OffT, K> J, int64_t G, uint32_t *__restrict__ padded)
+__global__ void seg_pad_kernel(const SegEncJobs<OffT, K> J, int D, uint32_t *__restrict__ padded)
 {
     const int j = seg_frame<K>();
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < G) padded[(size_t)j * (size_t)G + g] = (J.seg_bytes[j][g] + 3u) & ~3u;
+    if (g < (int64_t)D * J.nseg[j]) padded[(size_t)J.slot0[j] + g] = (J.seg_bytes[j][g] + 3u) & ~3u;
 }
 
 // one wave per segment: its words from the slot to its offset in the container
 // (also closes every frame's offset table: seg_off[G] = its container's bytes, left in the frame's flag words by the scan)
 template <typename OffT, int K>
-__global__ __launch_bounds__(256) void seg_compact_kernel(const SegEncJobs<OffT, K> J, const uint8_t *__restrict__ slots, uint32_t slot, int64_t G,
+__global__ __launch_bounds__(256) void seg_compact_kernel(const SegEncJobs<OffT, K> J, const uint8_t *__restrict__ slots, uint32_t slot, int D,
                                                           uint32_t *__restrict__ flags)
 {
     const int j = seg_frame<K>();
+    const int64_t G = (int64_t)D * J.nseg[j];
     const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (blockIdx.x == 0 && threadIdx.x == 0) J.seg_off[j][G] = *SegFlags<OffT>::total(flags, j);
@@ -565,20 +576,21 @@ __global__ __launch_bounds__(256) void seg_compact_kernel(const SegEncJobs<OffT,
     if (4ull * nw > slot) return;                                     // it outgrew its slot (the encoder raised the flag): nothing of it is there
     const uint64_t off = J.seg_off[j][g];
     if (off + 4ull * nw > J.cap[j]) { if (lane == 0) atomicOr(flags + SegFlags<OffT>::WORDS * j, 2u); return; }
-    const uint32_t *src = (const uint32_t *)(slots + ((size_t)j * (size_t)G + (size_t)g) * slot);
+    const uint32_t *src = (const uint32_t *)(slots + ((size_t)J.slot0[j] + (size_t)g) * slot);
     uint32_t *dst = (uint32_t *)(J.out[j] + off);
     for (uint32_t i = lane; i < nw; i += 64) dst[i] = src[i];
 }
 
 // bad: bit j when a table entry of frame j reached outside in[j]; bit 16 + j when a symbol of frame j differs from expect[j]
 template <typename OffT, int K>
-__global__ __launch_bounds__(64) void seg_decode_kernel(const SegDecJobs<OffT, K> J, int64_t N, int D, int S, int nseg, int flag_signed, int64_t sym_stride,
-                                                        int64_t chan_stride, uint32_t *__restrict__ bad, int out_mode, int sync_rows)
+__global__ __launch_bounds__(64) void seg_decode_kernel(const SegDecJobs<OffT, K> J, int D, int S, int flag_signed, uint32_t *__restrict__ bad, int out_mode,
+                                                        int sync_rows)
 {
     __shared__ int32_t s_col[DEC_LDS_WORDS];
     const int j = seg_frame<K>();
+    const int64_t sym_stride = J.sym_stride[j], chan_stride = J.chan_stride[j];
     SegLane ln;
-    if (!ln.init(N, D, S, nseg, sym_stride != 1)) return;
+    if (!ln.init(J.N[j], D, S, J.nseg[j], sym_stride != 1)) return;
     const uint64_t off = J.seg_off[j][ln.g], in_bytes = J.in_bytes[j];
     const uint32_t nb = J.seg_bytes[j][ln.g];
     const int64_t at = ln.at(sym_stride, chan_stride);
@@ -654,14 +666,41 @@ int seg_shape(const char *fn, int64_t N, int D, int seg_len, int64_t *nseg, int6
     return RAHT_OK;
 }
 
+// What the host knows of the k frames of a call: every frame's shape, and where its slots begin (the running sum of G)
+struct SegFrames {
+    int k = 0;
+    int64_t N[RAHT_RLGR_BATCH_MAX], sym_stride[RAHT_RLGR_BATCH_MAX], chan_stride[RAHT_RLGR_BATCH_MAX];
+    int64_t nseg[RAHT_RLGR_BATCH_MAX], G[RAHT_RLGR_BATCH_MAX], slot0[RAHT_RLGR_BATCH_MAX];
+    int64_t sumG = 0, maxG = 0;
+
+    void add(int64_t n, int D, int64_t sym, int64_t chan, int seg_len)          // (k < RAHT_RLGR_BATCH_MAX; n, D >= 1: checked by the caller)
+    {
+        N[k] = n; sym_stride[k] = sym; chan_stride[k] = chan;
+        nseg[k] = (n - 1) / seg_len + 1;
+        G[k] = nseg[k] < ((int64_t)1 << 31) ? nseg[k] * D : (int64_t)1 << 31;
+        slot0[k] = sumG;
+        sumG += G[k];
+        maxG = G[k] > maxG ? G[k] : maxG;
+        ++k;
+    }
+    // the shape of frame j < K into a job table (the entries behind k repeat frame 0: no kernel reads them)
+    template <typename Jobs> void fill(Jobs &J, int j) const
+    {
+        const int q = j < k ? j : 0;
+        J.N[j] = N[q]; J.sym_stride[j] = sym_stride[q]; J.chan_stride[j] = chan_stride[q]; J.nseg[j] = (int)nseg[q];
+    }
+};
+
 // the kernels' view of k <= K frames (the entries behind k repeat frame 0: no kernel reads them)
 template <typename OffT, int K>
-rlgr_seg::SegEncJobs<OffT, K> enc_jobs(int k, const int32_t *const *Q, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap)
+rlgr_seg::SegEncJobs<OffT, K> enc_jobs(const SegFrames &F, const int32_t *const *Q, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap)
 {
     rlgr_seg::SegEncJobs<OffT, K> J;
     for (int j = 0; j < K; ++j) {
-        const int q = j < k ? j : 0;
+        const int q = j < F.k ? j : 0;
         J.Q[j] = Q[q]; J.seg_bytes[j] = seg_bytes[q]; J.seg_off[j] = seg_off[q]; J.out[j] = out[q]; J.cap[j] = (uint64_t)cap[q];
+        J.slot0[j] = F.slot0[q];
+        F.fill(J, j);
     }
     return J;
 }
@@ -670,35 +709,35 @@ rlgr_seg::SegEncJobs<OffT, K> enc_jobs(int k, const int32_t *const *Q, uint32_t 
 // 16-byte aligned starts; 64: whole pieces). Fits: raht_rlgr_bound(seg_len) < 2^32.
 inline uint32_t slot_bytes(int seg_len, bool lds_out) { return lds_out ? (4u * (uint32_t)seg_len + 16u + 63u) & ~63u : 4u * (uint32_t)seg_len + 16u; }
 
-// The slots pass over the k frames of J: every segment into its slot, the padded sizes, one offset scan per frame, the compaction
-// (which closes the frames' tables), the flag words back (synchronises: the scratch may go back to the pool).
+// The slots pass over the frames of J / F: every segment into its slot, the padded sizes, one offset scan per frame, the compaction
+// (which closes the frames' tables), the flag words back (synchronises: the scratch may go back to the pool). The grid is as wide
+// as the largest frame; the lanes in flight -- which decide between words and LDS columns -- are those of all frames together.
 //   RAHT_OK              total_bytes[] are set and the containers written
 //   RAHT_ERR_NOMEM       total_bytes[] are set and some container is too small (the text names the frame when name_frame)
-//   RAHT_ERR_UNSUPPORTED a segment outgrew its slot (incompressible data), or there is no scratch for k sets of slots: nothing
+//   RAHT_ERR_UNSUPPORTED a segment outgrew its slot (incompressible data), or there is no scratch for the slots: nothing
 //                        useful was written and the caller runs the two exact passes
 template <typename OffT, int K>
-int seg_encode_slots(const char *fn, bool name_frame, int k, const rlgr_seg::SegEncJobs<OffT, K> &J, int64_t N, int D, int64_t sym_stride, int64_t chan_stride,
-                     int seg_len, int64_t nseg, int64_t G, int flag_signed, int64_t *total_bytes, hipStream_t s)
+int seg_encode_slots(const char *fn, bool name_frame, const rlgr_seg::SegEncJobs<OffT, K> &J, const SegFrames &F, int D, int seg_len, int flag_signed,
+                     int64_t *total_bytes, hipStream_t s)
 {
     constexpr int FW = SegFlags<OffT>::WORDS;
-    const bool lds_out = rlgr_seg::encode_lds_out((int64_t)k * G);
+    const int k = F.k;
+    const bool lds_out = rlgr_seg::encode_lds_out(F.sumG);
     const uint32_t slot = slot_bytes(seg_len, lds_out);
-    const size_t npad = ((size_t)k * (size_t)G + 1) & ~(size_t)1;           // (the flag words behind it stay 8-byte aligned)
+    const size_t npad = ((size_t)F.sumG + 1) & ~(size_t)1;                  // (the flag words behind it stay 8-byte aligned)
     Scratch tmp(sizeof(uint32_t) * (npad + FW * (size_t)k), s);
-    Scratch slots((size_t)k * (size_t)G * slot, s);
+    Scratch slots((size_t)F.sumG * slot, s);
     if (!tmp.ok() || !slots.ok()) { (void)hipGetLastError(); return RAHT_ERR_UNSUPPORTED; }
     uint32_t *padded = tmp.as<uint32_t>(), *flags = padded + npad;
     RAHT_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * FW * (size_t)k, s));
-    const dim3 lanes((unsigned)ceil_div(G, 64), (unsigned)k);
+    const dim3 lanes((unsigned)ceil_div(F.maxG, 64), (unsigned)k);
     if (lds_out)
-        hipLaunchKernelGGL((rlgr_seg::seg_encode_slots_kernel<OffT, K, true>), lanes, dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
-                           slots.as<uint8_t>(), slot, flags);
+        hipLaunchKernelGGL((rlgr_seg::seg_encode_slots_kernel<OffT, K, true>), lanes, dim3(64), 0, s, J, D, seg_len, flag_signed, slots.as<uint8_t>(), slot, flags);
     else
-        hipLaunchKernelGGL((rlgr_seg::seg_encode_slots_kernel<OffT, K, false>), lanes, dim3(64), 0, s, J, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
-                           slots.as<uint8_t>(), slot, flags);
-    hipLaunchKernelGGL((rlgr_seg::seg_pad_kernel<OffT, K>), dim3((unsigned)ceil_div(G, 256), (unsigned)k), dim3(256), 0, s, J, G, padded);
-    for (int j = 0; j < k; ++j) RAHT_RET(scan_offsets<OffT>(padded + (size_t)j * (size_t)G, J.seg_off[j], G, SegFlags<OffT>::total(flags, j), s));
-    hipLaunchKernelGGL((rlgr_seg::seg_compact_kernel<OffT, K>), dim3((unsigned)ceil_div(G * 64, 256), (unsigned)k), dim3(256), 0, s, J, (const uint8_t *)slots.as<uint8_t>(), slot, G, flags);
+        hipLaunchKernelGGL((rlgr_seg::seg_encode_slots_kernel<OffT, K, false>), lanes, dim3(64), 0, s, J, D, seg_len, flag_signed, slots.as<uint8_t>(), slot, flags);
+    hipLaunchKernelGGL((rlgr_seg::seg_pad_kernel<OffT, K>), dim3((unsigned)ceil_div(F.maxG, 256), (unsigned)k), dim3(256), 0, s, J, D, padded);
+    for (int j = 0; j < k; ++j) RAHT_RET(scan_offsets<OffT>(padded + (size_t)F.slot0[j], J.seg_off[j], F.G[j], SegFlags<OffT>::total(flags, j), s));
+    hipLaunchKernelGGL((rlgr_seg::seg_compact_kernel<OffT, K>), dim3((unsigned)ceil_div(F.maxG * 64, 256), (unsigned)k), dim3(256), 0, s, J, (const uint8_t *)slots.as<uint8_t>(), slot, D, flags);
     RAHT_HIP_CHECK(hipGetLastError());
     uint32_t back[FW * K] = {0};
     RAHT_RET(read_back_u32(back, flags, FW * k, nullptr, nullptr, 0, s));
@@ -733,11 +772,13 @@ int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t 
     hipStream_t s = (hipStream_t)stream;
     constexpr int FW = SegFlags<OffT>::WORDS;
     return guarded(fn, [&]() -> int {
-        const rlgr_seg::SegEncJobs<OffT, 1> J = enc_jobs<OffT, 1>(1, &Q, &seg_bytes, &seg_off, &out, &cap);
+        SegFrames F;
+        F.add(N, D, sym_stride, chan_stride, seg_len);
+        const rlgr_seg::SegEncJobs<OffT, 1> J = enc_jobs<OffT, 1>(F, &Q, &seg_bytes, &seg_off, &out, &cap);
         // ONE encoding pass into fixed slots + a compaction, when a scratch buffer of the raw size is to be had; the two exact
         // passes (sizes, then streams) otherwise, and whenever a segment outgrows its slot
         if ((uint64_t)G * slot_bytes(seg_len, rlgr_seg::encode_lds_out(G)) < ((uint64_t)1 << 33)) {
-            const int rc = seg_encode_slots<OffT, 1>(fn, false, 1, J, N, D, sym_stride, chan_stride, seg_len, nseg, G, flag_signed, total_bytes, s);
+            const int rc = seg_encode_slots<OffT, 1>(fn, false, J, F, D, seg_len, flag_signed, total_bytes, s);
             if (rc != RAHT_ERR_UNSUPPORTED) return rc;
         }
         const size_t npad = ((size_t)G + 1) & ~(size_t)1;                   // (the flag words behind it stay 8-byte aligned)
@@ -749,7 +790,7 @@ int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t 
         const unsigned gb = (unsigned)ceil_div(G, 64);
         hipLaunchKernelGGL((rlgr_seg::seg_encode_kernel<false, OffT>), dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
                            seg_bytes, (const OffT *)nullptr, (uint8_t *)nullptr, (uint64_t)0, flags);
-        hipLaunchKernelGGL((rlgr_seg::seg_pad_kernel<OffT, 1>), dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, J, G, padded);
+        hipLaunchKernelGGL((rlgr_seg::seg_pad_kernel<OffT, 1>), dim3((unsigned)ceil_div(G, 256)), dim3(256), 0, s, J, D, padded);
         RAHT_RET(scan_offsets<OffT>(padded, seg_off, G, dtotal, s));
         RAHT_HIP_CHECK(hipMemcpyAsync(seg_off + G, dtotal, sizeof(OffT), hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL((rlgr_seg::seg_encode_kernel<true, OffT>), dim3(gb), dim3(64), 0, s, Q, N, D, sym_stride, chan_stride, seg_len, (int)nseg, flag_signed,
@@ -764,20 +805,20 @@ int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t 
     });
 }
 
-// one launch for k <= K frames whose arguments have been checked
+// one launch for the k <= K frames of F, whose arguments have been checked
 template <typename OffT, int K>
-int seg_decode_launch(int k, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes, int64_t N, int D,
-                      int seg_len, int64_t nseg, int64_t G, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
-                      int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
+int seg_decode_launch(const SegFrames &F, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes, int D,
+                      int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, uint32_t *bad_dev, raht_stream_t stream)
 {
     rlgr_seg::SegDecJobs<OffT, K> J;
     for (int j = 0; j < K; ++j) {
-        const int q = j < k ? j : 0;
+        const int q = j < F.k ? j : 0;
         J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
         J.expect[j] = expect ? expect[q] : nullptr;
+        F.fill(J, j);
     }
-    hipLaunchKernelGGL((rlgr_seg::seg_decode_kernel<OffT, K>), dim3((unsigned)ceil_div(G, 64), (unsigned)k), dim3(64), 0, (hipStream_t)stream, J, N, D, seg_len, (int)nseg,
-                       flag_signed, sym_stride, chan_stride, bad_dev, rlgr_seg::decode_out_mode((int64_t)k * G), (int)rlgr_seg::decode_sync_rows());
+    hipLaunchKernelGGL((rlgr_seg::seg_decode_kernel<OffT, K>), dim3((unsigned)ceil_div(F.maxG, 64), (unsigned)F.k), dim3(64), 0, (hipStream_t)stream, J, D, seg_len,
+                       flag_signed, bad_dev, rlgr_seg::decode_out_mode(F.sumG), (int)rlgr_seg::decode_sync_rows());
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }
@@ -791,12 +832,37 @@ int seg_decode_impl(const char *fn, const uint8_t *in, int64_t in_bytes, const O
         set_error("%s: bad argument", fn);
         return RAHT_ERR_INVALID;
     }
-    const int64_t nseg = (N - 1) / seg_len + 1, G = nseg < ((int64_t)1 << 31) ? nseg * D : (int64_t)1 << 31;
-    if (G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    return seg_decode_launch<OffT, 1>(1, &in, &in_bytes, &seg_off, &seg_bytes, N, D, seg_len, nseg, G, flag_signed, &Q, nullptr, sym_stride, chan_stride, bad_dev, stream);
+    SegFrames F;
+    F.add(N, D, sym_stride, chan_stride, seg_len);
+    if (F.maxG >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
+    return seg_decode_launch<OffT, 1>(F, &in, &in_bytes, &seg_off, &seg_bytes, D, seg_len, flag_signed, &Q, nullptr, bad_dev, stream);
 }
 
+// The frames of F (arguments checked) through the encoder: one set of launches, or frame by frame -- a lone frame (its own
+// instantiation, its checks and its texts) and whenever the slots pass gives up.
 // fn: the batch entry point's name; fn1: the one-frame entry point of the same width (the frame-by-frame fallback reports as it)
+template <typename OffT>
+int seg_encode_frames(const char *fn, const char *fn1, const SegFrames &F, const int32_t *const *Q, int D, int seg_len, int flag_signed, uint32_t *const *seg_bytes,
+                      OffT *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes, raht_stream_t stream)
+{
+    int rc = RAHT_ERR_UNSUPPORTED;
+    if (F.k > 1)
+        rc = guarded(fn, [&]() -> int {
+            return seg_encode_slots<OffT, RAHT_RLGR_BATCH_MAX>(fn, true, enc_jobs<OffT, RAHT_RLGR_BATCH_MAX>(F, Q, seg_bytes, seg_off, out, cap), F, D, seg_len, flag_signed,
+                                                              total_bytes, (hipStream_t)stream);
+        });
+    if (rc != RAHT_ERR_UNSUPPORTED) return rc;
+    int rc_all = RAHT_OK;                                                   // frame by frame
+    for (int j = 0; j < F.k; ++j) {
+        rc = seg_encode_impl<OffT>(fn1, Q[j], F.N[j], D, F.sym_stride[j], F.chan_stride[j], seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j],
+                                   stream);
+        if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
+        if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
+    }
+    return rc_all;
+}
+
+// k frames of ONE shape: the ragged launch with N[j] = N
 template <typename OffT>
 int seg_encode_batch_impl(const char *fn, const char *fn1, int k, const int32_t *const *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len,
                           int flag_signed, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
@@ -815,21 +881,9 @@ int seg_encode_batch_impl(const char *fn, const char *fn1, int k, const int32_t 
         if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
     int64_t nseg, G;
     RAHT_RET(seg_shape<OffT>(fn, N, D, seg_len, &nseg, &G));
-    // (k = 1 goes the one-frame way as well: its checks and its texts)
-    int rc = RAHT_ERR_UNSUPPORTED;
-    if (k > 1)
-        rc = guarded(fn, [&]() -> int {
-            return seg_encode_slots<OffT, RAHT_RLGR_BATCH_MAX>(fn, true, k, enc_jobs<OffT, RAHT_RLGR_BATCH_MAX>(k, Q, seg_bytes, seg_off, out, cap), N, D, sym_stride, chan_stride, seg_len, nseg, G, flag_signed,
-                                          total_bytes, (hipStream_t)stream);
-        });
-    if (rc != RAHT_ERR_UNSUPPORTED) return rc;
-    int rc_all = RAHT_OK;                                                   // frame by frame
-    for (int j = 0; j < k; ++j) {
-        rc = seg_encode_impl<OffT>(fn1, Q[j], N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j], stream);
-        if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
-        if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
-    }
-    return rc_all;
+    SegFrames F;
+    for (int j = 0; j < k; ++j) F.add(N, D, sym_stride, chan_stride, seg_len);
+    return seg_encode_frames<OffT>(fn, fn1, F, Q, D, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
 }
 
 template <typename OffT>
@@ -847,9 +901,41 @@ int seg_decode_batch_impl(const char *fn, int k, const uint8_t *const *in, const
             set_error("%s: bad argument (frame %d)", fn, j);
             return RAHT_ERR_INVALID;
         }
-    const int64_t nseg = (N - 1) / seg_len + 1, G = nseg < ((int64_t)1 << 31) ? nseg * D : (int64_t)1 << 31;
-    if (G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    return seg_decode_launch<OffT, RAHT_RLGR_BATCH_MAX>(k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, nseg, G, flag_signed, Q, expect, sym_stride, chan_stride, bad_dev, stream);
+    SegFrames F;
+    for (int j = 0; j < k; ++j) F.add(N, D, sym_stride, chan_stride, seg_len);
+    if (F.maxG >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
+    return seg_decode_launch<OffT, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, expect, bad_dev, stream);
+}
+
+// The shapes of a ragged call -> F. Shared D and seg_len; per frame N and strides, all frames of one layout kind, each within
+// the 32-bit offset tables (a frame that is not fills the chip alone: the one-frame *64 entry points take it).
+int ragged_frames(const char *fn, int k, const int64_t *N, int D, const int64_t *sym_stride, const int64_t *chan_stride, int seg_len, SegFrames *F)
+{
+    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !N || !sym_stride || !chan_stride || D < 1 || seg_len < 64) {
+        set_error("%s: bad argument (1 <= k <= %d, D >= 1, seg_len >= 64)", fn, RAHT_RLGR_BATCH_MAX);
+        return RAHT_ERR_INVALID;
+    }
+    bool all_cm = true, all_rm = true;
+    for (int j = 0; j < k; ++j) {
+        const bool cm = N[j] >= 1 && sym_stride[j] == 1 && chan_stride[j] >= N[j], rm = N[j] >= 1 && chan_stride[j] == 1 && sym_stride[j] >= D;
+        if (!cm && !rm) {
+            set_error("%s: bad argument (frame %d: N >= 1; channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn, j);
+            return RAHT_ERR_INVALID;
+        }
+        all_cm = all_cm && cm;
+        all_rm = all_rm && rm;
+    }
+    if (!all_cm && !all_rm) { set_error("%s: the frames of a call are all channel-major or all row-major", fn); return RAHT_ERR_INVALID; }
+    for (int j = 0; j < k; ++j) {
+        const int width = raht_rlgr_seg_offsets_width(N[j], D, seg_len);
+        if (width != 32) {
+            if (width == 64) set_error("%s: frame %d: %lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): code it alone, with 64-bit offsets", fn, j, (long long)N[j], D);
+            else set_error("%s: frame %d: no entry point takes %lld x %d symbols at seg_len = %d", fn, j, (long long)N[j], D, seg_len);
+            return RAHT_ERR_INVALID;
+        }
+        F->add(N[j], D, sym_stride[j], chan_stride[j], seg_len);
+    }
+    return RAHT_OK;
 }
 
 }  // namespace
@@ -994,6 +1080,48 @@ int raht_rlgr_seg_decode_batch64(int k, const uint8_t *const *in, const int64_t 
     }
     return seg_decode_batch_impl<uint64_t>("raht_rlgr_seg_decode_batch64", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, expect, sym_stride, chan_stride,
                                            bad_dev, stream);
+}
+
+/* k frames of k SHAPES in one set of launches: the frames of a sequence. D, seg_len and flag_signed are shared; N[j] and the two
+ * strides are per frame (all frames channel-major or all row-major, each within the rules of raht_rlgr_seg_encode_strided);
+ * 32-bit offset tables only: a frame raht_rlgr_seg_offsets_width does not call 32 is refused (RAHT_ERR_INVALID, the text names
+ * it). Every frame gets exactly the bytes, seg_bytes, seg_off and total_bytes[j] raht_rlgr_seg_encode_strided leaves for it
+ * alone. Synchronises; RAHT_ERR_NOMEM when some cap[j] is too small (total_bytes[] holds what every frame needs). */
+int raht_rlgr_seg_encode_ragged(int k, const int32_t *const *Q, const int64_t *N, int D, const int64_t *sym_stride, const int64_t *chan_stride, int seg_len,
+                                int flag_signed, uint32_t *const *seg_bytes, uint32_t *const *seg_off, uint8_t *const *out, const int64_t *cap,
+                                int64_t *total_bytes, raht_stream_t stream)
+{
+    const char *fn = "raht_rlgr_seg_encode_ragged";
+    if (!Q || !seg_bytes || !seg_off || !out || !cap || !total_bytes) { set_error("%s: bad argument (a table is NULL)", fn); return RAHT_ERR_INVALID; }
+    SegFrames F;
+    RAHT_RET(ragged_frames(fn, k, N, D, sym_stride, chan_stride, seg_len, &F));
+    for (int j = 0; j < k; ++j)
+        if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
+    return seg_encode_frames<uint32_t>(fn, "raht_rlgr_seg_encode", F, Q, D, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
+}
+
+/* The inverse, one launch, no synchronisation. *bad_dev (DEVICE uint32; may be NULL without expect): bit j when a table entry of
+ * frame j reached outside in[j] (that segment decodes as zeros); with expect (may be NULL; ROW-MAJOR frames only, every
+ * expect[j] set, in the layout and strides of Q[j]) bit 16 + j when frame j differs from expect[j]. */
+int raht_rlgr_seg_decode_ragged(int k, const uint8_t *const *in, const int64_t *in_bytes, const uint32_t *const *seg_off, const uint32_t *const *seg_bytes,
+                                const int64_t *N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect,
+                                const int64_t *sym_stride, const int64_t *chan_stride, uint32_t *bad_dev, raht_stream_t stream)
+{
+    const char *fn = "raht_rlgr_seg_decode_ragged";
+    if (!in || !in_bytes || !seg_off || !seg_bytes || !Q) { set_error("%s: bad argument (a table is NULL)", fn); return RAHT_ERR_INVALID; }
+    SegFrames F;
+    RAHT_RET(ragged_frames(fn, k, N, D, sym_stride, chan_stride, seg_len, &F));
+    for (int j = 0; j < k; ++j) {
+        if (!in[j] || in_bytes[j] < 0 || (in_bytes[j] & 3) || ((uintptr_t)in[j] & 3) || !seg_off[j] || !seg_bytes[j] || !Q[j]) {
+            set_error("%s: bad argument (frame %d)", fn, j);
+            return RAHT_ERR_INVALID;
+        }
+        if (expect && (!bad_dev || chan_stride[j] != 1 || sym_stride[j] < D || !expect[j])) {
+            set_error("%s: expect[] needs bad_dev, row-major frames (chan_stride 1) and every expect[j] (frame %d)", fn, j);
+            return RAHT_ERR_INVALID;
+        }
+    }
+    return seg_decode_launch<uint32_t, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, expect, bad_dev, stream);
 }
 
 }  // extern "C"

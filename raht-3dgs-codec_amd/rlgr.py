@@ -457,6 +457,109 @@ class SegmentedCoder:
                     check((L.raht_rlgr_seg_decode_batch64 if c0.wide else L.raht_rlgr_seg_decode_batch_check)(*args, VP(*[e.data_ptr() for e in ex]), sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
         return outs
 
+    @staticmethod
+    def _same_kind(coders, what):
+        """the coders of a ragged call: everything of ``_same_shape`` but N, and 32-bit offsets"""
+        c0 = coders[0]
+        for c in coders:
+            if (c.D, c.S, c.flag, c.device) != (c0.D, c0.S, c0.flag, c0.device):
+                raise ValueError(f"SegmentedCoder.{what}: the coders of a ragged batch share D, seg_len, flag and device")
+            if c.wide:
+                raise ValueError(f"SegmentedCoder.{what}: a ragged batch takes 32-bit offset tables only (a {c.N} x {c.D} frame goes alone)")
+        return c0
+
+    @staticmethod
+    def _one_layout(coders, mats, what, row_major=None):
+        """[(sym_stride, chan_stride)] of the matrices of a ragged call, all (N_j, D) row-major or all (D, N_j) channel-major.
+        ``row_major`` True / False SAYS which; None reads it off the shapes, and a SQUARE matrix (N_j == D) is then channel-major,
+        whatever its company: that is how ``_strides`` -- ``encode`` / ``decode`` of that coder alone -- reads it, and the bytes of a
+        frame cannot depend on the other frames of the call. A square matrix among row-major ones therefore needs
+        ``row_major=True``."""
+        if len(mats) != len(coders):
+            raise ValueError(f"SegmentedCoder.{what}: one matrix per coder")
+        for c, m in zip(coders, mats):
+            c._strides(m, what)                                   # (dtype, device, shape)
+        rows = [tuple(m.shape) == (c.N, c.D) and (c.N == 1 or m.stride(0) >= c.D) for c, m in zip(coders, mats)]
+        chans = [tuple(m.shape) == (c.D, c.N) and (c.D == 1 or m.stride(0) >= c.N) for c, m in zip(coders, mats)]
+        if row_major is None:
+            rows = [r and c.N != c.D for r, c in zip(rows, coders)]
+        if all(rows) and row_major is not False:
+            return [(m.stride(0) if c.N > 1 else c.D, 1) for c, m in zip(coders, mats)]
+        if all(chans) and not row_major:
+            return [(1, m.stride(0) if c.D > 1 else c.N) for c, m in zip(coders, mats)]
+        if row_major is None and any(c.N == c.D for c in coders):
+            raise ValueError(f"SegmentedCoder.{what}: a square matrix (N == D) is read as (D, N) channel-major, as encode / decode of one "
+                             "frame read it; among (N, D) row-major matrices say row_major=True")
+        raise ValueError(f"SegmentedCoder.{what}: the matrices of a ragged batch are all (N, D) row-major or all (D, N) channel-major")
+
+    @classmethod
+    def encode_ragged(cls, coders, Qs, row_major=None):
+        """The frames of a sequence coded together (raht_rlgr_seg_encode_ragged): ``coders[j].encode(Qs[j])`` for every j in ONE set
+        of launches, for coders that share D, seg_len, flag, device and 32-bit offsets and differ in N. Same containers, byte for
+        byte. All Qs row-major (N_j, D) or all channel-major (D, N_j); strides may differ. ``row_major``: None reads the layout off
+        the shapes, with a square Q (N_j == D) channel-major as ``encode`` reads it; True / False say it (``_one_layout``).
+        -> list of container payload sizes (synchronises)."""
+        import torch
+        if len(coders) != len(Qs) or not coders:
+            raise ValueError("SegmentedCoder.encode_ragged: one input per coder")
+        c0 = cls._same_kind(coders, "encode_ragged")
+        st = cls._one_layout(coders, Qs, "encode_ragged", row_major)
+        fn = _lib.lib().raht_rlgr_seg_encode_ragged
+        for lo in range(0, len(coders), cls.BATCH_MAX):
+            cs, qs, ss = coders[lo: lo + cls.BATCH_MAX], Qs[lo: lo + cls.BATCH_MAX], st[lo: lo + cls.BATCH_MAX]
+            k = len(cs)
+            VP, I64 = C.c_void_p * k, C.c_int64 * k
+            tot = I64()
+            for attempt in (0, 1):
+                with torch.cuda.device(c0.device):
+                    rc = fn(k, VP(*[q.data_ptr() for q in qs]), I64(*[c.N for c in cs]), c0.D, I64(*[s[0] for s in ss]), I64(*[s[1] for s in ss]),
+                            c0.S, c0.flag, VP(*[c.seg_bytes.data_ptr() for c in cs]), VP(*[c.seg_off.data_ptr() for c in cs]),
+                            VP(*[c.out.data_ptr() for c in cs]), I64(*[c.cap for c in cs]), tot, c0._stream())
+                if rc == _lib.RAHT_OK or attempt == 1 or all(int(tot[j]) <= cs[j].cap for j in range(k)):
+                    check(rc)
+                    break
+                for j, c in enumerate(cs):                    # incompressible data: the exact sizes are known now
+                    if int(tot[j]) > c.cap:
+                        c.cap = int(tot[j]) + 64
+                        c.out = torch.empty(c.cap, dtype=torch.uint8, device=c.device)
+            for j, c in enumerate(cs):
+                c.total = int(tot[j])
+        return [c.total for c in coders]
+
+    @classmethod
+    def decode_ragged(cls, coders, outs=None, row_major=False, expect=None):
+        """``coders[j].decode()`` for every j in ONE launch (raht_rlgr_seg_decode_ragged), for coders as ``encode_ragged`` takes them
+        -> list of (D, N_j) int32 CUDA tensors ((N_j, D) with ``row_major=True``); enqueued on the current stream, no
+        synchronisation. Given ``outs``, their layout is read off their shapes unless ``row_major=True`` says it; a square out
+        (N_j == D) is channel-major otherwise, as ``decode`` reads it (``_one_layout``). ``coders[0].bad`` and ``expect`` (row-major
+        only) as in ``decode_batch``; ``roundtrip_failed(coders)`` reads the result."""
+        import torch
+        if not coders:
+            return []
+        c0 = cls._same_kind(coders, "decode_ragged")
+        fresh = outs is None
+        if fresh:
+            outs = [torch.empty((c.N, c.D) if row_major else (c.D, c.N), dtype=torch.int32, device=c.device) for c in coders]
+        kind = bool(row_major) if fresh else (True if row_major else None)
+        st = cls._one_layout(coders, outs, "decode_ragged", kind)
+        if expect is not None:
+            if any(chan != 1 for _, chan in st):
+                raise ValueError("SegmentedCoder.decode_ragged: expect= goes with row-major frames")
+            if len(expect) != len(coders) or cls._one_layout(coders, expect, "decode_ragged", True) != st:
+                raise ValueError("SegmentedCoder.decode_ragged: one expected frame per coder, in the layout and strides of the outputs")
+        fn = _lib.lib().raht_rlgr_seg_decode_ragged
+        for lo in range(0, len(coders), cls.BATCH_MAX):
+            cs, os_, ss = coders[lo: lo + cls.BATCH_MAX], outs[lo: lo + cls.BATCH_MAX], st[lo: lo + cls.BATCH_MAX]
+            k = len(cs)
+            VP, I64 = C.c_void_p * k, C.c_int64 * k
+            ex = None if expect is None else VP(*[e.data_ptr() for e in expect[lo: lo + cls.BATCH_MAX]])
+            with torch.cuda.device(c0.device):                    # (every chunk reports into its own first coder)
+                check(fn(k, VP(*[c.out.data_ptr() for c in cs]), I64(*[(c.total + 3) // 4 * 4 for c in cs]),
+                         VP(*[c.seg_off.data_ptr() for c in cs]), VP(*[c.seg_bytes.data_ptr() for c in cs]), I64(*[c.N for c in cs]),
+                         c0.D, c0.S, c0.flag, VP(*[o.data_ptr() for o in os_]), ex, I64(*[s[0] for s in ss]), I64(*[s[1] for s in ss]),
+                         C.c_void_p(cs[0].bad.data_ptr()), c0._stream()))
+        return outs
+
     @classmethod
     def roundtrip_failed(cls, coders):
         """after ``decode_batch(..., expect=...)``: -> list of the indices of the frames that did not decode to what was expected, or
