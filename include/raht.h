@@ -149,8 +149,13 @@ int raht_plan_set_max_stages(raht_plan *plan, int max_stages);
 
 /* Plans, schedules and workspaces take their device memory from a process-wide cache of freed blocks
  * (a codec that builds one plan per frame stops paying hipMalloc / hipFree once the cache is warm;
- * at most RAHT_POOL_MAX_BYTES, default 8 GiB, stay cached). This returns the cached blocks to HIP. */
+ * at most 8 GiB stay cached by default). This returns the cached blocks to HIP. */
 int raht_release_cached_memory(void);
+/* Upper bound, in bytes, on what the cache keeps (process-wide, all devices together; default 8 GiB). A block that is given
+ * back while the cache holds that much goes to hipFree instead. 0 caches nothing. Takes effect for the blocks given back
+ * after the call: what is cached already stays until it is handed out again or raht_release_cached_memory() is called.
+ * RAHT_ERR_INVALID for bytes < 0. */
+int raht_set_cached_memory_limit(int64_t bytes);
 
 /* Reference-shaped views, for parity tests and the drivers' DEBUG save_lists
  * (reference python/encode_3dgs.py:165). HOST output buffers.
@@ -468,8 +473,8 @@ int raht_sort_keys(const uint64_t *keys_in, int64_t N, int nbits, uint64_t *keys
  * bounded by the wall clock (0.2 s): a tile that gives up raises an error word, nothing is written through stale offsets, and
  * the call (raht_sort_keys, raht_voxelize*) REPEATS the sort with one launch chain per digit, which needs no such property.
  * The caller sees a correct result and a slower call; this counter (process-wide, monotonic) says how often it happened.
- * Expected 0: tools/check_big.py and the GPU suite assert it. RAHT_SORT_TICKET=1 numbers the tiles by an atomic ticket
- * instead (acyclic whatever the dispatch order; +4 us per pass). */
+ * Expected 0: tools/check_big.py and the GPU suite assert it. The tests make a tile give up through raht_debug_sort_form and
+ * watch this counter grow. */
 int64_t raht_sort_fallbacks(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -730,10 +735,23 @@ int raht_debug_rlgr_encode_out(int mode);
  * restores the default. While a non-default value is set, the heights are launched behind the schedule builder's read-back
  * instead of in front of it. Same schedules, same transforms; a testing hook, process-wide. Returns the previous value. */
 int raht_debug_height_stages_per_launch(int n);
+/* The form the key sort takes (csrc/scan_sort.hip), for the tests and tools that walk every form of one sort:
+ *   onesweep  : 1 = one launch per digit pass with look-back between the tiles (default), 0 = pass by pass, four launches per digit
+ *   rounds    : items per lane of a one-sweep tile, 8 / 12 / 16 = tiles of 2048 / 3072 / 4096 items; 0 = chosen by N (default)
+ *   fail_tile : this tile of every one-sweep pass gives up as if its bounded wait had run out (the tiles behind it pass the
+ *               error on, the grid drains, the call repeats the sort pass by pass and raht_sort_fallbacks() grows);
+ *               < 0 = none (default), at most 2^24 - 1
+ * Same keys and permutation in every form. A testing hook, process-wide; a sort reads it once, when it is called. Returns the
+ * previous form packed as onesweep | rounds << 1 | (fail_tile + 1) << 6 (never negative), so that
+ * raht_debug_sort_form(p & 1, (p >> 1) & 31, (p >> 6) - 1) restores it; RAHT_ERR_INVALID (nothing changed) for any other
+ * rounds or a larger fail_tile. */
+int raht_debug_sort_form(int onesweep, int rounds, int64_t fail_tile);
 /* Device blocks of the library's block cache that are handed out and not yet given back (plan arrays, schedules, workspaces
  * of every live plan, on every device). Scratch-pool blocks and borrowed key arrays are not counted. A testing hook: after a plan
  * is destroyed, or a constructor has failed, the count is what it was before. */
 int64_t raht_debug_live_blocks(void);
+/* Freed blocks the cache currently keeps (what raht_release_cached_memory() would return to HIP), on every device. */
+int64_t raht_debug_cached_blocks(void);
 
 /* out[c] = sum over rows of (A[i, c] - B[i, c])^2, DEVICE double[D]: what the drivers' five PSNR columns are made of
  * (python/encode_3dgs.py:298-310: torch.mean((C - C_rec) ** 2) over all / quats / scales / opacity / colour columns -- each a

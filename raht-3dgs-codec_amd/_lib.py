@@ -2,6 +2,7 @@
 
 The product path fails loudly when the HIP library is missing -- there is no CPU fallback.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -19,7 +20,7 @@ ENGINE_TILE, ENGINE_LEVEL = 0, 1
 # every symbol include/raht.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "raht_last_error", "raht_version", "raht_plan_create", "raht_plan_create_from_keys", "raht_plan_create_from_keys_borrowed",
-    "raht_plan_destroy", "raht_plan_set_top_level", "raht_plan_roots", "raht_plan_set_root_buffer", "raht_plan_set_root_buffer_wide", "raht_plan_size", "raht_plan_nbits", "raht_plan_set_engine", "raht_plan_set_tail_tile", "raht_release_cached_memory", "raht_quant_rows", "raht_dequant_rows", "raht_quant_rows_f64", "raht_dequant_rows_f64",
+    "raht_plan_destroy", "raht_plan_set_top_level", "raht_plan_roots", "raht_plan_set_root_buffer", "raht_plan_set_root_buffer_wide", "raht_plan_size", "raht_plan_nbits", "raht_plan_set_engine", "raht_plan_set_tail_tile", "raht_release_cached_memory", "raht_set_cached_memory_limit", "raht_quant_rows", "raht_dequant_rows", "raht_quant_rows_f64", "raht_dequant_rows_f64",
     "raht_plan_levels", "raht_plan_export_level", "raht_plan_order", "raht_plan_arrays",
     "raht_plan_copy_array", "raht_plan_stage_stats", "raht_fwd", "raht_fwd_f64", "raht_inv", "raht_inv_f64", "raht_debug_run_stage", "raht_plan_set_stage0_events", "raht_fwd_quant", "raht_dequant_inv", "raht_plan_prepare",
     "raht_quant_reorder", "raht_dequant_unreorder", "raht_voxelize", "raht_voxelize_all", "raht_voxelize_plan", "raht_morton", "raht_sort_keys",
@@ -29,7 +30,7 @@ EXPORTS = [
     "raht_fwd_quant_mixed_multi", "raht_dequant_inv_mixed_sqdiff",
     "raht_fwd_batch", "raht_inv_batch", "raht_fwd_quant_batch", "raht_dequant_inv_batch",
     "raht_fwd_quant_mixed_batch", "raht_dequant_inv_mixed_batch", "raht_mixed_batch_stats",
-    "raht_rlgr_bound", "raht_rlgr_encode", "raht_rlgr_decode", "raht_rlgr_encode_channels", "raht_rlgr_decode_channels", "raht_transpose_i32", "raht_i32_equal", "raht_sqdiff_columns", "raht_merge_clusters", "raht_voxelize_merge", "raht_rlgr_seg_encode", "raht_rlgr_seg_decode", "raht_rlgr_seg_encode_strided", "raht_rlgr_seg_decode_strided", "raht_rlgr_seg_encode_batch", "raht_rlgr_seg_decode_batch", "raht_rlgr_seg_decode_batch_check", "raht_rlgr_seg_offsets_width", "raht_rlgr_seg_encode64", "raht_rlgr_seg_decode64", "raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_decode_batch64", "raht_rlgr_seg_encode_ragged", "raht_rlgr_seg_decode_ragged", "raht_debug_rlgr_decode_out", "raht_debug_rlgr_encode_out", "raht_rlgr_seg_rate", "raht_debug_height_stages_per_launch", "raht_debug_live_blocks",
+    "raht_rlgr_bound", "raht_rlgr_encode", "raht_rlgr_decode", "raht_rlgr_encode_channels", "raht_rlgr_decode_channels", "raht_transpose_i32", "raht_i32_equal", "raht_sqdiff_columns", "raht_merge_clusters", "raht_voxelize_merge", "raht_rlgr_seg_encode", "raht_rlgr_seg_decode", "raht_rlgr_seg_encode_strided", "raht_rlgr_seg_decode_strided", "raht_rlgr_seg_encode_batch", "raht_rlgr_seg_decode_batch", "raht_rlgr_seg_decode_batch_check", "raht_rlgr_seg_offsets_width", "raht_rlgr_seg_encode64", "raht_rlgr_seg_decode64", "raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_decode_batch64", "raht_rlgr_seg_encode_ragged", "raht_rlgr_seg_decode_ragged", "raht_debug_rlgr_decode_out", "raht_debug_rlgr_encode_out", "raht_rlgr_seg_rate", "raht_debug_height_stages_per_launch", "raht_debug_live_blocks", "raht_debug_cached_blocks", "raht_debug_sort_form",
     "raht_xchg_bytes", "raht_xchg_alloc", "raht_xchg_open", "raht_xchg_close", "raht_xchg_free", "raht_xchg_gather", "raht_xchg_buffer", "raht_xchg_status",
     "raht_octree_counts", "raht_octree_encode", "raht_octree_decode", "raht_octree_symbols", "raht_octree_bytes", "raht_demorton",
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
@@ -162,6 +163,10 @@ def lib():
     L.raht_debug_height_stages_per_launch.argtypes = [i32]
     L.raht_debug_live_blocks.argtypes = []
     L.raht_debug_live_blocks.restype = i64
+    L.raht_debug_cached_blocks.argtypes = []
+    L.raht_debug_cached_blocks.restype = i64
+    L.raht_set_cached_memory_limit.argtypes = [i64]
+    L.raht_debug_sort_form.argtypes = [i32, i32, i64]
     L.raht_rlgr_seg_encode_batch.argtypes = [i32, C.POINTER(vp), i64, i32, i64, i64, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), vp]
     L.raht_rlgr_seg_decode_batch.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), i64, i32, i32, i32, C.POINTER(vp), i64, i64, vp, vp]
     L.raht_rlgr_seg_decode_batch_check.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), i64, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), i64, i64, vp, vp]
@@ -197,3 +202,15 @@ def lib():
 def check(rc):
     if rc != RAHT_OK:
         raise RahtError(rc, lib().raht_last_error().decode("utf-8", "replace"))
+
+
+@contextlib.contextmanager
+def sort_form(onesweep=1, rounds=0, fail_tile=-1):
+    """The key sort in one of its forms (include/raht.h: raht_debug_sort_form) while the block runs; the form that was set
+    before comes back afterwards. Process-wide: for tests and tools."""
+    prev = lib().raht_debug_sort_form(onesweep, rounds, fail_tile)
+    check(min(prev, 0))
+    try:
+        yield
+    finally:
+        lib().raht_debug_sort_form(prev & 1, (prev >> 1) & 31, (prev >> 6) - 1)

@@ -112,6 +112,7 @@ struct PerDeviceOnce {
     bool first(int device) { if (done[device]) return false; done[device] = true; return true; }
 };
 
+// ---- device memory and host read-backs (device_memory.hip) -------------------------------------
 // Device scratch memory from a thread-local grow-only pool (one per device): plan / sort / voxelizer
 // temporaries are reused across calls instead of paying hipMalloc + hipFree (each a device
 // synchronisation) per use. A block is released when its Scratch object dies, i.e. possibly while the kernels
@@ -137,7 +138,7 @@ private:
 // Long-lived device blocks (plan arrays, schedules, workspaces) come from a process-wide cache of freed
 // blocks in ~12 % size classes: a codec that builds one plan per frame pays hipMalloc / hipFree (each a
 // device synchronisation, ~0.1-0.3 ms for the six N-sized plan arrays) only until the cache is warm.
-// dev_free keeps at most RAHT_POOL_MAX_BYTES (default 8 GiB) cached; raht_release_cached_memory() empties it.
+// dev_free keeps at most 8 GiB cached (raht_set_cached_memory_limit changes that); raht_release_cached_memory() empties it.
 // The cache is keyed by (device, size class): a block freed by a plan on device 0 is never handed to a
 // plan on device 1.
 hipError_t dev_malloc(void **p, size_t bytes);
@@ -182,6 +183,15 @@ struct OwnedEvent {
     operator hipEvent_t() const { return ev; }
 };
 
+// Host read-back of a few 32-bit words produced on `s` (na + nb <= 192; b may be NULL): a one-wave kernel
+// stores them into a mapped pinned mailbox and the host polls it -- 9 us instead of the 22 us of a
+// pageable hipMemcpyAsync + hipStreamSynchronize (tools/native/probe_readback.hip). Returns once the
+// words (and therefore all earlier work on `s`) are complete. `behind` (may be empty) is called once the read-back has been
+// enqueued and before the host starts waiting: work it enqueues on `s` runs while the host waits and is NOT waited for.
+// `behind` runs under the mailbox lock: it must not itself reach read_back_u32 (directly or through a helper that reads back).
+int read_back_u32(uint32_t *dst_a, const uint32_t *dev_a, int na, uint32_t *dst_b, const uint32_t *dev_b, int nb,
+                  hipStream_t s, const std::function<void()> &behind = std::function<void()>());
+
 // ---- device primitives (scan_sort.hip) ---------------------------------------------------------
 // Exclusive prefix sum of n uint32 values, in place allowed (out may equal in). `total` (device
 // uint32*, may be NULL) receives the sum. Allocates its own small workspace (plan/voxelize time
@@ -192,36 +202,25 @@ int exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *t
 // that may pass 4 GiB (rlgr_seg.hip).
 int exclusive_scan_u32_u64(const uint32_t *in, uint64_t *out, int64_t n, uint64_t *total, hipStream_t s);
 
-// One stable LSD radix pass on `bits`-wide digits (bits <= 8) taken at `shift`.
-// keys are uint64; payload is uint32. keys_out / vals_in / vals_out may be NULL
-// (vals_in == NULL means payload = original index).
-int radix_pass_u64(const uint64_t *keys_in, const uint32_t *vals_in, uint64_t *keys_out,
-                   uint32_t *vals_out, int64_t n, int shift, int bits, hipStream_t s);
-// The whole stable sort of (key, original index) by the low nbits key bits in npass + 2 launches: one histogram launch for
-// every digit, one for the digit bases, one launch per digit pass whose tiles chain their offsets by decoupled look-back
-// (scan_sort.hip). tmp_keys / tmp_idx: N-sized ping-pong buffers. err_dev: device word, zeroed by the first launch and set
-// when a tile gave up waiting for its predecessors (bounded waits: the grid always drains) -- the caller reads it back
-// once the stream has drained and falls back to the pass-by-pass sort. Returns 1 (nothing enqueued) when the input does
-// not fit (more than 8 digit passes, N >= 2^30) or RAHT_SORT_ONESWEEP=0. idx64_out (may be NULL): the indices once more as
-// int64, written by the last pass. grid (may be NULL): keys_in is not an input but the voxel keys of the cloud's points
-// (raht_device.h: vox_key), which the histogram launch computes AND stores there on its way.
+// THE stable sort of (key, original index) by the low nbits key bits (uint64 keys, uint32 indices; N < 2^31), enqueued on `s`.
+// sort_err (device word, may be NULL) selects the one-sweep form: npass + 2 launches whose tiles chain their offsets by
+// decoupled look-back with bounded waits. The word is zeroed by the first launch and set when a tile gave up waiting (the grid
+// always drains): the caller reads it back once the stream has drained and, in the never-seen case that it is set, calls
+// note_sort_fallback() and repeats the call with onesweep = false -- the pass-by-pass form, four launches per 8-bit digit,
+// which is also what runs when the input does not fit the one-sweep form (more than 8 digit passes, N >= 2^30); the word
+// is cleared. idx64_out (may be NULL): the indices once more as int64. grid (may be NULL): keys_in is an OUTPUT as well -- the
+// voxel keys of the cloud's points (raht_device.h: vox_key), computed on the way (inside the one-sweep form's histogram launch,
+// or by vox_keys in front of the pass-by-pass form).
 struct VoxGrid;
-int sort_pairs_onesweep(const uint64_t *keys_in, int64_t n, int nbits, uint64_t *keys_out, uint32_t *idx_out, uint64_t *tmp_keys,
-                        uint32_t *tmp_idx, uint32_t *err_dev, hipStream_t s, int64_t *idx64_out = nullptr,
-                        const VoxGrid *grid = nullptr);
-// Same for uint8 bucket ids (< 2^bits); produces the stable permutation and, optionally, the
+int sort_keys_u32idx(const uint64_t *keys_in, int64_t N, int nbits, uint64_t *keys_out, uint32_t *idx_out, hipStream_t s,
+                     uint32_t *sort_err = nullptr, int64_t *idx64_out = nullptr, const VoxGrid *grid = nullptr, bool onesweep = true);
+void note_sort_fallback();       // counted by raht_sort_fallbacks()
+// keys[i] = voxel key of point i of the grid's cloud (one launch).
+int vox_keys(const VoxGrid &grid, int64_t N, uint64_t *keys, hipStream_t s);
+// One stable radix pass over uint8 bucket ids (< 2^bits, bits <= 8); produces the stable permutation and, optionally, the
 // start offset of every bucket (bucket_off: device uint32[(1<<bits)+1]).
 int bucket_sort_u8(const uint8_t *bucket, uint32_t *perm_out, int64_t n, int bits,
                    uint32_t *bucket_off, hipStream_t s);
-
-// Host read-back of a few 32-bit words produced on `s` (na + nb <= 192; b may be NULL): a one-wave kernel
-// stores them into a mapped pinned mailbox and the host polls it -- 9 us instead of the 22 us of a
-// pageable hipMemcpyAsync + hipStreamSynchronize (tools/native/probe_readback.hip). Returns once the
-// words (and therefore all earlier work on `s`) are complete. `behind` (may be empty) is called once the read-back has been
-// enqueued and before the host starts waiting: work it enqueues on `s` runs while the host waits and is NOT waited for.
-// `behind` runs under the mailbox lock: it must not itself reach read_back_u32 (directly or through a helper that reads back).
-int read_back_u32(uint32_t *dst_a, const uint32_t *dev_a, int na, uint32_t *dst_b, const uint32_t *dev_b, int nb,
-                  hipStream_t s, const std::function<void()> &behind = std::function<void()>());
 
 // out[k] = in[j] (or j when in == NULL) for the k-th j with flag[j] != 0. *count_host gets the
 // number of kept items (synchronises the stream).

@@ -1,169 +1,22 @@
-// scan_sort.hip -- device primitives for the plan and the voxelizer: exclusive scan, stable LSD
-// radix pass (wave64 ballot ranking), bucket sort, stream compaction. Hand-written for gfx950:
-// 64-lane ballots, LDS histograms, no library calls.
+// scan_sort.hip -- device primitives for the plan and the voxelizer: exclusive scan (one implementation, 32- and 64-bit sums),
+// stable LSD radix pass (wave64 ballot ranking) and bucket sort, the one-sweep key sort and the sort's host driver
+// (raht_sort_keys, sort_keys_u32idx), stream compaction, run starts. Hand-written for gfx950: 64-lane ballots, LDS
+// histograms, no library calls. (Device memory and read-backs: device_memory.hip.)
 //
 // These are integer/HBM-bound kernels (no MFMA). They run at plan / voxelize time, not inside the
 // transform entry points.
 #include "raht_common.h"
 #include "raht_device.h"
-#include <map>
-#include <mutex>
-#include <unordered_map>
+#include <atomic>
 
 namespace raht {
 
 // ------------------------------------------------------------------------------------------------
-// Scratch pool
-// ------------------------------------------------------------------------------------------------
-struct PoolBlock { void *p; size_t bytes; bool used; int device; hipStream_t last_stream; bool touched; };
-static thread_local std::vector<PoolBlock> g_pool;
-
-Scratch::Scratch(size_t bytes, hipStream_t stream)
-{
-    if (bytes == 0) bytes = 16;
-    const int dev = current_device();
-    int best = -1, n_dev = 0;
-    // best fit among the free blocks whose last user ran on THIS stream (or that were never used): a block last used on another
-    // stream costs a device synchronisation before it may be handed out, which would serialise a caller that works on two
-    // streams at once (raht_voxelize_plan: the plan build next to the voxelizer's mean kernel) -- such a block is only taken
-    // when the pool is already large
-    int n_free_other = 0, best_other = -1;
-    for (int i = 0; i < (int)g_pool.size(); ++i) {
-        const PoolBlock &b = g_pool[(size_t)i];
-        if (b.device != dev || !b.p) continue;
-        ++n_dev;
-        if (b.used || b.bytes < bytes) continue;
-        if (!b.touched || b.last_stream == stream) { if (best < 0 || b.bytes < g_pool[(size_t)best].bytes) best = i; }
-        else { ++n_free_other; if (best_other < 0 || b.bytes < g_pool[(size_t)best_other].bytes) best_other = i; }
-    }
-    if (best < 0 && best_other >= 0 && n_dev >= 40) best = best_other;
-    (void)n_free_other;
-    if (best < 0) {
-        // recycle the largest free block (of this device) that is too small, else grow the pool
-        int victim = -1, empty = -1;
-        for (int i = 0; i < (int)g_pool.size(); ++i) {
-            const PoolBlock &b = g_pool[(size_t)i];
-            if (!b.p && !b.used) { if (empty < 0) empty = i; continue; }
-            if (b.device == dev && !b.used && (victim < 0 || b.bytes > g_pool[(size_t)victim].bytes)) victim = i;
-        }
-        void *q = nullptr;
-        const size_t want = bytes + bytes / 4;                 // head-room against slow growth
-        if (victim >= 0 && n_dev >= 48) {
-            (void)hipFree(g_pool[(size_t)victim].p);
-            // a failed allocation leaves an EMPTY slot behind: erasing it would shift the slot indices that
-            // live Scratch objects hold, and a later destructor would release somebody else's block
-            g_pool[(size_t)victim] = {nullptr, 0, false, dev, nullptr, false};
-            if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); set_error("scratch: out of device memory (%zu bytes)", want); return; }
-            g_pool[(size_t)victim] = {q, want, false, dev, nullptr, false};
-            best = victim;
-        } else {
-            if (hipMalloc(&q, want) != hipSuccess) { (void)hipGetLastError(); set_error("scratch: out of device memory (%zu bytes)", want); return; }
-            if (empty >= 0) { g_pool[(size_t)empty] = {q, want, false, dev, nullptr, false}; best = empty; }
-            else { g_pool.push_back({q, want, false, dev, nullptr, false}); best = (int)g_pool.size() - 1; }
-        }
-    }
-    PoolBlock &blk = g_pool[(size_t)best];
-    // the block's previous user may still be running on another stream (see raht_common.h)
-    if (blk.touched && blk.last_stream != stream) (void)hipDeviceSynchronize();
-    blk.used = true;
-    blk.touched = true;
-    blk.last_stream = stream;
-    p_ = blk.p;
-    slot_ = best;
-}
-
-Scratch::~Scratch()
-{
-    if (slot_ >= 0 && slot_ < (int)g_pool.size()) g_pool[(size_t)slot_].used = false;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Cache of long-lived device blocks (see raht_common.h).
-// ------------------------------------------------------------------------------------------------
-namespace {
-struct LiveBlock { size_t cls; int device; };
-struct DevCache {
-    std::mutex mu;
-    std::unordered_map<void *, LiveBlock> live;                    // block -> (class size, device)
-    std::multimap<std::pair<int, size_t>, void *> free_blocks;     // (device, class size) -> block
-    size_t cached = 0, limit = 0;
-};
-DevCache &dev_cache()
-{
-    static DevCache c;
-    if (c.limit == 0) {
-        const char *e = getenv("RAHT_POOL_MAX_BYTES");
-        c.limit = e ? (size_t)strtoull(e, nullptr, 10) : ((size_t)8 << 30);
-        if (c.limit == 0) c.limit = 1;                    // "0" = cache nothing
-    }
-    return c;
-}
-size_t size_class(size_t bytes)
-{
-    if (bytes < 4096) return 4096;
-    int hb = 63 - __builtin_clzll((unsigned long long)bytes);
-    const size_t step = (size_t)1 << (hb - 3);           // eight classes per power of two
-    return (bytes + step - 1) / step * step;
-}
-}  // namespace
-
-hipError_t dev_malloc(void **p, size_t bytes)
-{
-    DevCache &c = dev_cache();
-    const size_t cls = size_class(bytes);
-    const int dev = current_device();
-    {
-        std::lock_guard<std::mutex> g(c.mu);
-        auto it = c.free_blocks.find(std::make_pair(dev, cls));
-        if (it != c.free_blocks.end()) {
-            *p = it->second;
-            c.free_blocks.erase(it);
-            c.cached -= cls;
-            c.live[*p] = LiveBlock{cls, dev};
-            return hipSuccess;
-        }
-    }
-    hipError_t e = hipMalloc(p, cls);
-    if (e != hipSuccess) {                               // under memory pressure: drop the cache and retry
-        (void)hipGetLastError();
-        raht_release_cached_memory();
-        e = hipMalloc(p, cls);
-    }
-    if (e == hipSuccess) {
-        std::lock_guard<std::mutex> g(c.mu);
-        c.live[*p] = LiveBlock{cls, dev};
-    }
-    return e;
-}
-
-void dev_free(void *p)
-{
-    if (!p) return;
-    DevCache &c = dev_cache();
-    size_t cls = 0;
-    {
-        std::lock_guard<std::mutex> g(c.mu);
-        int dev = 0;
-        auto it = c.live.find(p);
-        if (it != c.live.end()) { cls = it->second.cls; dev = it->second.device; c.live.erase(it); }
-        if (cls && c.cached + cls <= c.limit) {
-            c.free_blocks.emplace(std::make_pair(dev, cls), p);      // back to the bucket of the block's OWN device
-            c.cached += cls;
-            return;
-        }
-    }
-    (void)hipFree(p);
-}
-
-extern "C" int64_t raht_debug_live_blocks(void)
-{
-    DevCache &c = dev_cache();
-    std::lock_guard<std::mutex> g(c.mu);
-    return (int64_t)c.live.size();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Exclusive scan (3 kernels, recursive on the block sums).
+// Exclusive scan, written once for 32-bit and 64-bit sums: block-local scans and block sums, the sums of up to
+// SCAN_FUSE_BLOCKS blocks added up by every block for itself, and above that one more level of the same.
+// 64-bit sums: uint32 items (the padded lengths of the segments of an RLGR container that may pass 4 GiB, rlgr_seg.hip) ->
+// uint64 exclusive offsets and a uint64 grand total. A thread's eight items already sum past 32 bits, so everything
+// above the single item is carried in the sum type.
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
@@ -179,20 +32,32 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
     }
     return v;
 }
+// (the one piece the sum type specialises: a 64-bit value travels as two 32-bit shuffles)
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
+        if (lane >= d) v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
 
 // Block-wide exclusive scan of one value per thread (256 threads). Returns the exclusive prefix;
 // *block_total receives the sum (valid in every thread).
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *block_total)
+template <typename Sum>
+__device__ __forceinline__ Sum block_excl_scan_256(Sum v, Sum *block_total)
 {
-    __shared__ uint32_t wsum[4];
+    __shared__ Sum wsum[4];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t inc = wave_incl_scan(v);
+    Sum inc = wave_incl_scan(v);
     if (lane == 63) wsum[wid] = inc;
     __syncthreads();
-    uint32_t base = 0, tot = 0;
+    Sum base = 0, tot = 0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-        uint32_t s = wsum[w];
+        Sum s = wsum[w];
         if (w < wid) base += s;
         tot += s;
     }
@@ -201,22 +66,21 @@ __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *bl
     return base + inc - v;
 }
 
-__global__ __launch_bounds__(SCAN_THREADS) void scan_block_kernel(const uint32_t *in,   // may alias out
-                                                                  uint32_t *out,
-                                                                  uint32_t *sums,
-                                                                  int64_t n,
-                                                                  uint32_t *total)      // single-block scans only
+template <typename In, typename Sum>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_block_kernel(const In *in,        // may alias out (In = Sum)
+                                                                  Sum *out, Sum *sums, int64_t n,
+                                                                  Sum *total)          // single-block scans only
 {
     const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t v[SCAN_ITEMS];
-    uint32_t tsum = 0;
+    Sum v[SCAN_ITEMS];
+    Sum tsum = 0;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
-        v[k] = (base + k < n) ? in[base + k] : 0u;
+        v[k] = (base + k < n) ? (Sum)in[base + k] : (Sum)0;
         tsum += v[k];
     }
-    uint32_t tot;
-    uint32_t ex = block_excl_scan_256(tsum, &tot);
+    Sum tot;
+    Sum ex = block_excl_scan_256(tsum, &tot);
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         if (base + k < n) out[base + k] = ex;
@@ -227,17 +91,17 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_block_kernel(const uint32_t
 }
 
 // Second and last launch of a scan of up to SCAN_FUSE_BLOCKS blocks: every block sums the totals of the
-// blocks before it by itself (<= 8 KB from L2) instead of waiting for a scan of the totals, and the last
+// blocks before it by itself (<= 8 KB of 32-bit sums from L2) instead of waiting for a scan of the totals, and the last
 // block also writes the grand total. (Scans of this size are launch-bound: 2 launches instead of 3-5.)
 constexpr int SCAN_FUSE_BLOCKS = 2048;
 
-__global__ __launch_bounds__(SCAN_THREADS) void scan_finish_kernel(uint32_t *__restrict__ out,
-                                                                   const uint32_t *__restrict__ sums,
-                                                                   int64_t n, uint32_t *__restrict__ total)
+template <typename Sum>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_finish_kernel(Sum *__restrict__ out, const Sum *__restrict__ sums,
+                                                                   int64_t n, Sum *__restrict__ total)
 {
-    uint32_t part = 0;
+    Sum part = 0;
     for (int b = threadIdx.x; b < (int)blockIdx.x; b += SCAN_THREADS) part += sums[b];
-    uint32_t add;
+    Sum add;
     (void)block_excl_scan_256(part, &add);
     if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = add + sums[blockIdx.x];
     if (blockIdx.x == 0) return;
@@ -247,186 +111,62 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_finish_kernel(uint32_t *__r
         if (base + k < n) out[base + k] += add;
 }
 
-__global__ __launch_bounds__(SCAN_THREADS) void scan_add_kernel(uint32_t *__restrict__ out,
-                                                                const uint32_t *__restrict__ sums,
-                                                                int64_t n)
+template <typename Sum>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_add_kernel(Sum *__restrict__ out, const Sum *__restrict__ sums, int64_t n)
 {
-    const uint32_t add = sums[blockIdx.x];
+    const Sum add = sums[blockIdx.x];
     const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k)
         if (base + k < n) out[base + k] += add;
 }
 
-__global__ void scan_total_kernel(const uint32_t *in_last, const uint32_t *out_last, uint32_t *total)
-{
-    *total = *in_last + *out_last;
-}
-
-static int scan_rec(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *ws, hipStream_t s)
+// one or two launches: n items in up to SCAN_FUSE_BLOCKS blocks (sums: one word per block)
+template <typename In, typename Sum>
+static void scan_fused(const In *in, Sum *out, int64_t n, Sum *sums, Sum *total, hipStream_t s)
 {
     const int64_t nb = ceil_div(n, SCAN_BLOCK);
     if (nb == 1) {
-        hipLaunchKernelGGL(scan_block_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, in, out,
-                           (uint32_t *)nullptr, n, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((scan_block_kernel<In, Sum>), dim3(1), dim3(SCAN_THREADS), 0, s, in, out, (Sum *)nullptr, n, total);
+    } else {
+        hipLaunchKernelGGL((scan_block_kernel<In, Sum>), dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n, (Sum *)nullptr);
+        hipLaunchKernelGGL(scan_finish_kernel<Sum>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n, total);
+    }
+}
+
+template <typename Sum>
+static int exclusive_scan(const uint32_t *in, Sum *out, int64_t n, Sum *total, hipStream_t s)
+{
+    if (n <= 0) {
+        if (total) RAHT_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(Sum), s));
         return RAHT_OK;
     }
-    uint32_t *sums = ws;
-    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n,
-                       (uint32_t *)nullptr);
-    RAHT_RET(scan_rec(sums, sums, nb, ws + nb, s));
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n);
+    const int64_t nb = ceil_div(n, SCAN_BLOCK), nb2 = ceil_div(nb, SCAN_BLOCK);
+    // two levels reach SCAN_FUSE_BLOCKS * SCAN_BLOCK blocks of SCAN_BLOCK items: 2^33 items
+    if (nb2 > SCAN_FUSE_BLOCKS) { set_error("exclusive scan: too many items"); return RAHT_ERR_INVALID; }
+    Scratch ws(sizeof(Sum) * (size_t)(nb + nb2), s);
+    if (!ws.ok()) return RAHT_ERR_NOMEM;
+    Sum *sums = ws.as<Sum>();
+    if (nb <= SCAN_FUSE_BLOCKS) {
+        scan_fused(in, out, n, sums, total, s);
+    } else {
+        // block-local offsets and block sums; the sums scanned in place (their total is the grand total); added back
+        hipLaunchKernelGGL((scan_block_kernel<uint32_t, Sum>), dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n, (Sum *)nullptr);
+        scan_fused((const Sum *)sums, sums, nb, sums + nb, total, s);
+        hipLaunchKernelGGL(scan_add_kernel<Sum>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n);
+    }
+    RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }
 
 int exclusive_scan_u32(const uint32_t *in, uint32_t *out, int64_t n, uint32_t *total, hipStream_t s)
 {
-    if (n <= 0) {
-        if (total) RAHT_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(uint32_t), s));
-        return RAHT_OK;
-    }
-    // workspace: nb + nb/2048 + ... entries, plus one word to keep in[n-1] (out may alias in)
-    int64_t wsn = 1;
-    for (int64_t m = ceil_div(n, SCAN_BLOCK); m > 1; m = ceil_div(m, SCAN_BLOCK)) wsn += m;
-    Scratch ws(sizeof(uint32_t) * (size_t)wsn, s);
-    if (!ws.ok()) return RAHT_ERR_NOMEM;
-    const int64_t nb = ceil_div(n, SCAN_BLOCK);
-    if (nb <= SCAN_FUSE_BLOCKS) {
-        uint32_t *sums = ws.as<uint32_t>();
-        if (nb == 1) {
-            hipLaunchKernelGGL(scan_block_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, in, out, (uint32_t *)nullptr, n, total);
-        } else {
-            hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n,
-                               (uint32_t *)nullptr);
-            hipLaunchKernelGGL(scan_finish_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n, total);
-        }
-        RAHT_HIP_CHECK(hipGetLastError());
-        return RAHT_OK;
-    }
-    uint32_t *last_in = ws.as<uint32_t>();
-    if (total)
-        RAHT_HIP_CHECK(hipMemcpyAsync(last_in, in + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    int rc = scan_rec(in, out, n, ws.as<uint32_t>() + 1, s);
-    if (rc == RAHT_OK && total)
-        hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(1), 0, s, last_in, out + (n - 1), total);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same scan with 64-bit sums: uint32 items (the padded lengths of the segments of an RLGR container
-// that may pass 4 GiB, rlgr_seg.hip) -> uint64 exclusive offsets and a uint64 grand total. A thread's eight
-// items already sum past 32 bits, so everything above the single item is carried in 64 bits. The second
-// level (block sums of a scan of more than SCAN_FUSE_BLOCKS blocks) scans uint64 items with the same kernel.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t block_excl_scan_256_u64(uint64_t v, uint64_t *block_total)
-{
-    __shared__ uint64_t wsum[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)inc, d, 64), hi = __shfl_up((uint32_t)(inc >> 32), d, 64);
-        if (lane >= d) inc += ((uint64_t)hi << 32) | lo;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const uint64_t s = wsum[w];
-        if (w < wid) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *block_total = tot;
-    return base + inc - v;
-}
-
-template <typename In>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_block_u64_kernel(const In *in,    // may alias out (In = uint64_t)
-                                                                      uint64_t *out, uint64_t *sums, int64_t n,
-                                                                      uint64_t *total)  // single-block scans only
-{
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t v[SCAN_ITEMS];
-    uint64_t tsum = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        v[k] = (base + k < n) ? (uint64_t)in[base + k] : 0ull;
-        tsum += v[k];
-    }
-    uint64_t tot;
-    uint64_t ex = block_excl_scan_256_u64(tsum, &tot);
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        if (base + k < n) out[base + k] = ex;
-        ex += v[k];
-    }
-    if (threadIdx.x == 0 && sums) sums[blockIdx.x] = tot;
-    if (threadIdx.x == 0 && total) *total = tot;
-}
-
-// (scan_finish_kernel with 64-bit sums: up to SCAN_FUSE_BLOCKS blocks, every block adds up the totals before it)
-__global__ __launch_bounds__(SCAN_THREADS) void scan_finish_u64_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ sums,
-                                                                       int64_t n, uint64_t *__restrict__ total)
-{
-    uint64_t part = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += SCAN_THREADS) part += sums[b];
-    uint64_t add;
-    (void)block_excl_scan_256_u64(part, &add);
-    if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = add + sums[blockIdx.x];
-    if (blockIdx.x == 0) return;
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k)
-        if (base + k < n) out[base + k] += add;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void scan_add_u64_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ sums, int64_t n)
-{
-    const uint64_t add = sums[blockIdx.x];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k)
-        if (base + k < n) out[base + k] += add;
-}
-
-// one or two launches: n items in up to SCAN_FUSE_BLOCKS blocks (sums: one uint64 per block)
-template <typename In>
-static void scan_fused_u64(const In *in, uint64_t *out, int64_t n, uint64_t *sums, uint64_t *total, hipStream_t s)
-{
-    const int64_t nb = ceil_div(n, SCAN_BLOCK);
-    if (nb == 1) {
-        hipLaunchKernelGGL(scan_block_u64_kernel<In>, dim3(1), dim3(SCAN_THREADS), 0, s, in, out, (uint64_t *)nullptr, n, total);
-    } else {
-        hipLaunchKernelGGL(scan_block_u64_kernel<In>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n, (uint64_t *)nullptr);
-        hipLaunchKernelGGL(scan_finish_u64_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n, total);
-    }
+    return exclusive_scan<uint32_t>(in, out, n, total, s);
 }
 
 int exclusive_scan_u32_u64(const uint32_t *in, uint64_t *out, int64_t n, uint64_t *total, hipStream_t s)
 {
-    if (n <= 0) {
-        if (total) RAHT_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(uint64_t), s));
-        return RAHT_OK;
-    }
-    const int64_t nb = ceil_div(n, SCAN_BLOCK), nb2 = ceil_div(nb, SCAN_BLOCK);
-    // two levels reach SCAN_FUSE_BLOCKS * SCAN_BLOCK blocks of SCAN_BLOCK items: 2^33 items
-    if (nb2 > SCAN_FUSE_BLOCKS) { set_error("exclusive_scan_u32_u64: too many items"); return RAHT_ERR_INVALID; }
-    Scratch ws(sizeof(uint64_t) * (size_t)(nb + nb2), s);
-    if (!ws.ok()) return RAHT_ERR_NOMEM;
-    uint64_t *sums = ws.as<uint64_t>();
-    if (nb <= SCAN_FUSE_BLOCKS) {
-        scan_fused_u64(in, out, n, sums, total, s);
-    } else {
-        // block-local offsets and block sums; the sums scanned in place (their total is the grand total); added back
-        hipLaunchKernelGGL(scan_block_u64_kernel<uint32_t>, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, sums, n, (uint64_t *)nullptr);
-        scan_fused_u64((const uint64_t *)sums, sums, nb, sums + nb, total, s);
-        hipLaunchKernelGGL(scan_add_u64_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, out, sums, n);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return exclusive_scan<uint64_t>(in, out, n, total, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -467,18 +207,49 @@ __global__ __launch_bounds__(RP_THREADS) void radix_hist_kernel(const KeyT *__re
     if (threadIdx.x <= mask) ghist[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
 }
 
-// Lanes of the wave holding the same digit as this lane (among `valid` lanes).
-__device__ __forceinline__ uint64_t match_digit(uint32_t digit, int bits, uint64_t valid)
+// Lanes of `valid` that hold the same digit as this lane. Per bit: bal = lanes with the bit set; the lanes that DIFFER from
+// this one in that bit are bal ^ t with t = all ones when this lane's bit is clear... (sign-extended bit: 0 or -1, inverted
+// sense folded into the final complement): the differences of all bits are OR-ed (two bits per v_or3) and complemented once.
+__device__ __forceinline__ uint64_t os_match(uint32_t digit, int bits, uint64_t valid)
 {
-    uint64_t m = valid;
+    uint32_t lo = 0, hi = 0;
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
-        if (b < bits) {
-            const uint64_t bal = __ballot((digit >> b) & 1u);
-            m &= ((digit >> b) & 1u) ? bal : ~bal;
+        if (b < bits) {                                 // (uniform)
+            const int32_t t = ((int32_t)(digit << (31 - b))) >> 31;          // -1: bit set
+            const uint64_t bal = __ballot(t != 0);
+            lo |= (uint32_t)bal ^ (uint32_t)t;                               // set bit: differs from the lanes NOT in bal = ~bal = bal ^ -1
+            hi |= (uint32_t)(bal >> 32) ^ (uint32_t)t;
         }
     }
-    return m;
+    return ~(((uint64_t)hi << 32) | lo) & valid;
+}
+
+// The ranking core of both radix passes, one round of a wave: every valid lane holds one item (key, payload, its digit dg).
+// Ranks the wave's 64 items of this round among the items of the same digit by ballots, bumps the wave's slot counter of the
+// digit (wcnt: this wave's 256 counters in LDS, preset to the first slot of every digit) and places key and payload into LDS
+// at that slot. Rounds are called in memory order, which is what makes the pass stable. Returns false (wave-uniform) when
+// the round holds no item: none of the rounds after it does either.
+// (wavefront-scope atomics, not a volatile pointer: hipcc turns volatile LDS accesses through a pointer into FLAT loads /
+// stores with system-scope cache bits and a s_waitcnt vmcnt(0) each. Within a wave LDS operations execute in order: the slot
+// counter a round's first lane of a digit writes is what the next round reads.)
+template <typename KeyT>
+__device__ __forceinline__ bool rank_round_to_lds(bool valid, KeyT key, uint32_t val, uint32_t dg, int bits, uint32_t *wcnt,
+                                                  KeyT *skey, uint32_t *sval)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t vmask = __ballot(valid);
+    if (vmask == 0) return false;
+    const uint64_t same = os_match(dg, bits, vmask);
+    const uint32_t rank = (uint32_t)__popcll(same & lt);
+    uint32_t slot = 0;
+    if (valid) slot = __hip_atomic_load(&wcnt[dg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + rank;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && rank == 0) __hip_atomic_store(&wcnt[dg], slot + (uint32_t)__popcll(same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __builtin_amdgcn_wave_barrier();
+    if (valid) { skey[slot] = key; sval[slot] = val; }
+    return true;
 }
 
 // The block's items are first sorted by digit INSIDE LDS (stable: ranks in (wave, round, lane) order) and
@@ -530,24 +301,10 @@ __global__ __launch_bounds__(RP_THREADS) void radix_scatter_kernel(
     }
     __syncthreads();
     // phase 3: rank inside the round by ballots, bump the wave's running slot, place into LDS
-    // (wavefront-scope atomics, not a volatile pointer: hipcc turns volatile LDS accesses through a pointer into FLAT loads /
-    // stores with system-scope cache bits and a s_waitcnt vmcnt(0) each. Within a wave LDS operations execute in order.)
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll
     for (int r = 0; r < RP_ROUNDS; ++r) {
         const int64_t i = wbase + r * 64 + lane;
-        const bool valid = i < n;
-        const uint64_t vmask = __ballot(valid);
-        if (vmask == 0) break;                       // wave-uniform
-        const uint32_t d = digit_of(key[r], shift, mask);
-        const uint64_t same = match_digit(d, bits, vmask);
-        const uint32_t rank = (uint32_t)__popcll(same & lt);
-        uint32_t slot = 0;
-        if (valid) slot = __hip_atomic_load(&wcnt[wid][d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + rank;
-        __builtin_amdgcn_wave_barrier();
-        if (valid && rank == 0) __hip_atomic_store(&wcnt[wid][d], slot + (uint32_t)__popcll(same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __builtin_amdgcn_wave_barrier();
-        if (valid) { skey[slot] = key[r]; sval[slot] = val[r]; }
+        if (!rank_round_to_lds(i < n, key[r], val[r], digit_of(key[r], shift, mask), bits, wcnt[wid], skey, sval)) break;
     }
     __syncthreads();
     // phase 4: slots in order -> global memory; consecutive slots of one digit are consecutive there
@@ -583,21 +340,11 @@ static int radix_pass_impl(const KeyT *keys_in, const uint32_t *vals_in, KeyT *k
                                         sizeof(uint32_t), nd, hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL(store_u32_kernel, dim3(1), dim3(1), 0, s, bucket_off + nd, (uint32_t)n);
     }
-    if (vals_in) {
-        if (keys_out)
-            hipLaunchKernelGGL((radix_scatter_kernel<KeyT, true, true>), dim3(nb), dim3(RP_THREADS), 0,
-                               s, keys_in, vals_in, keys_out, vals_out, n, shift, bits, ghist, nb);
-        else
-            hipLaunchKernelGGL((radix_scatter_kernel<KeyT, true, false>), dim3(nb), dim3(RP_THREADS), 0,
-                               s, keys_in, vals_in, keys_out, vals_out, n, shift, bits, ghist, nb);
-    } else {
-        if (keys_out)
-            hipLaunchKernelGGL((radix_scatter_kernel<KeyT, false, true>), dim3(nb), dim3(RP_THREADS), 0,
-                               s, keys_in, vals_in, keys_out, vals_out, n, shift, bits, ghist, nb);
-        else
-            hipLaunchKernelGGL((radix_scatter_kernel<KeyT, false, false>), dim3(nb), dim3(RP_THREADS), 0,
-                               s, keys_in, vals_in, keys_out, vals_out, n, shift, bits, ghist, nb);
-    }
+    auto scatter = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(RP_THREADS), 0, s, keys_in, vals_in, keys_out, vals_out, n, shift, bits, ghist, nb);
+    };
+    if (vals_in) { if (keys_out) scatter(radix_scatter_kernel<KeyT, true, true>); else scatter(radix_scatter_kernel<KeyT, true, false>); }
+    else { if (keys_out) scatter(radix_scatter_kernel<KeyT, false, true>); else scatter(radix_scatter_kernel<KeyT, false, false>); }
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }
@@ -611,12 +358,6 @@ static int radix_pass_impl(const KeyT *keys_in, const uint32_t *vals_in, KeyT *k
 // 512 x blocks scan), so 30-bit keys, which need 4 passes either way, got slower: not kept either. A one-launch scan of the
 // digit-major histogram (workgroup per digit, digit totals by global atomics from the histogram kernel): 0.254 -> 0.360 ms --
 // ~1500 atomics on each of 256 hot words serialise in L2; the two-launch generic scan stays.)
-int radix_pass_u64(const uint64_t *keys_in, const uint32_t *vals_in, uint64_t *keys_out,
-                   uint32_t *vals_out, int64_t n, int shift, int bits, hipStream_t s)
-{
-    return radix_pass_impl<uint64_t>(keys_in, vals_in, keys_out, vals_out, n, shift, bits, nullptr, s);
-}
-
 int bucket_sort_u8(const uint8_t *bucket, uint32_t *perm_out, int64_t n, int bits,
                    uint32_t *bucket_off, hipStream_t s)
 {
@@ -632,7 +373,7 @@ int bucket_sort_u8(const uint8_t *bucket, uint32_t *perm_out, int64_t n, int bit
 //
 // A tile = OS_TILE consecutive items, one workgroup of four waves; with 16 items per lane a tile takes 42 of the CU's
 // 128 LDS granules, so 768 tiles are resident at once and the 733 tiles of a 3 M-key pass all start together. Tile t
-// is workgroup t (RAHT_SORT_TICKET=1: the t-th workgroup to take a ticket -- see "order" below). Per digit d (thread d)
+// is workgroup t (see "order" below). Per digit d (thread d)
 // the tile publishes ONE word, state[t][d] = OS_PART | its count, as soon as its histogram is known. Tiles form groups
 // of 32: thread d adds the published counts of the tiles before its own in its group (31 loads in flight at once);
 // the LAST tile of a group then knows the group's total and publishes gstate[g][d] = OS_PART | total, and everybody
@@ -648,8 +389,9 @@ int bucket_sort_u8(const uint8_t *bucket, uint32_t *perm_out, int64_t n, int bit
 // over the XCDs, in order inside each), so the lowest-numbered unfinished tile is always resident and the waits cannot
 // cycle. The library does not stake a GPU on that: every wait is bounded by the 100 MHz wall clock (OS_WAIT_TICKS);
 // a tile that gives up publishes OS_ERR, which later tiles pass on -- they write nothing, the grid drains, the host
-// finds the error word set and repeats the sort pass by pass. RAHT_SORT_TICKET=1 numbers the tiles by an atomic
-// ticket instead (provably free of cycles whatever the dispatch order; 733 atomics on one word: +4 us per pass).
+// finds the error word set and repeats the sort pass by pass (raht_sort_fallbacks() counts that). So a call is correct
+// under any dispatch order. (Numbering the tiles by an atomic ticket instead -- free of cycles by construction; 733 atomics
+// on one word: +4 us per pass -- was kept as a switch for a while and is gone: DESIGN.md section 6.)
 // Ranks inside a tile are assigned in (wave, round, lane) = memory order, tiles are numbered in memory order: stable.
 // ------------------------------------------------------------------------------------------------
 constexpr int OS_THREADS = 256;
@@ -778,24 +520,6 @@ __device__ __forceinline__ void block_excl_scan2_256(uint32_t a, uint32_t b, uin
     *eb = bb + ib - b;
 }
 
-// Lanes of `valid` that hold the same digit as this lane. Per bit: bal = lanes with the bit set; the lanes that DIFFER from
-// this one in that bit are bal ^ t with t = all ones when this lane's bit is clear... (sign-extended bit: 0 or -1, inverted
-// sense folded into the final complement): the differences of all bits are OR-ed (two bits per v_or3) and complemented once.
-__device__ __forceinline__ uint64_t os_match(uint32_t digit, int bits, uint64_t valid)
-{
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        if (b < bits) {                                 // (uniform)
-            const int32_t t = ((int32_t)(digit << (31 - b))) >> 31;          // -1: bit set
-            const uint64_t bal = __ballot(t != 0);
-            lo |= (uint32_t)bal ^ (uint32_t)t;                               // set bit: differs from the lanes NOT in bal = ~bal = bal ^ -1
-            hi |= (uint32_t)(bal >> 32) ^ (uint32_t)t;
-        }
-    }
-    return ~(((uint64_t)hi << 32) | lo) & valid;
-}
-
 #ifdef RAHT_OS_CLOCKS
 // profiling build only (make EXTRA=-DRAHT_OS_CLOCKS): 100 MHz wall-clock stamps at the phase boundaries of every tile of the
 // pass whose shift is os_dbg_shift (tools/sort_phase_clocks.py)
@@ -806,14 +530,14 @@ __device__ int os_dbg_shift = 8;
 #define OS_STAMP(k) do { } while (0)
 #endif
 
-template <int ROUNDS, bool HAS_VALS_IN, bool TICKET>
+template <int ROUNDS, bool HAS_VALS_IN>
 __global__ __launch_bounds__(OS_THREADS) void os_pass_kernel(const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
                                                              uint64_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, int64_t n,
                                                              int shift, int bits, const uint32_t *__restrict__ slices,
                                                              uint32_t *__restrict__ state, uint32_t *__restrict__ gstate,
-                                                             uint32_t *__restrict__ ticket, uint32_t *__restrict__ err,
+                                                             uint32_t *__restrict__ err,
                                                              int64_t *__restrict__ vals64_out /* last pass: the payload widened, or NULL */,
-                                                             uint32_t fail_tile /* tests: this tile gives up (RAHT_SORT_DEBUG_FAIL_TILE) */)
+                                                             uint32_t fail_tile /* tests: this tile gives up (raht_debug_sort_form) */)
 {
     constexpr int WAVE_ITEMS = 64 * ROUNDS, TILE = OS_WAVES * WAVE_ITEMS;
     // 53 272 bytes with 16 rounds = 42 of the CU's 128 LDS granules: three tiles per CU, 768 on the chip (the 733 tiles of a
@@ -822,13 +546,13 @@ __global__ __launch_bounds__(OS_THREADS) void os_pass_kernel(const uint64_t *__r
     uint32_t *gdelta = wcnt[0];                        // global position - tile-local slot, per digit (once the ranks are out)
     __shared__ uint64_t skey[TILE];
     __shared__ uint32_t sval[TILE];
-    __shared__ uint32_t s_tile, s_bad;
+    __shared__ uint32_t s_bad;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint32_t mask = (1u << bits) - 1u;
     for (int k = threadIdx.x; k < OS_WAVES * 256; k += OS_THREADS) (&wcnt[0][0])[k] = 0;
-    if (threadIdx.x == 0) { s_tile = TICKET ? atomicAdd(ticket, 1u) : blockIdx.x; s_bad = 0; }
+    if (threadIdx.x == 0) s_bad = 0;
     __syncthreads();
-    const uint32_t tile = TICKET ? s_tile : blockIdx.x;
+    const uint32_t tile = blockIdx.x;
     OS_STAMP(0);
     const int64_t bbase = (int64_t)tile * TILE;
     if (bbase >= n) return;                            // (cannot happen: the grid is exactly the tile count)
@@ -879,27 +603,9 @@ __global__ __launch_bounds__(OS_THREADS) void os_pass_kernel(const uint64_t *__r
     }
     __syncthreads();
     OS_STAMP(2);
-    // phase 3: rank inside the round by ballots, bump the wave's running slot, place into LDS. Within a wave LDS operations
-    // execute in order: the slot counter a round's first lane of a digit writes is what the next round reads.
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    auto rank_round = [&](int r) {
-        const int64_t i = wbase + r * 64 + lane;
-        const bool valid = i < n;
-        const uint64_t vmask = __ballot(valid);
-        if (vmask != 0) {                                // wave-uniform
-            const uint32_t dg = dig[r];
-            const uint64_t same = os_match(dg, bits, vmask);
-            const uint32_t rank = (uint32_t)__popcll(same & lt);
-            uint32_t slot = 0;
-            if (valid) slot = __hip_atomic_load(&wcnt[wid][dg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) + rank;
-            __builtin_amdgcn_wave_barrier();
-            if (valid && rank == 0) __hip_atomic_store(&wcnt[wid][dg], slot + (uint32_t)__popcll(same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __builtin_amdgcn_wave_barrier();
-            if (valid) { skey[slot] = key[r]; sval[slot] = val[r]; }
-        }
-    };
+    // phase 3: rank inside the round by ballots, bump the wave's running slot, place into LDS
 #pragma unroll
-    for (int r = 0; r < ROUNDS / 2; ++r) rank_round(r);
+    for (int r = 0; r < ROUNDS / 2; ++r) (void)rank_round_to_lds(wbase + r * 64 + lane < n, key[r], val[r], dig[r], bits, wcnt[wid], skey, sval);
     OS_STAMP(3);
     // phase 4a: keys of digit d in the tiles before this one in its group; the group's last tile publishes the group's total
     bool bad = (tile == fail_tile);
@@ -916,7 +622,7 @@ __global__ __launch_bounds__(OS_THREADS) void os_pass_kernel(const uint64_t *__r
     if (leader) os_store(gmine, bad ? OS_ERR : ((g == 0 ? OS_INCL : OS_PART) | ((sum_in + tot) & OS_VALUE)));
     OS_STAMP(4);
 #pragma unroll
-    for (int r = ROUNDS / 2; r < ROUNDS; ++r) rank_round(r);
+    for (int r = ROUNDS / 2; r < ROUNDS; ++r) (void)rank_round_to_lds(wbase + r * 64 + lane < n, key[r], val[r], dig[r], bits, wcnt[wid], skey, sval);
     OS_STAMP(5);
     // phase 4b: ... and in the groups before it
     uint32_t gs = 0;
@@ -958,17 +664,16 @@ __global__ __launch_bounds__(OS_THREADS) void os_pass_kernel(const uint64_t *__r
     OS_STAMP(7);
 }
 
+// The form the sort takes, for tests and tools (raht.h: raht_debug_sort_form). Process-wide; a sort reads it once, on entry.
+static std::atomic<int> g_form_onesweep{1}, g_form_rounds{0};
+static std::atomic<int64_t> g_form_fail_tile{-1};
+
 // Items per lane of a tile: the smallest tile whose tile count still fits the chip at once (2048 items: five tiles per CU,
 // 3072 / 4096: three) -- more, smaller tiles overlap their phases better, but a tile that has to wait for a second round of
-// workgroups costs a whole tile lifetime. RAHT_SORT_ROUNDS = 8 / 12 / 16 pins it.
+// workgroups costs a whole tile lifetime. raht_debug_sort_form pins it to 8 / 12 / 16.
 static int os_rounds(int64_t n)
 {
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("RAHT_SORT_ROUNDS");
-        forced = e ? atoi(e) : 0;
-        if (forced != 8 && forced != 12 && forced != 16) forced = 0;
-    }
+    const int forced = g_form_rounds.load(std::memory_order_relaxed);
     if (forced) return forced;
     static int cus[RAHT_MAX_DEVICES] = {};
     const int dev = current_device();
@@ -981,47 +686,30 @@ static int os_rounds(int64_t n)
     return 16;
 }
 
-static bool sort_onesweep_enabled()
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("RAHT_SORT_ONESWEEP"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
-
 template <int ROUNDS>
 static void os_launch_pass(const uint64_t *kin, const uint32_t *vin, uint64_t *kout, uint32_t *vout, int64_t n, int shift, int bits,
-                           const uint32_t *slices, uint32_t *state, uint32_t *gstate, uint32_t *ticket, uint32_t *err, int64_t *v64, hipStream_t s)
+                           const uint32_t *slices, uint32_t *state, uint32_t *gstate, uint32_t *err, int64_t *v64, uint32_t fail_tile, hipStream_t s)
 {
     const unsigned nt = (unsigned)ceil_div(n, (int64_t)OS_WAVES * 64 * ROUNDS);
-    static int tk = -1;
-    static uint32_t fail_tile = 0xffffffffu;
-    if (tk < 0) {
-        const char *e = getenv("RAHT_SORT_TICKET"); tk = (e && e[0] == '1') ? 1 : 0;
-        const char *f = getenv("RAHT_SORT_DEBUG_FAIL_TILE"); if (f) fail_tile = (uint32_t)strtoul(f, nullptr, 10);
-    }
-    if (tk) {
-        if (vin)
-            hipLaunchKernelGGL((os_pass_kernel<ROUNDS, true, true>), dim3(nt), dim3(OS_THREADS), 0, s, kin, vin, kout, vout, n, shift, bits, slices, state, gstate, ticket, err, v64, fail_tile);
-        else
-            hipLaunchKernelGGL((os_pass_kernel<ROUNDS, false, true>), dim3(nt), dim3(OS_THREADS), 0, s, kin, vin, kout, vout, n, shift, bits, slices, state, gstate, ticket, err, v64, fail_tile);
-    } else {
-        if (vin)
-            hipLaunchKernelGGL((os_pass_kernel<ROUNDS, true, false>), dim3(nt), dim3(OS_THREADS), 0, s, kin, vin, kout, vout, n, shift, bits, slices, state, gstate, ticket, err, v64, fail_tile);
-        else
-            hipLaunchKernelGGL((os_pass_kernel<ROUNDS, false, false>), dim3(nt), dim3(OS_THREADS), 0, s, kin, vin, kout, vout, n, shift, bits, slices, state, gstate, ticket, err, v64, fail_tile);
-    }
+    if (vin)
+        hipLaunchKernelGGL((os_pass_kernel<ROUNDS, true>), dim3(nt), dim3(OS_THREADS), 0, s, kin, vin, kout, vout, n, shift, bits, slices, state, gstate, err, v64, fail_tile);
+    else
+        hipLaunchKernelGGL((os_pass_kernel<ROUNDS, false>), dim3(nt), dim3(OS_THREADS), 0, s, kin, vin, kout, vout, n, shift, bits, slices, state, gstate, err, v64, fail_tile);
 }
 
-// Stable sort of (key, original index) by the low `nbits` key bits. tmp_keys / tmp_idx: N-sized ping-pong buffers (unused
-// when one pass is enough). err_dev: device word, zeroed here and set when a tile gave up waiting (the caller reads it back
-// with whatever it reads back anyway, once the stream has drained). Returns 1 when the input does not fit this form (the
-// caller then uses the pass-by-pass sort).
-int sort_pairs_onesweep(const uint64_t *keys_in, int64_t n, int nbits, uint64_t *keys_out, uint32_t *idx_out, uint64_t *tmp_keys,
-                        uint32_t *tmp_idx, uint32_t *err_dev, hipStream_t s, int64_t *idx64_out, const VoxGrid *grid)
+// The whole stable sort of (key, original index) by the low nbits key bits in npass + 2 launches (above). tmp_keys / tmp_idx:
+// N-sized ping-pong buffers (unused when one pass is enough). err_dev: device word, zeroed by the first launch and set when a
+// tile gave up waiting for its predecessors (the caller reads it back with whatever it reads back anyway, once the stream has
+// drained). Returns 1 (nothing enqueued) when the input does not fit this form (more than 8 digit passes, N >= 2^30) or
+// raht_debug_sort_form has switched it off: the caller then uses the pass-by-pass sort. idx64_out (may be NULL): the indices
+// once more as int64, written by the last pass. grid (may be NULL): keys_in is not an input but the voxel keys of the cloud's
+// points (raht_device.h: vox_key), which the histogram launch computes AND stores there on its way.
+static int sort_pairs_onesweep(const uint64_t *keys_in, int64_t n, int nbits, uint64_t *keys_out, uint32_t *idx_out, uint64_t *tmp_keys,
+                               uint32_t *tmp_idx, uint32_t *err_dev, hipStream_t s, int64_t *idx64_out, const VoxGrid *grid)
 {
     if (n <= 0) return RAHT_OK;
     const int npass = std::max(1, (nbits + 7) / 8);
-    if (npass > OS_MAX_PASSES || n >= ((int64_t)1 << 30) || !err_dev || !sort_onesweep_enabled()) return 1;
+    if (npass > OS_MAX_PASSES || n >= ((int64_t)1 << 30) || !err_dev || !g_form_onesweep.load(std::memory_order_relaxed)) return 1;
     OsPasses P;
     P.npass = npass;
     for (int p = 0, sh = 0; p < OS_MAX_PASSES; ++p) {
@@ -1031,20 +719,20 @@ int sort_pairs_onesweep(const uint64_t *keys_in, int64_t n, int nbits, uint64_t 
         if (p < npass) sh += b;
     }
     const int R = os_rounds(n);
+    const int64_t fail = g_form_fail_tile.load(std::memory_order_relaxed);
+    const uint32_t fail_tile = fail < 0 ? 0xffffffffu : (uint32_t)fail;
     const int64_t ntiles = ceil_div(n, (int64_t)OS_WAVES * 64 * R);
     // (from the cloud: every point costs a 128-byte line, the launch is bound by loads in flight -- more, shorter blocks)
-    static int hb_cloud = 0;
-    if (!hb_cloud) { const char *e = getenv("RAHT_SORT_CLOUD_BLOCKS"); hb_cloud = e ? std::max(1, atoi(e)) : 4 * OS_HIST_BLOCKS; }
-    const int hb = (int)std::min<int64_t>(ceil_div(n, OS_THREADS * 16), grid ? hb_cloud : OS_HIST_BLOCKS);
-    // [ tickets (npass) | tile and group words (npass x (ntiles + ngroups) x 256) ] zeroed by the histogram launch, then partial, slices
+    const int hb = (int)std::min<int64_t>(ceil_div(n, OS_THREADS * 16), grid ? 4 * OS_HIST_BLOCKS : OS_HIST_BLOCKS);
+    // [ tile and group words (npass x (ntiles + ngroups) x 256) ] zeroed by the histogram launch, then partial, slices
     const int64_t ngroups = ceil_div(ntiles, (int64_t)OS_GROUP);
-    const int64_t n_zero = OS_MAX_PASSES + (int64_t)npass * (ntiles + ngroups) * 256;
+    const int64_t n_zero = (int64_t)npass * (ntiles + ngroups) * 256;
     Scratch ws(sizeof(uint32_t) * ((size_t)n_zero + (size_t)hb * npass * 256 + (size_t)npass * OS_SLICES * 256), s);
     if (!ws.ok()) return RAHT_ERR_NOMEM;
-    uint32_t *ticket = ws.as<uint32_t>(), *state = ticket + OS_MAX_PASSES, *err = err_dev;
-    uint32_t *partial = ticket + n_zero, *slices = partial + (size_t)hb * npass * 256;
-    if (grid) hipLaunchKernelGGL(os_hist_kernel<true>, dim3(hb), dim3(OS_THREADS), 0, s, (uint64_t *)keys_in, n, P, partial, ticket, n_zero, err, *grid);
-    else hipLaunchKernelGGL(os_hist_kernel<false>, dim3(hb), dim3(OS_THREADS), 0, s, (uint64_t *)keys_in, n, P, partial, ticket, n_zero, err, VoxGrid{});
+    uint32_t *state = ws.as<uint32_t>(), *err = err_dev;
+    uint32_t *partial = state + n_zero, *slices = partial + (size_t)hb * npass * 256;
+    if (grid) hipLaunchKernelGGL(os_hist_kernel<true>, dim3(hb), dim3(OS_THREADS), 0, s, (uint64_t *)keys_in, n, P, partial, state, n_zero, err, *grid);
+    else hipLaunchKernelGGL(os_hist_kernel<false>, dim3(hb), dim3(OS_THREADS), 0, s, (uint64_t *)keys_in, n, P, partial, state, n_zero, err, VoxGrid{});
     hipLaunchKernelGGL(os_base_kernel, dim3(npass * OS_SLICES), dim3(OS_THREADS), 0, s, partial, hb, npass, slices);
     const uint64_t *kin = keys_in;
     const uint32_t *vin = nullptr;
@@ -1054,14 +742,91 @@ int sort_pairs_onesweep(const uint64_t *keys_in, int64_t n, int nbits, uint64_t 
         uint32_t *vo = to_out ? idx_out : tmp_idx;
         uint32_t *st = state + (size_t)ps * (ntiles + ngroups) * 256, *gst = st + (size_t)ntiles * 256;
         const uint32_t *sl = slices + (size_t)ps * OS_SLICES * 256;
-        if (R == 8) os_launch_pass<8>(kin, vin, ko, vo, n, P.shift[ps], P.bits[ps], sl, st, gst, ticket + ps, err, ps == npass - 1 ? idx64_out : nullptr, s);
-        else if (R == 12) os_launch_pass<12>(kin, vin, ko, vo, n, P.shift[ps], P.bits[ps], sl, st, gst, ticket + ps, err, ps == npass - 1 ? idx64_out : nullptr, s);
-        else os_launch_pass<16>(kin, vin, ko, vo, n, P.shift[ps], P.bits[ps], sl, st, gst, ticket + ps, err, ps == npass - 1 ? idx64_out : nullptr, s);
+        int64_t *v64 = ps == npass - 1 ? idx64_out : nullptr;
+        if (R == 8) os_launch_pass<8>(kin, vin, ko, vo, n, P.shift[ps], P.bits[ps], sl, st, gst, err, v64, fail_tile, s);
+        else if (R == 12) os_launch_pass<12>(kin, vin, ko, vo, n, P.shift[ps], P.bits[ps], sl, st, gst, err, v64, fail_tile, s);
+        else os_launch_pass<16>(kin, vin, ko, vo, n, P.shift[ps], P.bits[ps], sl, st, gst, err, v64, fail_tile, s);
         kin = ko;
         vin = vo;
     }
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The sort's host driver: one-sweep form first, pass-by-pass form when that does not apply or gave up.
+// ------------------------------------------------------------------------------------------------
+// Voxel keys of a cloud's points. Every load instruction of a wave touches 64 different 128-byte lines here (row stride 236
+// bytes at d = 56): the kernel moves one line per point (384 MB on 3 M points) whatever the instruction mix -- 126 us with three
+// dword loads per row and with one dwordx3 alike (3 TB/s of lines for 36 MB of coordinates). Only a layout with the positions
+// apart from the attributes would change that, and the reference's PC matrix is the boundary. (raht_voxelize computes its keys
+// inside the one-sweep form's histogram launch, os_hist_kernel<true>; this kernel serves raht_voxel_keys and the pass-by-pass
+// form.)
+__global__ __launch_bounds__(256) void vox_keys_kernel(const VoxGrid G, int64_t N, uint64_t *__restrict__ keys)
+{
+    constexpr int U = 4;                                             // rows per thread: four independent loads in flight
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x) * U + threadIdx.x;
+    Xyz p[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t i = min(i0 + (int64_t)u * blockDim.x, N - 1);
+        p[u] = *(const Xyz *)(G.PC + i * G.ld);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t i = i0 + (int64_t)u * blockDim.x;
+        if (i < N) keys[i] = vox_key(p[u], G);
+    }
+}
+
+int vox_keys(const VoxGrid &grid, int64_t N, uint64_t *keys, hipStream_t s)
+{
+    hipLaunchKernelGGL(vox_keys_kernel, dim3((unsigned)ceil_div(N, 256 * 4)), dim3(256), 0, s, grid, N, keys);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+__global__ void u32_to_i64_kernel(const uint32_t *__restrict__ in, int64_t n, int64_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (int64_t)in[i];
+}
+
+// How often a one-sweep sort gave up (a tile's bounded wait for its predecessors ran out) and the call repeated the sort pass
+// by pass: raht_sort_fallbacks(). Expected to stay 0; the result of the call is correct either way.
+static std::atomic<int64_t> g_sort_fallbacks{0};
+void note_sort_fallback() { g_sort_fallbacks.fetch_add(1, std::memory_order_relaxed); }
+
+int sort_keys_u32idx(const uint64_t *keys_in, int64_t N, int nbits, uint64_t *keys_out, uint32_t *idx_out, hipStream_t s,
+                     uint32_t *sort_err, int64_t *idx64_out, const VoxGrid *grid, bool onesweep)
+{
+    // LSD passes of 8 bits; ping-pong between two (key, index) buffers, last pass lands in *_out
+    const int npass = std::max(1, (nbits + 7) / 8);
+    Scratch tmp(npass > 1 ? (sizeof(uint64_t) + sizeof(uint32_t)) * (size_t)N : 16, s);
+    if (!tmp.ok()) return RAHT_ERR_NOMEM;
+    uint64_t *ktmp = tmp.as<uint64_t>();
+    uint32_t *itmp = (uint32_t *)(ktmp + N);
+    if (sort_err) {
+        const int rc1 = onesweep ? sort_pairs_onesweep(keys_in, N, nbits, keys_out, idx_out, ktmp, itmp, sort_err, s, idx64_out, grid) : 1;
+        if (rc1 <= 0) return rc1;                        // enqueued (or failed); 1 = not applicable
+        RAHT_HIP_CHECK(hipMemsetAsync(sort_err, 0, sizeof(uint32_t), s));
+    }
+    if (grid) RAHT_RET(vox_keys(*grid, N, (uint64_t *)keys_in, s));
+    const uint64_t *kin = keys_in;
+    const uint32_t *iin = nullptr;
+    int rc = RAHT_OK;
+    for (int ps = 0; ps < npass && rc == RAHT_OK; ++ps) {
+        const bool to_out = ((npass - 1 - ps) % 2 == 0);
+        uint64_t *ko = to_out ? keys_out : ktmp;
+        uint32_t *io = to_out ? idx_out : itmp;
+        const int bits = std::min(8, nbits - 8 * ps);
+        rc = radix_pass_impl<uint64_t>(kin, iin, ko, io, N, 8 * ps, bits < 1 ? 1 : bits, nullptr, s);
+        kin = ko;
+        iin = io;
+    }
+    if (rc == RAHT_OK && idx64_out)
+        hipLaunchKernelGGL(u32_to_i64_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, idx_out, N, idx64_out);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1180,100 +945,57 @@ int run_starts_u64(const uint64_t *keys_sorted, int64_t n, uint32_t *starts, int
     return RAHT_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Small device -> host read-backs through a polled mailbox in mapped pinned memory.
-// ------------------------------------------------------------------------------------------------
-static constexpr int MAILBOX_WORDS = 192;
+}  // namespace raht
 
-__global__ void __launch_bounds__(64) mailbox_publish_kernel(const uint32_t *__restrict__ a, int na,
-                                                             const uint32_t *__restrict__ b, int nb,
-                                                             volatile uint32_t *box, uint32_t seq)
+using namespace raht;
+
+extern "C" {
+
+int raht_sort_keys(const uint64_t *keys_in, int64_t N, int nbits, uint64_t *keys_out, int64_t *idx_out,
+                   raht_stream_t stream)
 {
-    // one wave: the data stores are complete (system scope) before lane 0 raises the sequence word
-    for (int t = threadIdx.x; t < na; t += 64) box[1 + t] = a[t];
-    for (int t = threadIdx.x; t < nb; t += 64) box[1 + na + t] = b[t];
-    __threadfence_system();
-    if (threadIdx.x == 0) box[0] = seq;
-}
-
-struct Mailbox {
-    std::mutex mu;
-    uint32_t *box = nullptr;      // [0] = sequence word, [1 ..] = payload
-    uint32_t seq = 0;
-};
-static Mailbox &mailbox() { static Mailbox m; return m; }
-
-int read_back_u32(uint32_t *dst_a, const uint32_t *dev_a, int na, uint32_t *dst_b, const uint32_t *dev_b, int nb,
-                  hipStream_t s, const std::function<void()> &behind)
-{
-    bool behind_called = false;
-    if (na < 0 || nb < 0 || na + nb > MAILBOX_WORDS) { set_error("read_back_u32: too many words"); return RAHT_ERR_INVALID; }
-    Mailbox &m = mailbox();
-    std::lock_guard<std::mutex> g(m.mu);
-    if (!m.box) {
-        // portable + mapped + coherent: the same pointer is valid on the host and on every device
-        if (hipHostMalloc((void **)&m.box, sizeof(uint32_t) * (MAILBOX_WORDS + 1),
-                          hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-            m.box = nullptr;
-            (void)hipGetLastError();
-        } else {
-            m.box[0] = 0;
-        }
-    }
-    bool done = false;
-    if (m.box) {
-        const uint32_t seq = ++m.seq ? m.seq : ++m.seq;            // never 0
-        hipLaunchKernelGGL(mailbox_publish_kernel, dim3(1), dim3(64), 0, s, dev_a, na, dev_b, nb, m.box, seq);
-        if (hipGetLastError() == hipSuccess) {
-            if (behind) { behind(); behind_called = true; }
-            volatile uint32_t *flag = m.box;
-            for (uint32_t it = 1;; ++it) {
-                if (*flag == seq) { done = true; break; }
-                if ((it & 0xfffu) == 0) {
-                    // a failed or finished stream ends the wait even if the word never arrives
-                    const hipError_t q = hipStreamQuery(s);
-                    if (q != hipErrorNotReady) { done = (q == hipSuccess && *flag == seq); break; }
-                }
-                __builtin_ia32_pause();
-            }
-            if (done) {
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                for (int t = 0; t < na; ++t) dst_a[t] = flag[1 + t];
-                for (int t = 0; t < nb; ++t) dst_b[t] = flag[1 + na + t];
-            }
-        }
-    }
-    if (!done) {                                                     // no mailbox / stream error: the plain way
-        if (behind && !behind_called) behind();
-        hipError_t e = hipSuccess;
-        if (na) e = hipMemcpyAsync(dst_a, dev_a, sizeof(uint32_t) * (size_t)na, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && nb) e = hipMemcpyAsync(dst_b, dev_b, sizeof(uint32_t) * (size_t)nb, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_error("read-back: %s", hipGetErrorString(e)); return RAHT_ERR_HIP; }
+    // an empty input is valid and needs no buffers (an empty device tensor's data pointer is NULL): ranks of a sharded scene
+    // may hold no points, and must reach the next collective like every other rank
+    if (N < 0 || nbits < 1 || nbits > 64) { set_error("raht_sort_keys: bad argument"); return RAHT_ERR_INVALID; }
+    if (N == 0) return RAHT_OK;
+    if (!keys_in || !keys_out) { set_error("raht_sort_keys: NULL argument"); return RAHT_ERR_INVALID; }
+    if (N >= ((int64_t)1 << 31)) { set_error("raht_sort_keys: N too large"); return RAHT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch ib(sizeof(uint32_t) * ((size_t)N + 1), s);
+    if (!ib.ok()) return RAHT_ERR_NOMEM;
+    uint32_t *idx32 = ib.as<uint32_t>(), *sort_err = idx32 + N;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        RAHT_RET(sort_keys_u32idx(keys_in, N, nbits, keys_out, idx32, s, sort_err, idx_out, nullptr, attempt == 0));
+        RAHT_HIP_CHECK(hipGetLastError());
+        // idx32 returns to the pool when this frame ends: the read-back of the sort's error word is also the wait for the stream
+        uint32_t bad = 0;
+        RAHT_RET(read_back_u32(&bad, sort_err, 1, nullptr, nullptr, 0, s));
+        if (!bad) break;
+        note_sort_fallback();
     }
     return RAHT_OK;
 }
 
-}  // namespace raht
+int64_t raht_sort_fallbacks(void) { return g_sort_fallbacks.load(std::memory_order_relaxed); }
+
+int raht_debug_sort_form(int onesweep, int rounds, int64_t fail_tile)
+{
+    if ((rounds != 0 && rounds != 8 && rounds != 12 && rounds != 16) || fail_tile >= ((int64_t)1 << 24)) {
+        set_error("raht_debug_sort_form: rounds must be 0, 8, 12 or 16 and fail_tile below 2^24");
+        return RAHT_ERR_INVALID;
+    }
+    const int prev_onesweep = g_form_onesweep.exchange(onesweep ? 1 : 0);
+    const int prev_rounds = g_form_rounds.exchange(rounds);
+    const int64_t prev_fail = g_form_fail_tile.exchange(fail_tile < 0 ? -1 : fail_tile);
+    return prev_onesweep | prev_rounds << 1 | (int)(prev_fail + 1) << 6;
+}
 
 #ifdef RAHT_OS_CLOCKS
-extern "C" int raht_debug_sort_clocks(unsigned long long *host_out, int n_tiles, int shift)
+int raht_debug_sort_clocks(unsigned long long *host_out, int n_tiles, int shift)
 {
     if (shift >= 0) return hipMemcpyToSymbol(HIP_SYMBOL(raht::os_dbg_shift), &shift, sizeof(int)) == hipSuccess ? 0 : -4;
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(raht::os_dbg), sizeof(unsigned long long) * 8 * (size_t)n_tiles) == hipSuccess ? 0 : -4;
 }
 #endif
 
-extern "C" int raht_release_cached_memory(void)
-{
-    auto &c = raht::dev_cache();
-    std::vector<void *> blocks;
-    {
-        std::lock_guard<std::mutex> g(c.mu);
-        for (auto &kv : c.free_blocks) blocks.push_back(kv.second);
-        c.free_blocks.clear();
-        c.cached = 0;
-    }
-    for (void *q : blocks) (void)hipFree(q);
-    return RAHT_OK;
-}
+}  // extern "C"

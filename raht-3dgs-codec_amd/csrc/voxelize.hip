@@ -3,7 +3,6 @@
 // Replaces voxelize_pc_batched (reference python/voxelize_pc.py:62-172). Float32 arithmetic, as
 // torch performs it on a float32 point cloud; integer outputs are bit-exact.
 #include "raht_common.h"
-#include <atomic>
 #include "raht_device.h"
 
 #include <algorithm>
@@ -46,29 +45,6 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float *__restrict__ P
         float v = sm[0][threadIdx.x];
         for (int w = 1; w < 4; ++w) v = (threadIdx.x < 3) ? fminf(v, sm[w][threadIdx.x]) : fmaxf(v, sm[w][threadIdx.x]);
         part[blockIdx.x * 4 + threadIdx.x] = v;
-    }
-}
-
-// ---- keys --------------------------------------------------------------------------------------
-// Every load instruction of a wave touches 64 different 128-byte lines here (row stride 236 bytes at d = 56): the kernel
-// moves one line per point (384 MB on 3 M points) whatever the instruction mix -- 126 us with three dword loads per row and
-// with one dwordx3 alike (3 TB/s of lines for 36 MB of coordinates). Only a layout with the positions apart from the
-// attributes would change that, and the reference's PC matrix is the boundary. (raht_voxelize computes its keys inside the
-// sort's histogram launch -- scan_sort.hip, os_hist_kernel<true> -- this kernel serves raht_voxel_keys.)
-__global__ __launch_bounds__(256) void vox_keys_kernel(const VoxGrid G, int64_t N, uint64_t *__restrict__ keys)
-{
-    constexpr int U = 4;                                             // rows per thread: four independent loads in flight
-    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x) * U + threadIdx.x;
-    Xyz p[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = min(i0 + (int64_t)u * blockDim.x, N - 1);
-        p[u] = *(const Xyz *)(G.PC + i * G.ld);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = i0 + (int64_t)u * blockDim.x;
-        if (i < N) keys[i] = vox_key(p[u], G);
     }
 }
 
@@ -153,12 +129,6 @@ __global__ __launch_bounds__(256) void residual_chunk_kernel(const float *__rest
             }
         }
     }
-}
-
-__global__ void u32_to_i64_kernel(const uint32_t *__restrict__ in, int64_t n, int64_t *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (int64_t)in[i];
 }
 
 // Per-voxel attribute mean. A wave takes 16 voxels per iteration: lanes fetch the 16 (+1) voxel
@@ -329,80 +299,11 @@ __global__ __launch_bounds__(256) void voxel_full_chunk_kernel(const float *__re
     }
 }
 
-// How often a one-sweep sort gave up (a tile's bounded wait for its predecessors ran out) and the call repeated the sort pass
-// by pass: raht_sort_fallbacks(). Expected to stay 0; the result of the call is correct either way.
-static std::atomic<int64_t> g_sort_fallbacks{0};
-
-// Stable sort of (key, original index). `sort_err` (device word, may be NULL) selects the one-sweep form
-// (scan_sort.hip: npass + 2 launches); the caller checks the word once the stream has drained and repeats the call with
-// onesweep = false -- the pass-by-pass form, four launches per digit; the word is cleared -- in the never-seen case that it is set.
-// `grid` (may be NULL): keys_in is an OUTPUT as well -- the keys of the cloud's points, computed on the way (inside the
-// one-sweep form's histogram launch, or by vox_keys_kernel in front of the pass-by-pass form).
-static int sort_keys_u32idx(const uint64_t *keys_in, int64_t N, int nbits, uint64_t *keys_out,
-                                  uint32_t *idx_out, hipStream_t s, uint32_t *sort_err = nullptr, int64_t *idx64_out = nullptr,
-                                  const VoxGrid *grid = nullptr, bool onesweep = true)
-{
-    // LSD passes of 8 bits; ping-pong between two (key, index) buffers, last pass lands in *_out
-    const int npass = std::max(1, (nbits + 7) / 8);
-    Scratch tmp(npass > 1 ? (sizeof(uint64_t) + sizeof(uint32_t)) * (size_t)N : 16, s);
-    if (!tmp.ok()) return RAHT_ERR_NOMEM;
-    uint64_t *ktmp = tmp.as<uint64_t>();
-    uint32_t *itmp = (uint32_t *)(ktmp + N);
-    if (sort_err) {
-        const int rc1 = onesweep ? sort_pairs_onesweep(keys_in, N, nbits, keys_out, idx_out, ktmp, itmp, sort_err, s, idx64_out, grid) : 1;
-        if (rc1 <= 0) return rc1;                        // enqueued (or failed); 1 = not applicable
-        RAHT_HIP_CHECK(hipMemsetAsync(sort_err, 0, sizeof(uint32_t), s));
-    }
-    if (grid) hipLaunchKernelGGL(vox_keys_kernel, dim3((unsigned)ceil_div(N, 256 * 4)), dim3(256), 0, s, *grid, N, (uint64_t *)keys_in);
-    const uint64_t *kin = keys_in;
-    const uint32_t *iin = nullptr;
-    int rc = RAHT_OK;
-    for (int ps = 0; ps < npass && rc == RAHT_OK; ++ps) {
-        const bool to_out = ((npass - 1 - ps) % 2 == 0);
-        uint64_t *ko = to_out ? keys_out : ktmp;
-        uint32_t *io = to_out ? idx_out : itmp;
-        const int bits = std::min(8, nbits - 8 * ps);
-        rc = radix_pass_u64(kin, iin, ko, io, N, 8 * ps, bits < 1 ? 1 : bits, s);
-        kin = ko;
-        iin = io;
-    }
-    if (rc == RAHT_OK && idx64_out)
-        hipLaunchKernelGGL(u32_to_i64_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, idx_out, N, idx64_out);
-    return rc;
-}
-
 }  // namespace raht
 
 using namespace raht;
 
 extern "C" {
-
-int raht_sort_keys(const uint64_t *keys_in, int64_t N, int nbits, uint64_t *keys_out, int64_t *idx_out,
-                   raht_stream_t stream)
-{
-    // an empty input is valid and needs no buffers (an empty device tensor's data pointer is NULL): ranks of a sharded scene
-    // may hold no points, and must reach the next collective like every other rank
-    if (N < 0 || nbits < 1 || nbits > 64) { set_error("raht_sort_keys: bad argument"); return RAHT_ERR_INVALID; }
-    if (N == 0) return RAHT_OK;
-    if (!keys_in || !keys_out) { set_error("raht_sort_keys: NULL argument"); return RAHT_ERR_INVALID; }
-    if (N >= ((int64_t)1 << 31)) { set_error("raht_sort_keys: N too large"); return RAHT_ERR_INVALID; }
-    hipStream_t s = (hipStream_t)stream;
-    Scratch ib(sizeof(uint32_t) * ((size_t)N + 1), s);
-    if (!ib.ok()) return RAHT_ERR_NOMEM;
-    uint32_t *idx32 = ib.as<uint32_t>(), *sort_err = idx32 + N;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        RAHT_RET(sort_keys_u32idx(keys_in, N, nbits, keys_out, idx32, s, sort_err, idx_out, nullptr, attempt == 0));
-        RAHT_HIP_CHECK(hipGetLastError());
-        // idx32 returns to the pool when this frame ends: the read-back of the sort's error word is also the wait for the stream
-        uint32_t bad = 0;
-        RAHT_RET(read_back_u32(&bad, sort_err, 1, nullptr, nullptr, 0, s));
-        if (!bad) break;
-        g_sort_fallbacks.fetch_add(1, std::memory_order_relaxed);
-    }
-    return RAHT_OK;
-}
-
-int64_t raht_sort_fallbacks(void) { return g_sort_fallbacks.load(std::memory_order_relaxed); }
 
 int raht_voxel_keys(const float *PC, int64_t ldpc, int64_t N, const float vmin[3], double width, int J,
                     uint64_t *keys, raht_stream_t stream)
@@ -413,9 +314,7 @@ int raht_voxel_keys(const float *PC, int64_t ldpc, int64_t N, const float vmin[3
     if (!PC || !keys || ldpc < 3) { set_error("raht_voxel_keys: bad argument"); return RAHT_ERR_INVALID; }
     const float vs = (float)(width / (double)((uint64_t)1 << J));        // voxelize_pc.py:97, as raht_voxelize
     const VoxGrid G = {PC, ldpc, vmin[0], vmin[1], vmin[2], vs, J};
-    hipLaunchKernelGGL(vox_keys_kernel, dim3((unsigned)ceil_div(N, 256 * 4)), dim3(256), 0, (hipStream_t)stream, G, N, keys);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return vox_keys(G, N, keys, (hipStream_t)stream);
 }
 
 int raht_voxelize_residuals(const float *PC, int64_t ldpc, int64_t N, int d, const uint64_t *keys_sorted,
@@ -637,7 +536,7 @@ static int voxelize_impl(const float *PC, int64_t ldpc, int64_t N, int d, const 
             RAHT_RET(read_back_u32(back, sort_err, 2, nullptr, nullptr, 0, s));
             nv = back[1];
             if (!back[0]) break;                             // (else: once more with the pass-by-pass sort)
-            g_sort_fallbacks.fetch_add(1, std::memory_order_relaxed);
+            note_sort_fallback();
         }
         if (want_res && !fused) {
             // narrow clouds: the two-call sequence (sort_idx as int64 is what raht_voxelize_residuals takes)

@@ -1029,31 +1029,66 @@ def test_voxelize_plan_feeds_the_plan_from_the_voxelizers_keys(rt, oracle):
     assert torch.equal(plan.inverse(T0), rt.plan_of(ListC).inverse(T0))
 
 
-# ---- the key sort in its three forms (csrc/scan_sort.hip) --------------------------------------------------------------
+# ---- the key sort in its forms (csrc/scan_sort.hip) ---------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{}, {"RAHT_SORT_TICKET": "1"}, {"RAHT_SORT_ONESWEEP": "0"}, {"RAHT_SORT_ROUNDS": "8"}, {"RAHT_SORT_ROUNDS": "12"},
-                                 {"RAHT_SORT_DEBUG_FAIL_TILE": "0"}, {"RAHT_SORT_DEBUG_FAIL_TILE": "37"}],
-                         ids=["one-sweep", "one-sweep, ticketed tiles", "pass by pass", "2048-item tiles", "3072-item tiles",
+@pytest.mark.parametrize("form", [dict(), dict(onesweep=0), dict(rounds=8), dict(rounds=12), dict(fail_tile=0), dict(fail_tile=37)],
+                         ids=["one-sweep", "pass by pass", "2048-item tiles", "3072-item tiles",
                               "tile 0 gives up -> fallback", "tile 37 gives up -> fallback"])
-def test_key_sort_forms_equal_a_stable_sort(env):
+def test_key_sort_forms_equal_a_stable_sort(form):
     """raht_sort_keys == torch.sort(stable=True), keys AND permutation, for sizes around the tile edges (1 ... 3 000 017), every
-    digit-pass count (1 ... 63 key bits) and inputs full of duplicates -- in the default one-sweep form (tiles numbered by
-    workgroup index), with ticketed tiles, and in the pass-by-pass form the library falls back to; and with one tile of every
-    one-sweep pass made to give up (RAHT_SORT_DEBUG_FAIL_TILE): the tiles after it pass the error on and write nothing, the grid
-    drains, the host finds the error word and repeats the sort pass by pass -- same results, and the voxelizer (whose mean
-    kernel is enqueued BEHIND the sort without a host round trip) must not gather through the stale indices. The knobs are read
-    once per process: each form runs tools/check_sort.py in its own interpreter."""
-    import subprocess
-    import sys
+    digit-pass count (1 ... 63 key bits) and inputs full of duplicates -- in the default one-sweep form, with the tile size
+    pinned, and in the pass-by-pass form the library falls back to; and with one tile of every one-sweep pass made to give up:
+    the tiles after it pass the error on and write nothing, the grid drains, the host finds the error word and repeats the
+    sort pass by pass -- same results, and the voxelizer (whose mean kernel is enqueued BEHIND the sort without a host round
+    trip) must not gather through the stale indices. The form is set through raht_debug_sort_form (tools/check_sort.py does
+    that and restores the previous form in a finally)."""
+    import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_sort.py")], env={**os.environ, **env}, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "correctness: 0 mismatches" in r.stdout
-    # raht_sort_fallbacks(): 0 unless a tile was made to give up (then > 0: the fallback is observable, not silent)
-    if "RAHT_SORT_DEBUG_FAIL_TILE" in env:
-        assert "sort fallbacks: 0" not in r.stdout
+    spec = importlib.util.spec_from_file_location("check_sort", os.path.join(root, "tools", "check_sort.py"))
+    check_sort = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(check_sort)
+    from raht_3dgs_codec_amd import _lib
+    form_before = _lib.lib().raht_debug_sort_form(1, 0, -1)
+    try:
+        log = []
+        bad, grown = check_sort.check(out=log.append, **form)
+    finally:
+        _lib.lib().raht_debug_sort_form(form_before & 1, (form_before >> 1) & 31, (form_before >> 6) - 1)
+    assert bad == 0, "\n".join(log[-20:])
+    # raht_sort_fallbacks(): unchanged unless a tile was made to give up (then it has grown: the fallback is observable, not
+    # silent). The counter is process-wide: its growth over the form is what counts.
+    if "fail_tile" in form:
+        assert grown > 0
     else:
-        assert "sort fallbacks: 0" in r.stdout
+        assert grown == 0
+
+
+@pytest.fixture(scope="module")
+def big_scan_keys():
+    """sorted unique keys for the scans of more than 2048 blocks, and the binary level of every row (numpy)"""
+    from tests.numpy_ops import _msb
+    n = 2048 * 2048 + 2049
+    keys = np.cumsum(np.random.default_rng(2048).integers(1, 200, size=n, dtype=np.int64)).astype(np.uint64)
+    lvl = np.full(n, 255, dtype=np.int64)
+    lvl[1:] = _msb(keys[1:] ^ keys[:-1])
+    return keys, lvl
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [2048 * 2048, 2048 * 2048 + 2049], ids=["2048 blocks: the last fused size", "2049 blocks + 1 item: two levels"])
+def test_root_rows_of_a_plan_past_the_fused_scan(rt, big_scan_keys, n):
+    """The root rows of a truncated plan come from compact_u32: a 32-bit exclusive scan of N flags with its total read back.
+    Up to 2048 blocks of 2048 items the scan is block + finish; one item into the third block past that it is block, a scan of
+    the block sums in place (whose total is the grand total) and add. Integers: equal to the numpy model, row for row."""
+    import torch
+    keys, lvl = big_scan_keys
+    keys, lvl = keys[:n], lvl[:n]
+    top = int(np.median(lvl[1:]))
+    want = np.nonzero((np.arange(n) == 0) | (lvl >= top))[0]
+    assert 0.2 * n < want.shape[0] < 0.9 * n              # flags on both sides of every block boundary
+    p = rt.RahtPlan.from_keys(torch.from_numpy(keys.view(np.int64)).cuda(), 30, top_level=top)
+    assert p.n_roots == want.shape[0]
+    assert np.array_equal(p.root_rows.cpu().numpy(), want)
 
 
 # ---- raht_dequant_inv_sqdiff: the fused inverse that measures its own distortion (encode_3dgs.py:274,298-310) -----------------

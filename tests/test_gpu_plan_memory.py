@@ -117,3 +117,39 @@ def test_constructions_that_fail_part_way_leave_nothing_behind(rt):
     del small
     gc.collect()
     assert _live() == base
+
+
+def test_a_cache_limit_of_zero_keeps_nothing(rt):
+    """raht_set_cached_memory_limit(0): every block a dropped plan gives back goes to hipFree -- the live count is back where it
+    started and the cache holds nothing that raht_release_cached_memory() could free; with the default limit the same plan
+    leaves its blocks cached. Blocks are counted, never the device's free memory."""
+    import torch
+    from raht_3dgs_codec_amd import _lib
+    L = _lib.lib()
+
+    def build_and_drop():
+        p = rt.RahtPlan.from_keys(torch.from_numpy(_keys(47)).cuda(), NBITS)
+        p.forward(torch.zeros((N, 7), device="cuda"), want_w=False)        # a schedule and its workspaces
+        torch.cuda.synchronize()
+        del p
+        gc.collect()
+
+    gc.collect()
+    _lib.check(L.raht_release_cached_memory())
+    assert L.raht_debug_cached_blocks() == 0
+    base = _live()
+    try:
+        _lib.check(L.raht_set_cached_memory_limit(0))
+        build_and_drop()
+        assert _live() == base
+        assert L.raht_debug_cached_blocks() == 0
+        assert L.raht_set_cached_memory_limit(-1) != 0                   # refused, the limit stays
+        build_and_drop()
+        assert L.raht_debug_cached_blocks() == 0
+    finally:
+        _lib.check(L.raht_set_cached_memory_limit(8 << 30))
+    build_and_drop()
+    assert _live() == base
+    assert L.raht_debug_cached_blocks() > 0
+    _lib.check(L.raht_release_cached_memory())
+    assert L.raht_debug_cached_blocks() == 0

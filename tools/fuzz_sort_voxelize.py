@@ -1,9 +1,12 @@
 """One-off stress of the key sort and the voxelizer on the GPU box: 300 random (size, key width, ordering) sort cases against
 torch.sort(stable=True), 60 random clouds (points, columns, depth, duplicates) against a torch restatement of keys / voxel starts /
-means / residuals. SEED picks the sequence; the sort's knobs (RAHT_SORT_TICKET, RAHT_SORT_ONESWEEP, RAHT_SORT_ROUNDS) apply."""
+means / residuals. SEED picks the sequence; --onesweep 0 / --rounds 8|12|16 pick the sort's form (include/raht.h: raht_debug_sort_form)."""
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.getcwd())
 import raht_3dgs_codec_amd as R
+from raht_3dgs_codec_amd import _lib
+def _arg(name, default): return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+_lib.check(min(_lib.lib().raht_debug_sort_form(_arg("--onesweep", 1), _arg("--rounds", 0), -1), 0))
 rng = np.random.default_rng(int(os.environ.get("SEED", "1")))
 g = torch.Generator(device="cuda"); g.manual_seed(5)
 bad = 0

@@ -2,7 +2,7 @@
 boundaries of every tile of one digit pass, from a library built with -DRAHT_OS_CLOCKS:
   make -C raht-3dgs-codec_amd/csrc EXTRA=-DRAHT_OS_CLOCKS OUT=../lib_variant_osclk.bin BUILD=/tmp/b_osclk
 and swapped in for this run (RAHT_LIB_SWAP=raht-3dgs-codec_amd/lib_variant_osclk.bin copies it over libraht_hip.so in the
-box's scratch copy of the repo)."""
+box's scratch copy of the repo). ROUNDS = 8 / 12 / 16 (default 16) is the tile the sort is pinned to (raht_debug_sort_form)."""
 import ctypes as C
 import os
 import shutil
@@ -28,9 +28,10 @@ keys = synth.sorted_unique_keys(n, J, seed)
 kd = torch.from_numpy(keys.view(np.int64)).cuda()
 g = torch.Generator(device="cuda"); g.manual_seed(1)
 ku = kd[torch.randperm(kd.shape[0], device="cuda", generator=g)].contiguous()
-rounds = int(os.environ.get("RAHT_SORT_ROUNDS", "16"))
+rounds = int(os.environ.get("ROUNDS", "16"))
+_lib.check(min(_lib.lib().raht_debug_sort_form(1, rounds, -1), 0))
 nt = -(-ku.shape[0] // (256 * rounds))
-names = ["ticket", "loads + wave histograms", "publish + slot scan", "ranks -> LDS", "tiles before, in group", "groups before", "write-out"]
+names = ["start", "loads + wave histograms", "publish + slot scan", "ranks -> LDS", "tiles before, in group", "groups before", "write-out"]
 for shift in (8, 29):
     raw.raht_debug_sort_clocks(None, 0, shift)
     for _ in range(3):
