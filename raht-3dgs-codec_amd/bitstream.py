@@ -13,7 +13,7 @@ with the transform and entropy stages of all frames in common launches (DESIGN.m
     RAHTS001 | int64 n_frames | int64 offset[n_frames + 1] (from the start of the blob) | the frames
 
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
-sides, as ``ops._steps`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
+sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
 """
 import math
@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 from .geometry import MAX_J, OctreeCoder
+from .ops import step_list
 from .rlgr import SegmentedCoder
 
 MAGIC = b"RAHTF001"
@@ -29,9 +30,7 @@ MIN_FRAME_BYTES = len(MAGIC) + 40 + 8 * 5 + 2 * (8 + 48)      # header, one step
 
 
 def _step_list(step, D):
-    if isinstance(step, (int, float)):
-        step = [step]
-    steps = [float(s) for s in step]
+    steps = step_list(step)
     if len(steps) not in (1, D):
         raise ValueError("step must be a scalar or have one entry per attribute column")
     if any(not (math.isfinite(s) and s > 0) for s in steps):
@@ -109,7 +108,7 @@ def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scal
     n_wide = int(n_wide)
     if not 0 <= n_wide <= D:
         raise ValueError("encode_frame_bytes_target: n_wide outside 0 .. D")
-    base = _step_list(SegmentedCoder.step_row(step), D)                  # (any scalar or sequence, as rate and rate_curve take them)
+    base = _step_list(step, D)
     lo, hi = float(scale_range[0]), float(scale_range[1])
     if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi) or int(rounds) < 1:
         raise ValueError("encode_frame_bytes_target: scale_range must be 0 < lo <= hi, rounds >= 1")

@@ -6,11 +6,12 @@
 // row, a wave instruction moves 64 / G rows; the last chunk of a row whose length is not a multiple
 // of 4 is the 16 bytes that END it (overlapping its neighbour: same value written twice). The
 // division is the hoisted-reciprocal refinement of the fused kernels (bit-identical to x / step).
-// HBM-bound, 8 bytes/element. Rows narrower than one chunk (D < 4) take the scalar kernels.
+// HBM-bound, 8 bytes/element. Rows narrower than one chunk (D < 4) take the scalar row kernel.
 #include "raht_common.h"
 #include "raht_device.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace raht {
 
@@ -72,119 +73,41 @@ __global__ __launch_bounds__(256) void reorder_chunk_kernel(const void *__restri
     }
 }
 
-// scalar fall-backs for matrices narrower than one chunk (D < 4): one wave per row, lanes = channels
-__global__ __launch_bounds__(256) void quant_reorder_kernel(const float *__restrict__ T, int64_t ldt, int D,
-                                                            const uint32_t *__restrict__ order, int64_t N,
-                                                            const StepTable steps, int32_t *__restrict__ Q,
-                                                            int64_t ldq)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t k = wave; k < N; k += nwaves) {
-        const float *src = T + (int64_t)order[k] * ldt;          // :210
-        int32_t *dst = Q + k * ldq;
-        for (int c = lane; c < D; c += 64) {
-            const float st = steps.v[steps.n == 1 ? 0 : c];
-            dst[c] = (int32_t)floorf(src[c] / st + 0.5f);         // :204, :215
-        }
-    }
-}
+// ---- the scalar row kernel: one wave per row, lanes over the channels in steps of 64 ---------------------------------
+// Rows narrower than one chunk (float32, D < 4), every float64 matrix (the reference's own precision, python/encode_3dgs.py:82-83,
+// 204), and a few rows at explicit positions (the <= 512 top coefficients of a Morton-prefix sharded scene, which the shard-local
+// fused kernels leave to the caller). One template over the element type, the direction, and where a row's partner comes from:
+struct PlanPerm {                  // the plan's permutation, always as a GATHER (as reorder_chunk_kernel above): destination row k <-
+    const uint32_t *perm;          // source row perm[k]; perm = order_RAGFT when quantizing (:210), its inverse when not (:267-268)
+    template <bool QUANT> static constexpr bool on_source() { return true; }
+    __device__ __forceinline__ int64_t operator()(int64_t k) const { return (int64_t)perm[k]; }
+};
+struct RowPos {                    // explicit rows of the integer matrix (NULL: identity): Q[pos[i], :] = quantize(X[i, :]) and
+    const int64_t *pos;            // X[i, :] = Q[pos[i], :] * step
+    template <bool QUANT> static constexpr bool on_source() { return !QUANT; }
+    __device__ __forceinline__ int64_t operator()(int64_t i) const { return pos ? pos[i] : i; }
+};
 
-__global__ __launch_bounds__(256) void dequant_unreorder_kernel(const int32_t *__restrict__ Q, int64_t ldq, int D,
-                                                                const uint32_t *__restrict__ order, int64_t N,
-                                                                const StepTable steps, float *__restrict__ T,
-                                                                int64_t ldt)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t k = wave; k < N; k += nwaves) {
-        const int32_t *src = Q + k * ldq;
-        float *dst = T + (int64_t)order[k] * ldt;                 // inverse of :210 == :267-268
-        for (int c = lane; c < D; c += 64) {
-            const float st = steps.v[steps.n == 1 ? 0 : c];
-            dst[c] = (float)src[c] * st;                          // :261
-        }
-    }
-}
+// the true IEEE division in both precisions (this file is built with -fno-fast-math)
+__device__ __forceinline__ int32_t quantize_div(float x, float step) { return (int32_t)floorf(x / step + 0.5f); }    // :204, :215
+__device__ __forceinline__ int32_t quantize_div(double x, double step) { return quantize_one_f64(x, step); }
 
-// A few rows at explicit positions (the <= 512 top coefficients of a Morton-prefix sharded scene, which
-// the shard-local fused kernels leave to the caller): Q[pos[i], :] = quantize(X[i, :]) and back.
-__global__ __launch_bounds__(256) void quant_rows_kernel(const float *__restrict__ X, int64_t ldx, int64_t n, int D,
-                                                         const int64_t *__restrict__ pos, const StepTable steps,
-                                                         int32_t *__restrict__ Q, int64_t ldq)
+template <typename T, bool QUANT, typename Index>
+__global__ __launch_bounds__(256) void row_kernel(const void *__restrict__ src_, int64_t lds, int64_t n, int D, const Index index,
+                                                  const typename StepsFor<T>::type steps, void *__restrict__ dst_, int64_t ldd)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t i = wave; i < n; i += nwaves) {
-        const float *src = X + i * ldx;
-        int32_t *dst = Q + (pos ? pos[i] : i) * ldq;
-        for (int c = lane; c < D; c += 64) dst[c] = (int32_t)floorf(src[c] / steps.v[steps.n == 1 ? 0 : c] + 0.5f);
-    }
-}
-
-__global__ __launch_bounds__(256) void dequant_rows_kernel(const int32_t *__restrict__ Q, int64_t ldq,
-                                                           const int64_t *__restrict__ pos, int64_t n, int D,
-                                                           const StepTable steps, float *__restrict__ X, int64_t ldx)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave; i < n; i += nwaves) {
-        const int32_t *src = Q + (pos ? pos[i] : i) * ldq;
-        float *dst = X + i * ldx;
-        for (int c = lane; c < D; c += 64) dst[c] = (float)src[c] * steps.v[steps.n == 1 ? 0 : c];
-    }
-}
-
-// float64 (the reference's own precision, python/encode_3dgs.py:82-83,204): one lane per element, rows gathered
-// through the permutation as above. The division is the IEEE double division of the reference's CPU path.
-
-template <bool QUANT>
-__global__ __launch_bounds__(256) void reorder_f64_kernel(const void *__restrict__ src_, int64_t lds, int D,
-                                                          const uint32_t *__restrict__ perm, int64_t N,
-                                                          const StepTable64 steps, void *__restrict__ dst_, int64_t ldd)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t k = wave; k < N; k += nwaves) {
-        const int64_t r = (int64_t)perm[k];
+        const int64_t r = index(i);
+        const int64_t s = (Index::template on_source<QUANT>() ? r : i) * lds, d = (Index::template on_source<QUANT>() ? i : r) * ldd;
         for (int c = lane; c < D; c += 64) {
-            const double st = steps.v[steps.n == 1 ? 0 : c];
-            if constexpr (QUANT) ((int32_t *)dst_)[k * ldd + c] = quantize_one_f64(((const double *)src_)[r * lds + c], st);        // :204, :210, :215
-            else ((double *)dst_)[k * ldd + c] = (double)((const int32_t *)src_)[r * lds + c] * st;                                // :261, :267-268
+            const T st = steps.v[steps.n == 1 ? 0 : c];
+            if constexpr (QUANT) ((int32_t *)dst_)[d + c] = quantize_div(((const T *)src_)[s + c], st);
+            else ((T *)dst_)[d + c] = (T)((const int32_t *)src_)[s + c] * st;                                            // :261
         }
     }
-}
-
-// A few rows at explicit positions, float64 (raht_quant_rows_f64 / raht_dequant_rows_f64): QUANT: Q[pos[i], :] = quantize(X[i, :]);
-// else X[i, :] = Q[pos[i], :] * step
-template <bool QUANT>
-__global__ __launch_bounds__(256) void rows_f64_kernel(const void *__restrict__ src_, int64_t lds, int64_t n, int D,
-                                                       const int64_t *__restrict__ pos, const StepTable64 steps,
-                                                       void *__restrict__ dst_, int64_t ldd)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave; i < n; i += nwaves) {
-        const int64_t r = pos ? pos[i] : i;
-        for (int c = lane; c < D; c += 64) {
-            const double st = steps.v[steps.n == 1 ? 0 : c];
-            if constexpr (QUANT) ((int32_t *)dst_)[r * ldd + c] = quantize_one_f64(((const double *)src_)[i * lds + c], st);   // :204, :215
-            else ((double *)dst_)[i * ldd + c] = (double)((const int32_t *)src_)[r * lds + c] * st;                         // :261
-        }
-    }
-}
-
-static int fill_steps64(StepTable64 &t, const double *steps, int n_steps, int D)
-{
-    RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
-    fill_step_table(t, steps, n_steps);
-    return RAHT_OK;
 }
 
 // Rows of 32-bit words at explicit positions, without arithmetic: GATHER dst[i, :] = src[pos[i], :] or
@@ -225,7 +148,8 @@ __global__ __launch_bounds__(256) void transpose_i32_kernel(const int32_t *__res
     }
 }
 
-static int fill_steps(StepTable &t, const float *steps, int n_steps, int D)
+template <typename T>
+static int fill_steps(typename StepsFor<T>::type &t, const T *steps, int n_steps, int D)
 {
     RAHT_RET(check_quant_steps("quant", steps, n_steps, D));
     fill_step_table(t, steps, n_steps);
@@ -300,6 +224,55 @@ __global__ __launch_bounds__(256) void sqdiff_final_kernel(const double *__restr
     if (lane == 0) out[c] = s;
 }
 
+// Q[k] = quantize(T[order[k]]) / T[k] = Q[inv_order[k]] * step behind the four raht_*_reorder* entry points. float32 rows of at
+// least one chunk take the chunked kernel; narrower ones and float64 the scalar one. Dequantizing used to SCATTER the narrow
+// float32 rows through order (T[order[k]] = Q[k] * step); order is a permutation, so gathering through its inverse writes the same
+// matrix, as the other two kernels always did.
+template <typename T, bool QUANT>
+static int reorder_rows(const char *name, const raht_plan *p, const void *src, int64_t lds, int D, const T *steps, int n_steps,
+                        void *dst, int64_t ldd, raht_stream_t stream)
+{
+    if (!p || !src || !dst || D < 1 || lds < D || ldd < D) { set_error("%s: bad argument", name); return RAHT_ERR_INVALID; }
+    RAHT_RET(check_plan_device(p, name));
+    typename StepsFor<T>::type st;
+    RAHT_RET(fill_steps(st, steps, n_steps, D));
+    const uint32_t *perm = QUANT ? p->order : p->inv_order;
+    constexpr bool f32 = std::is_same<T, float>::value;
+    if constexpr (f32) {
+        if (D >= 4) {
+            const int lg = lanes_log2(D);
+            const int64_t rows_per_block = (int64_t)4 * 4 * (64 >> lg);           // 4 waves x 4 row groups in flight
+            const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, rows_per_block), 16384);
+            hipLaunchKernelGGL(reorder_chunk_kernel<QUANT>, dim3(gb), dim3(256), 0, (hipStream_t)stream, src, lds, D, lg, perm, p->N, st,
+                               dst, ldd);
+            RAHT_HIP_CHECK(hipGetLastError());
+            return RAHT_OK;
+        }
+    }
+    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, 4), f32 ? 4096 : 16384);
+    hipLaunchKernelGGL((row_kernel<T, QUANT, PlanPerm>), dim3(gb), dim3(256), 0, (hipStream_t)stream, src, lds, p->N, D, PlanPerm{perm},
+                       st, dst, ldd);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+// the four raht_*_rows* entry points: a few rows of the integer matrix at explicit positions
+template <typename T, bool QUANT>
+static int pos_rows(const char *name, const void *src, int64_t lds, const int64_t *pos, int64_t n, int D, const T *steps, int n_steps,
+                    void *dst, int64_t ldd, raht_stream_t stream)
+{
+    if (n < 0 || D < 1) { set_error("%s: bad argument", name); return RAHT_ERR_INVALID; }
+    typename StepsFor<T>::type st;
+    RAHT_RET(fill_steps(st, steps, n_steps, D));
+    if (n == 0) return RAHT_OK;                              // no rows: no buffers needed (empty device tensors are NULL, their strides 0)
+    if (!src || !dst || lds < D || ldd < D) { set_error("%s: bad argument", name); return RAHT_ERR_INVALID; }
+    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
+    hipLaunchKernelGGL((row_kernel<T, QUANT, RowPos>), dim3(gb), dim3(256), 0, (hipStream_t)stream, src, lds, n, D, RowPos{pos}, st,
+                       dst, ldd);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
 }  // namespace raht
 
 using namespace raht;
@@ -309,129 +282,49 @@ extern "C" {
 int raht_quant_reorder(const raht_plan *p, const float *T, int64_t ldt, int D, const float *steps, int n_steps,
                        int32_t *Q, int64_t ldq, raht_stream_t stream)
 {
-    if (!p || !T || !Q || D < 1 || ldt < D || ldq < D) { set_error("raht_quant_reorder: bad argument"); return RAHT_ERR_INVALID; }
-    RAHT_RET(check_plan_device(p, "raht_quant_reorder"));
-    StepTable st;
-    RAHT_RET(fill_steps(st, steps, n_steps, D));
-    if (D >= 4) {
-        const int lg = lanes_log2(D);
-        const int64_t rows_per_block = (int64_t)4 * 4 * (64 >> lg);           // 4 waves x 4 row groups in flight
-        const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, rows_per_block), 16384);
-        hipLaunchKernelGGL(reorder_chunk_kernel<true>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)T, ldt, D,
-                           lg, p->order, p->N, st, (void *)Q, ldq);
-    } else {
-        const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, 4), 4096);
-        hipLaunchKernelGGL(quant_reorder_kernel, dim3(gb), dim3(256), 0, (hipStream_t)stream, T, ldt, D, p->order,
-                           p->N, st, Q, ldq);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return reorder_rows<float, true>("raht_quant_reorder", p, T, ldt, D, steps, n_steps, Q, ldq, stream);
 }
 
 int raht_dequant_unreorder(const raht_plan *p, const int32_t *Q, int64_t ldq, int D, const float *steps,
                            int n_steps, float *T, int64_t ldt, raht_stream_t stream)
 {
-    if (!p || !T || !Q || D < 1 || ldt < D || ldq < D) { set_error("raht_dequant_unreorder: bad argument"); return RAHT_ERR_INVALID; }
-    RAHT_RET(check_plan_device(p, "raht_dequant_unreorder"));
-    StepTable st;
-    RAHT_RET(fill_steps(st, steps, n_steps, D));
-    if (D >= 4) {
-        const int lg = lanes_log2(D);
-        const int64_t rows_per_block = (int64_t)4 * 4 * (64 >> lg);
-        const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, rows_per_block), 16384);
-        hipLaunchKernelGGL(reorder_chunk_kernel<false>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)Q, ldq, D,
-                           lg, p->inv_order, p->N, st, (void *)T, ldt);
-    } else {
-        const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, 4), 4096);
-        hipLaunchKernelGGL(dequant_unreorder_kernel, dim3(gb), dim3(256), 0, (hipStream_t)stream, Q, ldq, D,
-                           p->order, p->N, st, T, ldt);
-    }
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return reorder_rows<float, false>("raht_dequant_unreorder", p, Q, ldq, D, steps, n_steps, T, ldt, stream);
 }
 
 int raht_quant_reorder_f64(const raht_plan *p, const double *T, int64_t ldt, int D, const double *steps, int n_steps,
                            int32_t *Q, int64_t ldq, raht_stream_t stream)
 {
-    if (!p || !T || !Q || D < 1 || ldt < D || ldq < D) { set_error("raht_quant_reorder_f64: bad argument"); return RAHT_ERR_INVALID; }
-    RAHT_RET(check_plan_device(p, "raht_quant_reorder_f64"));
-    StepTable64 st;
-    RAHT_RET(fill_steps64(st, steps, n_steps, D));
-    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, 4), 16384);
-    hipLaunchKernelGGL(reorder_f64_kernel<true>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)T, ldt, D, p->order,
-                       p->N, st, (void *)Q, ldq);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return reorder_rows<double, true>("raht_quant_reorder_f64", p, T, ldt, D, steps, n_steps, Q, ldq, stream);
 }
 
 int raht_dequant_unreorder_f64(const raht_plan *p, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps,
                                double *T, int64_t ldt, raht_stream_t stream)
 {
-    if (!p || !T || !Q || D < 1 || ldt < D || ldq < D) { set_error("raht_dequant_unreorder_f64: bad argument"); return RAHT_ERR_INVALID; }
-    RAHT_RET(check_plan_device(p, "raht_dequant_unreorder_f64"));
-    StepTable64 st;
-    RAHT_RET(fill_steps64(st, steps, n_steps, D));
-    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(p->N, 4), 16384);
-    hipLaunchKernelGGL(reorder_f64_kernel<false>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)Q, ldq, D,
-                       p->inv_order, p->N, st, (void *)T, ldt);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return reorder_rows<double, false>("raht_dequant_unreorder_f64", p, Q, ldq, D, steps, n_steps, T, ldt, stream);
 }
 
 int raht_quant_rows(const float *X, int64_t ldx, int64_t n, int D, const float *steps, int n_steps,
                     const int64_t *pos, int32_t *Q, int64_t ldq, raht_stream_t stream)
 {
-    if (n < 0 || D < 1) { set_error("raht_quant_rows: bad argument"); return RAHT_ERR_INVALID; }
-    StepTable st;
-    RAHT_RET(fill_steps(st, steps, n_steps, D));
-    if (n == 0) return RAHT_OK;                              // no rows: no buffers needed (empty device tensors are NULL, their strides 0)
-    if (!X || !Q || ldx < D || ldq < D) { set_error("raht_quant_rows: bad argument"); return RAHT_ERR_INVALID; }
-    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
-    hipLaunchKernelGGL(quant_rows_kernel, dim3(gb), dim3(256), 0, (hipStream_t)stream, X, ldx, n, D, pos, st, Q, ldq);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return pos_rows<float, true>("raht_quant_rows", X, ldx, pos, n, D, steps, n_steps, Q, ldq, stream);
 }
 
 int raht_dequant_rows(const int32_t *Q, int64_t ldq, const int64_t *pos, int64_t n, int D, const float *steps,
                       int n_steps, float *X, int64_t ldx, raht_stream_t stream)
 {
-    if (n < 0 || D < 1) { set_error("raht_dequant_rows: bad argument"); return RAHT_ERR_INVALID; }
-    StepTable st;
-    RAHT_RET(fill_steps(st, steps, n_steps, D));
-    if (n == 0) return RAHT_OK;
-    if (!X || !Q || ldx < D || ldq < D) { set_error("raht_dequant_rows: bad argument"); return RAHT_ERR_INVALID; }
-    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
-    hipLaunchKernelGGL(dequant_rows_kernel, dim3(gb), dim3(256), 0, (hipStream_t)stream, Q, ldq, pos, n, D, st, X, ldx);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return pos_rows<float, false>("raht_dequant_rows", Q, ldq, pos, n, D, steps, n_steps, X, ldx, stream);
 }
 
 int raht_quant_rows_f64(const double *X, int64_t ldx, int64_t n, int D, const double *steps, int n_steps,
                         const int64_t *pos, int32_t *Q, int64_t ldq, raht_stream_t stream)
 {
-    if (n < 0 || D < 1) { set_error("raht_quant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
-    StepTable64 st;
-    RAHT_RET(fill_steps64(st, steps, n_steps, D));
-    if (n == 0) return RAHT_OK;
-    if (!X || !Q || ldx < D || ldq < D) { set_error("raht_quant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
-    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
-    hipLaunchKernelGGL(rows_f64_kernel<true>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)X, ldx, n, D, pos, st, (void *)Q, ldq);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return pos_rows<double, true>("raht_quant_rows_f64", X, ldx, pos, n, D, steps, n_steps, Q, ldq, stream);
 }
 
 int raht_dequant_rows_f64(const int32_t *Q, int64_t ldq, const int64_t *pos, int64_t n, int D, const double *steps,
                           int n_steps, double *X, int64_t ldx, raht_stream_t stream)
 {
-    if (n < 0 || D < 1) { set_error("raht_dequant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
-    StepTable64 st;
-    RAHT_RET(fill_steps64(st, steps, n_steps, D));
-    if (n == 0) return RAHT_OK;
-    if (!X || !Q || ldx < D || ldq < D) { set_error("raht_dequant_rows_f64: bad argument"); return RAHT_ERR_INVALID; }
-    const unsigned gb = (unsigned)std::min<int64_t>(ceil_div(n, 4), 4096);
-    hipLaunchKernelGGL(rows_f64_kernel<false>, dim3(gb), dim3(256), 0, (hipStream_t)stream, (const void *)Q, ldq, n, D, pos, st, (void *)X, ldx);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return pos_rows<double, false>("raht_dequant_rows_f64", Q, ldq, pos, n, D, steps, n_steps, X, ldx, stream);
 }
 
 static int rows_move(bool scatter, const void *src, int64_t ld_src, const int64_t *pos, int64_t n, int D, int elem_size,

@@ -19,6 +19,7 @@ Differences from the reference, all deliberate:
     float64 kernels (the reference's own precision). The reference always returns float64.
 """
 import collections
+import contextlib
 import ctypes as C
 
 import torch
@@ -44,6 +45,55 @@ def _need_cuda(t, name):
 
 _VDT = {torch.float32: _lib.RAHT_F32, torch.float64: _lib.RAHT_F64, torch.int32: _lib.RAHT_I32,
         torch.int64: _lib.RAHT_I64}
+_STEP_CTYPE = {torch.float32: C.c_float, torch.float64: C.c_double}
+_FN_SUFFIX = {torch.float32: "", torch.float64: "_f64"}      # raht_fwd_quant / raht_fwd_quant_f64, ...: one name per precision
+
+
+def _fn(name, dtype):
+    return getattr(_lib.lib(), name + _FN_SUFFIX[dtype])
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _call(fn, device, *args):
+    """one call through the C ABI on ``device``, on its current stream (every entry point's last argument)"""
+    with torch.cuda.device(device):
+        check(fn(*args, _stream()))
+
+
+def _rows(X, dtype, name):
+    """X as a matrix the kernels take: on the GPU, of ``dtype`` (None: float32 or float64 as it comes, anything else float32),
+    unit column stride and a row stride of at least D -- column slices of wider matrices pass as they are"""
+    _need_cuda(X, name)
+    if dtype is None:
+        dtype = X.dtype if X.dtype in (torch.float32, torch.float64) else torch.float32
+    X = X.to(dtype)
+    if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+        X = X.contiguous()
+    return X
+
+
+def _qmat(Q):
+    _need_cuda(Q, "Q")
+    return Q.to(torch.int32).contiguous()
+
+
+def step_list(steps, D=None):
+    """A quantization step argument as a list of Python floats: [step] for a scalar (Python or numpy number, 0-d array or tensor),
+    else the entries of a list, tuple, numpy array or tensor (which comes to the host once). With ``D``: one entry or D."""
+    if hasattr(steps, "tolist"):
+        steps = steps.tolist()
+    out = [float(steps)] if isinstance(steps, (int, float)) else [float(x) for x in steps]
+    if D is not None and len(out) not in (1, D):
+        raise ValueError("steps must be a scalar or have D entries")
+    return out
+
+
+def _step_array(steps, D, ctype):
+    st = step_list(steps, D)
+    return (ctype * len(st))(*st)
 
 
 class RahtPlan:
@@ -163,9 +213,24 @@ class RahtPlan:
         self._set_roots_buffer(roots, D, torch.float32)
         check(_lib.lib().raht_plan_set_root_buffer_wide(self._h, C.c_void_p(roots_wide.data_ptr())))
 
-    def _reset_mixed_roots(self):
-        check(_lib.lib().raht_plan_set_root_buffer(self._h, None))
-        check(_lib.lib().raht_plan_set_root_buffer_wide(self._h, None))
+    @contextlib.contextmanager
+    def _with_roots(self, D, roots, dtype, roots_wide=None, n_wide=None):
+        """these root buffers are set for the duration of a call and reset afterwards, also when the call raises: one (n_roots, D)
+        buffer of ``dtype``, or with ``n_wide`` the pair of the mixed-precision entries (_set_mixed_roots); None: nothing to set"""
+        try:
+            if n_wide is None:
+                self._set_roots_buffer(roots, D, dtype)
+            else:
+                self._set_mixed_roots(roots, roots_wide, D, n_wide)
+            yield
+        finally:
+            if roots is not None:
+                check(_lib.lib().raht_plan_set_root_buffer(self._h, None))
+                check(_lib.lib().raht_plan_set_root_buffer_wide(self._h, None))
+
+    def _quant(self, fn, src, st, *rest):
+        """the argument head every quantizing entry point shares: plan, source matrix, its row stride, D, the step array"""
+        _call(fn, src.device, self._h, _p(src), src.stride(0), src.shape[1], st, len(st), *rest)
 
     def __del__(self):
         try:
@@ -257,12 +322,8 @@ class RahtPlan:
         w = torch.empty((self.N, 1), dtype=X.dtype, device=X.device) if want_w else None
         L = _lib.lib()
         f64 = X.dtype == torch.float64
-        self._set_roots_buffer(roots, D, X.dtype)
-        try:
+        with self._with_roots(D, roots, X.dtype):
             self._run(L, X, out, w, D, inverse, f64)
-        finally:
-            if roots is not None:
-                self._set_roots_buffer(None, D, X.dtype)
         return (out, w) if want_w else out
 
     def _run(self, L, X, out, w, D, inverse, f64):
@@ -314,103 +375,59 @@ class RahtPlan:
         with torch.cuda.device(self.device):
             check(_lib.lib().raht_plan_set_max_stages(self._h, int(max_stages)))
 
-    def _f64_quant_call(self, fn, src, D, steps, dst):
-        st = _steps64(steps, D)
-        with torch.cuda.device(src.device):
-            check(fn(self._h, C.c_void_p(src.data_ptr()), src.stride(0), D, st, len(st), C.c_void_p(dst.data_ptr()),
-                     dst.stride(0), _stream()))
+    def _quant_to(self, name, src, steps, out_dtype, step_dtype, roots=None):
+        """``src`` through the entry point ``name`` of ``step_dtype``'s precision -> a new (N, D) matrix of ``out_dtype``"""
+        D = src.shape[1]
+        st = _step_array(steps, D, _STEP_CTYPE[step_dtype])
+        dst = torch.empty((self.N, D), dtype=out_dtype, device=src.device)
+        with self._with_roots(D, roots, step_dtype):
+            self._quant(_fn(name, step_dtype), src, st, _p(dst), D)
         return dst
 
     def forward_quant(self, Cmat, steps, roots=None):
         """Forward RAHT + quantize + reorder -> int32 Q. float32 (default): ONE fused pass, T is never
         materialised. float64 input: the same at the reference's precision (encode_3dgs.py:82-83,204): the float64 tile
         kernels with the float64 quantizer in their write-back."""
-        _need_cuda(Cmat, "C")
-        if Cmat.dtype == torch.float64:
-            X = Cmat if (Cmat.stride(1) == 1 and Cmat.stride(0) >= Cmat.shape[1]) else Cmat.contiguous()
-            Q = torch.empty((self.N, X.shape[1]), dtype=torch.int32, device=X.device)
-            self._set_roots_buffer(roots, X.shape[1], torch.float64)
-            try:
-                return self._f64_quant_call(_lib.lib().raht_fwd_quant_f64, X, X.shape[1], steps, Q)
-            finally:
-                if roots is not None:
-                    self._set_roots_buffer(None, X.shape[1], torch.float64)
-        X = Cmat.to(torch.float32)
-        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-            X = X.contiguous()
-        D = X.shape[1]
-        st = _steps(steps, D)
-        Q = torch.empty((self.N, D), dtype=torch.int32, device=X.device)
-        self._set_roots_buffer(roots, D, torch.float32)
-        try:
-            with torch.cuda.device(X.device):
-                check(_lib.lib().raht_fwd_quant(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, len(st),
-                                                C.c_void_p(Q.data_ptr()), D, _stream()))
-        finally:
-            if roots is not None:
-                self._set_roots_buffer(None, D, torch.float32)
-        return Q
+        X = _rows(Cmat, None, "C")
+        return self._quant_to("raht_fwd_quant", X, steps, torch.int32, X.dtype, roots)
 
     def dequant_inverse(self, Q, steps, roots=None, dtype=torch.float32):
         """Un-reorder + dequantize + inverse RAHT -> C in ONE fused pass (dtype=torch.float64: at the reference's
         precision)."""
-        _need_cuda(Q, "Q")
-        Q = Q.to(torch.int32).contiguous()
-        D = Q.shape[1]
-        if dtype == torch.float64:
-            out = torch.empty((self.N, D), dtype=torch.float64, device=Q.device)
-            self._set_roots_buffer(roots, D, torch.float64)
-            try:
-                return self._f64_quant_call(_lib.lib().raht_dequant_inv_f64, Q, D, steps, out)
-            finally:
-                if roots is not None:
-                    self._set_roots_buffer(None, D, torch.float64)
-        st = _steps(steps, D)
-        out = torch.empty((self.N, D), dtype=torch.float32, device=Q.device)
-        self._set_roots_buffer(roots, D, torch.float32)
-        try:
-            with torch.cuda.device(Q.device):
-                check(_lib.lib().raht_dequant_inv(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st),
-                                                  C.c_void_p(out.data_ptr()), D, _stream()))
-        finally:
-            if roots is not None:
-                self._set_roots_buffer(None, D, torch.float32)
-        return out
+        dtype = torch.float64 if dtype == torch.float64 else torch.float32
+        return self._quant_to("raht_dequant_inv", _qmat(Q), steps, dtype, dtype, roots)
 
     def forward_quant_multi(self, Cmat, steps):
         """ONE forward pass, one quantization per (scalar) step: -> [Q_0, ..., Q_{k-1}], each bit-identical to
         ``forward_quant(C, steps[i])`` (the drivers quantize one coefficient matrix at nine steps, python/encode_3dgs.py:28,199-217)."""
-        _need_cuda(Cmat, "C")
-        X = Cmat.to(torch.float32)
-        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-            X = X.contiguous()
-        D = X.shape[1]
-        k = len(steps)
-        st = (C.c_float * k)(*[float(s) for s in steps])
-        Qs = [torch.empty((self.N, D), dtype=torch.int32, device=X.device) for _ in range(k)]
-        ptrs = (C.c_void_p * k)(*[q.data_ptr() for q in Qs])
-        with torch.cuda.device(X.device):
-            check(_lib.lib().raht_fwd_quant_multi(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, k, ptrs, D, _stream()))
+        X = _rows(Cmat, torch.float32, "C")
+        Qs, st, ptrs = self._multi_out(X, steps, C.c_float)
+        self._quant(_lib.lib().raht_fwd_quant_multi, X, st, ptrs, X.shape[1])
         return Qs
+
+    def _multi_out(self, X, steps, ctype):
+        """one output matrix per (scalar) step -> (matrices, step array, pointer array)"""
+        k = len(steps)
+        Qs = [torch.empty((self.N, X.shape[1]), dtype=torch.int32, device=X.device) for _ in range(k)]
+        return Qs, (ctype * k)(*[float(s) for s in steps]), (C.c_void_p * k)(*[q.data_ptr() for q in Qs])
 
     def dequant_inverse_sqdiff(self, Q, steps, C_ref, want_rec=True):
         """Un-reorder + dequantize + inverse RAHT (float32, fused) that also compares its output with the original attributes on the
         way out: -> (C_rec or None, float64[D] per-column sums of (C_rec - C_ref)^2). What the drivers' five PSNR columns are made of
         (python/encode_3dgs.py:274,298-310) without a pass of its own; with ``want_rec=False`` C_rec is never written."""
+        Q, X, st, out, ssd = self._sqdiff_args(Q, steps, C_ref, want_rec, C.c_float)
+        self._quant(_lib.lib().raht_dequant_inv_sqdiff, Q, st, _p(X), X.stride(0), _p(out), Q.shape[1], _p(ssd))
+        return out, ssd
+
+    def _sqdiff_args(self, Q, steps, C_ref, want_rec, ctype):
         _need_cuda(Q, "Q")
         _need_cuda(C_ref, "C_ref")
-        Q = Q.to(torch.int32).contiguous()
+        Q = _qmat(Q)
         D = Q.shape[1]
-        X = C_ref.to(torch.float32)
-        if X.stride(1) != 1 or X.stride(0) < D:
-            X = X.contiguous()
-        st = _steps(steps, D)
+        X = _rows(C_ref, torch.float32, "C_ref")
+        st = _step_array(steps, D, ctype)
         out = torch.empty((self.N, D), dtype=torch.float32, device=Q.device) if want_rec else None
-        ssd = torch.empty(D, dtype=torch.float64, device=Q.device)
-        with torch.cuda.device(Q.device):
-            check(_lib.lib().raht_dequant_inv_sqdiff(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st), C.c_void_p(X.data_ptr()), X.stride(0),
-                                                     C.c_void_p(out.data_ptr()) if want_rec else None, D, C.c_void_p(ssd.data_ptr()), _stream()))
-        return out, ssd
+        return Q, X, st, out, torch.empty(D, dtype=torch.float64, device=Q.device)
 
     def forward_quant_mixed(self, Cmat, steps, n_wide=3, roots=None, roots_wide=None):
         """Forward RAHT + quantize + reorder of a float32 matrix whose first ``n_wide`` channels (the xyz columns of a
@@ -420,90 +437,46 @@ class RahtPlan:
         roots / roots_wide (together; a truncated plan needs them): (n_roots, D) float32 and (n_roots, n_wide) float64 buffers
         receiving the roots' low-pass rows -- columns [n_wide, D) in the first (its columns [0, n_wide) are unspecified), columns
         [0, n_wide) unrounded in the second; the roots' Q rows are left to the caller."""
-        _need_cuda(Cmat, "C")
-        X = Cmat.to(torch.float32)
-        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-            X = X.contiguous()
+        X = _rows(Cmat, torch.float32, "C")
         D = X.shape[1]
-        st = _steps64(steps, D)
+        st = _step_array(steps, D, C.c_double)
         Q = torch.empty((self.N, D), dtype=torch.int32, device=X.device)
-        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
-        try:
-            with torch.cuda.device(X.device):
-                check(_lib.lib().raht_fwd_quant_mixed(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, len(st), int(n_wide),
-                                                      C.c_void_p(Q.data_ptr()), D, _stream()))
-        finally:
-            if roots is not None:
-                self._reset_mixed_roots()
+        with self._with_roots(D, roots, torch.float32, roots_wide, int(n_wide)):
+            self._quant(_lib.lib().raht_fwd_quant_mixed, X, st, int(n_wide), _p(Q), D)
         return Q
 
     def dequant_inverse_mixed(self, Q, steps, n_wide=3, out=None, roots=None, roots_wide=None):
         """Un-reorder + dequantize + inverse RAHT -> float32 C, the first ``n_wide`` channels computed in float64 and
         rounded once on output (counterpart of ``forward_quant_mixed``). roots / roots_wide: the two root buffers the
         roots' low-pass rows are read from instead of Q (as ``forward_quant_mixed`` writes them)."""
-        _need_cuda(Q, "Q")
-        Q = Q.to(torch.int32).contiguous()
+        Q = _qmat(Q)
         D = Q.shape[1]
-        st = _steps64(steps, D)
+        st = _step_array(steps, D, C.c_double)
         if out is None:
             out = torch.empty((self.N, D), dtype=torch.float32, device=Q.device)
-        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
-        try:
-            with torch.cuda.device(Q.device):
-                check(_lib.lib().raht_dequant_inv_mixed(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st), int(n_wide),
-                                                        C.c_void_p(out.data_ptr()), out.stride(0), _stream()))
-        finally:
-            if roots is not None:
-                self._reset_mixed_roots()
+        with self._with_roots(D, roots, torch.float32, roots_wide, int(n_wide)):
+            self._quant(_lib.lib().raht_dequant_inv_mixed, Q, st, int(n_wide), _p(out), out.stride(0))
         return out
 
     def forward_quant_mixed_multi(self, Cmat, steps, n_wide=3, roots=None, roots_wide=None):
         """ONE mixed-precision forward pass, one quantization per (scalar) step: -> [Q_0, ..., Q_{k-1}], each bit-identical to
         ``forward_quant_mixed(C, steps[i], n_wide)`` -- the nine steps of a frame (python/encode_3dgs.py:28,199-217) with the
         reference's integers on the first ``n_wide`` columns. roots / roots_wide: as for ``forward_quant_mixed``."""
-        _need_cuda(Cmat, "C")
-        X = Cmat.to(torch.float32)
-        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-            X = X.contiguous()
+        X = _rows(Cmat, torch.float32, "C")
         D = X.shape[1]
-        k = len(steps)
-        st = (C.c_double * k)(*[float(s) for s in steps])
-        Qs = [torch.empty((self.N, D), dtype=torch.int32, device=X.device) for _ in range(k)]
-        ptrs = (C.c_void_p * k)(*[q.data_ptr() for q in Qs])
-        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
-        try:
-            with torch.cuda.device(X.device):
-                check(_lib.lib().raht_fwd_quant_mixed_multi(self._h, C.c_void_p(X.data_ptr()), X.stride(0), D, st, k, int(n_wide), ptrs, D,
-                                                            _stream()))
-        finally:
-            if roots is not None:
-                self._reset_mixed_roots()
+        Qs, st, ptrs = self._multi_out(X, steps, C.c_double)
+        with self._with_roots(D, roots, torch.float32, roots_wide, int(n_wide)):
+            self._quant(_lib.lib().raht_fwd_quant_mixed_multi, X, st, int(n_wide), ptrs, D)
         return Qs
 
     def dequant_inverse_mixed_sqdiff(self, Q, steps, C_ref, n_wide=3, want_rec=True, roots=None, roots_wide=None):
         """``dequant_inverse_mixed`` that also compares its output with the original attributes on the way out: -> (C_rec or None,
         float64[D] per-column sums of (C_rec - C_ref)^2, from the float32 values C_rec holds). With ``want_rec=False`` C_rec is
         never written. roots / roots_wide: as for ``dequant_inverse_mixed``."""
-        _need_cuda(Q, "Q")
-        _need_cuda(C_ref, "C_ref")
-        Q = Q.to(torch.int32).contiguous()
+        Q, X, st, out, ssd = self._sqdiff_args(Q, steps, C_ref, want_rec, C.c_double)
         D = Q.shape[1]
-        X = C_ref.to(torch.float32)
-        if X.stride(1) != 1 or X.stride(0) < D:
-            X = X.contiguous()
-        st = _steps64(steps, D)
-        out = torch.empty((self.N, D), dtype=torch.float32, device=Q.device) if want_rec else None
-        ssd = torch.empty(D, dtype=torch.float64, device=Q.device)
-        self._set_mixed_roots(roots, roots_wide, D, int(n_wide))
-        try:
-            with torch.cuda.device(Q.device):
-                check(_lib.lib().raht_dequant_inv_mixed_sqdiff(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st), int(n_wide),
-                                                               C.c_void_p(X.data_ptr()), X.stride(0),
-                                                               C.c_void_p(out.data_ptr()) if want_rec else None, D,
-                                                               C.c_void_p(ssd.data_ptr()), _stream()))
-        finally:
-            if roots is not None:
-                self._reset_mixed_roots()
+        with self._with_roots(D, roots, torch.float32, roots_wide, int(n_wide)):
+            self._quant(_lib.lib().raht_dequant_inv_mixed_sqdiff, Q, st, int(n_wide), _p(X), X.stride(0), _p(out), D, _p(ssd))
         return out, ssd
 
     def rate_curve(self, Cmat, steps, n_wide=0, seg_len=2048):
@@ -525,7 +498,7 @@ class RahtPlan:
         D = int(Cmat.shape[1])
         rows = []
         for st in steps:
-            r = SegmentedCoder.step_row(st)
+            r = step_list(st)
             if len(r) not in (1, D):
                 raise ValueError("rate_curve: every step must be a scalar or have D entries")
             rows.append(r * D if len(r) == 1 else r)
@@ -573,52 +546,13 @@ class RahtPlan:
 
     def quant_reorder(self, T, steps):
         """int32 Q[k] = floor(T[order[k]] / step + 0.5)  (encode_3dgs.py:204,210,215)."""
-        _need_cuda(T, "T")
-        if T.dtype == torch.float64:
-            T = T.contiguous()
-            Q = torch.empty((self.N, T.shape[1]), dtype=torch.int32, device=T.device)
-            return self._f64_quant_call(_lib.lib().raht_quant_reorder_f64, T, T.shape[1], steps, Q)
-        T = T.to(torch.float32).contiguous()
-        D = T.shape[1]
-        st = _steps(steps, D)
-        Q = torch.empty((self.N, D), dtype=torch.int32, device=T.device)
-        with torch.cuda.device(T.device):
-            check(_lib.lib().raht_quant_reorder(self._h, C.c_void_p(T.data_ptr()), D, D, st, len(st),
-                                                C.c_void_p(Q.data_ptr()), D, _stream()))
-        return Q
+        T = _rows(T, None, "T")
+        return self._quant_to("raht_quant_reorder", T, steps, torch.int32, T.dtype)
 
     def dequant_unreorder(self, Q, steps, dtype=torch.float32):
         """T[order[k]] = Q[k] * step  (encode_3dgs.py:261,267-268); float32, or float64 like the reference."""
-        _need_cuda(Q, "Q")
-        Q = Q.to(torch.int32).contiguous()
-        D = Q.shape[1]
-        if dtype == torch.float64:
-            T = torch.empty((self.N, D), dtype=torch.float64, device=Q.device)
-            return self._f64_quant_call(_lib.lib().raht_dequant_unreorder_f64, Q, D, steps, T)
-        st = _steps(steps, D)
-        T = torch.empty((self.N, D), dtype=torch.float32, device=Q.device)
-        with torch.cuda.device(Q.device):
-            check(_lib.lib().raht_dequant_unreorder(self._h, C.c_void_p(Q.data_ptr()), D, D, st, len(st),
-                                                    C.c_void_p(T.data_ptr()), D, _stream()))
-        return T
-
-
-def _steps(steps, D):
-    if isinstance(steps, (int, float)):
-        steps = [float(steps)]
-    steps = [float(s) for s in steps]
-    if len(steps) not in (1, D):
-        raise ValueError("steps must be a scalar or have D entries")
-    return (C.c_float * len(steps))(*steps)
-
-
-def _steps64(steps, D):
-    if isinstance(steps, (int, float)):
-        steps = [float(steps)]
-    steps = [float(s) for s in steps]
-    if len(steps) not in (1, D):
-        raise ValueError("steps must be a scalar or have D entries")
-    return (C.c_double * len(steps))(*steps)
+        dtype = torch.float64 if dtype == torch.float64 else torch.float32
+        return self._quant_to("raht_dequant_unreorder", _qmat(Q), steps, dtype, dtype)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -650,71 +584,52 @@ def _batch_out(plans, D, dtype, device):
     return outs, (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs]), (C.c_int64 * len(outs))(*[D] * len(outs))
 
 
+@contextlib.contextmanager
+def _batch_mixed_roots(plans, roots, roots_wide, D, n_wide):
+    """the root buffers of every scene that brings some, set for the duration of a mixed batch call (one entry per scene, None
+    allowed) and reset afterwards, also when setting one of them or the call itself raises"""
+    n = len(plans)
+    roots = [None] * n if roots is None else list(roots)
+    wide = [None] * n if roots_wide is None else list(roots_wide)
+    if len(roots) != n or len(wide) != n:
+        raise ValueError("batch: roots / roots_wide need one entry per plan (None allowed)")
+    with contextlib.ExitStack() as stack:
+        for p, r, w in zip(plans, roots, wide):
+            stack.enter_context(p._with_roots(D, r, torch.float32, w, n_wide))
+        yield
+
+
+def _batch(fn, plans, mats, dtype, name, out_dtype, steps=None, ctype=None, n_wide=None, roots=None, roots_wide=None):
+    """one batch entry point: (n, plans, matrices, row strides, D, [steps, n_steps, [n_wide,]] outputs, their row strides);
+    with ``n_wide`` (the mixed entries) under the scenes' root buffers"""
+    n, D, ms, hp, mp, ld = _batch_arrays(plans, mats, dtype, name)
+    mid = []
+    if steps is not None:
+        st = _step_array(steps, D, ctype)
+        mid = [st, len(st)] if n_wide is None else [st, len(st), int(n_wide)]
+    outs, op, old = _batch_out(plans, D, out_dtype, ms[0].device)
+    with contextlib.nullcontext() if n_wide is None else _batch_mixed_roots(plans, roots, roots_wide, D, int(n_wide)):
+        _call(fn, ms[0].device, n, hp, mp, ld, D, *mid, op, old)
+    return outs
+
+
 def forward_batch(plans, Cs):
     """[T_i] = forward RAHT of every scene (plans[i], Cs[i]) in one set of launches; float32."""
-    n, D, ms, hp, mp, ld = _batch_arrays(plans, Cs, torch.float32, "C")
-    outs, op, old = _batch_out(plans, D, torch.float32, ms[0].device)
-    with torch.cuda.device(ms[0].device):
-        check(_lib.lib().raht_fwd_batch(n, hp, mp, ld, D, op, old, _stream()))
-    return outs
+    return _batch(_lib.lib().raht_fwd_batch, plans, Cs, torch.float32, "C", torch.float32)
 
 
 def inverse_batch(plans, Ts):
-    n, D, ms, hp, mp, ld = _batch_arrays(plans, Ts, torch.float32, "T")
-    outs, op, old = _batch_out(plans, D, torch.float32, ms[0].device)
-    with torch.cuda.device(ms[0].device):
-        check(_lib.lib().raht_inv_batch(n, hp, mp, ld, D, op, old, _stream()))
-    return outs
+    return _batch(_lib.lib().raht_inv_batch, plans, Ts, torch.float32, "T", torch.float32)
 
 
 def forward_quant_batch(plans, Cs, steps):
     """[Q_i] = forward RAHT + quantize + reorder of every scene in one set of launches (bit-identical to
     plans[i].forward_quant(Cs[i], steps))."""
-    n, D, ms, hp, mp, ld = _batch_arrays(plans, Cs, torch.float32, "C")
-    st = _steps(steps, D)
-    outs, op, old = _batch_out(plans, D, torch.int32, ms[0].device)
-    with torch.cuda.device(ms[0].device):
-        check(_lib.lib().raht_fwd_quant_batch(n, hp, mp, ld, D, st, len(st), op, old, _stream()))
-    return outs
+    return _batch(_lib.lib().raht_fwd_quant_batch, plans, Cs, torch.float32, "C", torch.int32, steps, C.c_float)
 
 
 def dequant_inverse_batch(plans, Qs, steps):
-    n, D, ms, hp, mp, ld = _batch_arrays(plans, Qs, torch.int32, "Q")
-    st = _steps(steps, D)
-    outs, op, old = _batch_out(plans, D, torch.float32, ms[0].device)
-    with torch.cuda.device(ms[0].device):
-        check(_lib.lib().raht_dequant_inv_batch(n, hp, mp, ld, D, st, len(st), op, old, _stream()))
-    return outs
-
-
-class _batch_mixed_roots:
-    """the root buffers of every scene that brings some, set for the duration of a mixed batch call (one entry per scene, None
-    allowed) and reset afterwards, also when setting one of them or the call itself raises"""
-
-    def __init__(self, plans, roots, roots_wide, D, n_wide):
-        n = len(plans)
-        self.roots = [None] * n if roots is None else list(roots)
-        self.wide = [None] * n if roots_wide is None else list(roots_wide)
-        if len(self.roots) != n or len(self.wide) != n:
-            raise ValueError("batch: roots / roots_wide need one entry per plan (None allowed)")
-        self.plans, self.D, self.n_wide, self.touched = plans, D, n_wide, []
-
-    def __enter__(self):
-        try:
-            for p, r, w in zip(self.plans, self.roots, self.wide):
-                if r is not None or w is not None:
-                    self.touched.append(p)
-                p._set_mixed_roots(r, w, self.D, self.n_wide)
-        except Exception:
-            self.__exit__(None, None, None)
-            raise
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.touched:
-            p._reset_mixed_roots()
-        self.touched = []
-        return False
+    return _batch(_lib.lib().raht_dequant_inv_batch, plans, Qs, torch.int32, "Q", torch.float32, steps, C.c_float)
 
 
 def forward_quant_mixed_batch(plans, Cs, steps, n_wide=3, roots=None, roots_wide=None):
@@ -722,25 +637,15 @@ def forward_quant_mixed_batch(plans, Cs, steps, n_wide=3, roots=None, roots_wide
     frames of a 59-column sequence: the reference's xyz integers and the batch's shared tail launches at once). roots /
     roots_wide: optional lists, one entry per scene (None allowed), with the meaning they have in ``forward_quant_mixed``; a
     scene with root buffers (a truncated plan needs them) runs through the single-scene call inside."""
-    n, D, ms, hp, mp, ld = _batch_arrays(plans, Cs, torch.float32, "C")
-    st = _steps64(steps, D)
-    outs, op, old = _batch_out(plans, D, torch.int32, ms[0].device)
-    with _batch_mixed_roots(plans, roots, roots_wide, D, int(n_wide)):
-        with torch.cuda.device(ms[0].device):
-            check(_lib.lib().raht_fwd_quant_mixed_batch(n, hp, mp, ld, D, st, len(st), int(n_wide), op, old, _stream()))
-    return outs
+    return _batch(_lib.lib().raht_fwd_quant_mixed_batch, plans, Cs, torch.float32, "C", torch.int32, steps, C.c_double, n_wide, roots,
+                  roots_wide)
 
 
 def dequant_inverse_mixed_batch(plans, Qs, steps, n_wide=3, roots=None, roots_wide=None):
     """[C_i] = ``plans[i].dequant_inverse_mixed(Qs[i], steps, n_wide)`` of every scene in one set of launches, bit for bit
     (counterpart of ``forward_quant_mixed_batch``; roots / roots_wide as there, read instead of written)."""
-    n, D, ms, hp, mp, ld = _batch_arrays(plans, Qs, torch.int32, "Q")
-    st = _steps64(steps, D)
-    outs, op, old = _batch_out(plans, D, torch.float32, ms[0].device)
-    with _batch_mixed_roots(plans, roots, roots_wide, D, int(n_wide)):
-        with torch.cuda.device(ms[0].device):
-            check(_lib.lib().raht_dequant_inv_mixed_batch(n, hp, mp, ld, D, st, len(st), int(n_wide), op, old, _stream()))
-    return outs
+    return _batch(_lib.lib().raht_dequant_inv_mixed_batch, plans, Qs, torch.int32, "Q", torch.float32, steps, C.c_double, n_wide, roots,
+                  roots_wide)
 
 
 def mixed_batch_stats(plans, D, n_wide, inverse=False):
@@ -756,79 +661,66 @@ def mixed_batch_stats(plans, D, n_wide, inverse=False):
     return {"tile_launches": t.value, "top_launches": u.value, "single_scene_calls": v.value}
 
 
-def quant_rows(X, steps, pos, Q):
-    """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place (X float32 (n, D), pos int64 (n,), Q int32). X and Q may be
-    column slices of wider matrices (contiguous rows, any row stride)."""
+def _quant_rows(X, steps, pos, Q, dtype):
     _need_cuda(X, "X")
     if X.shape[0] == 0:
         return Q
-    X = X.to(torch.float32)
-    if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-        X = X.contiguous()
+    if dtype == torch.float64 and X.dtype != dtype:
+        raise ValueError("quant_rows_f64: X must be float64")           # (the float32 call casts)
+    X = _rows(X, dtype, "X")
     n, D = X.shape
-    st = _steps(steps, D)
+    st = _step_array(steps, D, _STEP_CTYPE[dtype])
     pos = pos.to(torch.int64).contiguous()
     if Q.dtype != torch.int32 or Q.stride(1) != 1:
         raise ValueError("Q must be an int32 matrix with contiguous rows")
-    with torch.cuda.device(X.device):
-        check(_lib.lib().raht_quant_rows(C.c_void_p(X.data_ptr()), X.stride(0), n, D, st, len(st), C.c_void_p(pos.data_ptr()),
-                                         C.c_void_p(Q.data_ptr()), Q.stride(0), _stream()))
+    _call(_fn("raht_quant_rows", dtype), X.device, _p(X), X.stride(0), n, D, st, len(st), _p(pos), _p(Q), Q.stride(0))
     return Q
 
 
-def dequant_rows(Q, steps, pos, out=None):
-    """-> float32 (n, D): Q[pos[i], :] * step (written into ``out`` when given: a float32 (n, D) view with contiguous rows)."""
+def _dequant_rows(Q, steps, pos, out, dtype):
     _need_cuda(Q, "Q")
     if Q.dtype != torch.int32 or Q.stride(1) != 1:
         raise ValueError("Q must be an int32 matrix with contiguous rows")
     D = Q.shape[1]
-    st = _steps(steps, D)
+    st = _step_array(steps, D, _STEP_CTYPE[dtype])
     pos = pos.to(torch.int64).contiguous()
-    X = torch.empty((pos.shape[0], D), dtype=torch.float32, device=Q.device) if out is None else out
-    if X.dtype != torch.float32 or tuple(X.shape) != (pos.shape[0], D) or (X.shape[0] > 0 and (X.stride(1) != 1 or X.stride(0) < D)):
-        raise ValueError("out must be a float32 (n, D) tensor with contiguous rows")
-    with torch.cuda.device(Q.device):
-        check(_lib.lib().raht_dequant_rows(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(pos.data_ptr()), pos.shape[0], D,
-                                           st, len(st), C.c_void_p(X.data_ptr()), max(X.stride(0), D), _stream()))
+    X = torch.empty((pos.shape[0], D), dtype=dtype, device=Q.device) if out is None else out
+    if X.dtype != dtype or tuple(X.shape) != (pos.shape[0], D) or (X.shape[0] > 0 and (X.stride(1) != 1 or X.stride(0) < D)):
+        raise ValueError(f"out must be a {'float64' if dtype == torch.float64 else 'float32'} (n, D) tensor with contiguous rows")
+    _call(_fn("raht_dequant_rows", dtype), Q.device, _p(Q), Q.stride(0), _p(pos), pos.shape[0], D, st, len(st), _p(X), max(X.stride(0), D))
     return X
+
+
+def quant_rows(X, steps, pos, Q):
+    """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place (X float32 (n, D), pos int64 (n,), Q int32). X and Q may be
+    column slices of wider matrices (contiguous rows, any row stride)."""
+    return _quant_rows(X, steps, pos, Q, torch.float32)
+
+
+def dequant_rows(Q, steps, pos, out=None):
+    """-> float32 (n, D): Q[pos[i], :] * step (written into ``out`` when given: a float32 (n, D) view with contiguous rows)."""
+    return _dequant_rows(Q, steps, pos, out, torch.float32)
 
 
 def quant_rows_f64(X, steps, pos, Q):
     """Q[pos[i], :] = floor(X[i, :] / step + 0.5) in place, in float64 (X float64 (n, D), float64 steps, IEEE double
     division: the reference's arithmetic, python/encode_3dgs.py:204)."""
-    _need_cuda(X, "X")
-    if X.shape[0] == 0:
-        return Q
-    if X.dtype != torch.float64:
-        raise ValueError("quant_rows_f64: X must be float64")
-    if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
-        X = X.contiguous()
-    n, D = X.shape
-    st = _steps64(steps, D)
-    pos = pos.to(torch.int64).contiguous()
-    if Q.dtype != torch.int32 or Q.stride(1) != 1:
-        raise ValueError("Q must be an int32 matrix with contiguous rows")
-    with torch.cuda.device(X.device):
-        check(_lib.lib().raht_quant_rows_f64(C.c_void_p(X.data_ptr()), X.stride(0), n, D, st, len(st), C.c_void_p(pos.data_ptr()),
-                                             C.c_void_p(Q.data_ptr()), Q.stride(0), _stream()))
-    return Q
+    return _quant_rows(X, steps, pos, Q, torch.float64)
 
 
 def dequant_rows_f64(Q, steps, pos, out=None):
     """-> float64 (n, D): Q[pos[i], :] * step in float64 (written into ``out`` when given: a float64 (n, D) view with contiguous rows)."""
-    _need_cuda(Q, "Q")
-    if Q.dtype != torch.int32 or Q.stride(1) != 1:
-        raise ValueError("Q must be an int32 matrix with contiguous rows")
-    D = Q.shape[1]
-    st = _steps64(steps, D)
-    pos = pos.to(torch.int64).contiguous()
-    X = torch.empty((pos.shape[0], D), dtype=torch.float64, device=Q.device) if out is None else out
-    if X.dtype != torch.float64 or tuple(X.shape) != (pos.shape[0], D) or (X.shape[0] > 0 and (X.stride(1) != 1 or X.stride(0) < D)):
-        raise ValueError("out must be a float64 (n, D) tensor with contiguous rows")
-    with torch.cuda.device(Q.device):
-        check(_lib.lib().raht_dequant_rows_f64(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(pos.data_ptr()), pos.shape[0], D,
-                                               st, len(st), C.c_void_p(X.data_ptr()), max(X.stride(0), D), _stream()))
-    return X
+    return _dequant_rows(Q, steps, pos, out, torch.float64)
+
+
+def sqdiff_columns(A, B):
+    """-> float64 (D,) device tensor: the per-column sums of (A - B)^2 of two float32 or two float64 (N, D) matrices with
+    contiguous rows, in one pass (raht_sqdiff_columns; differences in the matrices' own type, sums in float64)."""
+    _need_cuda(A, "A")
+    N, D = A.shape
+    out = torch.empty(D, dtype=torch.float64, device=A.device)
+    _call(_lib.lib().raht_sqdiff_columns, A.device, _p(A), A.stride(0), _p(B), B.stride(0), N, D, _VDT[A.dtype], _p(out))
+    return out
 
 
 def _rows_move(fn, src, pos, dst):

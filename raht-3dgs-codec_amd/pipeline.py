@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import rlgr as rlgr_mod
-from .ops import RAHT_param_reorder_fast, plan_of, raht_fn
+from .ops import RAHT_param_reorder_fast, plan_of, raht_fn, sqdiff_columns, step_list
 
 CSV_HEADER = ("Frame,Quantization_Step,Rate_bpp,"
               "RAHT_prelude_time,RAHT_transform_time,Quant_time,"
@@ -36,6 +36,14 @@ def _sync():
 
 def _psnr(a, b):
     return -10 * math.log10(torch.mean((a - b) ** 2).item() + 1e-10)               # encode_3dgs.py:298-310
+
+
+def _step_args(step):
+    """A quantization step of a frame -> (what the quantizer calls take, the row's Quantization_Step): a scalar (the drivers'
+    colorStep entries) gives (float, the step as given); one step per channel (per_attribute_steps below) gives (list of floats,
+    "per_attribute")."""
+    st = step_list(step)
+    return (st, "per_attribute") if np.ndim(step) else (st[0], step)
 
 
 def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=torch.float32, fused=True,
@@ -91,16 +99,10 @@ def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=to
     rows = []
     coder = None
     for step in steps:
-        # a scalar step (the drivers' colorStep entries) or one step per channel (per_attribute_steps below)
-        per_channel = not isinstance(step, (int, float))
-        if per_channel:
-            step_list = [float(x) for x in (step.tolist() if hasattr(step, "tolist") else step)]
-            step_t = torch.tensor(step_list, dtype=dtype, device=device)           # tensor divisor: true division on the GPU
-            step_arg = step_list
-        else:
-            step_t, step_arg = step, float(step)
-        r = dict(Frame=frame, Quantization_Step="per_attribute" if per_channel else step)
-        step = step_t
+        step_arg, label = _step_args(step)
+        r = dict(Frame=frame, Quantization_Step=label)
+        if label == "per_attribute":
+            step = torch.tensor(step_arg, dtype=dtype, device=device)              # tensor divisor: true division on the GPU
         t_step0 = time.time()
         # ---------------- encoder ----------------
         if use_fused:
@@ -213,9 +215,8 @@ def _encode_frame_gpu_entropy(V_int, attributes, J, steps, frame, device, dtype,
     coder = rlgr_mod.SegmentedCoder(N, C.shape[1], seg_len, 1, dev)
     rows = []
     for step in steps:
-        per_channel = not isinstance(step, (int, float))
-        step_arg = [float(x) for x in (step.tolist() if hasattr(step, "tolist") else step)] if per_channel else float(step)
-        r = dict(Frame=frame, Quantization_Step="per_attribute" if per_channel else step)
+        step_arg, label = _step_args(step)
+        r = dict(Frame=frame, Quantization_Step=label)
         t_step0 = time.time()
         t0 = time.time()
         coeff_reordered = plan.forward_quant(C, step_arg)
@@ -338,15 +339,7 @@ def _psnr_columns(r, C, C_rec):
     trip each (2.0 -> 0.2 ms per step on a 3 M x 56 frame)."""
     if C.is_cuda and C.dtype in (torch.float32, torch.float64) and C.dim() == 2 and C.shape == C_rec.shape and C.dtype == C_rec.dtype \
             and C.stride(1) == 1 and C_rec.stride(1) == 1:
-        import ctypes as _C
-        from . import _lib
-        N, D = C.shape
-        out = torch.empty(D, dtype=torch.float64, device=C.device)
-        with torch.cuda.device(C.device):
-            _lib.check(_lib.lib().raht_sqdiff_columns(_C.c_void_p(C.data_ptr()), C.stride(0), _C.c_void_p(C_rec.data_ptr()), C_rec.stride(0), N, D,
-                                                      _lib.RAHT_F32 if C.dtype == torch.float32 else _lib.RAHT_F64, _C.c_void_p(out.data_ptr()),
-                                                      _C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        _psnr_from_ssd(r, out, N)
+        _psnr_from_ssd(r, sqdiff_columns(C, C_rec), C.shape[0])
         return
     r["PSNR_all"] = _psnr(C, C_rec)                                                 # encode_3dgs.py:298-310
     r["PSNR_quats"] = _psnr(C[:, 0:4], C_rec[:, 0:4])
@@ -413,12 +406,6 @@ def _encode_frame_overlapped(V_int, attributes, J, steps, frame, device, dtype, 
     steps = list(steps)
     n = len(steps)
 
-    def step_args(step):
-        if isinstance(step, (int, float)):
-            return float(step), step
-        lst = [float(x) for x in (step.tolist() if hasattr(step, "tolist") else step)]
-        return lst, "per_attribute"
-
     coder = rlgr_mod.ChannelCoder(N, D, 1, nthreads)
 
     def host_job(i, ev_dn):
@@ -438,7 +425,7 @@ def _encode_frame_overlapped(V_int, attributes, J, steps, frame, device, dtype, 
     with ThreadPoolExecutor(max_workers=1) as pool:
         for i in range(n + 1):
             if i < n:
-                sa, _ = step_args(steps[i])
+                sa, _ = _step_args(steps[i])
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(main)
                 q_dev = rlgr_mod.transpose_on_device(plan.forward_quant(C, sa))
@@ -454,8 +441,8 @@ def _encode_frame_overlapped(V_int, attributes, J, steps, frame, device, dtype, 
             if i >= 1:
                 k = i - 1
                 size_bytes, t_enc, t_dec, t_done = jobs[k].result()
-                sa, label = step_args(steps[k])
-                r = dict(Frame=frame, Quantization_Step=label if label == "per_attribute" else steps[k])
+                sa, label = _step_args(steps[k])
+                r = dict(Frame=frame, Quantization_Step=label)
                 f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0 = time.time()
                 qd = pin_up[k % 2].to(dev, non_blocking=True)

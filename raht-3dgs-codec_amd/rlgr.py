@@ -18,6 +18,7 @@ _STAGING = {}
 
 from . import _lib
 from ._lib import check
+from .ops import step_list
 
 
 def _as_i32(seq):
@@ -587,7 +588,7 @@ class SegmentedCoder:
             raise ValueError("SegmentedCoder.rate: expected an (N, D) float32 or float64 CUDA tensor with unit column stride")
         N, D = int(T.shape[0]), int(T.shape[1])
         f64 = T.dtype == torch.float64
-        rows = [SegmentedCoder.step_row(st) for st in steps]
+        rows = [step_list(st) for st in steps]
         k = len(rows)
         if k < 1 or any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) not in (1, D):
             raise ValueError("SegmentedCoder.rate: steps must be k scalars or k tables of D entries")
@@ -608,11 +609,7 @@ class SegmentedCoder:
         container = SegmentedCoder.container_size(G, padded.sum(dim=1).cpu().numpy())
         return container, seg_bytes, sse
 
-    @staticmethod
-    def step_row(st):
-        """one quantization step as a list of floats: [st] for a scalar (Python or numpy number, 0-d array or tensor), else its
-        entries"""
-        return [float(st)] if np.ndim(st) == 0 else [float(x) for x in st]
+    step_row = staticmethod(step_list)                        # (one quantization step as a list of floats: ops.step_list)
 
     @staticmethod
     def container_size(G, payload):

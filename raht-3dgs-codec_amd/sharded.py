@@ -467,13 +467,10 @@ class ShardedRaht:
     # ---- mixed precision (n_wide > 0) ------------------------------------------------------------------
     def _mixed_steps(self, step, D):
         """-> (steps of columns [n_wide, D), steps of columns [0, n_wide)): a scalar stays one; D per-channel values split"""
-        if isinstance(step, (int, float)):
-            return float(step), float(step)
-        st = [float(x) for x in (step.tolist() if hasattr(step, "tolist") else step)]
+        from .ops import step_list
+        st = step_list(step, D)
         if len(st) == 1:
             return st[0], st[0]
-        if len(st) != D:
-            raise ValueError("steps must be a scalar or have D entries")
         return st[self.n_wide:], st[: self.n_wide]
 
     def _mixed_buffers(self, D):
