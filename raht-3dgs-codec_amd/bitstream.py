@@ -20,6 +20,7 @@ import math
 
 import numpy as np
 
+from . import ops
 from .geometry import MAX_J, OctreeCoder
 from .ops import step_list
 from .rlgr import SegmentedCoder
@@ -38,33 +39,86 @@ def _step_list(step, D):
     return steps
 
 
+def _frame_input(who, V_int, attributes, J, n_wide, dev):
+    """What an encoder is handed for a frame, checked -> (V (N, 3) int64, A (N, D) float32) on ``dev``. ``who``: the function, and
+    the frame where there are several."""
+    import torch
+    V = torch.as_tensor(V_int).to(dev, torch.int64)
+    A = torch.as_tensor(attributes).to(dev, torch.float32)
+    if V.dim() != 2 or V.shape[1] != 3 or A.dim() != 2 or A.shape[0] != V.shape[0] or V.shape[0] < 1:
+        raise ValueError(f"{who}: expected (N, 3) coordinates and (N, D) attributes, N >= 1")
+    if not 1 <= J <= MAX_J:
+        raise ValueError(f"{who}: J outside 1 .. 21")
+    if not 0 <= n_wide <= A.shape[1]:
+        raise ValueError(f"{who}: n_wide outside 0 .. D")
+    return V, A
+
+
+def _geometry_and_plan(V, J, geometry):
+    """sorted voxel coordinates -> (geometry section, plan over their keys)"""
+    keys = ops.get_morton_code(V, J)
+    geo = OctreeCoder.encode(keys, J, entropy=geometry)                   # (also refuses rows that are not sorted and unique)
+    return geo, ops.RahtPlan.from_keys(keys, 3 * J)
+
+
+def _quantize(plans, As, steps, n_wide):
+    """[plan], [A] -> [Q]: transform + quantization in float32 or, with ``n_wide``, mixed precision; one frame through its plan,
+    several in one set of launches"""
+    if len(plans) == 1:
+        return [plans[0].forward_quant_mixed(As[0], steps, n_wide) if n_wide else plans[0].forward_quant(As[0], steps)]
+    return ops.forward_quant_mixed_batch(plans, As, steps, n_wide) if n_wide else ops.forward_quant_batch(plans, As, steps)
+
+
+def _reconstruct(plans, Qs, steps, n_wide, roots=None, roots_wide=None):
+    """[plan], [Q] -> [C_rec]: the inverse of ``_quantize``; one frame (of a truncated plan: with the ``roots`` of its cells, and
+    ``roots_wide`` for the wide columns) through its plan, several in one set of launches"""
+    if len(plans) == 1 and n_wide:
+        return [plans[0].dequant_inverse_mixed(Qs[0], steps, n_wide, roots=roots, roots_wide=roots_wide)]
+    if len(plans) == 1:
+        return [plans[0].dequant_inverse(Qs[0], steps, roots=roots)]
+    return ops.dequant_inverse_mixed_batch(plans, Qs, steps, n_wide) if n_wide else ops.dequant_inverse_batch(plans, Qs, steps)
+
+
+def _attribute_parts(Qs, seg_len, dev):
+    """quantized (N_i, D) matrices -> every frame's attribute container in pieces (header, length table, payload). One frame goes
+    through ``SegmentedCoder.encode``; so does, among several, a frame that needs 64-bit offsets (it fills the chip by itself) and a
+    frame of exactly D voxels (``encode`` reads a square matrix as (D, N): the same call for the same bytes whatever its company);
+    the others share one set of launches (``encode_ragged`` on the row-major integers)."""
+    coders = [SegmentedCoder(Q.shape[0], Q.shape[1], seg_len, 1, dev) for Q in Qs]
+    rest = []
+    for c, Q in zip(coders, Qs):
+        if len(Qs) == 1 or c.wide or c.N == c.D:
+            c.encode(Q)
+        else:
+            rest.append((c, Q))
+    if rest:
+        SegmentedCoder.encode_ragged([c for c, _ in rest], [Q for _, Q in rest], row_major=True)
+    out = []
+    for c in coders:
+        hdr, lens, payload = c.container_parts()
+        out.append([hdr, lens.tobytes(), payload.tobytes()])
+    return out
+
+
+def _refuse_outside(bad, who=""):
+    """bad: a coder's ``bad`` word is set -- a table entry reached outside the payload, and that segment decoded as zeros"""
+    if bad:
+        raise ValueError(f"{who}frame container: an attribute segment reaches outside its payload")
+
+
 def encode_frame_bytes(V_int, attributes, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None):
     """V_int: (N, 3) integer voxel coordinates in Morton order, no voxel twice (what the voxelizer yields); attributes: (N, D)
     float32; numpy arrays or tensors. -> bytes. Raises RahtError when the rows are not in strictly ascending Morton order."""
     import torch
-    from . import ops
     dev = torch.device(device)
-    J = int(J)
-    V = torch.as_tensor(V_int).to(dev, torch.int64)
-    A = torch.as_tensor(attributes).to(dev, torch.float32)
-    if V.dim() != 2 or V.shape[1] != 3 or A.dim() != 2 or A.shape[0] != V.shape[0] or V.shape[0] < 1:
-        raise ValueError("encode_frame_bytes: expected (N, 3) coordinates and (N, D) attributes, N >= 1")
-    if not 1 <= J <= MAX_J:
-        raise ValueError("encode_frame_bytes: J outside 1 .. 21")
+    J, n_wide = int(J), int(n_wide)
+    V, A = _frame_input("encode_frame_bytes", V_int, attributes, J, n_wide, dev)
     N, D = A.shape
-    n_wide = int(n_wide)
-    if not 0 <= n_wide <= D:
-        raise ValueError("encode_frame_bytes: n_wide outside 0 .. D")
     steps = _step_list(step, D)
     with torch.cuda.device(dev):
-        keys = ops.get_morton_code(V, J)
-        geo = OctreeCoder.encode(keys, J, entropy=geometry)               # (also refuses rows that are not sorted and unique)
-        plan = ops.RahtPlan.from_keys(keys, 3 * J)
-        Q = plan.forward_quant_mixed(A, steps, n_wide) if n_wide else plan.forward_quant(A, steps)
-        sc = SegmentedCoder(N, D, seg_len, 1, dev)
-        sc.encode(Q)
-        att = sc.container()
-    return _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att)
+        geo, plan = _geometry_and_plan(V, J, geometry)
+        att = _attribute_parts(_quantize([plan], [A], steps, n_wide), seg_len, dev)[0]
+    return b"".join(_frame_parts(J, N, D, n_wide, steps, vmin, width, geo, att))
 
 
 def _frame_parts(J, N, D, n_wide, steps, vmin, width, geo, att_parts):
@@ -75,10 +129,6 @@ def _frame_parts(J, N, D, n_wide, steps, vmin, width, geo, att_parts):
     box.append(0.0 if width is None else float(width))
     return [MAGIC + np.array([J, N, D, n_wide, len(steps)], np.int64).tobytes() + np.array(steps + box, np.float64).tobytes()
             + np.array([len(geo)], np.int64).tobytes(), geo, np.array([sum(len(a) for a in att_parts)], np.int64).tobytes(), *att_parts]
-
-
-def _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att):
-    return b"".join(_frame_parts(J, N, D, n_wide, steps, vmin, width, geo, [att]))
 
 
 def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scale_range=(2 ** -10, 2 ** 10), rounds=3, n_wide=0,
@@ -94,33 +144,22 @@ def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scal
     attribute_bytes, tried (every (multiplier, bytes) in evaluation order), sse (float64 [D] at the chosen point).
     ``ValueError`` when the geometry alone exceeds the target or not even the coarsest multiplier fits."""
     import torch
-    from . import ops
     dev = torch.device(device)
-    J = int(J)
+    J, n_wide = int(J), int(n_wide)
     target = int(target_bytes)
-    V = torch.as_tensor(V_int).to(dev, torch.int64)
-    A = torch.as_tensor(attributes).to(dev, torch.float32)
-    if V.dim() != 2 or V.shape[1] != 3 or A.dim() != 2 or A.shape[0] != V.shape[0] or V.shape[0] < 1:
-        raise ValueError("encode_frame_bytes_target: expected (N, 3) coordinates and (N, D) attributes, N >= 1")
-    if not 1 <= J <= MAX_J:
-        raise ValueError("encode_frame_bytes_target: J outside 1 .. 21")
+    V, A = _frame_input("encode_frame_bytes_target", V_int, attributes, J, n_wide, dev)
     N, D = A.shape
-    n_wide = int(n_wide)
-    if not 0 <= n_wide <= D:
-        raise ValueError("encode_frame_bytes_target: n_wide outside 0 .. D")
     base = _step_list(step, D)
     lo, hi = float(scale_range[0]), float(scale_range[1])
     if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi) or int(rounds) < 1:
         raise ValueError("encode_frame_bytes_target: scale_range must be 0 < lo <= hi, rounds >= 1")
     K = SegmentedCoder.RATE_MAX
     with torch.cuda.device(dev):
-        keys = ops.get_morton_code(V, J)
-        geo = OctreeCoder.encode(keys, J, entropy=geometry)               # (also refuses rows that are not sorted and unique)
+        geo, plan = _geometry_and_plan(V, J, geometry)
         # the frame around the attribute container: header, steps + box, the geometry section and the two length words
         budget = target - (len(MAGIC) + 40 + 8 * (len(base) + 4)) - (8 + len(geo)) - 8
         if budget < 0:
             raise ValueError(f"encode_frame_bytes_target: the geometry section and the header alone take {target - budget} bytes, target {target}")
-        plan = ops.RahtPlan.from_keys(keys, 3 * J)
         tried, sse_of, fits = [], {}, {}
         chosen = None
         for rnd in range(int(rounds)):
@@ -150,14 +189,11 @@ def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scal
         # the candidates that were seen to fit, from the chosen one towards coarser steps
         for m in sorted(x for x in fits if fits[x] and x >= chosen):
             steps = [s * m for s in base]
-            Q = plan.forward_quant_mixed(A, steps, n_wide) if n_wide else plan.forward_quant(A, steps)
-            sc = SegmentedCoder(N, D, seg_len, 1, dev)
-            sc.encode(Q)
-            att = sc.container()
-            blob = _frame_blob(J, N, D, n_wide, steps, vmin, width, geo, att)
+            att = _attribute_parts(_quantize([plan], [A], steps, n_wide), seg_len, dev)[0]
+            blob = b"".join(_frame_parts(J, N, D, n_wide, steps, vmin, width, geo, att))
             if len(blob) <= target:
-                info = dict(multiplier=m, steps=steps, predicted_attribute_bytes=predicted[m], attribute_bytes=len(att), tried=tried,
-                            sse=sse_of[m])
+                info = dict(multiplier=m, steps=steps, predicted_attribute_bytes=predicted[m], attribute_bytes=sum(len(a) for a in att),
+                            tried=tried, sse=sse_of[m])
                 return blob, info
     raise ValueError("encode_frame_bytes_target: no candidate that was predicted to fit did fit")
 
@@ -207,7 +243,6 @@ def decode_frame_bytes(blob, device="cuda", max_voxels=None):
     """-> (V_int (N, 3) int64, C_rec (N, D) float32), CUDA tensors on ``device``, from the bytes alone. ``max_voxels``: refuse
     frames that announce more voxels than this before anything is allocated for them. ``ValueError`` for a corrupt frame."""
     import torch
-    from . import ops
     h = parse_frame(blob, max_voxels)
     dev = torch.device(device)
     (go, gl), (ao, al) = h["geometry"], h["attributes"]
@@ -217,10 +252,8 @@ def decode_frame_bytes(blob, device="cuda", max_voxels=None):
         plan = ops.RahtPlan.from_keys(keys, 3 * h["J"])
         sc = SegmentedCoder.from_container(blob[ao: ao + al], dev, max_symbols=h["N"] * h["D"])
         Q = sc.decode(row_major=True)
-        steps = h["steps"]
-        C_rec = plan.dequant_inverse_mixed(Q, steps, h["n_wide"]) if h["n_wide"] else plan.dequant_inverse(Q, steps)
-        if int(sc.bad.item()) != 0:
-            raise ValueError("frame container: an attribute segment reaches outside its payload")
+        C_rec = _reconstruct([plan], [Q], h["steps"], h["n_wide"])[0]
+        _refuse_outside(int(sc.bad.item()))
     return V, C_rec
 
 
@@ -264,7 +297,6 @@ def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys
     keys. No N x D matrix is allocated: the only full-length arrays are the keys and the cell search's flags.
     ``ValueError`` for a corrupt frame or arguments outside the ranges above."""
     import torch
-    from . import ops
     h = parse_frame(blob, max_voxels)
     J, N, D, n_wide, steps = h["J"], h["N"], h["D"], h["n_wide"], h["steps"]
     try:
@@ -314,14 +346,10 @@ def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys
         # the region: a plan truncated at the cells over its own rows, its coded matrix put together from the decoded runs
         plan = ops.RahtPlan.from_keys(keys[a:b], 3 * J, top_level=tl)
         Qr = ops.region_assemble(Qc, [(compact(r), d, n) for r, d, n in runs], b - a)
-        if n_wide:
-            wide = top.dequant_inverse(Qc[:n_top, :n_wide], steps[:n_wide], dtype=torch.float64)[j0:j1]
-            C_rec = plan.dequant_inverse_mixed(Qr, steps, n_wide, roots=roots.contiguous(), roots_wide=wide.contiguous())
-        else:
-            C_rec = plan.dequant_inverse(Qr, steps, roots=roots.contiguous())
+        wide = top.dequant_inverse(Qc[:n_top, :n_wide], steps[:n_wide], dtype=torch.float64)[j0:j1].contiguous() if n_wide else None
+        C_rec = _reconstruct([plan], [Qr], steps, n_wide, roots=roots.contiguous(), roots_wide=wide)[0]
         V = ops.demorton(keys[a:b], J)
-        if int(sc.bad.item()) != 0:
-            raise ValueError("frame container: an attribute segment reaches outside its payload")
+        _refuse_outside(int(sc.bad.item()))
     ranges = [(0, ao)]                                                    # frame header, geometry section, the attributes' length word
     for off, ln in att_ranges:                                            # the first: header + table (+ the slots that follow them)
         if ranges[-1][0] + ranges[-1][1] == ao + off:
@@ -392,54 +420,25 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     (``SegmentedCoder.encode_ragged`` on the row-major integers). Device memory: the quantized matrices and the coders' buffers
     of a whole chunk are alive together, about 8 N D bytes per frame beside its attributes (12 frames of 1 M x 59: 5.7 GB)."""
     import torch
-    from . import ops
     dev = torch.device(device)
-    J = int(J)
+    J, n_wide = int(J), int(n_wide)
     if not frames:
         raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
-    if not 1 <= J <= MAX_J:
-        raise ValueError("encode_sequence_bytes: J outside 1 .. 21")
     VA = []
     for i, (V_int, attributes) in enumerate(frames):
-        V = torch.as_tensor(V_int).to(dev, torch.int64)
-        A = torch.as_tensor(attributes).to(dev, torch.float32)
-        if V.dim() != 2 or V.shape[1] != 3 or A.dim() != 2 or A.shape[0] != V.shape[0] or V.shape[0] < 1:
-            raise ValueError(f"encode_sequence_bytes: frame {i}: expected (N, 3) coordinates and (N, D) attributes, N >= 1")
+        V, A = _frame_input(f"encode_sequence_bytes: frame {i}", V_int, attributes, J, n_wide, dev)
         if VA and A.shape[1] != VA[0][1].shape[1]:
             raise ValueError(f"encode_sequence_bytes: frame {i} has {A.shape[1]} attribute columns, frame 0 has {VA[0][1].shape[1]}")
         VA.append((V, A))
     D = int(VA[0][1].shape[1])
-    n_wide = int(n_wide)
-    if not 0 <= n_wide <= D:
-        raise ValueError("encode_sequence_bytes: n_wide outside 0 .. D")
     steps = _step_list(step, D)
     parts = []                                                               # (the pieces of every frame: joined once, at the end)
     with torch.cuda.device(dev):
         for lo in range(0, len(VA), SEQ_CHUNK):
             chunk = VA[lo: lo + SEQ_CHUNK]
-            geos, plans = [], []
-            for V, _ in chunk:
-                keys = ops.get_morton_code(V, J)
-                geos.append(OctreeCoder.encode(keys, J, entropy=geometry))    # (also refuses rows that are not sorted and unique)
-                plans.append(ops.RahtPlan.from_keys(keys, 3 * J))
-            As = [A for _, A in chunk]
-            if len(chunk) == 1:
-                Qs = [plans[0].forward_quant_mixed(As[0], steps, n_wide) if n_wide else plans[0].forward_quant(As[0], steps)]
-            else:
-                Qs = ops.forward_quant_mixed_batch(plans, As, steps, n_wide) if n_wide else ops.forward_quant_batch(plans, As, steps)
-            coders = [SegmentedCoder(A.shape[0], D, seg_len, 1, dev) for A in As]
-            # alone: a frame that needs 64-bit offsets (it fills the chip by itself) and a frame of exactly D voxels, whose square Q
-            # encode_frame_bytes hands to a coder that reads a square matrix as (D, N) -- the same call here, for the same bytes
-            alone = [c.wide or c.N == c.D for c in coders]
-            for c, Q, a in zip(coders, Qs, alone):
-                if a:
-                    c.encode(Q)
-            rest = [(c, Q) for c, Q, a in zip(coders, Qs, alone) if not a]
-            if rest:
-                SegmentedCoder.encode_ragged([c for c, _ in rest], [Q for _, Q in rest], row_major=True)
-            for (V, A), geo, c in zip(chunk, geos, coders):
-                hdr, lens, payload = c.container_parts()
-                parts.append(_frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, [hdr, lens.tobytes(), payload.tobytes()]))
+            geos, plans = zip(*[_geometry_and_plan(V, J, geometry) for V, _ in chunk])
+            atts = _attribute_parts(_quantize(list(plans), [A for _, A in chunk], steps, n_wide), seg_len, dev)
+            parts += [_frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att) for (_, A), geo, att in zip(chunk, geos, atts)]
     return _pack_parts(parts)
 
 
@@ -452,7 +451,6 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
     its index -- for a header or an attribute length table that does not add up before any device work, for a corrupt geometry
     section or a segment outside its payload when that frame's group is decoded."""
     import torch
-    from . import ops
     off = parse_sequence(blob, max_frames)
     n = len(off) - 1
     if frames is None:
@@ -510,10 +508,10 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
             else:
                 Qs = SegmentedCoder.decode_ragged(coders, row_major=True)
                 bad = None
-            Cs = ops.dequant_inverse_mixed_batch(plans, Qs, steps, n_wide) if n_wide else ops.dequant_inverse_batch(plans, Qs, steps)
+            Cs = _reconstruct(plans, Qs, steps, n_wide)
             if bad is None:
                 bad = SegmentedCoder.roundtrip_failed(coders)
             if bad:
-                raise ValueError(f"sequence container: frame {group[bad[0]][0]}: frame container: an attribute segment reaches outside its payload")
+                _refuse_outside(True, f"sequence container: frame {group[bad[0]][0]}: ")
             out += list(zip(Vs, Cs))
     return out

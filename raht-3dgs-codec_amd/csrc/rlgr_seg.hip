@@ -649,21 +649,18 @@ template <typename OffT> inline uint64_t total_of(const uint32_t *back, int j)
     return sizeof(OffT) == 8 ? ((uint64_t)w[3] << 32) | w[2] : (uint64_t)w[1];
 }
 
-// nseg, G of a shape and the width its offsets need: refuses what no entry point takes ("too many segments") and, for the
-// 32-bit tables, what raht_rlgr_seg_offsets_width sends to the 64-bit ones. (Arguments already checked: N, D >= 1, seg_len >= 64.)
-template <typename OffT>
-int seg_shape(const char *fn, int64_t N, int D, int seg_len, int64_t *nseg, int64_t *G)
+// nseg and G of a shape (N, D >= 1, seg_len >= 64) -> the width its offsets need, as raht_rlgr_seg_offsets_width answers it: 32
+// when the container stays below 4 GiB whatever the data (worst case: every symbol escapes -- 8 bytes and a bit,
+// raht_rlgr_bound(seg_len) per segment -- plus the 4-byte padding of every segment), 64 otherwise. 0: too many segments
+// (nseg, G are not set); -1: the length of a segment may not fit 32 bits (the lengths stay uint32 in either table).
+int shape_width(int64_t N, int D, int seg_len, int64_t *nseg, int64_t *G)
 {
     *nseg = (N - 1) / seg_len + 1;
-    *G = *nseg < ((int64_t)1 << 31) ? *nseg * D : (int64_t)1 << 31;
-    if (*nseg >= ((int64_t)1 << 31) || *G >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    const int width = raht_rlgr_seg_offsets_width(N, D, seg_len);
-    if (sizeof(OffT) == 4 && width != 32) {
-        set_error("%s: %lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): split the frame", fn, (long long)N, D);
-        return RAHT_ERR_INVALID;
-    }
-    if (width < 0) { set_error("%s: seg_len = %d: the length of a segment may not fit 32 bits", fn, seg_len); return RAHT_ERR_INVALID; }
-    return RAHT_OK;
+    if (*nseg >= ((int64_t)1 << 31) || *nseg * D >= ((int64_t)1 << 31)) return 0;
+    *G = *nseg * D;
+    const int64_t per_seg = raht_rlgr_bound(seg_len) + 4;                       // < 2^35
+    if (per_seg - 4 >= ((int64_t)1 << 32)) return -1;
+    return per_seg * *G >= ((int64_t)1 << 32) ? 64 : 32;                        // (< 2^66 / 2: G < 2^31, per_seg < 2^32 -- no overflow)
 }
 
 // What the host knows of the k frames of a call: every frame's shape, and where its slots begin (the running sum of G)
@@ -673,16 +670,15 @@ struct SegFrames {
     int64_t nseg[RAHT_RLGR_BATCH_MAX], G[RAHT_RLGR_BATCH_MAX], slot0[RAHT_RLGR_BATCH_MAX];
     int64_t sumG = 0, maxG = 0;
 
-    void add(int64_t n, int D, int64_t sym, int64_t chan, int seg_len)          // (k < RAHT_RLGR_BATCH_MAX; n, D >= 1: checked by the caller)
+    void add(int64_t n, int64_t sym, int64_t chan, int64_t ns, int64_t g)       // (k < RAHT_RLGR_BATCH_MAX; ns, g: shape_width's)
     {
-        N[k] = n; sym_stride[k] = sym; chan_stride[k] = chan;
-        nseg[k] = (n - 1) / seg_len + 1;
-        G[k] = nseg[k] < ((int64_t)1 << 31) ? nseg[k] * D : (int64_t)1 << 31;
+        N[k] = n; sym_stride[k] = sym; chan_stride[k] = chan; nseg[k] = ns; G[k] = g;
         slot0[k] = sumG;
-        sumG += G[k];
-        maxG = G[k] > maxG ? G[k] : maxG;
+        sumG += g;
+        maxG = g > maxG ? g : maxG;
         ++k;
     }
+    SegFrames one(int j) const { SegFrames F1; F1.add(N[j], sym_stride[j], chan_stride[j], nseg[j], G[j]); return F1; }   // frame j alone
     // the shape of frame j < K into a job table (the entries behind k repeat frame 0: no kernel reads them)
     template <typename Jobs> void fill(Jobs &J, int j) const
     {
@@ -703,6 +699,90 @@ rlgr_seg::SegEncJobs<OffT, K> enc_jobs(const SegFrames &F, const int32_t *const 
         F.fill(J, j);
     }
     return J;
+}
+
+template <typename OffT, int K>
+rlgr_seg::SegDecJobs<OffT, K> dec_jobs(const SegFrames &F, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes,
+                                       int32_t *const *Q, const int32_t *const *expect)
+{
+    rlgr_seg::SegDecJobs<OffT, K> J;
+    for (int j = 0; j < K; ++j) {
+        const int q = j < F.k ? j : 0;
+        J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
+        J.expect[j] = expect ? expect[q] : nullptr;
+        F.fill(J, j);
+    }
+    return J;
+}
+
+// The k frames of a call as an entry point was handed them -> F, checked. D and seg_len are shared; N and the two strides are one
+// value for all frames (per_frame false: one frame, or k of one shape) or one per frame. Every frame is channel-major (sym_stride
+// 1, chan_stride >= N) or row-major (chan_stride 1, sym_stride >= D), all frames of a call the same; no frame has too many
+// segments or needs offsets wider than `widest` (32: what raht_rlgr_seg_offsets_width calls 64 is refused -- segment offsets and
+// the container's total could wrap; a decoder whose offsets came with its container takes either).
+int seg_frames(const char *fn, int widest, int k, const int64_t *N, const int64_t *sym_stride, const int64_t *chan_stride, bool per_frame, int D, int seg_len,
+               SegFrames *F)
+{
+    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !N || !sym_stride || !chan_stride || D < 1 || seg_len < 64) {
+        set_error("%s: bad argument (1 <= k <= %d, D >= 1, seg_len >= 64)", fn, RAHT_RLGR_BATCH_MAX);
+        return RAHT_ERR_INVALID;
+    }
+    bool all_cm = true, all_rm = true;
+    for (int j = 0; j < k; ++j) {
+        const int q = per_frame ? j : 0;
+        const int64_t n = N[q], sym = sym_stride[q], chan = chan_stride[q];
+        char who[24] = "";
+        if (per_frame) snprintf(who, sizeof(who), "frame %d: ", j);
+        const bool cm = n >= 1 && sym == 1 && chan >= n, rm = n >= 1 && chan == 1 && sym >= D;
+        if (!cm && !rm) {
+            set_error("%s: bad argument (%sN >= 1; channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn, who);
+            return RAHT_ERR_INVALID;
+        }
+        all_cm = all_cm && cm;
+        all_rm = all_rm && rm;
+        int64_t nseg, G;
+        const int width = shape_width(n, D, seg_len, &nseg, &G);
+        if (width == 0) { set_error("%s: %stoo many segments", fn, who); return RAHT_ERR_INVALID; }
+        if (width < 0) { set_error("%s: seg_len = %d: the length of a segment may not fit 32 bits", fn, seg_len); return RAHT_ERR_INVALID; }
+        if (width > widest) {
+            set_error("%s: %s%lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): code it alone, with 64-bit offsets", fn, who, (long long)n, D);
+            return RAHT_ERR_INVALID;
+        }
+        F->add(n, sym, chan, nseg, G);
+    }
+    if (!all_cm && !all_rm) { set_error("%s: the frames of a call are all channel-major or all row-major", fn); return RAHT_ERR_INVALID; }
+    return RAHT_OK;
+}
+
+// the tables of an encode call: every frame's input, tables and container (cap >= 16 bytes, 4-byte aligned)
+template <typename OffT>
+int enc_tables_ok(const char *fn, const SegFrames &F, const int32_t *const *Q, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap,
+                  const int64_t *total_bytes)
+{
+    if (!Q || !seg_bytes || !seg_off || !out || !cap || !total_bytes) { set_error("%s: bad argument (a table is NULL)", fn); return RAHT_ERR_INVALID; }
+    for (int j = 0; j < F.k; ++j)
+        if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
+    return RAHT_OK;
+}
+
+// the tables of a decode call: every frame's streams (4-byte aligned, a multiple of 4 bytes long), tables and output; with
+// expect[] (its faults report as fnx) bad_dev, row-major frames and every expect[j]
+template <typename OffT>
+int dec_tables_ok(const char *fn, const char *fnx, const SegFrames &F, int D, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off,
+                  const uint32_t *const *seg_bytes, int32_t *const *Q, const int32_t *const *expect, const uint32_t *bad_dev)
+{
+    if (!in || !in_bytes || !seg_off || !seg_bytes || !Q) { set_error("%s: bad argument (a table is NULL)", fn); return RAHT_ERR_INVALID; }
+    for (int j = 0; j < F.k; ++j) {
+        if (!in[j] || in_bytes[j] < 0 || (in_bytes[j] & 3) || ((uintptr_t)in[j] & 3) || !seg_off[j] || !seg_bytes[j] || !Q[j]) {
+            set_error("%s: bad argument (frame %d)", fn, j);
+            return RAHT_ERR_INVALID;
+        }
+        if (expect && (!bad_dev || F.chan_stride[j] != 1 || F.sym_stride[j] < D || !expect[j])) {
+            set_error("%s: expect[] needs bad_dev, row-major frames (chan_stride 1) and every expect[j] (frame %d)", fnx, j);
+            return RAHT_ERR_INVALID;
+        }
+    }
+    return RAHT_OK;
 }
 
 // a slot: what the raw integers of a segment would take, + 16; for the LDS-column output in whole 64-byte pieces (it needs
@@ -756,24 +836,15 @@ int seg_encode_slots(const char *fn, bool name_frame, const rlgr_seg::SegEncJobs
     return rc;
 }
 
+// The one frame of F (arguments checked) through the encoder, with the kernels of one frame
 template <typename OffT>
-int seg_encode_impl(const char *fn, const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
-                    uint32_t *seg_bytes, OffT *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
+int seg_encode_one(const char *fn, const SegFrames &F, const int32_t *Q, int D, int seg_len, int flag_signed, uint32_t *seg_bytes, OffT *seg_off, uint8_t *out,
+                   int64_t cap, int64_t *total_bytes, raht_stream_t stream)
 {
-    if (!Q || !seg_bytes || !seg_off || !out || !total_bytes || N < 1 || D < 1 || sym_stride < 1 || chan_stride < 1 || seg_len < 64 || cap < 16 || ((uintptr_t)out & 3) ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("%s: bad argument (channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn);
-        return RAHT_ERR_INVALID;
-    }
-    // 32-bit tables: segment offsets and the container's total could wrap for what raht_rlgr_seg_offsets_width calls 64 (worst
-    // case: every symbol escapes -- 8 bytes and a bit -- plus the 4-byte padding of every segment): refused there
-    int64_t nseg, G;
-    RAHT_RET(seg_shape<OffT>(fn, N, D, seg_len, &nseg, &G));
+    const int64_t N = F.N[0], sym_stride = F.sym_stride[0], chan_stride = F.chan_stride[0], nseg = F.nseg[0], G = F.G[0];
     hipStream_t s = (hipStream_t)stream;
     constexpr int FW = SegFlags<OffT>::WORDS;
     return guarded(fn, [&]() -> int {
-        SegFrames F;
-        F.add(N, D, sym_stride, chan_stride, seg_len);
         const rlgr_seg::SegEncJobs<OffT, 1> J = enc_jobs<OffT, 1>(F, &Q, &seg_bytes, &seg_off, &out, &cap);
         // ONE encoding pass into fixed slots + a compaction, when a scratch buffer of the raw size is to be had; the two exact
         // passes (sizes, then streams) otherwise, and whenever a segment outgrows its slot
@@ -810,36 +881,15 @@ template <typename OffT, int K>
 int seg_decode_launch(const SegFrames &F, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes, int D,
                       int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, uint32_t *bad_dev, raht_stream_t stream)
 {
-    rlgr_seg::SegDecJobs<OffT, K> J;
-    for (int j = 0; j < K; ++j) {
-        const int q = j < F.k ? j : 0;
-        J.in[j] = in[q]; J.in_bytes[j] = (uint64_t)in_bytes[q]; J.seg_off[j] = seg_off[q]; J.seg_bytes[j] = seg_bytes[q]; J.Q[j] = Q[q];
-        J.expect[j] = expect ? expect[q] : nullptr;
-        F.fill(J, j);
-    }
+    const rlgr_seg::SegDecJobs<OffT, K> J = dec_jobs<OffT, K>(F, in, in_bytes, seg_off, seg_bytes, Q, expect);
     hipLaunchKernelGGL((rlgr_seg::seg_decode_kernel<OffT, K>), dim3((unsigned)ceil_div(F.maxG, 64), (unsigned)F.k), dim3(64), 0, (hipStream_t)stream, J, D, seg_len,
                        flag_signed, bad_dev, rlgr_seg::decode_out_mode(F.sumG), (int)rlgr_seg::decode_sync_rows());
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
 }
 
-template <typename OffT>
-int seg_decode_impl(const char *fn, const uint8_t *in, int64_t in_bytes, const OffT *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
-                    int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
-{
-    if (!in || in_bytes < 0 || (in_bytes & 3) || !seg_off || !seg_bytes || !Q || N < 1 || D < 1 || seg_len < 64 || ((uintptr_t)in & 3) ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("%s: bad argument", fn);
-        return RAHT_ERR_INVALID;
-    }
-    SegFrames F;
-    F.add(N, D, sym_stride, chan_stride, seg_len);
-    if (F.maxG >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    return seg_decode_launch<OffT, 1>(F, &in, &in_bytes, &seg_off, &seg_bytes, D, seg_len, flag_signed, &Q, nullptr, bad_dev, stream);
-}
-
 // The frames of F (arguments checked) through the encoder: one set of launches, or frame by frame -- a lone frame (its own
-// instantiation, its checks and its texts) and whenever the slots pass gives up.
+// instantiation and its texts) and whenever the slots pass gives up.
 // fn: the batch entry point's name; fn1: the one-frame entry point of the same width (the frame-by-frame fallback reports as it)
 template <typename OffT>
 int seg_encode_frames(const char *fn, const char *fn1, const SegFrames &F, const int32_t *const *Q, int D, int seg_len, int flag_signed, uint32_t *const *seg_bytes,
@@ -854,88 +904,11 @@ int seg_encode_frames(const char *fn, const char *fn1, const SegFrames &F, const
     if (rc != RAHT_ERR_UNSUPPORTED) return rc;
     int rc_all = RAHT_OK;                                                   // frame by frame
     for (int j = 0; j < F.k; ++j) {
-        rc = seg_encode_impl<OffT>(fn1, Q[j], F.N[j], D, F.sym_stride[j], F.chan_stride[j], seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j],
-                                   stream);
+        rc = seg_encode_one<OffT>(fn1, F.one(j), Q[j], D, seg_len, flag_signed, seg_bytes[j], seg_off[j], out[j], cap[j], &total_bytes[j], stream);
         if (rc != RAHT_OK && rc_all == RAHT_OK) rc_all = rc;
         if (rc != RAHT_OK && rc != RAHT_ERR_NOMEM) return rc;
     }
     return rc_all;
-}
-
-// k frames of ONE shape: the ragged launch with N[j] = N
-template <typename OffT>
-int seg_encode_batch_impl(const char *fn, const char *fn1, int k, const int32_t *const *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len,
-                          int flag_signed, uint32_t *const *seg_bytes, OffT *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
-                          raht_stream_t stream)
-{
-    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !Q || !seg_bytes || !seg_off || !out || !cap || !total_bytes) {
-        set_error("%s: bad argument (1 <= k <= %d)", fn, RAHT_RLGR_BATCH_MAX);
-        return RAHT_ERR_INVALID;
-    }
-    if (N < 1 || D < 1 || sym_stride < 1 || chan_stride < 1 || seg_len < 64 ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("%s: bad argument (channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn);
-        return RAHT_ERR_INVALID;
-    }
-    for (int j = 0; j < k; ++j)
-        if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
-    int64_t nseg, G;
-    RAHT_RET(seg_shape<OffT>(fn, N, D, seg_len, &nseg, &G));
-    SegFrames F;
-    for (int j = 0; j < k; ++j) F.add(N, D, sym_stride, chan_stride, seg_len);
-    return seg_encode_frames<OffT>(fn, fn1, F, Q, D, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
-}
-
-template <typename OffT>
-int seg_decode_batch_impl(const char *fn, int k, const uint8_t *const *in, const int64_t *in_bytes, const OffT *const *seg_off, const uint32_t *const *seg_bytes,
-                          int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
-                          int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
-{
-    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !in || !in_bytes || !seg_off || !seg_bytes || !Q || N < 1 || D < 1 || seg_len < 64 ||
-        !((sym_stride == 1 && chan_stride >= N) || (chan_stride == 1 && sym_stride >= D))) {
-        set_error("%s: bad argument (1 <= k <= %d)", fn, RAHT_RLGR_BATCH_MAX);
-        return RAHT_ERR_INVALID;
-    }
-    for (int j = 0; j < k; ++j)
-        if (!in[j] || in_bytes[j] < 0 || (in_bytes[j] & 3) || ((uintptr_t)in[j] & 3) || !seg_off[j] || !seg_bytes[j] || !Q[j]) {
-            set_error("%s: bad argument (frame %d)", fn, j);
-            return RAHT_ERR_INVALID;
-        }
-    SegFrames F;
-    for (int j = 0; j < k; ++j) F.add(N, D, sym_stride, chan_stride, seg_len);
-    if (F.maxG >= ((int64_t)1 << 31)) { set_error("%s: too many segments", fn); return RAHT_ERR_INVALID; }
-    return seg_decode_launch<OffT, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, expect, bad_dev, stream);
-}
-
-// The shapes of a ragged call -> F. Shared D and seg_len; per frame N and strides, all frames of one layout kind, each within
-// the 32-bit offset tables (a frame that is not fills the chip alone: the one-frame *64 entry points take it).
-int ragged_frames(const char *fn, int k, const int64_t *N, int D, const int64_t *sym_stride, const int64_t *chan_stride, int seg_len, SegFrames *F)
-{
-    if (k < 1 || k > RAHT_RLGR_BATCH_MAX || !N || !sym_stride || !chan_stride || D < 1 || seg_len < 64) {
-        set_error("%s: bad argument (1 <= k <= %d, D >= 1, seg_len >= 64)", fn, RAHT_RLGR_BATCH_MAX);
-        return RAHT_ERR_INVALID;
-    }
-    bool all_cm = true, all_rm = true;
-    for (int j = 0; j < k; ++j) {
-        const bool cm = N[j] >= 1 && sym_stride[j] == 1 && chan_stride[j] >= N[j], rm = N[j] >= 1 && chan_stride[j] == 1 && sym_stride[j] >= D;
-        if (!cm && !rm) {
-            set_error("%s: bad argument (frame %d: N >= 1; channel-major: sym_stride 1, chan_stride >= N; row-major: chan_stride 1, sym_stride >= D)", fn, j);
-            return RAHT_ERR_INVALID;
-        }
-        all_cm = all_cm && cm;
-        all_rm = all_rm && rm;
-    }
-    if (!all_cm && !all_rm) { set_error("%s: the frames of a call are all channel-major or all row-major", fn); return RAHT_ERR_INVALID; }
-    for (int j = 0; j < k; ++j) {
-        const int width = raht_rlgr_seg_offsets_width(N[j], D, seg_len);
-        if (width != 32) {
-            if (width == 64) set_error("%s: frame %d: %lld x %d symbols may need a container of 4 GiB or more (32-bit segment offsets): code it alone, with 64-bit offsets", fn, j, (long long)N[j], D);
-            else set_error("%s: frame %d: no entry point takes %lld x %d symbols at seg_len = %d", fn, j, (long long)N[j], D, seg_len);
-            return RAHT_ERR_INVALID;
-        }
-        F->add(N[j], D, sym_stride[j], chan_stride[j], seg_len);
-    }
-    return RAHT_OK;
 }
 
 }  // namespace
@@ -948,12 +921,11 @@ extern "C" {
 int raht_rlgr_seg_offsets_width(int64_t N, int D, int seg_len)
 {
     if (N < 1 || D < 1 || seg_len < 64) { set_error("raht_rlgr_seg_offsets_width: bad argument (N, D >= 1, seg_len >= 64)"); return RAHT_ERR_INVALID; }
-    const int64_t nseg = (N - 1) / seg_len + 1;
-    if (nseg >= ((int64_t)1 << 31) || nseg * D >= ((int64_t)1 << 31)) { set_error("raht_rlgr_seg_offsets_width: too many segments"); return RAHT_ERR_INVALID; }
-    const int64_t G = nseg * D, per_seg = raht_rlgr_bound(seg_len) + 4;       // < 2^35
-    // the lengths of the segments stay uint32 in either table
-    if (raht_rlgr_bound(seg_len) >= ((int64_t)1 << 32)) { set_error("raht_rlgr_seg_offsets_width: seg_len = %d: the length of a segment may not fit 32 bits", seg_len); return RAHT_ERR_INVALID; }
-    return per_seg * G >= ((int64_t)1 << 32) ? 64 : 32;                         // (< 2^66 / 2: G < 2^31, per_seg < 2^32 -- no overflow)
+    int64_t nseg, G;
+    const int width = shape_width(N, D, seg_len, &nseg, &G);
+    if (width == 0) { set_error("raht_rlgr_seg_offsets_width: too many segments"); return RAHT_ERR_INVALID; }
+    if (width < 0) { set_error("raht_rlgr_seg_offsets_width: seg_len = %d: the length of a segment may not fit 32 bits", seg_len); return RAHT_ERR_INVALID; }
+    return width;
 }
 
 /* Segmented RLGR on the device. Q: DEVICE int32, channel-major (symbol n of channel c at Q[c * chan_stride + n], what
@@ -972,7 +944,11 @@ int raht_rlgr_seg_encode(const int32_t *Q, int64_t N, int D, int64_t chan_stride
 int raht_rlgr_seg_encode_strided(const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
                                  uint32_t *seg_bytes, uint32_t *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
 {
-    return seg_encode_impl<uint32_t>("raht_rlgr_seg_encode", Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
+    const char *fn = "raht_rlgr_seg_encode";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 32, 1, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(enc_tables_ok(fn, F, &Q, &seg_bytes, &seg_off, &out, &cap, total_bytes));
+    return seg_encode_frames<uint32_t>(fn, fn, F, &Q, D, seg_len, flag_signed, &seg_bytes, &seg_off, &out, &cap, total_bytes, stream);
 }
 
 /* The same with 64-bit offsets (seg_off: DEVICE uint64[D * nseg + 1]) for the shapes raht_rlgr_seg_offsets_width calls 64 -- and
@@ -980,7 +956,11 @@ int raht_rlgr_seg_encode_strided(const int32_t *Q, int64_t N, int D, int64_t sym
 int raht_rlgr_seg_encode64(const int32_t *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
                            uint32_t *seg_bytes, uint64_t *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes, raht_stream_t stream)
 {
-    return seg_encode_impl<uint64_t>("raht_rlgr_seg_encode64", Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
+    const char *fn = "raht_rlgr_seg_encode64";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, 1, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(enc_tables_ok(fn, F, &Q, &seg_bytes, &seg_off, &out, &cap, total_bytes));
+    return seg_encode_frames<uint64_t>(fn, fn, F, &Q, D, seg_len, flag_signed, &seg_bytes, &seg_off, &out, &cap, total_bytes, stream);
 }
 
 /* The inverse: streams `in` (DEVICE, 4-byte aligned, in_bytes long -- a multiple of 4) with their offsets / lengths (DEVICE, as
@@ -997,14 +977,22 @@ int raht_rlgr_seg_decode(const uint8_t *in, int64_t in_bytes, const uint32_t *se
 int raht_rlgr_seg_decode_strided(const uint8_t *in, int64_t in_bytes, const uint32_t *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
                                  int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
-    return seg_decode_impl<uint32_t>("raht_rlgr_seg_decode", in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, sym_stride, chan_stride, bad_dev, stream);
+    const char *fn = "raht_rlgr_seg_decode";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, 1, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(dec_tables_ok(fn, fn, F, D, &in, &in_bytes, &seg_off, &seg_bytes, &Q, nullptr, bad_dev));
+    return seg_decode_launch<uint32_t, 1>(F, &in, &in_bytes, &seg_off, &seg_bytes, D, seg_len, flag_signed, &Q, nullptr, bad_dev, stream);
 }
 
 /* ... from 64-bit offsets (the whole offset is checked against in_bytes before anything is read) */
 int raht_rlgr_seg_decode64(const uint8_t *in, int64_t in_bytes, const uint64_t *seg_off, const uint32_t *seg_bytes, int64_t N, int D, int seg_len,
                            int flag_signed, int32_t *Q, int64_t sym_stride, int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
-    return seg_decode_impl<uint64_t>("raht_rlgr_seg_decode64", in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, sym_stride, chan_stride, bad_dev, stream);
+    const char *fn = "raht_rlgr_seg_decode64";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, 1, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(dec_tables_ok(fn, fn, F, D, &in, &in_bytes, &seg_off, &seg_bytes, &Q, nullptr, bad_dev));
+    return seg_decode_launch<uint64_t, 1>(F, &in, &in_bytes, &seg_off, &seg_bytes, D, seg_len, flag_signed, &Q, nullptr, bad_dev, stream);
 }
 
 int raht_debug_rlgr_decode_out(int mode)
@@ -1031,16 +1019,22 @@ int raht_rlgr_seg_encode_batch(int k, const int32_t *const *Q, int64_t N, int D,
                                uint32_t *const *seg_bytes, uint32_t *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
                                raht_stream_t stream)
 {
-    return seg_encode_batch_impl<uint32_t>("raht_rlgr_seg_encode_batch", "raht_rlgr_seg_encode", k, Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes, seg_off,
-                                           out, cap, total_bytes, stream);
+    const char *fn = "raht_rlgr_seg_encode_batch";
+    SegFrames F;                                                              // (k frames of ONE shape: the ragged launch with N[j] = N)
+    RAHT_RET(seg_frames(fn, 32, k, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(enc_tables_ok(fn, F, Q, seg_bytes, seg_off, out, cap, total_bytes));
+    return seg_encode_frames<uint32_t>(fn, "raht_rlgr_seg_encode", F, Q, D, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
 }
 
 int raht_rlgr_seg_encode_batch64(int k, const int32_t *const *Q, int64_t N, int D, int64_t sym_stride, int64_t chan_stride, int seg_len, int flag_signed,
                                  uint32_t *const *seg_bytes, uint64_t *const *seg_off, uint8_t *const *out, const int64_t *cap, int64_t *total_bytes,
                                  raht_stream_t stream)
 {
-    return seg_encode_batch_impl<uint64_t>("raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_encode64", k, Q, N, D, sym_stride, chan_stride, seg_len, flag_signed, seg_bytes,
-                                           seg_off, out, cap, total_bytes, stream);
+    const char *fn = "raht_rlgr_seg_encode_batch64";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, k, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(enc_tables_ok(fn, F, Q, seg_bytes, seg_off, out, cap, total_bytes));
+    return seg_encode_frames<uint64_t>(fn, "raht_rlgr_seg_encode64", F, Q, D, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
 }
 
 /* The inverse for k frames of one shape: in[j] / in_bytes[j] / seg_off[j] / seg_bytes[j] -> Q[j], one launch. Does not
@@ -1049,8 +1043,11 @@ int raht_rlgr_seg_decode_batch(int k, const uint8_t *const *in, const int64_t *i
                                int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, int64_t sym_stride, int64_t chan_stride,
                                uint32_t *bad_dev, raht_stream_t stream)
 {
-    return seg_decode_batch_impl<uint32_t>("raht_rlgr_seg_decode_batch", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, nullptr, sym_stride, chan_stride,
-                                           bad_dev, stream);
+    const char *fn = "raht_rlgr_seg_decode_batch";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, k, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(dec_tables_ok(fn, fn, F, D, in, in_bytes, seg_off, seg_bytes, Q, nullptr, bad_dev));
+    return seg_decode_launch<uint32_t, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, nullptr, bad_dev, stream);
 }
 
 /* ... and compares every frame with what it should decode to (expect[j]: DEVICE, the layout and strides of Q[j]; ROW-MAJOR only:
@@ -1060,11 +1057,12 @@ int raht_rlgr_seg_decode_batch_check(int k, const uint8_t *const *in, const int6
                                      int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
                                      int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
-    if (!expect || !bad_dev || chan_stride != 1) { set_error("raht_rlgr_seg_decode_batch_check: needs expect[], bad_dev and row-major frames (chan_stride 1)"); return RAHT_ERR_INVALID; }
-    for (int j = 0; j < k && j < RAHT_RLGR_BATCH_MAX; ++j)
-        if (!expect[j]) { set_error("raht_rlgr_seg_decode_batch_check: expect[%d] is NULL", j); return RAHT_ERR_INVALID; }
-    return seg_decode_batch_impl<uint32_t>("raht_rlgr_seg_decode_batch", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, expect, sym_stride, chan_stride,
-                                           bad_dev, stream);
+    const char *fn = "raht_rlgr_seg_decode_batch", *fnx = "raht_rlgr_seg_decode_batch_check";
+    if (!expect) { set_error("%s: needs expect[]", fnx); return RAHT_ERR_INVALID; }
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, k, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(dec_tables_ok(fn, fnx, F, D, in, in_bytes, seg_off, seg_bytes, Q, expect, bad_dev));
+    return seg_decode_launch<uint32_t, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, expect, bad_dev, stream);
 }
 
 /* Both of them from 64-bit offsets: expect == NULL decodes (any layout, bad_dev may be NULL); expect != NULL also compares
@@ -1073,13 +1071,11 @@ int raht_rlgr_seg_decode_batch64(int k, const uint8_t *const *in, const int64_t 
                                  int64_t N, int D, int seg_len, int flag_signed, int32_t *const *Q, const int32_t *const *expect, int64_t sym_stride,
                                  int64_t chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
-    if (expect) {
-        if (!bad_dev || chan_stride != 1) { set_error("raht_rlgr_seg_decode_batch64: expect[] needs bad_dev and row-major frames (chan_stride 1)"); return RAHT_ERR_INVALID; }
-        for (int j = 0; j < k && j < RAHT_RLGR_BATCH_MAX; ++j)
-            if (!expect[j]) { set_error("raht_rlgr_seg_decode_batch64: expect[%d] is NULL", j); return RAHT_ERR_INVALID; }
-    }
-    return seg_decode_batch_impl<uint64_t>("raht_rlgr_seg_decode_batch64", k, in, in_bytes, seg_off, seg_bytes, N, D, seg_len, flag_signed, Q, expect, sym_stride, chan_stride,
-                                           bad_dev, stream);
+    const char *fn = "raht_rlgr_seg_decode_batch64";
+    SegFrames F;
+    RAHT_RET(seg_frames(fn, 64, k, &N, &sym_stride, &chan_stride, false, D, seg_len, &F));
+    RAHT_RET(dec_tables_ok(fn, fn, F, D, in, in_bytes, seg_off, seg_bytes, Q, expect, bad_dev));
+    return seg_decode_launch<uint64_t, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, expect, bad_dev, stream);
 }
 
 /* k frames of k SHAPES in one set of launches: the frames of a sequence. D, seg_len and flag_signed are shared; N[j] and the two
@@ -1092,11 +1088,9 @@ int raht_rlgr_seg_encode_ragged(int k, const int32_t *const *Q, const int64_t *N
                                 int64_t *total_bytes, raht_stream_t stream)
 {
     const char *fn = "raht_rlgr_seg_encode_ragged";
-    if (!Q || !seg_bytes || !seg_off || !out || !cap || !total_bytes) { set_error("%s: bad argument (a table is NULL)", fn); return RAHT_ERR_INVALID; }
     SegFrames F;
-    RAHT_RET(ragged_frames(fn, k, N, D, sym_stride, chan_stride, seg_len, &F));
-    for (int j = 0; j < k; ++j)
-        if (!Q[j] || !seg_bytes[j] || !seg_off[j] || !out[j] || cap[j] < 16 || ((uintptr_t)out[j] & 3)) { set_error("%s: bad argument (frame %d)", fn, j); return RAHT_ERR_INVALID; }
+    RAHT_RET(seg_frames(fn, 32, k, N, sym_stride, chan_stride, true, D, seg_len, &F));
+    RAHT_RET(enc_tables_ok(fn, F, Q, seg_bytes, seg_off, out, cap, total_bytes));
     return seg_encode_frames<uint32_t>(fn, "raht_rlgr_seg_encode", F, Q, D, seg_len, flag_signed, seg_bytes, seg_off, out, cap, total_bytes, stream);
 }
 
@@ -1108,19 +1102,9 @@ int raht_rlgr_seg_decode_ragged(int k, const uint8_t *const *in, const int64_t *
                                 const int64_t *sym_stride, const int64_t *chan_stride, uint32_t *bad_dev, raht_stream_t stream)
 {
     const char *fn = "raht_rlgr_seg_decode_ragged";
-    if (!in || !in_bytes || !seg_off || !seg_bytes || !Q) { set_error("%s: bad argument (a table is NULL)", fn); return RAHT_ERR_INVALID; }
-    SegFrames F;
-    RAHT_RET(ragged_frames(fn, k, N, D, sym_stride, chan_stride, seg_len, &F));
-    for (int j = 0; j < k; ++j) {
-        if (!in[j] || in_bytes[j] < 0 || (in_bytes[j] & 3) || ((uintptr_t)in[j] & 3) || !seg_off[j] || !seg_bytes[j] || !Q[j]) {
-            set_error("%s: bad argument (frame %d)", fn, j);
-            return RAHT_ERR_INVALID;
-        }
-        if (expect && (!bad_dev || chan_stride[j] != 1 || sym_stride[j] < D || !expect[j])) {
-            set_error("%s: expect[] needs bad_dev, row-major frames (chan_stride 1) and every expect[j] (frame %d)", fn, j);
-            return RAHT_ERR_INVALID;
-        }
-    }
+    SegFrames F;                                                              // (32: a frame beyond the 32-bit tables fills the chip alone)
+    RAHT_RET(seg_frames(fn, 32, k, N, sym_stride, chan_stride, true, D, seg_len, &F));
+    RAHT_RET(dec_tables_ok(fn, fn, F, D, in, in_bytes, seg_off, seg_bytes, Q, expect, bad_dev));
     return seg_decode_launch<uint32_t, RAHT_RLGR_BATCH_MAX>(F, in, in_bytes, seg_off, seg_bytes, D, seg_len, flag_signed, Q, expect, bad_dev, stream);
 }
 

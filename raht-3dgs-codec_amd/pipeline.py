@@ -46,6 +46,31 @@ def _step_args(step):
     return (st, "per_attribute") if np.ndim(step) else (st[0], step)
 
 
+def _frame_prelude(V_int, attributes, J, device, dtype):
+    """What every driver of a 3DGS frame does before its first step: the attributes and the coordinates on the device, the timed
+    prelude (encode_3dgs.py:139-149) -> (C, lists = (ListC, FlagsC, weightsC, order_RAGFT), plan, seconds of the prelude)."""
+    C = attributes.to(dtype=dtype).contiguous().to(device)
+    _sync()
+    V = V_int.to(dtype=torch.float64).to(device)                                    # :139-142
+    origin = torch.tensor([0, 0, 0], dtype=V.dtype, device=device)
+    t0 = time.time()
+    lists = RAHT_param_reorder_fast(V, origin, 2 ** J, J)                           # :149
+    _sync()
+    t_prelude = time.time() - t0
+    return C, lists, plan_of(lists[0]), t_prelude
+
+
+def _close_row(r, t_prelude, size_bytes, N, period=None):
+    """The bookkeeping of a row whose stage times are set (encode_3dgs.py:279-296, :403): the prelude, the two totals, the
+    pipeline's time -- prelude + both totals, or prelude + ``period`` where the steps overlap -- and the rate."""
+    r["RAHT_prelude_time"] = t_prelude
+    r["Total_enc_time"] = r["RAHT_transform_time"] + r["Quant_time"] + r["Coeff_reorder_enc_time"] + r["Entropy_enc_time"]
+    r["Total_dec_time"] = r["Entropy_dec_time"] + r["Dequant_time"] + r["Coeff_reorder_dec_time"] + r["iRAHT_time"]
+    r["Pipeline_time"] = t_prelude + r["Total_enc_time"] + r["Total_dec_time"] if period is None else t_prelude + period
+    r["Rate_bpp"] = size_bytes * 8 / N                                              # :403
+    r["size_bytes"] = size_bytes
+
+
 def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=torch.float32, fused=True,
                  nthreads=0, channel_major=True, overlap=False, entropy="host", seg_len=2048, keep_rec=True, batch_steps=False):
     """One frame through the whole pipeline. Returns a list of dict rows (one per step) with the CSV
@@ -77,16 +102,7 @@ def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=to
     if overlap and fused:
         return _encode_frame_overlapped(V_int, attributes, J, steps, frame, device, dtype, nthreads, keep_rec)
     N = V_int.shape[0]
-    C = attributes.to(dtype=dtype).contiguous().to(device)
-    _sync()
-    V = V_int.to(dtype=torch.float64).to(device)                                    # :139-142
-    origin = torch.tensor([0, 0, 0], dtype=V.dtype, device=device)
-
-    t0 = time.time()
-    ListC, FlagsC, weightsC, order_RAGFT = RAHT_param_reorder_fast(V, origin, 2 ** J, J)   # :149
-    _sync()
-    t_prelude = time.time() - t0
-    plan = plan_of(ListC)
+    C, (ListC, FlagsC, weightsC, order_RAGFT), plan, t_prelude = _frame_prelude(V_int, attributes, J, device, dtype)
     use_fused = fused                     # float32 and float64 (the reference's precision) both have fused entry points
 
     Coeff, t_transform = None, 0.0
@@ -181,12 +197,7 @@ def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=to
             _sync()
             r["iRAHT_time"] = time.time() - t0
         # ---------------- bookkeeping (:279-310) ----------------
-        r["RAHT_prelude_time"] = t_prelude
-        r["Total_enc_time"] = r["RAHT_transform_time"] + r["Quant_time"] + r["Coeff_reorder_enc_time"] + r["Entropy_enc_time"]
-        r["Total_dec_time"] = r["Entropy_dec_time"] + r["Dequant_time"] + r["Coeff_reorder_dec_time"] + r["iRAHT_time"]
-        r["Pipeline_time"] = t_prelude + r["Total_enc_time"] + r["Total_dec_time"]
-        r["Rate_bpp"] = size_bytes * 8 / N                                          # :403
-        r["size_bytes"] = size_bytes
+        _close_row(r, t_prelude, size_bytes, N)
         t0 = time.time()
         if not measured:
             _psnr_columns(r, C, C_rec)
@@ -203,15 +214,7 @@ def _encode_frame_gpu_entropy(V_int, attributes, J, steps, frame, device, dtype,
     (device) -> round-trip check (device) -> dequantize + un-reorder + inverse RAHT -> PSNR. No transpose on either side."""
     N = V_int.shape[0]
     dev = torch.device(device)
-    C = attributes.to(dtype=dtype).contiguous().to(dev)
-    _sync()
-    V = V_int.to(dtype=torch.float64).to(dev)
-    origin = torch.tensor([0, 0, 0], dtype=V.dtype, device=dev)
-    t0 = time.time()
-    ListC, FlagsC, weightsC, order_RAGFT = RAHT_param_reorder_fast(V, origin, 2 ** J, J)
-    _sync()
-    t_prelude = time.time() - t0
-    plan = plan_of(ListC)
+    C, _, plan, t_prelude = _frame_prelude(V_int, attributes, J, dev, dtype)
     coder = rlgr_mod.SegmentedCoder(N, C.shape[1], seg_len, 1, dev)
     rows = []
     for step in steps:
@@ -244,12 +247,7 @@ def _encode_frame_gpu_entropy(V_int, attributes, J, steps, frame, device, dtype,
         C_rec = _decode_and_measure(plan, qd, step_arg, C, dtype, r, keep_rec)      # inverse + the PSNR columns' sums, one pass
         _sync()
         r["iRAHT_time"], r["Dequant_time"], r["Coeff_reorder_dec_time"] = time.time() - t0, 0.0, 0.0
-        r["RAHT_prelude_time"] = t_prelude
-        r["Total_enc_time"] = r["RAHT_transform_time"] + r["Entropy_enc_time"]
-        r["Total_dec_time"] = r["Entropy_dec_time"] + r["iRAHT_time"]
-        r["Pipeline_time"] = t_prelude + r["Total_enc_time"] + r["Total_dec_time"]
-        r["Rate_bpp"] = size_bytes * 8 / N
-        r["size_bytes"] = size_bytes
+        _close_row(r, t_prelude, size_bytes, N)
         r["PSNR_time"] = 0.0                                   # (inside iRAHT_time: the fused inverse measures on its way out)
         r["Step_wall_time"] = time.time() - t_step0
         r["C_rec"] = C_rec
@@ -265,15 +263,7 @@ def _encode_frame_gpu_entropy_batched(V_int, attributes, J, steps, frame, device
     N = V_int.shape[0]
     dev = torch.device(device)
     dtype = torch.float32
-    C = attributes.to(dtype=dtype).contiguous().to(dev)
-    _sync()
-    V = V_int.to(dtype=torch.float64).to(dev)
-    origin = torch.tensor([0, 0, 0], dtype=V.dtype, device=dev)
-    t0 = time.time()
-    ListC, FlagsC, weightsC, order_RAGFT = RAHT_param_reorder_fast(V, origin, 2 ** J, J)
-    _sync()
-    t_prelude = time.time() - t0
-    plan = plan_of(ListC)
+    C, _, plan, t_prelude = _frame_prelude(V_int, attributes, J, dev, dtype)
     D = C.shape[1]
     rows = []
     KMAX = rlgr_mod.SegmentedCoder.BATCH_MAX
@@ -320,12 +310,7 @@ def _encode_frame_gpu_entropy_batched(V_int, attributes, J, steps, frame, device
             _sync()
             r["iRAHT_time"], r["Dequant_time"], r["Coeff_reorder_dec_time"] = time.time() - t0, 0.0, 0.0
             qds[j] = None
-            r["RAHT_prelude_time"] = t_prelude
-            r["Total_enc_time"] = r["RAHT_transform_time"] + r["Entropy_enc_time"]
-            r["Total_dec_time"] = r["Entropy_dec_time"] + r["iRAHT_time"]
-            r["Pipeline_time"] = t_prelude + r["Total_enc_time"] + r["Total_dec_time"]
-            r["Rate_bpp"] = sizes[j] * 8 / N
-            r["size_bytes"] = sizes[j]
+            _close_row(r, t_prelude, sizes[j], N)
             r["PSNR_time"] = 0.0
             r["Step_wall_time"] = t_shared / k + (time.time() - t_step0)
             r["C_rec"] = C_rec if (keep_rec and lo + j == len(steps) - 1) else None   # (k reconstructions of 0.7 GB each: the last one only)
@@ -389,15 +374,7 @@ def _encode_frame_overlapped(V_int, attributes, J, steps, frame, device, dtype, 
     from concurrent.futures import ThreadPoolExecutor
     N = V_int.shape[0]
     dev = torch.device(device)
-    C = attributes.to(dtype=dtype).contiguous().to(dev)
-    _sync()
-    V = V_int.to(dtype=torch.float64).to(dev)
-    origin = torch.tensor([0, 0, 0], dtype=V.dtype, device=dev)
-    t0 = time.time()
-    ListC, FlagsC, weightsC, order_RAGFT = RAHT_param_reorder_fast(V, origin, 2 ** J, J)
-    _sync()
-    t_prelude = time.time() - t0
-    plan = plan_of(ListC)
+    C, _, plan, t_prelude = _frame_prelude(V_int, attributes, J, dev, dtype)
     D = C.shape[1]
     pin_dn = [torch.empty((D, N), dtype=torch.int32, pin_memory=True) for _ in range(2)]
     pin_up = [torch.empty((D, N), dtype=torch.int32, pin_memory=True) for _ in range(2)]
@@ -457,16 +434,11 @@ def _encode_frame_overlapped(V_int, attributes, J, steps, frame, device, dtype, 
                 r["iRAHT_time"] = f0.elapsed_time(f1) * 1e-3
                 r["Quant_time"] = r["Coeff_reorder_enc_time"] = r["Dequant_time"] = r["Coeff_reorder_dec_time"] = 0.0
                 r["Entropy_enc_time"], r["Entropy_dec_time"] = t_enc, t_dec
-                r["RAHT_prelude_time"] = t_prelude
-                r["Total_enc_time"] = r["RAHT_transform_time"] + r["Entropy_enc_time"]
-                r["Total_dec_time"] = r["Entropy_dec_time"] + r["iRAHT_time"]
                 now = time.time()
                 r["Step_wall_time"] = now - t_mark             # the pipeline's period: what a step costs end to end here
                 t_mark = now
-                r["Pipeline_time"] = t_prelude + r["Step_wall_time"]
+                _close_row(r, t_prelude, size_bytes, N, period=r["Step_wall_time"])
                 r["GPU_decode_side_time"] = t_gpu_dec
-                r["Rate_bpp"] = size_bytes * 8 / N
-                r["size_bytes"] = size_bytes
                 r["C_rec"] = C_rec
                 rows[k] = r
     return rows

@@ -10,6 +10,8 @@ backed by the byte-exact host coder in libraht_hip.so (csrc/rlgr.hip).
 threads, without the per-channel tensor -> list -> vector copies of the reference driver.
 """
 import ctypes as C
+import functools
+import operator
 import time
 
 import numpy as np
@@ -225,22 +227,7 @@ class SegmentedCoder:
     def encode(self, Q):
         """Q: (D, N) channel-major OR (N, D) row-major int32 CUDA tensor (the latter: the quantized coefficients as forward_quant
         returns them, no transpose) -> total container payload bytes (synchronises: it returns a size). Same container either way."""
-        import torch
-        sym, chan = self._strides(Q, "encode")
-        Qcm = Q
-        tot = C.c_int64()
-        fn = _lib.lib().raht_rlgr_seg_encode64 if self.wide else _lib.lib().raht_rlgr_seg_encode_strided
-        for attempt in (0, 1):
-            with torch.cuda.device(self.device):
-                rc = fn(C.c_void_p(Qcm.data_ptr()), self.N, self.D, sym, chan, self.S, self.flag,
-                        C.c_void_p(self.seg_bytes.data_ptr()), C.c_void_p(self.seg_off.data_ptr()),
-                        C.c_void_p(self.out.data_ptr()), self.cap, C.byref(tot), self._stream())
-            if rc == _lib.RAHT_OK or attempt == 1 or tot.value <= self.cap:
-                check(rc)
-                break
-            self.cap = int(tot.value) + 64                    # incompressible data: the exact size is known now
-            self.out = torch.empty(self.cap, dtype=torch.uint8, device=self.device)
-        self.total = int(tot.value)
+        self._encode_core("one", [self], [Q], [self._strides(Q, "encode")])
         return self.total
 
     @property
@@ -361,50 +348,51 @@ class SegmentedCoder:
         import torch
         if out is None:
             out = torch.empty((self.N, self.D) if row_major else (self.D, self.N), dtype=torch.int32, device=self.device)
-        sym, chan = self._strides(out, "decode")
-        fn = _lib.lib().raht_rlgr_seg_decode64 if self.wide else _lib.lib().raht_rlgr_seg_decode_strided
-        with torch.cuda.device(self.device):
-            check(fn(C.c_void_p(self.out.data_ptr()), (self.total + 3) // 4 * 4, C.c_void_p(self.seg_off.data_ptr()),
-                     C.c_void_p(self.seg_bytes.data_ptr()), self.N, self.D, self.S, self.flag,
-                     C.c_void_p(out.data_ptr()), sym, chan, C.c_void_p(self.bad.data_ptr()), self._stream()))
-        return out
+        return self._decode_core("one", [self], [out], [self._strides(out, "decode")])[0]
 
     BATCH_MAX = 12                                            # RAHT_RLGR_BATCH_MAX
 
+    # (direction, form of the call: "one" frame, a "batch" of one shape, a "ragged" batch) -> the entry point with 32-bit and the one
+    # with 64-bit offset tables, each with whether it has an expect[] argument. A 32-bit batch has two decoders: the one that
+    # compares takes expect[], the plain one has no such argument. A ragged batch has 32-bit tables only (``_same_kind``).
+    _ENTRY = {("encode", "one"): (("raht_rlgr_seg_encode_strided", False), ("raht_rlgr_seg_encode64", False)),
+              ("encode", "batch"): (("raht_rlgr_seg_encode_batch", False), ("raht_rlgr_seg_encode_batch64", False)),
+              ("encode", "ragged"): (("raht_rlgr_seg_encode_ragged", False), None),
+              ("decode", "one"): (("raht_rlgr_seg_decode_strided", False), ("raht_rlgr_seg_decode64", False)),
+              ("decode", "batch"): (("raht_rlgr_seg_decode_batch", False), ("raht_rlgr_seg_decode_batch64", True)),
+              ("decode", "batch", "expect"): (("raht_rlgr_seg_decode_batch_check", True), ("raht_rlgr_seg_decode_batch64", True)),
+              ("decode", "ragged"): (("raht_rlgr_seg_decode_ragged", True), None)}
+
     @staticmethod
-    def _same_shape(coders, what):
-        c0 = coders[0]
-        for c in coders[1:]:
-            if (c.N, c.D, c.S, c.flag, c.device, c.wide) != (c0.N, c0.D, c0.S, c0.flag, c0.device, c0.wide):
-                raise ValueError(f"SegmentedCoder.{what}: the coders of a batch share N, D, seg_len, flag, device and offset width")
-        return c0
+    @functools.lru_cache(maxsize=None)
+    def _marshal(form, k):
+        """How an entry point of ``form`` takes the k frames of a call -> (head, ptrs, ints, shape, I64). head: the leading k (the
+        one-frame entry points have none). ptrs / ints: what every frame has of its own -- a table of pointers / of int64, or the
+        value itself for one frame. shape: N and the two strides -- a table in a ragged call, the value all frames share otherwise.
+        I64: the type of a table of k int64. Cached: a one-frame call costs no more than its ctypes arguments."""
+        VP, I64 = C.c_void_p * k, C.c_int64 * k
+        first = operator.itemgetter(0)
+        if form == "one":
+            return (), first, first, first, I64
+        return (k,), (lambda xs: VP(*xs)), (lambda xs: I64(*xs)), ((lambda xs: I64(*xs)) if form == "ragged" else first), I64
 
     @classmethod
-    def encode_batch(cls, coders, Qs):
-        """The quantization steps of a frame coded together (raht_rlgr_seg_encode_batch): ``coders[j].encode(Qs[j])`` for every j,
-        in ONE set of launches -- k times the independent streams of one frame, which is what the coder's speed depends on. Same
-        containers, byte for byte. All Qs in the same layout ((N, D) row-major or (D, N) channel-major) with the same strides.
-        -> list of container payload sizes (synchronises)."""
+    def _encode_core(cls, form, coders, Qs, st):
+        """``coders[j].encode(Qs[j])`` (strides ``st[j]``) through the entry point of ``form``, in chunks of ``BATCH_MAX``: the tables
+        of a chunk, one call, and when a container turns out too small larger ones and ONE more call; leaves every ``total``."""
         import torch
-        if len(coders) != len(Qs) or not coders:
-            raise ValueError("SegmentedCoder.encode_batch: one input per coder")
-        c0 = cls._same_shape(coders, "encode_batch")
-        st = [c._strides(Q, "encode_batch") for c, Q in zip(coders, Qs)]
-        if any(x != st[0] for x in st):
-            raise ValueError("SegmentedCoder.encode_batch: the inputs of a batch share their layout and strides")
-        sym, chan = st[0]
-        L = _lib.lib()
-        fn = L.raht_rlgr_seg_encode_batch64 if c0.wide else L.raht_rlgr_seg_encode_batch
+        c0 = coders[0]
+        fn = getattr(_lib.lib(), cls._ENTRY["encode", form][c0.wide][0])
         for lo in range(0, len(coders), cls.BATCH_MAX):
-            cs, qs = coders[lo: lo + cls.BATCH_MAX], Qs[lo: lo + cls.BATCH_MAX]
+            cs, qs, ss = coders[lo: lo + cls.BATCH_MAX], Qs[lo: lo + cls.BATCH_MAX], st[lo: lo + cls.BATCH_MAX]
             k = len(cs)
-            VP, I64 = C.c_void_p * k, C.c_int64 * k
+            head, ptrs, ints, shape, I64 = cls._marshal(form, k)
             tot = I64()
             for attempt in (0, 1):
                 with torch.cuda.device(c0.device):
-                    rc = fn(k, VP(*[q.data_ptr() for q in qs]), c0.N, c0.D, sym, chan, c0.S, c0.flag,
-                            VP(*[c.seg_bytes.data_ptr() for c in cs]), VP(*[c.seg_off.data_ptr() for c in cs]),
-                            VP(*[c.out.data_ptr() for c in cs]), I64(*[c.cap for c in cs]), tot, c0._stream())
+                    rc = fn(*head, ptrs([q.data_ptr() for q in qs]), shape([c.N for c in cs]), c0.D, shape([s[0] for s in ss]), shape([s[1] for s in ss]),
+                            c0.S, c0.flag, ptrs([c.seg_bytes.data_ptr() for c in cs]), ptrs([c.seg_off.data_ptr() for c in cs]),
+                            ptrs([c.out.data_ptr() for c in cs]), ints([c.cap for c in cs]), tot, c0._stream())
                 if rc == _lib.RAHT_OK or attempt == 1 or all(int(tot[j]) <= cs[j].cap for j in range(k)):
                     check(rc)
                     break
@@ -414,6 +402,53 @@ class SegmentedCoder:
                         c.out = torch.empty(c.cap, dtype=torch.uint8, device=c.device)
             for j, c in enumerate(cs):
                 c.total = int(tot[j])
+
+    @classmethod
+    def _decode_core(cls, form, coders, outs, st, expect=None):
+        """``coders[j].decode(outs[j])`` (strides ``st[j]``) through the entry point of ``form``, one launch per chunk of ``BATCH_MAX``,
+        compared with ``expect[j]`` on the way when given; every chunk reports into its own first coder's ``bad``. -> outs"""
+        import torch
+        c0 = coders[0]
+        name, has_expect = cls._ENTRY[("decode", form) + (("expect",) if form == "batch" and expect is not None else ())][c0.wide]
+        fn = getattr(_lib.lib(), name)
+        for lo in range(0, len(coders), cls.BATCH_MAX):
+            cs, os_, ss = coders[lo: lo + cls.BATCH_MAX], outs[lo: lo + cls.BATCH_MAX], st[lo: lo + cls.BATCH_MAX]
+            k = len(cs)
+            head, ptrs, ints, shape, _ = cls._marshal(form, k)
+            ex = ((None if expect is None else ptrs([e.data_ptr() for e in expect[lo: lo + cls.BATCH_MAX]])),) if has_expect else ()
+            with torch.cuda.device(c0.device):
+                check(fn(*head, ptrs([c.out.data_ptr() for c in cs]), ints([(c.total + 3) // 4 * 4 for c in cs]),
+                         ptrs([c.seg_off.data_ptr() for c in cs]), ptrs([c.seg_bytes.data_ptr() for c in cs]), shape([c.N for c in cs]), c0.D, c0.S, c0.flag,
+                         ptrs([o.data_ptr() for o in os_]), *ex, shape([s[0] for s in ss]), shape([s[1] for s in ss]),
+                         C.c_void_p(cs[0].bad.data_ptr()), c0._stream()))
+        return outs
+
+    @staticmethod
+    def _same_kind(coders, what, ragged=False):
+        """the coders of one call: they share D, seg_len, flag and device, and N and the offset width (a batch of one shape) or
+        32-bit offsets (a ragged batch) -> the first"""
+        c0 = coders[0]
+        for c in coders:
+            if (c.D, c.S, c.flag, c.device) != (c0.D, c0.S, c0.flag, c0.device) or (not ragged and (c.N, c.wide) != (c0.N, c0.wide)):
+                raise ValueError(f"SegmentedCoder.{what}: the coders of a ragged batch share D, seg_len, flag and device" if ragged else
+                                 f"SegmentedCoder.{what}: the coders of a batch share N, D, seg_len, flag, device and offset width")
+            if ragged and c.wide:
+                raise ValueError(f"SegmentedCoder.{what}: a ragged batch takes 32-bit offset tables only (a {c.N} x {c.D} frame goes alone)")
+        return c0
+
+    @classmethod
+    def encode_batch(cls, coders, Qs):
+        """The quantization steps of a frame coded together (raht_rlgr_seg_encode_batch): ``coders[j].encode(Qs[j])`` for every j,
+        in ONE set of launches -- k times the independent streams of one frame, which is what the coder's speed depends on. Same
+        containers, byte for byte. All Qs in the same layout ((N, D) row-major or (D, N) channel-major) with the same strides.
+        -> list of container payload sizes (synchronises)."""
+        if len(coders) != len(Qs) or not coders:
+            raise ValueError("SegmentedCoder.encode_batch: one input per coder")
+        cls._same_kind(coders, "encode_batch")
+        st = [c._strides(Q, "encode_batch") for c, Q in zip(coders, Qs)]
+        if any(x != st[0] for x in st):
+            raise ValueError("SegmentedCoder.encode_batch: the inputs of a batch share their layout and strides")
+        cls._encode_core("batch", coders, Qs, st)
         return [c.total for c in coders]
 
     @classmethod
@@ -427,47 +462,18 @@ class SegmentedCoder:
         import torch
         if not coders:
             return []
-        c0 = cls._same_shape(coders, "decode_batch")
+        c0 = cls._same_kind(coders, "decode_batch")
         if outs is None:
             outs = [torch.empty((c0.N, c0.D) if row_major else (c0.D, c0.N), dtype=torch.int32, device=c0.device) for _ in coders]
         st = [c._strides(o, "decode_batch") for c, o in zip(coders, outs)]
         if len(outs) != len(coders) or any(x != st[0] for x in st):
             raise ValueError("SegmentedCoder.decode_batch: one output per coder, all in the same layout")
-        sym, chan = st[0]
         if expect is not None:
-            if not row_major and chan != 1:
+            if not row_major and st[0][1] != 1:
                 raise ValueError("SegmentedCoder.decode_batch: expect= goes with row-major frames")
-            if len(expect) != len(coders) or any(c._strides(e, "decode_batch") != (sym, chan) for c, e in zip(coders, expect)):
+            if len(expect) != len(coders) or any(c._strides(e, "decode_batch") != st[0] for c, e in zip(coders, expect)):
                 raise ValueError("SegmentedCoder.decode_batch: one expected frame per coder, in the layout and strides of the outputs")
-        L = _lib.lib()
-        for lo in range(0, len(coders), cls.BATCH_MAX):
-            cs, os_ = coders[lo: lo + cls.BATCH_MAX], outs[lo: lo + cls.BATCH_MAX]
-            k = len(cs)
-            VP, I64 = C.c_void_p * k, C.c_int64 * k
-            args = (k, VP(*[c.out.data_ptr() for c in cs]), I64(*[(c.total + 3) // 4 * 4 for c in cs]),
-                    VP(*[c.seg_off.data_ptr() for c in cs]), VP(*[c.seg_bytes.data_ptr() for c in cs]),
-                    c0.N, c0.D, c0.S, c0.flag, VP(*[o.data_ptr() for o in os_]))
-            bad = cs[0].bad                                       # (every chunk reports into its own first coder)
-            with torch.cuda.device(c0.device):
-                if expect is None and c0.wide:
-                    check(L.raht_rlgr_seg_decode_batch64(*args, None, sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
-                elif expect is None:
-                    check(L.raht_rlgr_seg_decode_batch(*args, sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
-                else:
-                    ex = expect[lo: lo + cls.BATCH_MAX]
-                    check((L.raht_rlgr_seg_decode_batch64 if c0.wide else L.raht_rlgr_seg_decode_batch_check)(*args, VP(*[e.data_ptr() for e in ex]), sym, chan, C.c_void_p(bad.data_ptr()), c0._stream()))
-        return outs
-
-    @staticmethod
-    def _same_kind(coders, what):
-        """the coders of a ragged call: everything of ``_same_shape`` but N, and 32-bit offsets"""
-        c0 = coders[0]
-        for c in coders:
-            if (c.D, c.S, c.flag, c.device) != (c0.D, c0.S, c0.flag, c0.device):
-                raise ValueError(f"SegmentedCoder.{what}: the coders of a ragged batch share D, seg_len, flag and device")
-            if c.wide:
-                raise ValueError(f"SegmentedCoder.{what}: a ragged batch takes 32-bit offset tables only (a {c.N} x {c.D} frame goes alone)")
-        return c0
+        return cls._decode_core("batch", coders, outs, st, expect)
 
     @staticmethod
     def _one_layout(coders, mats, what, row_major=None):
@@ -500,31 +506,10 @@ class SegmentedCoder:
         byte. All Qs row-major (N_j, D) or all channel-major (D, N_j); strides may differ. ``row_major``: None reads the layout off
         the shapes, with a square Q (N_j == D) channel-major as ``encode`` reads it; True / False say it (``_one_layout``).
         -> list of container payload sizes (synchronises)."""
-        import torch
         if len(coders) != len(Qs) or not coders:
             raise ValueError("SegmentedCoder.encode_ragged: one input per coder")
-        c0 = cls._same_kind(coders, "encode_ragged")
-        st = cls._one_layout(coders, Qs, "encode_ragged", row_major)
-        fn = _lib.lib().raht_rlgr_seg_encode_ragged
-        for lo in range(0, len(coders), cls.BATCH_MAX):
-            cs, qs, ss = coders[lo: lo + cls.BATCH_MAX], Qs[lo: lo + cls.BATCH_MAX], st[lo: lo + cls.BATCH_MAX]
-            k = len(cs)
-            VP, I64 = C.c_void_p * k, C.c_int64 * k
-            tot = I64()
-            for attempt in (0, 1):
-                with torch.cuda.device(c0.device):
-                    rc = fn(k, VP(*[q.data_ptr() for q in qs]), I64(*[c.N for c in cs]), c0.D, I64(*[s[0] for s in ss]), I64(*[s[1] for s in ss]),
-                            c0.S, c0.flag, VP(*[c.seg_bytes.data_ptr() for c in cs]), VP(*[c.seg_off.data_ptr() for c in cs]),
-                            VP(*[c.out.data_ptr() for c in cs]), I64(*[c.cap for c in cs]), tot, c0._stream())
-                if rc == _lib.RAHT_OK or attempt == 1 or all(int(tot[j]) <= cs[j].cap for j in range(k)):
-                    check(rc)
-                    break
-                for j, c in enumerate(cs):                    # incompressible data: the exact sizes are known now
-                    if int(tot[j]) > c.cap:
-                        c.cap = int(tot[j]) + 64
-                        c.out = torch.empty(c.cap, dtype=torch.uint8, device=c.device)
-            for j, c in enumerate(cs):
-                c.total = int(tot[j])
+        cls._same_kind(coders, "encode_ragged", ragged=True)
+        cls._encode_core("ragged", coders, Qs, cls._one_layout(coders, Qs, "encode_ragged", row_major))
         return [c.total for c in coders]
 
     @classmethod
@@ -537,7 +522,7 @@ class SegmentedCoder:
         import torch
         if not coders:
             return []
-        c0 = cls._same_kind(coders, "decode_ragged")
+        cls._same_kind(coders, "decode_ragged", ragged=True)
         fresh = outs is None
         if fresh:
             outs = [torch.empty((c.N, c.D) if row_major else (c.D, c.N), dtype=torch.int32, device=c.device) for c in coders]
@@ -548,18 +533,7 @@ class SegmentedCoder:
                 raise ValueError("SegmentedCoder.decode_ragged: expect= goes with row-major frames")
             if len(expect) != len(coders) or cls._one_layout(coders, expect, "decode_ragged", True) != st:
                 raise ValueError("SegmentedCoder.decode_ragged: one expected frame per coder, in the layout and strides of the outputs")
-        fn = _lib.lib().raht_rlgr_seg_decode_ragged
-        for lo in range(0, len(coders), cls.BATCH_MAX):
-            cs, os_, ss = coders[lo: lo + cls.BATCH_MAX], outs[lo: lo + cls.BATCH_MAX], st[lo: lo + cls.BATCH_MAX]
-            k = len(cs)
-            VP, I64 = C.c_void_p * k, C.c_int64 * k
-            ex = None if expect is None else VP(*[e.data_ptr() for e in expect[lo: lo + cls.BATCH_MAX]])
-            with torch.cuda.device(c0.device):                    # (every chunk reports into its own first coder)
-                check(fn(k, VP(*[c.out.data_ptr() for c in cs]), I64(*[(c.total + 3) // 4 * 4 for c in cs]),
-                         VP(*[c.seg_off.data_ptr() for c in cs]), VP(*[c.seg_bytes.data_ptr() for c in cs]), I64(*[c.N for c in cs]),
-                         c0.D, c0.S, c0.flag, VP(*[o.data_ptr() for o in os_]), ex, I64(*[s[0] for s in ss]), I64(*[s[1] for s in ss]),
-                         C.c_void_p(cs[0].bad.data_ptr()), c0._stream()))
-        return outs
+        return cls._decode_core("ragged", coders, outs, st, expect)
 
     @classmethod
     def roundtrip_failed(cls, coders):

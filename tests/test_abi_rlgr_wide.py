@@ -1,8 +1,9 @@
 """CPU-only checks of the segmented RLGR coder's 64-bit-offset entry points at the C-ABI boundary (raht_rlgr_seg_offsets_width,
 raht_rlgr_seg_encode64 / _decode64 / _encode_batch64 / _decode_batch64): exported and bound; the width rule (the one place that
 decides which shapes the 32-bit tables take) against the formula it stands for; the 32-bit entry points still refuse what the rule
-sends to the 64-bit ones; and every argument rule of the 64-bit entry points is refused with RAHT_ERR_INVALID and the function's
-name before any HIP call. No compute calls: the "device pointers" are addresses that must never be read, and no entry point is
+sends to the 64-bit ones; and every argument rule of the 64-bit entry points and of their seven 32-bit twins (the same tables, on a
+shape the 32-bit tables take) is refused with RAHT_ERR_INVALID and the name the entry point reports under before any HIP call. No
+compute calls: the "device pointers" are addresses that must never be read, and no entry point is
 called with them in a case that would get as far as a launch."""
 import ctypes
 import os
@@ -111,17 +112,26 @@ def test_the_32_bit_entry_points_still_refuse_the_wide_shapes(L):
 
 def _refused(L, name, rc, what):
     assert rc == INVALID, (name, what, rc)
-    assert name.encode() in L.raht_last_error(), (name, what, L.raht_last_error())
+    assert (name + ":").encode() in L.raht_last_error(), (name, what, L.raht_last_error())
 
 
-N0, D0, S0 = 6_000_000, 56, 2048
+# the shape the broken-rule tables below start from, by the width of the offset tables that take it
+SHAPES = {32: (3_000_000, 56, 2048), 64: (6_000_000, 56, 2048)}
 
 
-def test_encode64_argument_validation(L):
+# (entry point, width, the name its errors carry, channel-major only: no sym_stride argument)
+@pytest.mark.parametrize("entry,width,name,cm_only", [("raht_rlgr_seg_encode64", 64, "raht_rlgr_seg_encode64", False),
+                                                      ("raht_rlgr_seg_encode_strided", 32, "raht_rlgr_seg_encode", False),
+                                                      ("raht_rlgr_seg_encode", 32, "raht_rlgr_seg_encode", True)])
+def test_encode_argument_validation(L, entry, width, name, cm_only):
+    N0, D0, S0 = SHAPES[width]
     tot = ctypes.c_int64(0)
 
     def call(Q=A, N=N0, D=D0, sym=1, chan=N0, S=S0, sb=B, so=Cc, out=Dd, cap=1 << 20, tb=ctypes.byref(tot)):
-        return L.raht_rlgr_seg_encode64(Q, N, D, sym, chan, S, 1, sb, so, out, cap, tb, None)
+        if cm_only:
+            assert sym == 1
+            return L.raht_rlgr_seg_encode(Q, N, D, chan, S, 1, sb, so, out, cap, tb, None)
+        return getattr(L, entry)(Q, N, D, sym, chan, S, 1, sb, so, out, cap, tb, None)
 
     cases = {
         "NULL Q": dict(Q=None), "NULL seg_bytes": dict(sb=None), "NULL seg_off": dict(so=None), "NULL out": dict(out=None),
@@ -131,14 +141,27 @@ def test_encode64_argument_validation(L):
         "cap < 0": dict(cap=-1), "out not 4-byte aligned": dict(out=Dd + 2), "too many segments": dict(N=2 ** 31, D=64, S=64, chan=2 ** 31),
         "a segment longer than uint32": dict(N=10 ** 9, D=1, S=400_000_000, chan=10 ** 9),
     }
+    if cm_only:
+        cases = {what: cases[what] for what in ("NULL Q", "NULL seg_bytes", "NULL seg_off", "NULL out", "NULL total_bytes", "D = 0", "seg_len = 63",
+                                                "channel-major with chan_stride < N", "cap = 15")}
     for what, kw in cases.items():
-        _refused(L, "raht_rlgr_seg_encode64", call(**kw), what)
-    assert call(N=2 ** 31, D=64, S=64, chan=2 ** 31) == INVALID and b"too many segments" in L.raht_last_error()
+        _refused(L, name, call(**kw), what)
+    if not cm_only:
+        assert call(N=2 ** 31, D=64, S=64, chan=2 ** 31) == INVALID and b"too many segments" in L.raht_last_error()
 
 
-def test_decode64_argument_validation(L):
-    def call(inp=A, nbytes=1 << 20, so=B, sb=Cc, N=N0, D=D0, S=S0, Q=Dd, sym=D0, chan=1, bad=E):
-        return L.raht_rlgr_seg_decode64(inp, nbytes, so, sb, N, D, S, 1, Q, sym, chan, bad, None)
+@pytest.mark.parametrize("entry,width,name,cm_only", [("raht_rlgr_seg_decode64", 64, "raht_rlgr_seg_decode64", False),
+                                                      ("raht_rlgr_seg_decode_strided", 32, "raht_rlgr_seg_decode", False),
+                                                      ("raht_rlgr_seg_decode", 32, "raht_rlgr_seg_decode", True)])
+def test_decode_argument_validation(L, entry, width, name, cm_only):
+    N0, D0, S0 = SHAPES[width]
+    sym0, chan0 = (1, N0) if cm_only else (D0, 1)
+
+    def call(inp=A, nbytes=1 << 20, so=B, sb=Cc, N=N0, D=D0, S=S0, Q=Dd, sym=sym0, chan=chan0, bad=E):
+        if cm_only:
+            assert sym == 1
+            return L.raht_rlgr_seg_decode(inp, nbytes, so, sb, N, D, S, 1, Q, chan, bad, None)
+        return getattr(L, entry)(inp, nbytes, so, sb, N, D, S, 1, Q, sym, chan, bad, None)
 
     cases = {
         "NULL in": dict(inp=None), "NULL seg_off": dict(so=None), "NULL seg_bytes": dict(sb=None), "NULL Q": dict(Q=None),
@@ -147,14 +170,20 @@ def test_decode64_argument_validation(L):
         "row-major with sym_stride < D": dict(sym=D0 - 1), "channel-major with chan_stride < N": dict(sym=1, chan=N0 - 1),
         "neither layout": dict(sym=3, chan=3), "too many segments": dict(N=2 ** 31, D=64, S=64, sym=64),
     }
+    if cm_only:
+        cases = {what: cases[what] for what in ("NULL in", "NULL seg_off", "NULL seg_bytes", "NULL Q", "D = 0", "seg_len = 63",
+                                                "channel-major with chan_stride < N")}
     for what, kw in cases.items():
-        _refused(L, "raht_rlgr_seg_decode64", call(**kw), what)
+        _refused(L, name, call(**kw), what)
 
 
-def test_encode_batch64_argument_validation(L):
+@pytest.mark.parametrize("entry,width", [("raht_rlgr_seg_encode_batch64", 64), ("raht_rlgr_seg_encode_batch", 32)])
+def test_encode_batch_argument_validation(L, entry, width):
+    N0, D0, S0 = SHAPES[width]
+
     def call(k=3, Q=_vp(A, A + 64, A + 128), N=N0, D=D0, sym=D0, chan=1, S=S0, sb=_vp(B, B + 64, B + 128), so=_vp(Cc, Cc + 64, Cc + 128),
              out=_vp(Dd, Dd + 64, Dd + 128), cap=_i64(1 << 20, 1 << 20, 1 << 20), tb=_i64(0, 0, 0)):
-        return L.raht_rlgr_seg_encode_batch64(k, Q, N, D, sym, chan, S, 1, sb, so, out, cap, tb, None)
+        return getattr(L, entry)(k, Q, N, D, sym, chan, S, 1, sb, so, out, cap, tb, None)
 
     many = BATCH_MAX + 1
     cases = {
@@ -170,18 +199,30 @@ def test_encode_batch64_argument_validation(L):
         "too many segments": dict(N=2 ** 31, D=64, S=64, sym=64),
     }
     for what, kw in cases.items():
-        _refused(L, "raht_rlgr_seg_encode_batch64", call(**kw), what)
+        _refused(L, entry, call(**kw), what)
     assert call(Q=_vp(A, None, A + 128)) == INVALID and b"frame 1" in L.raht_last_error()
 
 
-def test_decode_batch64_argument_validation(L):
-    def call(k=3, inp=_vp(A, A + 64, A + 128), nbytes=_i64(1 << 20, 1 << 20, 1 << 20), so=_vp(B, B + 64, B + 128), sb=_vp(Cc, Cc + 64, Cc + 128),
-             N=N0, D=D0, S=S0, Q=_vp(Dd, Dd + 64, Dd + 128), expect=None, sym=D0, chan=1, bad=E):
-        return L.raht_rlgr_seg_decode_batch64(k, inp, nbytes, so, sb, N, D, S, 1, Q, expect, sym, chan, bad, None)
-
+# (entry point, width, how it takes expect[]: "optional" argument, "none" at all, "required": the faults of expect[] then carry
+# the entry point's own name and every other fault raht_rlgr_seg_decode_batch's)
+@pytest.mark.parametrize("entry,width,expects", [("raht_rlgr_seg_decode_batch64", 64, "optional"), ("raht_rlgr_seg_decode_batch", 32, "none"),
+                                                 ("raht_rlgr_seg_decode_batch_check", 32, "required")])
+def test_decode_batch_argument_validation(L, entry, width, expects):
+    N0, D0, S0 = SHAPES[width]
     many = BATCH_MAX + 1
     EX = _vp(E + 64, E + 128, E + 192)
-    cases = {
+    UNSET = object()
+
+    def call(k=3, inp=_vp(A, A + 64, A + 128), nbytes=_i64(1 << 20, 1 << 20, 1 << 20), so=_vp(B, B + 64, B + 128), sb=_vp(Cc, Cc + 64, Cc + 128),
+             N=N0, D=D0, S=S0, Q=_vp(Dd, Dd + 64, Dd + 128), expect=UNSET, sym=D0, chan=1, bad=E):
+        if expects == "none":
+            assert expect is UNSET
+            return L.raht_rlgr_seg_decode_batch(k, inp, nbytes, so, sb, N, D, S, 1, Q, sym, chan, bad, None)
+        if expect is UNSET:                                           # (k = 13: as many entries as the call may look at)
+            expect = _vp(*[E + 64] * k) if expects == "required" and k > 3 else EX if expects == "required" else None
+        return getattr(L, entry)(k, inp, nbytes, so, sb, N, D, S, 1, Q, expect, sym, chan, bad, None)
+
+    general = {
         "k = 0": dict(k=0),
         "k = RAHT_RLGR_BATCH_MAX + 1": dict(k=many, inp=_vp(*[A] * many), nbytes=_i64(*[1 << 20] * many), so=_vp(*[B] * many), sb=_vp(*[Cc] * many),
                                             Q=_vp(*[Dd] * many)),
@@ -190,11 +231,22 @@ def test_decode_batch64_argument_validation(L):
         "NULL Q[1]": dict(Q=_vp(Dd, None, Dd + 128)), "in[1] not 4-byte aligned": dict(inp=_vp(A, A + 66, A + 128)),
         "in_bytes[2] < 0": dict(nbytes=_i64(1 << 20, 1 << 20, -4)), "in_bytes[0] not a multiple of 4": dict(nbytes=_i64(1001, 1 << 20, 1 << 20)),
         "N = 0": dict(N=0), "D = 0": dict(D=0), "seg_len = 63": dict(S=63), "row-major with sym_stride < D": dict(sym=D0 - 1),
-        "channel-major with chan_stride < N": dict(sym=1, chan=N0 - 1), "neither layout": dict(sym=2, chan=2),
-        "too many segments": dict(N=2 ** 31, D=64, S=64, sym=64),
+        "neither layout": dict(sym=2, chan=2), "too many segments": dict(N=2 ** 31, D=64, S=64, sym=64),
+        "channel-major with chan_stride < N": dict(sym=1, chan=N0 - 1), "expect and k = 0": dict(expect=EX, k=0),
+    }
+    of_expect = {
         "expect with a NULL inside": dict(expect=_vp(E + 64, None, E + 192)), "expect without bad_dev": dict(expect=EX, bad=None),
         "expect with channel-major frames": dict(expect=EX, sym=1, chan=N0),
-        "expect and k = 0": dict(expect=EX, k=0),
     }
-    for what, kw in cases.items():
-        _refused(L, "raht_rlgr_seg_decode_batch64", call(**kw), what)
+    if expects == "required":
+        of_expect["NULL expect"] = dict(expect=None)
+        for what in ("channel-major with chan_stride < N", "neither layout"):
+            # (chan_stride != 1 breaks the layout rule AND the row-major rule of expect[]: either name may report it)
+            assert call(**general.pop(what)) == INVALID and b"raht_rlgr_seg_decode_batch" in L.raht_last_error(), what
+    for what, kw in general.items():
+        if expects == "none" and "expect" in kw:
+            continue
+        _refused(L, "raht_rlgr_seg_decode_batch" if expects == "required" else entry, call(**kw), what)
+    if expects != "none":
+        for what, kw in of_expect.items():
+            _refused(L, entry, call(**kw), what)

@@ -84,7 +84,7 @@ for D, n_wide in ((56, 0), (59, 3)):
         c.encode(Q)
     assert [c.container() for c in coders] == ragged
     geos = [OctreeCoder.encode(k, J) for k in keys]
-    blobs = [bitstream._frame_blob(J, A.shape[0], D, n_wide, [STEP], None, None, g, a) for A, g, a in zip(As, geos, ragged)]
+    blobs = [b"".join(bitstream._frame_parts(J, A.shape[0], D, n_wide, [STEP], None, None, g, [a])) for A, g, a in zip(As, geos, ragged)]
     outs = [torch.empty((A.shape[0], D), dtype=torch.int32, device="cuda") for A in As]
     iq1 = (lambda p, Q: p.dequant_inverse_mixed(Q, STEP, n_wide)) if n_wide else (lambda p, Q: p.dequant_inverse(Q, STEP))
     iqb = (lambda: ops.dequant_inverse_mixed_batch(plans, Qs, STEP, n_wide)) if n_wide else (lambda: ops.dequant_inverse_batch(plans, Qs, STEP))
