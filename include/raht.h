@@ -836,6 +836,31 @@ int raht_region_cells(const uint64_t *keys_sorted, int64_t N, int nbits, int top
 int raht_region_assemble(const int32_t *src, int64_t ld_src, int64_t n_src_rows, int32_t *dst, int64_t ld_dst, int64_t n_dst_rows, int D,
                          const int64_t *runs, int n_runs, raht_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Inter-frame prediction (csrc/predict.hip): a frame of a sequence predicted from the RECONSTRUCTION of another one, so that only
+ * the residual is coded (python: bitstream.encode_sequence_bytes(..., gop, up, inter) / decode_sequence_bytes).
+ *
+ * The predictor. keys_sorted: the N strictly ascending keys of the frame; ref_keys_sorted / C_ref: the N_ref strictly ascending
+ * keys of the reference frame (the same depth) and its N_ref x D float32 attributes, row stride ld_ref. shift = 3 up, up = 0 .. 3.
+ * Row i lies in the cell c = key[i] >> shift; its run [lo, hi) in the reference is every row r with ref_key[r] >> shift == c
+ * (contiguous: the keys are sorted; at most 8^up rows). P[i, ch] = 0 for an empty run; otherwise s = C_ref[lo, ch], then
+ * s = s + C_ref[r, ch] for r = lo + 1 .. hi - 1 in this order in float32, and P[i, ch] = s / (float)(hi - lo), one IEEE division.
+ * The order of the sum is part of the definition: encoder and decoder, and every implementation, give the same bits. With
+ * shift = 0 the prediction is the co-located voxel's row, exactly.
+ *   raht_predict : Y (N x D, row stride ldy) = X - P (add = 0) or X + P (add = 1), one float32 operation per element; Y = P when X
+ *                  is NULL. Y may be X (in place). n_matched (DEVICE int64, may be NULL) = the number of rows with a non-empty run.
+ *                  One launch (and a memset when n_matched is given); enqueues only, never synchronises.
+ * RAHT_ERR_INVALID, with nothing enqueued: NULL keys / ref keys / C_ref / Y, N or N_ref outside 1 .. 2^31 - 1, shift not one of
+ * 0, 3, 6, 9, D < 1, a row stride below D, add not 0 or 1.
+ *
+ *   predicted frame   : "RAHTP001" | int64 ref_back (>= 1: the reference is ref_back frames earlier; encoders write 1) |
+ *                       int64 up (0 .. 3) | a whole "RAHTF001" frame container whose attributes are the residual X - P.
+ *                       It exists only inside a sequence container ("RAHTS001"), never at index 0; its reconstruction is the
+ *                       inner frame's plus P of the reference's reconstruction. */
+int raht_predict(const uint64_t *keys_sorted, int64_t N, const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref,
+                 int64_t ld_ref, const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched,
+                 raht_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

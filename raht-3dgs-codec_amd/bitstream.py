@@ -12,6 +12,14 @@ with the transform and entropy stages of all frames in common launches (DESIGN.m
 
     RAHTS001 | int64 n_frames | int64 offset[n_frames + 1] (from the start of the blob) | the frames
 
+Inside a sequence a frame may be PREDICTED from the reconstruction of an earlier one (``encode_sequence_bytes(..., gop, up,
+inter)``): a wrapper around an ordinary frame whose attributes are the residual ``A - P``, P being ``ops.predict`` of
+the reference's reconstruction (the mean of the reference voxels in the same cell ``up`` octree levels above the voxels; ``up = 0``:
+the co-located voxel). ``decode_frame_bytes`` / ``decode_region_bytes`` refuse the wrapper; ``decode_sequence_bytes`` resolves it.
+
+    RAHTP001 | int64 ref_back (>= 1: the reference is ref_back frames earlier; this version writes 1) | int64 up (0 .. 3) |
+    a whole RAHTF001 frame
+
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
 sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
@@ -27,6 +35,8 @@ from .rlgr import SegmentedCoder
 
 MAGIC = b"RAHTF001"
 SEQ_MAGIC = b"RAHTS001"
+P_MAGIC = b"RAHTP001"
+P_HEAD = len(P_MAGIC) + 16                                     # what a predicted frame's wrapper adds to its inner frame
 MIN_FRAME_BYTES = len(MAGIC) + 40 + 8 * 5 + 2 * (8 + 48)      # header, one step + box, two sections of 48 bytes at least
 
 
@@ -54,11 +64,16 @@ def _frame_input(who, V_int, attributes, J, n_wide, dev):
     return V, A
 
 
-def _geometry_and_plan(V, J, geometry):
-    """sorted voxel coordinates -> (geometry section, plan over their keys)"""
+def _keys_geometry_plan(V, J, geometry):
+    """sorted voxel coordinates -> (their keys, geometry section, plan over the keys)"""
     keys = ops.get_morton_code(V, J)
     geo = OctreeCoder.encode(keys, J, entropy=geometry)                   # (also refuses rows that are not sorted and unique)
-    return geo, ops.RahtPlan.from_keys(keys, 3 * J)
+    return keys, geo, ops.RahtPlan.from_keys(keys, 3 * J)
+
+
+def _geometry_and_plan(V, J, geometry):
+    """sorted voxel coordinates -> (geometry section, plan over their keys)"""
+    return _keys_geometry_plan(V, J, geometry)[1:]
 
 
 def _quantize(plans, As, steps, n_wide):
@@ -243,8 +258,12 @@ def decode_frame_bytes(blob, device="cuda", max_voxels=None):
     """-> (V_int (N, 3) int64, C_rec (N, D) float32), CUDA tensors on ``device``, from the bytes alone. ``max_voxels``: refuse
     frames that announce more voxels than this before anything is allocated for them. ``ValueError`` for a corrupt frame."""
     import torch
-    h = parse_frame(blob, max_voxels)
-    dev = torch.device(device)
+    return _decode_frame(blob, parse_frame(blob, max_voxels), torch.device(device), max_voxels)[:2]
+
+
+def _decode_frame(blob, h, dev, max_voxels):
+    """a frame container and its parsed header -> (V_int, C_rec, keys)"""
+    import torch
     (go, gl), (ao, al) = h["geometry"], h["attributes"]
     with torch.cuda.device(dev):
         keys = OctreeCoder.decode(blob[go: go + gl], dev, max_voxels)
@@ -254,7 +273,7 @@ def decode_frame_bytes(blob, device="cuda", max_voxels=None):
         Q = sc.decode(row_major=True)
         C_rec = _reconstruct([plan], [Q], h["steps"], h["n_wide"])[0]
         _refuse_outside(int(sc.bad.item()))
-    return V, C_rec
+    return V, C_rec, keys
 
 
 def region_runs(table, J, depth, n_roots):
@@ -409,21 +428,100 @@ def sequence_frame(blob, i, offsets=None):
     return memoryview(blob)[off[i]: off[i + 1]]
 
 
+def parse_pframe(fb):
+    """The wrapper of a predicted frame, checked (pure host code) -> (ref_back, up, the inner RAHTF001 container as a memoryview).
+    ``ValueError`` for another magic, a wrapper too short to hold a frame, ``ref_back < 1`` or ``up`` outside 0 .. 3; the inner
+    frame is ``parse_frame``'s to judge."""
+    if bytes(fb[:len(P_MAGIC)]) != P_MAGIC:
+        raise ValueError("not a RAHT predicted-frame wrapper")
+    if len(fb) < P_HEAD + MIN_FRAME_BYTES:
+        raise ValueError("predicted frame: truncated wrapper")
+    ref_back, up = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(P_MAGIC))]
+    if ref_back < 1:
+        raise ValueError(f"predicted frame: ref_back = {ref_back}, must be at least 1")
+    if not 0 <= up <= 3:
+        raise ValueError(f"predicted frame: up = {up} outside 0 .. 3")
+    return ref_back, up, memoryview(fb)[P_HEAD:]
+
+
+def _frame_head(view, off, i, max_voxels):
+    """frame i of a sequence from its headers alone -> dict: kind ("I" / "P"), ref (the frame it is predicted from, or None), up,
+    fb (its RAHTF001 container: the inner one of a predicted frame), h (``parse_frame`` of it), seg_len. ``ValueError`` naming i."""
+    fb = view[off[i]: off[i + 1]]
+    kind, ref, up = "I", None, 0
+    try:
+        if bytes(fb[:len(P_MAGIC)]) == P_MAGIC:
+            kind = "P"
+            ref_back, up, fb = parse_pframe(fb)
+            if i == 0:
+                raise ValueError("a predicted frame cannot open a sequence")
+            if ref_back > i:
+                raise ValueError(f"predicted frame: ref_back = {ref_back} reaches before frame 0")
+            ref = i - ref_back
+        h = parse_frame(fb, max_voxels)
+        ao, al = h["attributes"]
+        S = SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[2]
+    except ValueError as e:
+        raise ValueError(f"sequence container: frame {i}: {e}") from None
+    return dict(kind=kind, ref=ref, up=up, fb=fb, h=h, seg_len=S)
+
+
+def _frame_heads(view, off, idx, max_voxels):
+    """the heads of the frames ``idx`` and of every frame they depend on, back to the nearest intra frame -> {i: head}; a predicted
+    frame whose J or D is not its reference's is refused here, before any device work"""
+    heads = {}
+    for i in idx:                                                            # (in the order asked for: the first bad frame is the one named)
+        while i is not None and i not in heads:
+            heads[i] = _frame_head(view, off, i, max_voxels)
+            i = heads[i]["ref"]
+    for i in sorted(heads):
+        hd = heads[i]
+        if hd["ref"] is not None:
+            h, r = hd["h"], heads[hd["ref"]]["h"]
+            if (h["J"], h["D"]) != (r["J"], r["D"]):
+                raise ValueError(f"sequence container: frame {i}: a predicted frame of J = {h['J']}, D = {h['D']} against a reference "
+                                 f"(frame {hd['ref']}) of J = {r['J']}, D = {r['D']}")
+    return heads
+
+
+def sequence_kinds(blob, max_voxels=None, max_frames=None):
+    """-> ["I" | "P"] per frame of a sequence container, from the headers alone (pure host code). Every frame's headers are checked
+    on the way as ``decode_sequence_bytes`` checks them: ``ValueError`` naming the frame for a predicted frame at index 0, a
+    ``ref_back`` below 1 or reaching before frame 0, ``up`` outside 0 .. 3, a truncated wrapper, a frame ``parse_frame`` refuses, a
+    predicted frame whose J or D differs from its reference's."""
+    off = parse_sequence(blob, max_frames)
+    heads = _frame_heads(memoryview(blob), off, range(len(off) - 1), max_voxels)
+    return [heads[i]["kind"] for i in range(len(off) - 1)]
+
+
 SEQ_CHUNK = SegmentedCoder.BATCH_MAX                                     # frames whose transform and entropy stages share launches
 
 
-def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None):
+def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None, gop=1, up=0,
+                          inter="auto"):
     """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
     container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
     frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
     when ``n_wide`` is set, ``forward_quant_batch`` otherwise) and their entropy stage in another
     (``SegmentedCoder.encode_ragged`` on the row-major integers). Device memory: the quantized matrices and the coders' buffers
-    of a whole chunk are alive together, about 8 N D bytes per frame beside its attributes (12 frames of 1 M x 59: 5.7 GB)."""
+    of a whole chunk are alive together, about 8 N D bytes per frame beside its attributes (12 frames of 1 M x 59: 5.7 GB).
+
+    ``gop`` > 1: inter-frame prediction. Frame i with i % gop == 0 is intra; every other frame is a candidate for
+    prediction from frame i - 1's RECONSTRUCTION (closed loop: the encoder predicts from what the decoder will have, so nothing
+    drifts): R = A - P with P = ``ops.predict(keys_i, keys_(i-1), C_rec_(i-1), up=up)``. ``inter="always"`` codes R as an RAHTP001
+    frame; ``inter="auto"`` asks ``RahtPlan.rate_curve`` for the exact attribute bytes of A and of R at the frame's steps and codes R
+    iff bytes_R + 24 < bytes_A (the wrapper costs 24 bytes; a tie goes to intra). The chain is a true dependency -- frame i's residual
+    needs frame i - 1's reconstruction, which needs its integers -- so with ``gop`` > 1 the transform + quantization (and, where a
+    frame is predicted from, the inverse) run frame by frame, for I and P frames alike; the entropy stage still goes through one
+    set of launches per ``SEQ_CHUNK`` frames. With the default ``gop=1`` the result is byte for byte what it was without these
+    arguments."""
     import torch
     dev = torch.device(device)
-    J, n_wide = int(J), int(n_wide)
+    J, n_wide, gop, up = int(J), int(n_wide), int(gop), int(up)
     if not frames:
         raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
+    if gop < 1 or not 0 <= up <= 3 or inter not in ("auto", "always"):
+        raise ValueError('encode_sequence_bytes: gop >= 1, up in 0 .. 3, inter "auto" or "always"')
     VA = []
     for i, (V_int, attributes) in enumerate(frames):
         V, A = _frame_input(f"encode_sequence_bytes: frame {i}", V_int, attributes, J, n_wide, dev)
@@ -436,9 +534,29 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     with torch.cuda.device(dev):
         for lo in range(0, len(VA), SEQ_CHUNK):
             chunk = VA[lo: lo + SEQ_CHUNK]
-            geos, plans = zip(*[_geometry_and_plan(V, J, geometry) for V, _ in chunk])
-            atts = _attribute_parts(_quantize(list(plans), [A for _, A in chunk], steps, n_wide), seg_len, dev)
-            parts += [_frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att) for (_, A), geo, att in zip(chunk, geos, atts)]
+            if gop == 1:
+                geos, plans = zip(*[_geometry_and_plan(V, J, geometry) for V, _ in chunk])
+                Qs, wraps = _quantize(list(plans), [A for _, A in chunk], steps, n_wide), [[]] * len(chunk)
+            else:
+                geos, Qs, wraps = [], [], []
+                for i, (V, A) in enumerate(chunk, lo):
+                    keys, geo, plan = _keys_geometry_plan(V, J, geometry)
+                    src = A
+                    if i % gop:                                              # (ref: frame i - 1's keys and reconstruction)
+                        R = ops.predict(keys, ref[0], ref[1], X=A, up=up)
+                        if inter == "always" or (int(plan.rate_curve(R, [steps], n_wide, seg_len)["bytes"][0]) + P_HEAD
+                                                 < int(plan.rate_curve(A, [steps], n_wide, seg_len)["bytes"][0])):
+                            src = R
+                    Q = _quantize([plan], [src], steps, n_wide)[0]
+                    if i + 1 < len(VA) and (i + 1) % gop:                    # the next frame may be predicted from this one
+                        C = _reconstruct([plan], [Q], steps, n_wide)[0]
+                        ref = (keys, C if src is A else ops.predict(keys, ref[0], ref[1], X=C, up=up, add=True, out=C))
+                    geos.append(geo)
+                    Qs.append(Q)
+                    wraps.append([] if src is A else [P_MAGIC + np.array([1, up], np.int64).tobytes()])
+            atts = _attribute_parts(Qs, seg_len, dev)
+            parts += [w + _frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att)
+                      for (_, A), geo, att, w in zip(chunk, geos, atts, wraps)]
     return _pack_parts(parts)
 
 
@@ -449,7 +567,15 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
     inverse transform launches (a frame of exactly D voxels goes alone). ``max_voxels`` per frame and ``max_frames`` are checked
     before anything is allocated from the numbers of the blob. ``ValueError`` for a corrupt container; a corrupt frame is named by
     its index -- for a header or an attribute length table that does not add up before any device work, for a corrupt geometry
-    section or a segment outside its payload when that frame's group is decoded."""
+    section or a segment outside its payload when that frame's group is decoded.
+
+    A predicted frame (RAHTP001) comes back as (V_int, fl(R_rec + P)): R_rec is what ``decode_frame_bytes`` returns for its inner
+    frame, P is ``ops.predict`` of its reference's decoded attributes. The requested indices are closed under dependencies, back to
+    the nearest intra frame, and that set is decoded in ascending order; only the requested frames are returned. R_rec does not
+    depend on the prediction, so the entropy decode and the inverse transform of a group stay batched, for I and P frames alike;
+    only the additions run in frame order. A predicted frame at index 0, a ``ref_back`` below 1 or reaching before frame 0, ``up``
+    outside 0 .. 3, a truncated wrapper, an inner frame ``parse_frame`` refuses or one whose J or D is not its reference's are
+    refused from the headers, before any device work."""
     import torch
     off = parse_sequence(blob, max_frames)
     n = len(off) - 1
@@ -463,18 +589,14 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
         raise ValueError(f"decode_sequence_bytes: frame indices must be in 0 .. {n - 1}")
     dev = torch.device(device)
     view = memoryview(blob)
+    by_index = _frame_heads(view, off, idx, max_voxels)
+    inter = any(hd["kind"] == "P" for hd in by_index.values())
     heads = []
-    for i in idx:
-        fb = view[off[i]: off[i + 1]]
-        try:
-            h = parse_frame(fb, max_voxels)
-            ao, al = h["attributes"]
-            S = SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[2]
-        except ValueError as e:
-            raise ValueError(f"sequence container: frame {i}: {e}") from None
+    for i in (sorted(by_index) if inter else idx):                           # (no predicted frame: the frames as they were asked for)
+        fb, h, S = by_index[i]["fb"], by_index[i]["h"], by_index[i]["seg_len"]
         # (a frame of exactly D voxels is a group of its own: decode_frame_bytes reads its square matrix as the encoder wrote it)
         heads.append((i, fb, h, (h["D"], S, h["n_wide"], tuple(h["steps"])) + ((len(heads),) if h["N"] == h["D"] else ())))
-    out = []
+    out = []                                                                 # (V, C_rec or R_rec, keys) per head
     with torch.cuda.device(dev):
         lo = 0
         while lo < len(heads):
@@ -484,13 +606,13 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
             group = heads[lo:hi]
             lo = hi
             if len(group) == 1:
-                i, fb, _, _ = group[0]
+                i, fb, h, _ = group[0]
                 try:
-                    out.append(decode_frame_bytes(fb, dev, max_voxels))
+                    out.append(_decode_frame(fb, h, dev, max_voxels))
                 except ValueError as e:
                     raise ValueError(f"sequence container: frame {i}: {e}") from None
                 continue
-            Vs, plans, coders = [], [], []
+            Vs, plans, coders, ks = [], [], [], []
             for i, fb, h, _ in group:
                 (go, gl), (ao, al) = h["geometry"], h["attributes"]
                 try:
@@ -500,6 +622,7 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
                     raise ValueError(f"sequence container: frame {i}: {e}") from None
                 Vs.append(ops.demorton(keys, h["J"]))
                 plans.append(ops.RahtPlan.from_keys(keys, 3 * h["J"]))
+                ks.append(keys)
             _, _, n_wide, steps = group[0][3][:4]
             steps = list(steps)
             if any(c.wide for c in coders):                              # (64-bit offsets: such a frame goes alone)
@@ -513,5 +636,14 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
                 bad = SegmentedCoder.roundtrip_failed(coders)
             if bad:
                 _refuse_outside(True, f"sequence container: frame {group[bad[0]][0]}: ")
-            out += list(zip(Vs, Cs))
-    return out
+            out += list(zip(Vs, Cs, ks))
+        if not inter:
+            return [(V, C) for V, C, _ in out]
+        done = {}                                                            # frame -> (V, C_rec, keys), in ascending frame order
+        for (i, _, _, _), (V, C, keys) in zip(heads, out):
+            hd = by_index[i]
+            if hd["kind"] == "P":
+                _, C_ref, ref_keys = done[hd["ref"]]
+                C = ops.predict(keys, ref_keys, C_ref, X=C, up=hd["up"], add=True, out=C)
+            done[i] = (V, C, keys)
+    return [done[i][:2] for i in idx]

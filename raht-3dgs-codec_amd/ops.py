@@ -895,6 +895,44 @@ def region_assemble(src, runs, n_dst_rows):
     return dst
 
 
+def _predict_rows(M, n_rows, D, name):
+    """a float32 CUDA matrix of the predictor, as it is: (n_rows, D), unit column stride, a row stride of at least D"""
+    _need_cuda(M, name)
+    if M.dtype != torch.float32 or M.dim() != 2 or tuple(M.shape) != (n_rows, D) or M.stride(1) != 1 or M.stride(0) < D:
+        raise ValueError(f"predict: {name} must be a ({n_rows}, {D}) float32 matrix with contiguous rows")
+    return M
+
+
+@torch.no_grad()
+def predict(keys, ref_keys, C_ref, X=None, up=0, add=False, out=None, want_matched=False):
+    """The inter-frame predictor (raht_predict). keys (N,), ref_keys (N_ref,): the sorted int64 Morton keys of the frame
+    and of its reference, as ``get_morton_code`` returns them; C_ref: (N_ref, D) float32, the reference's reconstruction. P[i] is the
+    mean of the reference rows in the cell ``keys[i] >> 3 up`` (summed in row order in float32, divided once; 0 where the cell is
+    empty; ``up = 0``: the co-located voxel's row). -> P when ``X`` is None, X - P, or X + P with ``add``; into ``out`` when given
+    (``out`` may be ``X``: in place). Column slices of wider matrices pass as they are. ``want_matched``: -> (result, n_matched), a
+    (1,) int64 device tensor with the number of rows whose cell is not empty. Enqueued only."""
+    k, r = _region_keys(keys, "predict"), _region_keys(ref_keys, "predict")
+    up = int(up)
+    if not 0 <= up <= 3:
+        raise ValueError("predict: up must be 0 .. 3")
+    _need_cuda(C_ref, "C_ref")
+    if C_ref.dim() != 2:
+        raise ValueError("predict: C_ref must be a matrix")
+    N, D = int(k.shape[0]), int(C_ref.shape[1])
+    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
+    if X is not None:
+        X = _predict_rows(X, N, D, "X")
+    elif add:
+        raise ValueError("predict: add needs X")
+    out = torch.empty((N, D), dtype=torch.float32, device=k.device) if out is None else _predict_rows(out, N, D, "out")
+    if len({t.device for t in (k, r, C_ref, out) + (() if X is None else (X,))}) != 1:
+        raise ValueError("predict: all tensors must be on one device")
+    matched = torch.empty(1, dtype=torch.int64, device=k.device) if want_matched else None
+    _call(_lib.lib().raht_predict, k.device, _p(k), N, _p(r), int(r.shape[0]), 3 * up, _p(C_ref), C_ref.stride(0), _p(X),
+          0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched))
+    return (out, matched) if want_matched else out
+
+
 @torch.no_grad()
 def voxel_keys(PC, vmin, width, J):
     """Unsorted 3J-bit Morton keys (int64) of the points of PC (n, >= 3) float32 for a given bounding box: the
