@@ -8,12 +8,12 @@
   the two collectives is what runs here.
 """
 import os
-import socket
 import sys
-import traceback
 
 import numpy as np
 import pytest
+
+from tests.rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -106,139 +106,97 @@ def test_rows_gather_scatter_and_voxel_keys(rt, oracle):
 
 
 # ------------------------------------------------------------------ four ranks, one GPU, gloo collectives
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _rank_main(rank, world, J, n, d):
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    from raht_3dgs_codec_amd import sharded, synth
+    from oracle import oracle as orc
 
+    rng = np.random.default_rng(321)
+    P = synth.blob_positions(n, seed=19, nblobs=40, sigma=0.04).astype(np.float32) * np.float32(3.0) + np.float32(0.5)
+    P[::5] = P[2::5][: P[::5].shape[0]]                           # several points per voxel
+    A = rng.standard_normal((n, d)).astype(np.float32)
+    PC = np.concatenate([P, A], axis=1)
+    bounds = [0] + sorted(rng.choice(np.arange(1, n), size=world - 1, replace=False).tolist()) + [n]
+    mine = torch.from_numpy(PC[bounds[rank]:bounds[rank + 1]].copy()).cuda()
 
-def _rank_main(rank, world, port, J, n, d, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch
-        import torch.distributed as dist
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        from raht_3dgs_codec_amd import sharded, synth
-        from oracle import oracle as orc
+    PCvox, keys, info = sharded.exchange_by_prefix(mine, J, prefix_bits=9)          # HIP local ops
+    ref = orc.voxelize(PC, J)
+    cnt = torch.tensor([PCvox.shape[0]], dtype=torch.int64)
+    allc = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(allc, cnt)
+    lo = int(sum(int(c.item()) for c in allc[:rank]))
+    nloc = int(PCvox.shape[0])
+    assert int(sum(int(c.item()) for c in allc)) == ref["Nvox"]
+    ref_keys = ref["keys_sorted"][ref["voxel_indices"]]
+    np.testing.assert_array_equal(keys.cpu().numpy().view(np.uint64), ref_keys[lo:lo + nloc])
+    np.testing.assert_array_equal(PCvox.cpu().numpy(), ref["PCvox"][lo:lo + nloc])   # float32 means, bit-exact
 
-        rng = np.random.default_rng(321)
-        P = synth.blob_positions(n, seed=19, nblobs=40, sigma=0.04).astype(np.float32) * np.float32(3.0) + np.float32(0.5)
-        P[::5] = P[2::5][: P[::5].shape[0]]                           # several points per voxel
-        A = rng.standard_normal((n, d)).astype(np.float32)
-        PC = np.concatenate([P, A], axis=1)
-        bounds = [0] + sorted(rng.choice(np.arange(1, n), size=world - 1, replace=False).tolist()) + [n]
-        mine = torch.from_numpy(PC[bounds[rank]:bounds[rank + 1]].copy()).cuda()
-
-        PCvox, keys, info = sharded.exchange_by_prefix(mine, J, prefix_bits=9)          # HIP local ops
-        ref = orc.voxelize(PC, J)
-        cnt = torch.tensor([PCvox.shape[0]], dtype=torch.int64)
-        allc = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
-        dist.all_gather(allc, cnt)
-        lo = int(sum(int(c.item()) for c in allc[:rank]))
-        nloc = int(PCvox.shape[0])
-        assert int(sum(int(c.item()) for c in allc)) == ref["Nvox"]
-        ref_keys = ref["keys_sorted"][ref["voxel_indices"]]
-        np.testing.assert_array_equal(keys.cpu().numpy().view(np.uint64), ref_keys[lo:lo + nloc])
-        np.testing.assert_array_equal(PCvox.cpu().numpy(), ref["PCvox"][lo:lo + nloc])   # float32 means, bit-exact
-
-        sh = sharded.ShardedRaht(keys, 3 * J, prefix_bits=9)
-        assert sh.world == world and sh.total_rows == ref["Nvox"]
-        C_loc = PCvox[:, 3:].contiguous()
-        V = synth.keys_to_coords(ref_keys, J)
-        po = orc.raht_param(V.astype(np.float64), np.zeros(3), 2 ** J, J)
-        Cw = ref["PCvox"][:, 3:].astype(np.float64)
-        To, _ = orc.raht_fwd(Cw, po)
-        colmax = np.abs(To).max(axis=0)
-        T = sh.forward(C_loc)
-        err = np.abs(T.cpu().numpy().astype(np.float64) - To[lo:lo + nloc]).max(axis=0)
-        assert np.all(err <= 2e-6 * colmax), float((err / colmax).max())
-        R = sh.inverse(T)
-        assert (R - C_loc).abs().max().item() <= 1e-5 * float(np.abs(Cw).max())
-        step = 0.02
-        Q = sh.forward_quant(C_loc, step)
-        Tq = np.empty((nloc, d), dtype=np.float64)
-        Tq[sh.plan.order_RAGFT.cpu().numpy()] = Q.cpu().numpy().astype(np.float64) * step
-        assert np.all(np.abs(Tq - To[lo:lo + nloc]) <= 0.5 * step * 1.0001 + 2e-6 * colmax)
-        Rq = sh.dequant_inverse(Q, step)
-        e = torch.tensor([float(((Rq.double() - C_loc.double()) ** 2).sum()), float(((torch.from_numpy(Tq).cuda() - T.double()) ** 2).sum())], dtype=torch.float64)
-        dist.all_reduce(e)
-        assert abs(e[0].item() - e[1].item()) <= 1e-3 * max(e[1].item(), 1e-30)         # orthonormal: error energies agree
-        chk = sh.check_against_unsharded(C_loc, step)
-        assert chk["ok"], chk
-        # float64 through the same driver
-        T64 = sh.forward(C_loc.double())
-        np.testing.assert_allclose(T64.cpu().numpy(), To[lo:lo + nloc], rtol=1e-11, atol=1e-11 * float(colmax.max()))
-        dist.barrier()
-        dist.destroy_process_group()
-        q.put((rank, "ok"))
-    except Exception:
-        q.put((rank, traceback.format_exc()))
+    sh = sharded.ShardedRaht(keys, 3 * J, prefix_bits=9)
+    assert sh.world == world and sh.total_rows == ref["Nvox"]
+    C_loc = PCvox[:, 3:].contiguous()
+    V = synth.keys_to_coords(ref_keys, J)
+    po = orc.raht_param(V.astype(np.float64), np.zeros(3), 2 ** J, J)
+    Cw = ref["PCvox"][:, 3:].astype(np.float64)
+    To, _ = orc.raht_fwd(Cw, po)
+    colmax = np.abs(To).max(axis=0)
+    T = sh.forward(C_loc)
+    err = np.abs(T.cpu().numpy().astype(np.float64) - To[lo:lo + nloc]).max(axis=0)
+    assert np.all(err <= 2e-6 * colmax), float((err / colmax).max())
+    R = sh.inverse(T)
+    assert (R - C_loc).abs().max().item() <= 1e-5 * float(np.abs(Cw).max())
+    step = 0.02
+    Q = sh.forward_quant(C_loc, step)
+    Tq = np.empty((nloc, d), dtype=np.float64)
+    Tq[sh.plan.order_RAGFT.cpu().numpy()] = Q.cpu().numpy().astype(np.float64) * step
+    assert np.all(np.abs(Tq - To[lo:lo + nloc]) <= 0.5 * step * 1.0001 + 2e-6 * colmax)
+    Rq = sh.dequant_inverse(Q, step)
+    e = torch.tensor([float(((Rq.double() - C_loc.double()) ** 2).sum()), float(((torch.from_numpy(Tq).cuda() - T.double()) ** 2).sum())], dtype=torch.float64)
+    dist.all_reduce(e)
+    assert abs(e[0].item() - e[1].item()) <= 1e-3 * max(e[1].item(), 1e-30)         # orthonormal: error energies agree
+    chk = sh.check_against_unsharded(C_loc, step)
+    assert chk["ok"], chk
+    # float64 through the same driver
+    T64 = sh.forward(C_loc.double())
+    np.testing.assert_allclose(T64.cpu().numpy(), To[lo:lo + nloc], rtol=1e-11, atol=1e-11 * float(colmax.max()))
+    dist.barrier()
 
 
 @pytest.mark.parametrize("world", [4, 5])
 def test_four_ranks_share_the_gpu_exchange_and_transform(rt, world):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_rank_main, args=(r, world, port, 10, 300000 if world == 4 else 120000, 14, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=600) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=120)
-    for rank, msg in res:
-        assert msg == "ok", f"rank {rank}:\n{msg}"
+    run_ranks(_rank_main, world, 10, 300000 if world == 4 else 120000, 14, report_timeout=600, join_timeout=120)
 
 
-def _rccl_main(port, q):
-    try:
-        sys.path.insert(0, ROOT)
-        import torch
-        import torch.distributed as dist
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        import raht_3dgs_codec_amd as R
-        from raht_3dgs_codec_amd import sharded, synth
-        V, keys, C = synth.scene(150000, 11, 59, seed=21)
-        kd = torch.from_numpy(keys.view(np.int64)).cuda()
-        Cd = torch.from_numpy(C).cuda()
-        sh = sharded.ShardedRaht(kd, 33, prefix_bits=9, force_collectives=True)      # the two all-gathers go through RCCL
-        p = R.RahtPlan.from_keys(kd, 33)
-        T0 = p.forward(Cd, want_w=False)
-        T1 = sh.forward(Cd)
-        scale = T0.abs().amax(dim=0)
-        assert bool(((T1 - T0).abs().amax(dim=0) <= 2e-6 * scale).all())
-        for _ in range(3):
-            R1 = sh.step(Cd, 0.01)
-        assert (R1 - p.dequant_inverse(p.forward_quant(Cd, 0.01), 0.01)).abs().max().item() <= 0.02
-        chk = sh.check_against_unsharded(Cd, 0.01)
-        assert chk["ok"], chk
-        t = torch.ones(4, device="cuda")
-        dist.all_reduce(t); dist.barrier()
-        torch.cuda.synchronize()
-        dist.destroy_process_group()
-        q.put("ok")
-    except Exception:
-        q.put(traceback.format_exc())
+def _rccl_main(rank, world):
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    import raht_3dgs_codec_amd as R
+    from raht_3dgs_codec_amd import sharded, synth
+    V, keys, C = synth.scene(150000, 11, 59, seed=21)
+    kd = torch.from_numpy(keys.view(np.int64)).cuda()
+    Cd = torch.from_numpy(C).cuda()
+    sh = sharded.ShardedRaht(kd, 33, prefix_bits=9, force_collectives=True)      # the two all-gathers go through RCCL
+    p = R.RahtPlan.from_keys(kd, 33)
+    T0 = p.forward(Cd, want_w=False)
+    T1 = sh.forward(Cd)
+    scale = T0.abs().amax(dim=0)
+    assert bool(((T1 - T0).abs().amax(dim=0) <= 2e-6 * scale).all())
+    for _ in range(3):
+        R1 = sh.step(Cd, 0.01)
+    assert (R1 - p.dequant_inverse(p.forward_quant(Cd, 0.01), 0.01)).abs().max().item() <= 0.02
+    chk = sh.check_against_unsharded(Cd, 0.01)
+    assert chk["ok"], chk
+    t = torch.ones(4, device="cuda")
+    dist.all_reduce(t); dist.barrier()
+    torch.cuda.synchronize()
 
 
 def test_rccl_one_rank_group_carries_the_gathers(rt):
     """RCCL on the one GPU of this box: a one-rank NCCL process group, the sharded step with its all-gathers forced
     through the collective (what N ranks do over xGMI, minus the wire)."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_rccl_main, args=(_free_port(), q))
-    p.start()
-    msg = q.get(timeout=600)
-    p.join(timeout=120)
-    assert msg == "ok", msg
+    run_ranks(_rccl_main, 1, backend="nccl", report_timeout=600, join_timeout=120)
 
 
 # ------------------------------------------------------------------ bench.py starts its own ranks
@@ -279,112 +237,82 @@ def test_bench_one_rank_rccl_group(rt):
     assert mg["collective_ms"]["forward_all_gather"] > 0
 
 
-def _empty_rank_main(rank, world, port, q):
+def _empty_rank_main(rank, world):
     """Three gloo ranks on the one GPU; the scene occupies prefixes [0, 300) only, so the last rank owns no row, and rank 1
     starts the exchange with no point: HIP local ops with N = 0, every collective still entered by every rank."""
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch
-        import torch.distributed as dist
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        import raht_3dgs_codec_amd as R
-        from raht_3dgs_codec_amd import sharded, synth
-        J, D = 8, 14
-        V, keys, C = synth.scene(40000, J, D, seed=5, prefix_range=(0, 300, 9))
-        pref = (keys >> np.uint64(3 * J - 9)).astype(np.int64)
-        per = 512 // world
-        lo, hi = rank * per, ((rank + 1) * per if rank < world - 1 else 512)
-        mine = np.nonzero((pref >= lo) & (pref < hi))[0]
-        assert (mine.size == 0) == (rank == world - 1)
-        kd = torch.from_numpy(keys[mine].view(np.int64).copy()).cuda()
-        Cd = torch.from_numpy(C[mine]).cuda()
-        sh = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9)
-        full = R.RahtPlan.from_keys(torch.from_numpy(keys.view(np.int64).copy()).cuda(), 3 * J)
-        Tf = full.forward(torch.from_numpy(C).cuda(), want_w=False)
-        T = sh.forward(Cd)
-        if mine.size:
-            scale = Tf.abs().amax(dim=0)
-            assert bool(((T - Tf[mine[0]: mine[-1] + 1]).abs().amax(dim=0) <= 4e-6 * scale).all())
-        else:
-            assert sh.plan is None and tuple(T.shape) == (0, D)
-        Rr = sh.step(Cd, 0.01)
-        assert tuple(Rr.shape) == tuple(Cd.shape)
-        chk = sh.check_against_unsharded(Cd, 0.01, keys_sorted=kd)
-        assert chk["ok"], chk
-        # front end: rank 1 holds no point before the exchange
-        n = 30000
-        rng = np.random.default_rng(4)
-        P = (synth.blob_positions(n, seed=3, nblobs=10, sigma=0.05) * 5.0).astype(np.float32)
-        PC = np.concatenate([P, rng.standard_normal((n, 3)).astype(np.float32)], axis=1)
-        bounds = [0, n // 2, n // 2, n]
-        part = torch.from_numpy(PC[bounds[rank]:bounds[rank + 1]].copy()).cuda()
-        PCvox, vkeys, info = sharded.exchange_by_prefix(part, 7, prefix_bits=9)
-        cnt = torch.tensor([PCvox.shape[0]], dtype=torch.int64)
-        dist.all_reduce(cnt)
-        from oracle import oracle as orc
-        assert int(cnt.item()) == orc.voxelize(PC, 7)["Nvox"] and info["N_global"] == n
-        dist.barrier()
-        dist.destroy_process_group()
-        q.put((rank, "ok"))
-    except Exception:
-        q.put((rank, traceback.format_exc()))
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    import raht_3dgs_codec_amd as R
+    from raht_3dgs_codec_amd import sharded, synth
+    J, D = 8, 14
+    V, keys, C = synth.scene(40000, J, D, seed=5, prefix_range=(0, 300, 9))
+    pref = (keys >> np.uint64(3 * J - 9)).astype(np.int64)
+    per = 512 // world
+    lo, hi = rank * per, ((rank + 1) * per if rank < world - 1 else 512)
+    mine = np.nonzero((pref >= lo) & (pref < hi))[0]
+    assert (mine.size == 0) == (rank == world - 1)
+    kd = torch.from_numpy(keys[mine].view(np.int64).copy()).cuda()
+    Cd = torch.from_numpy(C[mine]).cuda()
+    sh = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9)
+    full = R.RahtPlan.from_keys(torch.from_numpy(keys.view(np.int64).copy()).cuda(), 3 * J)
+    Tf = full.forward(torch.from_numpy(C).cuda(), want_w=False)
+    T = sh.forward(Cd)
+    if mine.size:
+        scale = Tf.abs().amax(dim=0)
+        assert bool(((T - Tf[mine[0]: mine[-1] + 1]).abs().amax(dim=0) <= 4e-6 * scale).all())
+    else:
+        assert sh.plan is None and tuple(T.shape) == (0, D)
+    Rr = sh.step(Cd, 0.01)
+    assert tuple(Rr.shape) == tuple(Cd.shape)
+    chk = sh.check_against_unsharded(Cd, 0.01, keys_sorted=kd)
+    assert chk["ok"], chk
+    # front end: rank 1 holds no point before the exchange
+    n = 30000
+    rng = np.random.default_rng(4)
+    P = (synth.blob_positions(n, seed=3, nblobs=10, sigma=0.05) * 5.0).astype(np.float32)
+    PC = np.concatenate([P, rng.standard_normal((n, 3)).astype(np.float32)], axis=1)
+    bounds = [0, n // 2, n // 2, n]
+    part = torch.from_numpy(PC[bounds[rank]:bounds[rank + 1]].copy()).cuda()
+    PCvox, vkeys, info = sharded.exchange_by_prefix(part, 7, prefix_bits=9)
+    cnt = torch.tensor([PCvox.shape[0]], dtype=torch.int64)
+    dist.all_reduce(cnt)
+    from oracle import oracle as orc
+    assert int(cnt.item()) == orc.voxelize(PC, 7)["Nvox"] and info["N_global"] == n
+    dist.barrier()
 
 
 def test_rank_without_rows_on_the_gpu(rt):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    world = 3
-    procs = [ctx.Process(target=_empty_rank_main, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=600) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=120)
-    for rank, msg in res:
-        assert msg == "ok", f"rank {rank}:\n{msg}"
+    run_ranks(_empty_rank_main, 3, report_timeout=600, join_timeout=120)
 
 
 # ------------------------------------------------------------------ direct exchange (raht_xchg_*)
-def _direct_main(rank, world, port, q):
+def _direct_main(rank, world):
     """ranks share the one GPU; gloo carries the hipIpc handles once, the gathers themselves are direct writes + flags"""
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch
-        import torch.distributed as dist
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        from raht_3dgs_codec_amd import sharded, synth
-        J, D = 10, 59
-        per = 512 // world
-        V, keys, C = synth.scene(60000 + 7000 * rank, J, D, seed=31 + rank, prefix_range=(rank * per, (rank + 1) * per, 9))
-        kd = torch.from_numpy(keys.view(np.int64).copy()).cuda()
-        Cd = torch.from_numpy(C).cuda()
-        ref = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9)                    # gloo all-gathers (host staged)
-        drc = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9, direct=True, force_collectives=True)
-        T0, Q0 = ref.forward(Cd), ref.forward_quant(Cd, 0.01)
-        for it in range(5):                                                    # both buffer parities, several times
-            assert torch.equal(drc.forward(Cd), T0), it
-            assert torch.equal(drc.forward_quant(Cd, 0.01), Q0), it
-        assert torch.equal(drc.inverse(T0), ref.inverse(T0))
-        assert torch.equal(drc.dequant_inverse(Q0, 0.01), ref.dequant_inverse(Q0, 0.01))
-        T64 = drc.forward(Cd.double())                                         # another (D, dtype): another exchange block
-        assert torch.equal(T64, ref.forward(Cd.double()))
-        chk = drc.check_against_unsharded(Cd, 0.01, keys_sorted=kd)
-        assert chk["ok"], chk
-        assert drc.exchange_status() == 0
-        drc.close()
-        dist.barrier()
-        dist.destroy_process_group()
-        q.put((rank, "ok"))
-    except Exception:
-        q.put((rank, traceback.format_exc()))
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    from raht_3dgs_codec_amd import sharded, synth
+    J, D = 10, 59
+    per = 512 // world
+    V, keys, C = synth.scene(60000 + 7000 * rank, J, D, seed=31 + rank, prefix_range=(rank * per, (rank + 1) * per, 9))
+    kd = torch.from_numpy(keys.view(np.int64).copy()).cuda()
+    Cd = torch.from_numpy(C).cuda()
+    ref = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9)                    # gloo all-gathers (host staged)
+    drc = sharded.ShardedRaht(kd, 3 * J, prefix_bits=9, direct=True, force_collectives=True)
+    T0, Q0 = ref.forward(Cd), ref.forward_quant(Cd, 0.01)
+    for it in range(5):                                                    # both buffer parities, several times
+        assert torch.equal(drc.forward(Cd), T0), it
+        assert torch.equal(drc.forward_quant(Cd, 0.01), Q0), it
+    assert torch.equal(drc.inverse(T0), ref.inverse(T0))
+    assert torch.equal(drc.dequant_inverse(Q0, 0.01), ref.dequant_inverse(Q0, 0.01))
+    T64 = drc.forward(Cd.double())                                         # another (D, dtype): another exchange block
+    assert torch.equal(T64, ref.forward(Cd.double()))
+    chk = drc.check_against_unsharded(Cd, 0.01, keys_sorted=kd)
+    assert chk["ok"], chk
+    assert drc.exchange_status() == 0
+    drc.close()
+    dist.barrier()
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 5])
@@ -394,18 +322,7 @@ def test_direct_exchange_equals_the_collective(rt, world):
     ShardedRaht(direct=True): every rank writes its root slot into each peer's gather buffer (hipIpc-mapped fine-grained
     device memory) and raises a flag -- one launch per direction -- instead of all_gather_into_tensor. Bit-identical results;
     here the 'peers' are processes sharing this box's one GPU (IPC to the same device), on xGMI they are the other GPUs."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_direct_main, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=600) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=120)
-    for rank, msg in res:
-        assert msg == "ok", f"rank {rank}:\n{msg}"
+    run_ranks(_direct_main, world, report_timeout=600, join_timeout=120)
 
 
 def test_bench_direct_exchange(rt):

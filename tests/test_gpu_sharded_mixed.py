@@ -5,16 +5,12 @@ Bars, at steps 0.01, 1.0 and per-channel steps: check_mixed_against_unsharded (w
 kernels run on it) returns exact equality on all 59 columns; the xyz integers are the float64 oracle's on the whole scene
 except at near-ties (the oracle's T / step within 1e-9 relative of k + 0.5); columns [3, 59) are bit-identical to the same
 ShardedRaht built without n_wide."""
-import os
-import socket
-import sys
-import traceback
-
 import numpy as np
 import pytest
 
+from tests.rank_procs import run_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NW, D = 3, 59
 PER_CHANNEL = [0.01, 0.02, 0.05] + [0.002 * (1 + c % 9) for c in range(D - 3)]
 
@@ -27,14 +23,6 @@ def rt():
     from raht_3dgs_codec_amd import _lib
     _lib.lib()
     return R
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _check_rank(rank, world, J, n, seed, force, direct):
@@ -88,37 +76,18 @@ def _check_rank(rank, world, J, n, seed, force, direct):
     return ties
 
 
-def _gloo_main(rank, world, port, direct, q):
-    try:
-        sys.path.insert(0, ROOT)
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        import torch
-        import torch.distributed as dist
-        torch.cuda.set_device(0)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        ties = _check_rank(rank, world, 10, 240000, 61, direct, direct)
-        dist.barrier()
-        dist.destroy_process_group()
-        q.put((rank, f"ok ties={ties}"))
-    except Exception:
-        q.put((rank, traceback.format_exc()))
+def _gloo_main(rank, world, direct):
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    ties = _check_rank(rank, world, 10, 240000, 61, direct, direct)
+    dist.barrier()
+    return ties
 
 
-def _spawn(target, world, *args):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=target, args=(r, world, port) + args + (q,)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=600) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=120)
-    for rank, msg in sorted(res):
-        assert msg.startswith("ok"), f"rank {rank}:\n{msg}"
-    print("near-tie differences on the xyz columns per rank:", [m for _, m in sorted(res)])
+def _spawn(target, world, *args, backend="gloo"):
+    ties = run_ranks(target, world, *args, backend=backend, report_timeout=600, join_timeout=120)
+    print("near-tie differences on the xyz columns per rank:", ties)
 
 
 @pytest.mark.parametrize("world", [4, 5])
@@ -130,36 +99,30 @@ def test_mixed_sharded_direct_exchange(rt):
     _spawn(_gloo_main, 3, True)
 
 
-def _rccl_main(rank, world, port, q):
-    try:
-        sys.path.insert(0, ROOT)
-        import torch
-        import torch.distributed as dist
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        from raht_3dgs_codec_amd import sharded
-        ties = _check_rank(0, 1, 11, 300000, 67, True, False)
-        # the mixed step's collective time covers both gathers of a direction
-        from raht_3dgs_codec_amd import synth
-        _, keys, C = synth.scene(100000, 11, D, seed=5)
-        kd = torch.from_numpy(keys.view(np.int64).copy()).cuda()
-        sh = sharded.ShardedRaht(kd, 33, prefix_bits=9, force_collectives=True, n_wide=NW)
-        Cd = torch.from_numpy(C).cuda()
+def _rccl_main(rank, world):
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    from raht_3dgs_codec_amd import sharded
+    ties = _check_rank(0, 1, 11, 300000, 67, True, False)
+    # the mixed step's collective time covers both gathers of a direction
+    from raht_3dgs_codec_amd import synth
+    _, keys, C = synth.scene(100000, 11, D, seed=5)
+    kd = torch.from_numpy(keys.view(np.int64).copy()).cuda()
+    sh = sharded.ShardedRaht(kd, 33, prefix_bits=9, force_collectives=True, n_wide=NW)
+    Cd = torch.from_numpy(C).cuda()
+    sh.step(Cd, 0.01)
+    sh.time_collectives(True)
+    for _ in range(3):
         sh.step(Cd, 0.01)
-        sh.time_collectives(True)
-        for _ in range(3):
-            sh.step(Cd, 0.01)
-        assert len(sh._ev["fwd"]) == 3 and len(sh._ev["inv"]) == 3
-        f, i = sh.collective_ms()
-        assert f > 0 and i > 0
-        t = torch.ones(4, device="cuda")
-        dist.all_reduce(t); dist.barrier()
-        torch.cuda.synchronize()
-        dist.destroy_process_group()
-        q.put((0, f"ok ties={ties}"))
-    except Exception:
-        q.put((0, traceback.format_exc()))
+    assert len(sh._ev["fwd"]) == 3 and len(sh._ev["inv"]) == 3
+    f, i = sh.collective_ms()
+    assert f > 0 and i > 0
+    t = torch.ones(4, device="cuda")
+    dist.all_reduce(t); dist.barrier()
+    torch.cuda.synchronize()
+    return ties
 
 
 def test_mixed_sharded_one_rank_rccl_group(rt):
-    _spawn(_rccl_main, 1)
+    _spawn(_rccl_main, 1, backend="nccl")
