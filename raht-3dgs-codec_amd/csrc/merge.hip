@@ -10,6 +10,7 @@
 // flight (most voxels hold one Gaussian). Members are accumulated in index order with explicit
 // fmaf, so results are bit-reproducible (oracle: orc_merge_clusters).
 #include "raht_common.h"
+#include "raht_device.h"
 
 #include <algorithm>
 
@@ -35,12 +36,14 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs A)
         // this lane's column: which input array, row stride and offset inside the row
         const int col = c0 + lane;
         const bool act = col < ncol;
-        const float *src; float *dst; int stride, off; int kind;   // kind 0 weighted mean, 1 quat, 2 opacity sum, 3 colour
-        if (col < 3) { src = A.means; dst = A.m_means; stride = 3; off = col; kind = 0; }
-        else if (col < 7) { src = A.quats; dst = A.m_quats; stride = 4; off = col - 3; kind = 1; }
-        else if (col < 10) { src = A.scales; dst = A.m_scales; stride = 3; off = col - 7; kind = 0; }
-        else if (col == 10) { src = A.opacities; dst = A.m_opacities; stride = 1; off = 0; kind = 2; }
-        else { src = A.colors; dst = A.m_colors; stride = A.color_dim; off = act ? col - 11 : 0; kind = 3; }
+        const float *src; float *dst; int stride, off;
+        if (col < 3) { src = A.means; dst = A.m_means; stride = 3; off = col; }
+        else if (col < 7) { src = A.quats; dst = A.m_quats; stride = 4; off = col - 3; }
+        else if (col < 10) { src = A.scales; dst = A.m_scales; stride = 3; off = col - 7; }
+        else if (col == 10) { src = A.opacities; dst = A.m_opacities; stride = 1; off = 0; }
+        else { src = A.colors; dst = A.m_colors; stride = A.color_dim; off = act ? col - 11 : 0; }
+        const MergeKind kind = merge_kind(col);
+        const bool opacity = kind == MERGE_OPACITY;                 // summed unweighted; every other column is a weighted sum
 
         for (int64_t v0 = wave * 16; v0 < A.num_clusters; v0 += nwaves * 16) {
             const int64_t vi = v0 + lane;
@@ -68,34 +71,21 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs A)
                     float acc = 0.0f, tw = 0.0f;
                     if (e[u] > s[u]) {                                       // merge_cluster.cu:38-63
                         tw = wfirst[u];
-                        acc = (kind == 2) ? xfirst[u] : __fmaf_rn(xfirst[u], wfirst[u], 0.0f);
+                        acc = opacity ? xfirst[u] : __fmaf_rn(xfirst[u], wfirst[u], 0.0f);
                         for (int i = s[u] + 1; i < e[u]; ++i) {
                             const int idx = A.cluster_indices[i];
                             const float w = A.weight_by_opacity ? A.opacities[idx] : 1.0f;
                             tw += w;
                             const float x = act ? src[(int64_t)idx * stride + off] : 0.0f;
-                            acc = (kind == 2) ? acc + x : __fmaf_rn(x, w, acc);
+                            acc = opacity ? acc + x : __fmaf_rn(x, w, acc);
                         }
                     }
                     // quaternion norm: lanes 3..6 of the first column chunk (merge_cluster.cu:76-78)
                     float n2 = 0.0f;
-                    if (c0 == 0) {
-                        const float qx = __shfl(acc, 3, 64), qy = __shfl(acc, 4, 64), qz = __shfl(acc, 5, 64), qw = __shfl(acc, 6, 64);
-                        n2 = qx * qx;
-                        n2 = __fmaf_rn(qy, qy, n2);
-                        n2 = __fmaf_rn(qz, qz, n2);
-                        n2 = __fmaf_rn(qw, qw, n2);
-                    }
+                    if (c0 == 0) n2 = merge_quat_norm2(__shfl(acc, 3, 64), __shfl(acc, 4, 64), __shfl(acc, 5, 64), __shfl(acc, 6, 64));
                     if (!act) continue;
-                    float r;
-                    if (e[u] <= s[u]) r = 0.0f;                              // empty cluster: outputs stay zero (wrapper :66-70)
-                    else if (kind == 0) r = __fdiv_rn(acc, tw == 0.0f ? 1.0f : tw);      // :66-73, :91-93
-                    else if (kind == 1) {                                    // :76-89
-                        const float nrm = __fsqrt_rn(n2);
-                        r = (nrm > 0.0f) ? __fdiv_rn(acc, nrm) : (off == 3 ? 1.0f : 0.0f);
-                    } else if (kind == 2) r = fminf(acc, 1.0f);              // :96
-                    else r = (tw > 0.0f) ? __fdiv_rn(acc, tw) : 0.0f;        // :98-110
-                    dst[v * stride + off] = r;
+                    // empty cluster: outputs stay zero (wrapper :66-70)
+                    dst[v * stride + off] = (e[u] <= s[u]) ? 0.0f : merge_finish(kind, acc, tw, n2);
                 }
             }
         }

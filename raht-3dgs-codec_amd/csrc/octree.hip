@@ -15,6 +15,7 @@
 //   symbols  256-bin histogram (per-wave LDS bins, one global atomic per non-empty bin per workgroup), the rank table on the
 //            device (descending count, ties by ascending byte), byte -> int32 rank for the segmented RLGR coder; and back.
 #include "raht_common.h"
+#include "raht_device.h"
 
 #include <cstring>
 
@@ -371,25 +372,14 @@ __global__ __launch_bounds__(OCT_THREADS) void oct_bytes_kernel(const int32_t *_
 }
 
 // ---- keys -> coordinates -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t oct_compact3(uint64_t v)
-{
-    v &= 0x1249249249249249ull;
-    v = (v | (v >> 2)) & 0x10c30c30c30c30c3ull;
-    v = (v | (v >> 4)) & 0x100f00f00f00f00full;
-    v = (v | (v >> 8)) & 0x001f0000ff0000ffull;
-    v = (v | (v >> 16)) & 0x001f00000000ffffull;
-    v = (v | (v >> 32)) & 0x1fffffull;
-    return v;
-}
-
 __global__ __launch_bounds__(OCT_THREADS) void oct_demorton_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t mask,
                                                                    int64_t *__restrict__ V)
 {
     for (int64_t i = (int64_t)blockIdx.x * OCT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OCT_THREADS) {
         const uint64_t k = keys[i] & mask;
-        V[3 * i + 0] = (int64_t)oct_compact3(k >> 2);
-        V[3 * i + 1] = (int64_t)oct_compact3(k >> 1);
-        V[3 * i + 2] = (int64_t)oct_compact3(k);
+        V[3 * i + 0] = (int64_t)vx_compact3(k >> 2);
+        V[3 * i + 1] = (int64_t)vx_compact3(k >> 1);
+        V[3 * i + 2] = (int64_t)vx_compact3(k);
     }
 }
 

@@ -121,6 +121,30 @@ __device__ __forceinline__ uint64_t vx_spread3(uint64_t v)
     v = (v | (v << 2)) & 0x1249249249249249ull;
     return v;
 }
+// ... and its inverse: every third bit of a key (voxelize.hip, octree.hip)
+__device__ __forceinline__ uint64_t vx_compact3(uint64_t v)
+{
+    v &= 0x1249249249249249ull;
+    v = (v | (v >> 2)) & 0x10c30c30c30c30c3ull;
+    v = (v | (v >> 4)) & 0x100f00f00f00f00full;
+    v = (v | (v >> 8)) & 0x001f0000ff0000ffull;
+    v = (v | (v >> 16)) & 0x001f00000000ffffull;
+    v = (v | (v >> 32)) & 0x1fffffull;
+    return v;
+}
+// integer voxel coordinates from a voxel key (voxelize_pc.py:152,155); 21 bits each
+struct VoxCoords { uint32_t x, y, z; };
+__device__ __forceinline__ VoxCoords vox_coords(uint64_t key)
+{
+    return {(uint32_t)vx_compact3(key >> 2), (uint32_t)vx_compact3(key >> 1), (uint32_t)vx_compact3(key)};
+}
+// THE position residual of column c < 3 of a point (voxelize_pc.py:92, 103, 110-111): V0 - voxel_size * floor(V0 / voxel_size) with
+// an IEEE divide as torch on the CPU, and product and difference rounded SEPARATELY (two torch ops): no fma
+__device__ __forceinline__ float vox_pos_residual(float x, int c, float m0, float m1, float m2, float vs)
+{
+    const float v0 = x - (c == 0 ? m0 : (c == 1 ? m1 : m2));
+    return __fsub_rn(v0, __fmul_rn(vs, floorf(__fdiv_rn(v0, vs))));
+}
 // xyz of one point: 12 bytes at the start of a (3 + d)-float row, as ONE global_load_dwordx3 (element alignment)
 struct __attribute__((packed, aligned(4))) Xyz { float x, y, z; };
 // the cloud and its grid (voxelize_pc.py:87-98)
@@ -142,6 +166,49 @@ __device__ __forceinline__ uint64_t vox_key(const Xyz &p, const VoxGrid &g)
         q[a] = t < 0 ? 0 : (t > hi ? hi : t);
     }
     return vx_spread3((uint64_t)q[2]) | (vx_spread3((uint64_t)q[1]) << 1) | (vx_spread3((uint64_t)q[0]) << 2);
+}
+
+// ---- the Gaussian merge's finish (merge.hip and the voxelizer's merging pass, voxelize.hip; reference cuda/merge_cluster.cu) --
+// columns of a whole Gaussian: [mean(3) | quat(4) | scale(3) | opacity(1) | colour(cd)]
+// squared norm of the accumulated quaternion (merge_cluster.cu:76-78), in this order
+__device__ __forceinline__ float merge_quat_norm2(float qx, float qy, float qz, float qw)
+{
+    float n2 = qx * qx;
+    n2 = __fmaf_rn(qy, qy, n2);
+    n2 = __fmaf_rn(qz, qz, n2);
+    n2 = __fmaf_rn(qw, qw, n2);
+    return n2;
+}
+// how a column is finished: weighted mean (means, scales), quaternion component (w: the last one), opacity sum, colour
+enum MergeKind { MERGE_MEAN, MERGE_QUAT, MERGE_QUAT_W, MERGE_OPACITY, MERGE_COLOUR };
+__device__ __forceinline__ MergeKind merge_kind(int c)
+{
+    if (c < 3 || (c >= 7 && c < 10)) return MERGE_MEAN;
+    if (c < 7) return c == 6 ? MERGE_QUAT_W : MERGE_QUAT;
+    return c == 10 ? MERGE_OPACITY : MERGE_COLOUR;
+}
+// merged value of a column of a cluster with at least one member from its accumulator, the total weight and the quaternion's n2;
+// the column's kind as four flags (tested in this order)
+__device__ __forceinline__ float merge_finish(bool mean, bool quat, bool quat_w, bool opacity, float acc, float tw, float n2)
+{
+    if (mean) return __fdiv_rn(acc, tw == 0.0f ? 1.0f : tw);                              // :66-73, :91-93
+    if (quat) {                                                                           // :76-89 (no norm: identity)
+        // sqrtf: the correctly rounded root (hipcc's default, -fhip-fp32-correctly-rounded-divide-sqrt), which the oracle's sqrtf and
+        // the pinned bits are; __fsqrt_rn is the native 1-ulp root on this target
+        const float nrm = sqrtf(n2);
+        return (nrm > 0.0f) ? __fdiv_rn(acc, nrm) : (quat_w ? 1.0f : 0.0f);
+    }
+    if (opacity) return fminf(acc, 1.0f);                                                 // :96
+    return (tw > 0.0f) ? __fdiv_rn(acc, tw) : 0.0f;                                       // :98-110
+}
+// ... by a kind found once (merge_kernel: a lane keeps its column) or by column index (the voxelizer's chunks)
+__device__ __forceinline__ float merge_finish(MergeKind k, float acc, float tw, float n2)
+{
+    return merge_finish(k == MERGE_MEAN, k == MERGE_QUAT || k == MERGE_QUAT_W, k == MERGE_QUAT_W, k == MERGE_OPACITY, acc, tw, n2);
+}
+__device__ __forceinline__ float merge_finish(int c, float acc, float tw, float n2)
+{
+    return merge_finish(c < 3 || (c >= 7 && c < 10), c < 7, c == 6, c == 10, acc, tw, n2);
 }
 
 // StepTable from the caller's steps (host)

@@ -57,10 +57,15 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _call(fn, device, *args):
-    """one call through the C ABI on ``device``, on its current stream (every entry point's last argument)"""
+def _call(fn, device, *args, after=()):
+    """one call through the C ABI on ``device``, on its current stream (every entry point's last argument but for ``after``)"""
     with torch.cuda.device(device):
-        check(fn(*args, _stream()))
+        check(fn(*args, _stream(), *after))
+
+
+def _host_floats(v):
+    """host floats from a tensor (which comes to the host once), list or tuple: a bounding box corner as the caller gives it"""
+    return [float(x) for x in (v.detach().cpu().reshape(-1).tolist() if isinstance(v, torch.Tensor) else v)]
 
 
 def _rows(X, dtype, name):
@@ -131,10 +136,7 @@ class RahtPlan:
         if V.dtype not in _VDT:
             V = V.to(torch.float64)
         V = V.contiguous()
-        if isinstance(minV, torch.Tensor):
-            mv = [float(x) for x in minV.detach().cpu().reshape(-1).tolist()]
-        else:
-            mv = [float(x) for x in minV]
+        mv = _host_floats(minV)
         if len(mv) != 3:
             raise ValueError("minV must have 3 entries")
         arr = (C.c_double * 3)(*mv)
@@ -942,9 +944,7 @@ def voxel_keys(PC, vmin, width, J):
         PC = PC.to(torch.float32).contiguous()
     out = torch.empty(PC.shape[0], dtype=torch.int64, device=PC.device)
     vm = (C.c_float * 3)(*[float(x) for x in vmin])
-    with torch.cuda.device(PC.device):
-        check(_lib.lib().raht_voxel_keys(C.c_void_p(PC.data_ptr()), PC.stride(0), PC.shape[0], vm, float(width), int(J),
-                                         C.c_void_p(out.data_ptr()), _stream()))
+    _call(_lib.lib().raht_voxel_keys, PC.device, _p(PC), PC.stride(0), PC.shape[0], vm, float(width), int(J), _p(out))
     return out
 
 
@@ -955,9 +955,7 @@ def sort_keys(keys, nbits=64):
     k = keys.contiguous()
     ko = torch.empty_like(k)
     idx = torch.empty(k.shape[0], dtype=torch.int64, device=k.device)
-    with torch.cuda.device(k.device):
-        check(_lib.lib().raht_sort_keys(C.c_void_p(k.data_ptr()), k.shape[0], int(nbits), C.c_void_p(ko.data_ptr()),
-                                        C.c_void_p(idx.data_ptr()), _stream()))
+    _call(_lib.lib().raht_sort_keys, k.device, _p(k), k.shape[0], int(nbits), _p(ko), _p(idx))
     return ko, idx
 
 
@@ -976,6 +974,34 @@ def _vmin_tensor(vmin, dev):
     return t.clone()
 
 
+class _Voxelizer:
+    """THE call path of voxelize_pc_batched / voxelize_merge / voxelize_plan. Construction prepares the cloud (on ``device``, float32,
+    contiguous) and allocates what all three hand to the library: ``keys``, ``vidx`` (N int64 each) and ``rows`` (N x ld float32);
+    ``run`` parses vmin, makes the call -- fn(cloud, ld, N, *head, vmin, width, J, *outs, n_vox, vmin_out, width_out,
+    voxel_size_out, stream, *after), every wrapper spelling out its own ``head`` and ``outs`` in the order of its C signature
+    -- and returns what the three info dictionaries share (vmin as a tuple)."""
+
+    def __init__(self, PC, device, name):
+        PC = PC.to(device)
+        _need_cuda(PC, name)
+        self.PC = PC.to(torch.float32).contiguous()
+        self.N, self.ld = self.PC.shape
+        self.dev = self.PC.device
+        self.keys, self.vidx, self.rows = self.empty(), self.empty(), self.empty(self.ld, torch.float32)
+
+    def empty(self, cols=None, dtype=torch.int64):
+        return torch.empty(self.N if cols is None else (self.N, cols), dtype=dtype, device=self.dev)
+
+    def run(self, fn, head, vmin, width, J, outs, after=()):
+        nvox = C.c_int64()
+        vmin_out = (C.c_float * 3)()
+        w_out, vs_out = C.c_double(), C.c_double()
+        vm = None if vmin is None else (C.c_float * 3)(*_host_floats(vmin))
+        _call(fn, self.dev, _p(self.PC), self.ld, self.N, *head, vm, -1.0 if width is None else float(width), int(J),
+              *[_p(t) for t in outs], C.byref(nvox), vmin_out, C.byref(w_out), C.byref(vs_out), after=after)
+        return {"Nvox": nvox.value, "voxel_size": vs_out.value, "vmin": tuple(vmin_out), "width": w_out.value, "N": self.N}
+
+
 @torch.no_grad()
 def voxelize_pc_batched(PC, vmin=None, width=None, J=10, device="cuda", residuals=True, sorted_points=True):
     """Drop-in for reference python/voxelize_pc.py:62-172.
@@ -983,43 +1009,19 @@ def voxelize_pc_batched(PC, vmin=None, width=None, J=10, device="cuda", residual
     Returns (PCvox, PCsorted, voxel_indices, DeltaPC, info) like the reference. PCvox,
     voxel_indices, info['sort_idx'] and the sorted Morton keys (info['keys_sorted'], extra) come
     from the HIP voxelizer; PCsorted / DeltaPC are its secondary outputs, produced by the same call (``raht_voxelize_all``:
-    the pass that forms the voxel means writes them too; ``residuals=False`` skips DeltaPC; ``sorted_points=False`` skips
-    PCsorted and returns None in its place; the codec path only consumes PCvox).
+    the pass that forms the voxel means has every point's row in registers anyway and writes them too -- voxelize_pc.py:103-111,
+    147-156; raht_voxelize + raht_voxelize_residuals give the same bits; ``residuals=False`` skips DeltaPC;
+    ``sorted_points=False`` skips PCsorted and returns None in its place; the codec path only consumes PCvox).
     """
-    PC = PC.to(device)
-    _need_cuda(PC, "PC")
-    PC = PC.to(torch.float32).contiguous()
-    N, ld = PC.shape
-    d = ld - 3
-    dev = PC.device
-    keys = torch.empty(N, dtype=torch.int64, device=dev)
-    idx = torch.empty(N, dtype=torch.int64, device=dev)
-    vidx = torch.empty(N, dtype=torch.int64, device=dev)
-    pcv = torch.empty((N, ld), dtype=torch.float32, device=dev)
-    nvox = C.c_int64()
-    vmin_out = (C.c_float * 3)()
-    w_out, vs_out = C.c_double(), C.c_double()
-    vm = None
-    if vmin is not None:
-        vm = (C.c_float * 3)(*[float(x) for x in (vmin.detach().cpu().tolist() if isinstance(vmin, torch.Tensor) else vmin)])
-    # the secondary outputs (voxelize_pc.py:103-111, 147-156) come out of the same call: the pass that forms the voxel means
-    # has every point's row in registers anyway (raht_voxelize_all; raht_voxelize + raht_voxelize_residuals give the same bits)
-    PCsorted = torch.empty((N, ld), dtype=torch.float32, device=dev) if sorted_points else None
-    DeltaPC = torch.empty((N, ld), dtype=torch.float32, device=dev) if residuals else None
-    with torch.cuda.device(dev):
-        check(_lib.lib().raht_voxelize_all(C.c_void_p(PC.data_ptr()), ld, N, d, vm, -1.0 if width is None else float(width),
-                                           int(J), C.c_void_p(keys.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                           C.c_void_p(vidx.data_ptr()), C.c_void_p(pcv.data_ptr()), None,
-                                           C.c_void_p(PCsorted.data_ptr()) if PCsorted is not None else None,
-                                           C.c_void_p(DeltaPC.data_ptr()) if DeltaPC is not None else None, C.byref(nvox),
-                                           vmin_out, C.byref(w_out), C.byref(vs_out), _stream()))
-    nv = nvox.value
-    voxel_indices = vidx[:nv]
-    PCvox = pcv[:nv]
-    vmin_t = _vmin_tensor(tuple(vmin_out), dev)
-    info = {"Nvox": nv, "voxel_size": vs_out.value, "vmin": vmin_t, "width": w_out.value, "N": N,
-            "sort_idx": idx, "keys_sorted": keys}
-    return PCvox, PCsorted, voxel_indices, DeltaPC, info
+    v = _Voxelizer(PC, device, "PC")
+    idx = v.empty()
+    PCsorted = v.empty(v.ld, torch.float32) if sorted_points else None
+    DeltaPC = v.empty(v.ld, torch.float32) if residuals else None
+    info = v.run(_lib.lib().raht_voxelize_all, (v.ld - 3,), vmin, width, J,
+                 (v.keys, idx, v.vidx, v.rows, None, PCsorted, DeltaPC))               # (None: no Vvox)
+    nv = info["Nvox"]
+    info.update(vmin=_vmin_tensor(info["vmin"], v.dev), sort_idx=idx, keys_sorted=v.keys)
+    return v.rows[:nv], PCsorted, v.vidx[:nv], DeltaPC, info
 
 
 @torch.no_grad()
@@ -1029,33 +1031,17 @@ def voxelize_merge(G, vmin=None, width=None, J=10, device="cuda", weight_by_opac
     cuda/merge_cluster.cu:2-111), bit-identical to ``voxelize_pc_batched`` followed by ``merge_gaussian_clusters_with_indices``.
     Returns (Gvox (Nvox, 11 + cd): integer voxel coordinates as floats + merged attributes, info: Nvox, voxel_size, vmin, width,
     N, sort_idx, keys_sorted, voxel_indices, merged_means)."""
-    G = G.to(device)
-    _need_cuda(G, "G")
-    G = G.to(torch.float32).contiguous()
-    N, ld = G.shape
-    if ld < 11:
+    v = _Voxelizer(G, device, "G")
+    if v.ld < 11:
         raise ValueError("voxelize_merge: rows are [xyz | quat(4) | scale(3) | opacity | colours]: at least 11 columns")
-    dev = G.device
-    keys = torch.empty(N, dtype=torch.int64, device=dev)
-    idx = torch.empty(N, dtype=torch.int64, device=dev)
-    vidx = torch.empty(N, dtype=torch.int64, device=dev)
-    gv = torch.empty((N, ld), dtype=torch.float32, device=dev)
-    mm = torch.empty((N, 3), dtype=torch.float32, device=dev) if want_means else None
-    nvox = C.c_int64()
-    vmin_out = (C.c_float * 3)()
-    w_out, vs_out = C.c_double(), C.c_double()
-    vm = None
-    if vmin is not None:
-        vm = (C.c_float * 3)(*[float(x) for x in (vmin.detach().cpu().tolist() if isinstance(vmin, torch.Tensor) else vmin)])
-    with torch.cuda.device(dev):
-        check(_lib.lib().raht_voxelize_merge(C.c_void_p(G.data_ptr()), ld, N, ld - 11, 1 if weight_by_opacity else 0, vm,
-                                             -1.0 if width is None else float(width), int(J), C.c_void_p(keys.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                             C.c_void_p(vidx.data_ptr()), C.c_void_p(gv.data_ptr()), C.c_void_p(mm.data_ptr()) if mm is not None else None,
-                                             C.byref(nvox), vmin_out, C.byref(w_out), C.byref(vs_out), _stream()))
-    nv = nvox.value
-    info = {"Nvox": nv, "voxel_size": vs_out.value, "vmin": _vmin_tensor(tuple(vmin_out), dev), "width": w_out.value, "N": N,
-            "sort_idx": idx, "keys_sorted": keys, "voxel_indices": vidx[:nv], "merged_means": None if mm is None else mm[:nv]}
-    return gv[:nv], info
+    idx = v.empty()
+    mm = v.empty(3, torch.float32) if want_means else None
+    info = v.run(_lib.lib().raht_voxelize_merge, (v.ld - 11, 1 if weight_by_opacity else 0), vmin, width, J,
+                 (v.keys, idx, v.vidx, v.rows, mm))
+    nv = info["Nvox"]
+    info.update(vmin=_vmin_tensor(info["vmin"], v.dev), sort_idx=idx, keys_sorted=v.keys, voxel_indices=v.vidx[:nv],
+                merged_means=None if mm is None else mm[:nv])
+    return v.rows[:nv], info
 
 
 @torch.no_grad()
@@ -1066,29 +1052,12 @@ def voxelize_plan(PC, vmin=None, width=None, J=10, device="cuda"):
     No key recomputation, no key copy (the plan borrows the key tensor and keeps it alive), one plan build per frame, ONE call
     through the C ABI (raht_voxelize_plan). PCvox[:, 3:] is the attribute matrix in the plan's row order. info: Nvox,
     voxel_size, vmin (HOST tensor), width, N, voxel_keys, voxel_indices."""
-    PC = PC.to(device)
-    _need_cuda(PC, "PC")
-    PC = PC.to(torch.float32).contiguous()
-    N, ld = PC.shape
-    dev = PC.device
-    vkeys = torch.empty(N, dtype=torch.int64, device=dev)
-    vidx = torch.empty(N, dtype=torch.int64, device=dev)
-    pcv = torch.empty((N, ld), dtype=torch.float32, device=dev)
-    nvox = C.c_int64()
-    vmin_out = (C.c_float * 3)()
-    w_out, vs_out = C.c_double(), C.c_double()
-    vm = None
-    if vmin is not None:
-        vm = (C.c_float * 3)(*[float(x) for x in (vmin.detach().cpu().tolist() if isinstance(vmin, torch.Tensor) else vmin)])
+    v = _Voxelizer(PC, device, "PC")
     h = C.c_void_p()
-    with torch.cuda.device(dev):
-        check(_lib.lib().raht_voxelize_plan(C.c_void_p(PC.data_ptr()), ld, N, ld - 3, vm, -1.0 if width is None else float(width),
-                                            int(J), C.c_void_p(vkeys.data_ptr()), C.c_void_p(vidx.data_ptr()), C.c_void_p(pcv.data_ptr()),
-                                            C.byref(nvox), vmin_out, C.byref(w_out), C.byref(vs_out), _stream(), C.byref(h)))
-    nv = nvox.value
-    plan = RahtPlan(h, dev)
-    vkeys = vkeys[:nv]
+    info = v.run(_lib.lib().raht_voxelize_plan, (v.ld - 3,), vmin, width, J, (v.keys, v.vidx, v.rows), after=(C.byref(h),))
+    nv = info["Nvox"]
+    plan = RahtPlan(h, v.dev)
+    vkeys = v.keys[:nv]                                   # (here: the key of every voxel)
     plan._keys_ref = vkeys                                # borrowed by the plan: alive as long as it is
-    info = {"Nvox": nv, "voxel_size": vs_out.value, "vmin": torch.tensor(list(vmin_out), dtype=torch.float32), "width": w_out.value,
-            "N": N, "voxel_keys": vkeys, "voxel_indices": vidx[:nv]}
-    return pcv[:nv], plan, info
+    info.update(vmin=torch.tensor(list(info["vmin"]), dtype=torch.float32), voxel_keys=vkeys, voxel_indices=v.vidx[:nv])
+    return v.rows[:nv], plan, info

@@ -1,7 +1,8 @@
 """The Gaussian merge kernels against what cuda/merge_cluster.cu computes, not against their own restatement.
 
-tests/test_gpu_merge.py pins both kernels (``merge_kernel``, csrc/merge.hip; ``voxel_merge_chunk_kernel``, csrc/voxelize.hip) bit
-for bit to the C restatement ``oracle.merge_clusters``, which shares their float32 operation order: that proves determinism.
+tests/test_gpu_merge.py pins both kernels (``merge_kernel``, csrc/merge.hip; ``raht::voxel_merge_chunk_kernel``, csrc/voxelize.hip;
+both finish a column with ``merge_finish``, csrc/raht_device.h) bit for bit to the C restatement ``oracle.merge_clusters``, which
+shares their float32 operation order: that proves determinism.
 Here they are compared with the independent float64 model of the reference kernel (tests/numpy_merge.py) within its error
 bars, at the shapes where the kernels' geometry changes (column chunks of 64 lanes in merge_kernel, 4-column chunks and 17 /
 33 / 65-column steps in the voxel kernel, 16 clusters per wave, the grid-stride loops past 524 288 clusters or voxels), and

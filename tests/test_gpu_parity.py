@@ -410,6 +410,153 @@ def test_voxelize_matches_oracle_bitwise(rt, oracle):
     assert np.array_equal(PCvox.cpu().numpy(), r["PCvox"])
 
 
+def _voxels_per_iteration(cols, cap=6):
+    """voxels a wave of the voxelizer's chunk kernels takes per iteration for rows of ``cols`` floats (csrc/voxelize.hip: 2^lg lanes
+    per row, at most 2^cap -- 64 in voxel_full_chunk_kernel, 16 in voxel_merge_chunk_kernel; rpi row groups; up to four voxels
+    per row group in flight, at most 32 per iteration)"""
+    lg = 0
+    while (1 << lg) < (cols + 3) // 4 and lg < cap:
+        lg += 1
+    rpi = 64 >> lg
+    return min(4, 32 // rpi) * rpi
+
+
+def _grid_cloud(rng, nvox, cols, J=5):
+    """nvox voxels of the 2^J grid over [0, 2^J)^3 (vmin 0, width 2^J: voxel size 1, points well inside their cells, so the voxel
+    count is exact by construction); the LAST voxel in Morton order and one interior voxel hold three points each, every other
+    voxel one; rows of ``cols`` floats in shuffled order. Returns (PC, rows of the interior voxel)."""
+    cells = rng.permutation(8 ** J)[:nvox]
+    xyz = np.stack([(cells >> (2 * J)) & (2 ** J - 1), (cells >> J) & (2 ** J - 1), cells & (2 ** J - 1)], axis=1)
+    key = np.zeros(nvox, np.int64)
+    for b in range(J):
+        for a in range(3):
+            key |= ((xyz[:, a] >> b) & 1) << (3 * b + 2 - a)
+    order = np.argsort(key)
+    multi = [order[-1], order[nvox // 2]] if nvox > 1 else [order[-1]]
+    pos = [xyz + 0.5] + [xyz[m: m + 1] + off for m in multi for off in (0.25, 0.75)]
+    P = np.concatenate(pos).astype(np.float32)
+    owner = np.concatenate([np.arange(nvox)] + [[m, m] for m in multi])
+    PC = np.concatenate([P, rng.standard_normal((P.shape[0], cols - 3)).astype(np.float32)], axis=1)
+    perm = rng.permutation(PC.shape[0])
+    return PC[perm], np.flatnonzero(owner[perm] == multi[-1])
+
+
+_WALK_COUNTS = {"vpi-1": lambda vpi: vpi - 1, "vpi": lambda vpi: vpi, "vpi+1": lambda vpi: vpi + 1, "2vpi+1": lambda vpi: 2 * vpi + 1,
+                # more voxels than the grid's waves take in one iteration (the grid has four waves per 64 points, and there are at
+                # least as many points as voxels: reachable only where a wave takes 8 voxels or fewer): a SECOND iteration of the walk
+                "16vpi+1": lambda vpi: 16 * vpi + 1}
+_WALK_COLS = [8, 12, 20, 36, 68, 132, 260]
+_WALK_CASES = [(c, k) for c in _WALK_COLS for k in _WALK_COUNTS if k != "16vpi+1" or _voxels_per_iteration(c) <= 8]
+
+
+def _check_voxelize_merge(PC, heavy, nvox, vmin, width, J):
+    """raht_voxelize_merge on the rows of PC as Gaussians against the voxelizer followed by the merge kernel, bit for bit; the
+    voxel of the points ``heavy`` has zero total weight"""
+    import torch
+    from raht_3dgs_codec_amd import merge, ops
+    N = PC.shape[0]
+    G = PC.copy()
+    G[:, 10] = np.abs(G[:, 10])
+    G[heavy, 10] = 0.0
+    Gd = _dev(G)
+    Gvox, minfo = ops.voxelize_merge(Gd, vmin, width, J)
+    PCvox, _, vidx, _, info = ops.voxelize_pc_batched(Gd[:, :3].contiguous(), vmin, width, J, residuals=False, sorted_points=False)
+    assert minfo["Nvox"] == info["Nvox"] == nvox and torch.equal(minfo["sort_idx"], info["sort_idx"]) and torch.equal(minfo["voxel_indices"], vidx)
+    ci = info["sort_idx"].int()
+    co = torch.cat([vidx, torch.tensor([N], dtype=torch.int64, device="cuda")]).int()
+    mm, mq, ms, mo, mc = merge.merge_gaussian_clusters_with_indices(*(Gd[:, a:b].contiguous() for a, b in ((0, 3), (3, 7), (7, 10))),
+                                                                    Gd[:, 10].contiguous(), Gd[:, 11:].contiguous(), ci, co, True)
+    assert torch.equal(Gvox[:, :3], PCvox[:, :3])                   # integer voxel coordinates
+    assert torch.equal(minfo["merged_means"], mm)
+    assert torch.equal(Gvox[:, 3:7], mq) and torch.equal(Gvox[:, 7:10], ms) and torch.equal(Gvox[:, 10], mo)
+    assert torch.equal(Gvox[:, 11:], mc)
+    k = int(np.flatnonzero(info["sort_idx"].cpu().numpy() == heavy[0])[0])
+    v = int(np.searchsorted(vidx.cpu().numpy(), k, side="right")) - 1
+    assert mq[v].tolist() == [0.0, 0.0, 0.0, 1.0] and float(mo[v]) == 0.0          # the weightless voxel: identity quaternion
+
+
+@pytest.mark.parametrize("cols,k", _WALK_CASES)
+def test_voxel_walk_boundaries(rt, oracle, cols, k):
+    """The chunk kernels' voxel walk (voxel_full_chunk_kernel, voxel_merge_chunk_kernel) at the smallest shapes where it can go
+    wrong: every lanes-per-row geometry (rows of 8 ... 260 floats: 32, 32, 32, 16, 8, 4, 4 voxels per iteration, the last with
+    more than 64 chunks per row: two passes) with voxel counts one short of an iteration, exactly one, one over, two iterations
+    and one voxel, and (narrow iterations) enough for a wave's second turn of the loop -- the last voxel and one interior voxel
+    with three members. All outputs against the oracle, and (rows that can be Gaussians: 12 columns and more)
+    raht_voxelize_merge against the voxelizer followed by the merge kernel, one multi-member voxel with zero total weight, bit for
+    bit: on the same cloud and, where the merge kernel's 16 lanes per row give it another count per iteration (68 columns and
+    more: 16), on the cloud of the same rule for ITS count."""
+    vpi = _voxels_per_iteration(cols)
+    nvox = _WALK_COUNTS[k](vpi)
+    J, vmin, width = 5, [0.0, 0.0, 0.0], 32.0
+    PC, heavy = _grid_cloud(np.random.default_rng(1000 * cols + nvox), nvox, cols, J)
+    assert PC.shape == (nvox + 4, cols) and heavy.shape == (3,)
+    PCvox, PCsorted, vidx, DeltaPC, info = rt.voxelize_pc_batched(_dev(PC), vmin, width, J, device="cuda")
+    r = oracle.voxelize(PC, J, vmin=np.asarray(vmin, np.float32), width=width)
+    pcs, dl = oracle.voxel_residuals(PC, r)
+    assert info["Nvox"] == r["Nvox"] == nvox
+    assert np.array_equal(info["sort_idx"].cpu().numpy(), r["sort_idx"]) and np.array_equal(vidx.cpu().numpy(), r["voxel_indices"])
+    np.testing.assert_array_equal(PCvox.cpu().numpy(), r["PCvox"])
+    np.testing.assert_array_equal(PCsorted.cpu().numpy(), pcs)
+    np.testing.assert_array_equal(DeltaPC.cpu().numpy(), dl)
+    if cols < 12:
+        return
+    _check_voxelize_merge(PC, heavy, nvox, vmin, width, J)
+    vpi_merge = _voxels_per_iteration(cols, cap=4)
+    if vpi_merge != vpi and k != "16vpi+1":
+        nvox = _WALK_COUNTS[k](vpi_merge)
+        PC, heavy = _grid_cloud(np.random.default_rng(2000 * cols + nvox), nvox, cols, J)
+        _check_voxelize_merge(PC, heavy, nvox, vmin, width, J)
+
+
+def test_voxelizer_wrappers_keep_their_results(rt):
+    """What the three voxelizer wrappers (one core in ops.py) hand out: the info dictionaries' keys, the types, dtypes, devices
+    and slice lengths of everything, voxelize_plan's HOST vmin and borrowed key tensor, merged_means only when asked for."""
+    import torch
+    from raht_3dgs_codec_amd import ops
+    rng = np.random.default_rng(3)
+    N, ld, J = 500, 14, 3
+    PC = np.concatenate([rng.random((N, 3)) * 4.0, np.abs(rng.standard_normal((N, ld - 3)))], axis=1).astype(np.float32)
+    PCd = _dev(PC)
+
+    def tensor(t, shape, dtype, device="cuda"):
+        assert isinstance(t, torch.Tensor) and tuple(t.shape) == shape and t.dtype == dtype and t.device.type == device, (t.shape, t.dtype, t.device)
+
+    def common(info, extra):
+        assert list(info) == ["Nvox", "voxel_size", "vmin", "width", "N"] + extra
+        assert type(info["Nvox"]) is int and type(info["N"]) is int and type(info["voxel_size"]) is float and type(info["width"]) is float
+        assert info["N"] == N and 1 < info["Nvox"] < N and info["voxel_size"] == info["width"] / 2 ** J
+        return info["Nvox"]
+
+    PCvox, PCsorted, vidx, DeltaPC, info = rt.voxelize_pc_batched(PCd, None, None, J)
+    nv = common(info, ["sort_idx", "keys_sorted"])
+    tensor(PCvox, (nv, ld), torch.float32); tensor(PCsorted, (N, ld), torch.float32); tensor(DeltaPC, (N, ld), torch.float32)
+    tensor(vidx, (nv,), torch.int64); tensor(info["sort_idx"], (N,), torch.int64); tensor(info["keys_sorted"], (N,), torch.int64)
+    tensor(info["vmin"], (3,), torch.float32)
+    assert info["vmin"].tolist() == PC[:, :3].min(axis=0).tolist()
+    # a given box as a tensor or a list; the vmin handed out is the caller's own copy
+    vm, w = info["vmin"], info["width"]
+    again = rt.voxelize_pc_batched(PCd, vm, w, J, residuals=False, sorted_points=False)
+    assert again[1] is None and again[3] is None and torch.equal(again[0], PCvox) and torch.equal(again[4]["vmin"], vm)
+    again[4]["vmin"].zero_()
+    assert torch.equal(rt.voxelize_pc_batched(PCd, vm.tolist(), w, J)[4]["vmin"], vm)
+
+    Gvox, minfo = ops.voxelize_merge(PCd, None, None, J)
+    assert common(minfo, ["sort_idx", "keys_sorted", "voxel_indices", "merged_means"]) == nv
+    tensor(Gvox, (nv, ld), torch.float32); tensor(minfo["merged_means"], (nv, 3), torch.float32); tensor(minfo["vmin"], (3,), torch.float32)
+    tensor(minfo["voxel_indices"], (nv,), torch.int64); tensor(minfo["sort_idx"], (N,), torch.int64); tensor(minfo["keys_sorted"], (N,), torch.int64)
+    Gvox2, minfo2 = ops.voxelize_merge(PCd, None, None, J, want_means=False)
+    assert minfo2["merged_means"] is None and list(minfo2) == list(minfo) and torch.equal(Gvox2, Gvox)
+    with pytest.raises(ValueError):
+        ops.voxelize_merge(PCd[:, :10], None, None, J)
+
+    PCvox3, plan, pinfo = rt.voxelize_plan(PCd, None, None, J)
+    assert common(pinfo, ["voxel_keys", "voxel_indices"]) == nv and plan.N == nv and plan.nbits == 3 * J
+    tensor(PCvox3, (nv, ld), torch.float32); tensor(pinfo["voxel_keys"], (nv,), torch.int64); tensor(pinfo["voxel_indices"], (nv,), torch.int64)
+    tensor(pinfo["vmin"], (3,), torch.float32, "cpu")
+    assert plan._keys_ref is pinfo["voxel_keys"] and torch.equal(pinfo["vmin"], vm.cpu()) and torch.equal(PCvox3, PCvox)
+    assert torch.equal(pinfo["voxel_keys"], info["keys_sorted"][vidx])
+
+
 def test_radix_sort_60bit_keys(rt):
     import torch
     rng = np.random.default_rng(11)
