@@ -861,6 +861,52 @@ int raht_predict(const uint64_t *keys_sorted, int64_t N, const uint64_t *ref_key
                  int64_t ld_ref, const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched,
                  raht_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Motion compensation (csrc/motion.hip): the predictor above follows a motion field, one integer vector per block, and a block
+ * search finds the field (python: ops.motion_search / ops.predict_mc, bitstream.encode_sequence_bytes(..., motion, block_log2,
+ * motion_weights)).
+ *
+ * Blocks. The frame has depth J and N strictly ascending keys k[0 .. N); block_log2 = m, 1 <= m <= J. The block of row i is
+ * k[i] >> 3 m. The occupied blocks, ascending, are n_blocks = n_(J - m) of the geometry header's level counts, and
+ * block_first[0 .. n_blocks] (DEVICE int64; the last entry N) is cell_first of raht_region_cells(keys, N, 3 J, top_level = 3 m,
+ * n_blocks, ...) (m = J: one block, block_first = {0, N}).
+ * Shifted key. Digits as raht_morton writes them (digit = z + 2 y + 4 x, the finest digit in bits 0-2). (x, y, z) = the voxel
+ * of k[i], v = (dx, dy, dz), sums in int64. If x + dx, y + dy or z + dz lies outside [0, 2^J), row i has NO MATCH under v;
+ * otherwise k' = the key of (x + dx, y + dy, z + dz). v points from the current voxel to the reference voxel: a cloud translated
+ * by t between the reference and the current frame has v = -t.
+ * Compensated prediction. P_v[i, :] is raht_predict's P evaluated for the key k' instead of k[i], with the same shift = 3 up: the
+ * run ref_key[r] >> shift == k' >> shift, the sequential float32 sum in row order, one IEEE division; 0 for an empty run and for
+ * a row with no match. With a motion field mv[n_blocks][3] (int8), row i uses v = mv[block(i)]; with mv = 0 this is raht_predict
+ * bit for bit.
+ * Cost of a candidate. weights w[D] (DEVICE float32, finite and >= 0: the caller's contract) and candidates cand[K][3] (DEVICE
+ * int32, 1 <= K <= 512). Row cost: c = 0.0f; for ch ascending with w[ch] != 0: t = fl(X[i, ch] - P_v[i, ch]); t = |t|;
+ * t = fl(w[ch] t); c = fl(c + t) -- the product is rounded before the sum, nothing is fused; columns of weight 0 are not read.
+ * q = (uint64) floorf(fminf(c, 1048576.0f) * 1024.0f): +inf and NaN take the cap 2^30 (fminf(NaN, x) = x), the product is exact.
+ * cost[b][k] = the sum of q over the rows of block b: an integer sum, independent of order and of how rows are split up.
+ * Selection. best_k[b] = the smallest k among those with the smallest cost[b][k]; best_cost[b] = that cost.
+ *   raht_motion_search : best_k (DEVICE int32[n_blocks]), best_cost (DEVICE uint64[n_blocks], may be NULL) and, when the caller
+ *                        passes one, the whole table cost_table (DEVICE uint64[n_blocks * K]; NULL: scratch of the library's pool).
+ *                        A memset of the table and two launches; enqueues only, never synchronises.
+ *   raht_predict_mc    : raht_predict under the field mv (DEVICE int8[3 * n_blocks]): Y = X - P (add = 0), X + P (add = 1) or P
+ *                        (X NULL); Y may be X; n_matched (DEVICE int64, may be NULL) = the rows with a non-empty run. One launch
+ *                        (and a memset when n_matched is given); enqueues only, never synchronises.
+ * RAHT_ERR_INVALID, with nothing enqueued: NULL required pointers, N or N_ref outside 1 .. 2^31 - 1, J outside 1 .. 21, block_log2
+ * outside 1 .. J, n_blocks outside 1 .. N, shift not one of 0, 3, 6, 9, D < 1, a row stride below D, K outside 1 .. 512, add not
+ * 0 or 1.
+ *
+ *   compensated frame : "RAHTM001" | int64 ref_back | int64 up | int64 block_log2 | int64 n_blocks | int8 mv[n_blocks][3] | zero
+ *                       bytes up to a multiple of 8 | a whole "RAHTF001" frame container whose attributes are the residual
+ *                       X - P_mv. Every int8 value is legal (a vector that leaves the cube predicts 0). n_blocks is the inner
+ *                       geometry header's n_(J - block_log2). The rules of a predicted frame hold: only inside a sequence
+ *                       container, never at index 0; the reconstruction is the inner frame's plus P_mv of the reference's. */
+int raht_motion_search(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                       const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref, const float *X,
+                       int64_t ldx, int D, const float *weights, const int32_t *cand, int K, int32_t *best_k, uint64_t *best_cost,
+                       uint64_t *cost_table, raht_stream_t stream);
+int raht_predict_mc(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                    const int8_t *mv, const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref,
+                    const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched, raht_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,7 @@ EXPORTS = [
     "raht_xchg_bytes", "raht_xchg_alloc", "raht_xchg_open", "raht_xchg_close", "raht_xchg_free", "raht_xchg_gather", "raht_xchg_buffer", "raht_xchg_status",
     "raht_octree_counts", "raht_octree_encode", "raht_octree_decode", "raht_octree_symbols", "raht_octree_bytes", "raht_demorton",
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
-    "raht_predict",
+    "raht_predict", "raht_motion_search", "raht_predict_mc",
 ]
 
 
@@ -197,6 +197,8 @@ def lib():
     L.raht_region_cells.argtypes = [vp, i64, i32, i32, i64, vp, vp, vp]
     L.raht_region_assemble.argtypes = [vp, i64, i64, vp, i64, i64, i32, C.POINTER(i64), i32, vp]
     L.raht_predict.argtypes = [vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp]
+    L.raht_motion_search.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.raht_predict_mc.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp]
     _lib = L
     return L
 

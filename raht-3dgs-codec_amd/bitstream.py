@@ -20,6 +20,13 @@ the co-located voxel). ``decode_frame_bytes`` / ``decode_region_bytes`` refuse t
     RAHTP001 | int64 ref_back (>= 1: the reference is ref_back frames earlier; this version writes 1) | int64 up (0 .. 3) |
     a whole RAHTF001 frame
 
+With ``motion`` > 0 the prediction may follow a MOTION FIELD: one integer vector per occupied block of
+``2^block_log2`` voxels a side, found by ``ops.motion_search`` against the reference's reconstruction; P is then
+``ops.predict_mc``. Such a frame is still a predicted frame (kind "P"); ``sequence_motion`` hands out its field.
+
+    RAHTM001 | int64 ref_back | int64 up | int64 block_log2 | int64 n_blocks | int8 mv[n_blocks][3] | zero bytes up to a
+    multiple of 8 | a whole RAHTF001 frame
+
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
 sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
@@ -37,6 +44,8 @@ MAGIC = b"RAHTF001"
 SEQ_MAGIC = b"RAHTS001"
 P_MAGIC = b"RAHTP001"
 P_HEAD = len(P_MAGIC) + 16                                     # what a predicted frame's wrapper adds to its inner frame
+M_MAGIC = b"RAHTM001"
+M_HEAD = len(M_MAGIC) + 32                                     # ... and a motion-compensated frame's, before its motion field
 MIN_FRAME_BYTES = len(MAGIC) + 40 + 8 * 5 + 2 * (8 + 48)      # header, one step + box, two sections of 48 bytes at least
 
 
@@ -444,26 +453,75 @@ def parse_pframe(fb):
     return ref_back, up, memoryview(fb)[P_HEAD:]
 
 
+def _motion_field_bytes(n_blocks):
+    """the bytes of a motion field in its wrapper: three per block, zero-padded to a multiple of 8"""
+    return (3 * n_blocks + 7) // 8 * 8
+
+
+def _mframe_wrapper(up, block_log2, mv):
+    """the wrapper of a motion-compensated frame: everything before its inner frame (mv: (n_blocks, 3) int8 numpy)"""
+    field = np.ascontiguousarray(mv, np.int8).tobytes()
+    return (M_MAGIC + np.array([1, up, block_log2, len(field) // 3], np.int64).tobytes() + field
+            + bytes(_motion_field_bytes(len(field) // 3) - len(field)))
+
+
+def parse_mframe(fb):
+    """The wrapper of a motion-compensated frame, checked (pure host code) -> (ref_back, up, block_log2, mv (n_blocks, 3) int8 numpy,
+    the inner RAHTF001 container as a memoryview). ``ValueError`` for another magic, ``ref_back < 1``, ``up`` outside 0 .. 3,
+    ``block_log2`` outside 1 .. 21, a wrapper too short for its motion field plus a frame, padding that is not zero. Every int8
+    vector is legal. Whether ``block_log2`` and ``n_blocks`` go with the inner frame is for the sequence's checks (``_frame_head``)."""
+    if bytes(fb[:len(M_MAGIC)]) != M_MAGIC:
+        raise ValueError("not a RAHT motion-compensated frame wrapper")
+    if len(fb) < M_HEAD + MIN_FRAME_BYTES:
+        raise ValueError("motion-compensated frame: truncated wrapper")
+    ref_back, up, block_log2, n_blocks = [int(x) for x in np.frombuffer(fb, np.int64, 4, len(M_MAGIC))]
+    if ref_back < 1:
+        raise ValueError(f"motion-compensated frame: ref_back = {ref_back}, must be at least 1")
+    if not 0 <= up <= 3:
+        raise ValueError(f"motion-compensated frame: up = {up} outside 0 .. 3")
+    if not 1 <= block_log2 <= MAX_J:
+        raise ValueError(f"motion-compensated frame: block_log2 = {block_log2} outside 1 .. {MAX_J}")
+    if n_blocks < 1 or n_blocks >= 2 ** 31 or len(fb) < M_HEAD + _motion_field_bytes(n_blocks) + MIN_FRAME_BYTES:
+        raise ValueError(f"motion-compensated frame: too short for a motion field of {n_blocks} blocks and a frame")
+    field = np.frombuffer(fb, np.int8, _motion_field_bytes(n_blocks), M_HEAD)
+    if field[3 * n_blocks:].any():
+        raise ValueError("motion-compensated frame: the padding behind the motion field is not zero")
+    return ref_back, up, block_log2, field[:3 * n_blocks].reshape(n_blocks, 3), memoryview(fb)[M_HEAD + len(field):]
+
+
 def _frame_head(view, off, i, max_voxels):
     """frame i of a sequence from its headers alone -> dict: kind ("I" / "P"), ref (the frame it is predicted from, or None), up,
-    fb (its RAHTF001 container: the inner one of a predicted frame), h (``parse_frame`` of it), seg_len. ``ValueError`` naming i."""
+    motion (None, or (block_log2, mv) of a motion-compensated frame), fb (its RAHTF001 container: the inner one of a predicted
+    frame), h (``parse_frame`` of it), seg_len. ``ValueError`` naming i."""
     fb = view[off[i]: off[i + 1]]
-    kind, ref, up = "I", None, 0
+    kind, ref, up, motion = "I", None, 0, None
     try:
-        if bytes(fb[:len(P_MAGIC)]) == P_MAGIC:
+        magic = bytes(fb[:len(P_MAGIC)])
+        if magic in (P_MAGIC, M_MAGIC):
             kind = "P"
-            ref_back, up, fb = parse_pframe(fb)
+            if magic == M_MAGIC:
+                ref_back, up, block_log2, mv, fb = parse_mframe(fb)
+                motion = (block_log2, mv)
+            else:
+                ref_back, up, fb = parse_pframe(fb)
             if i == 0:
                 raise ValueError("a predicted frame cannot open a sequence")
             if ref_back > i:
                 raise ValueError(f"predicted frame: ref_back = {ref_back} reaches before frame 0")
             ref = i - ref_back
         h = parse_frame(fb, max_voxels)
+        if motion is not None:
+            if motion[0] > h["J"]:
+                raise ValueError(f"motion-compensated frame: block_log2 = {motion[0]} outside 1 .. J = {h['J']}")
+            go, gl = h["geometry"]
+            n_level = OctreeCoder.parse(fb[go: go + gl], max_voxels)["counts"][h["J"] - motion[0]]
+            if len(motion[1]) != n_level:
+                raise ValueError(f"motion-compensated frame: a motion field of {len(motion[1])} blocks, the geometry has {n_level}")
         ao, al = h["attributes"]
         S = SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[2]
     except ValueError as e:
         raise ValueError(f"sequence container: frame {i}: {e}") from None
-    return dict(kind=kind, ref=ref, up=up, fb=fb, h=h, seg_len=S)
+    return dict(kind=kind, ref=ref, up=up, motion=motion, fb=fb, h=h, seg_len=S)
 
 
 def _frame_heads(view, off, idx, max_voxels):
@@ -494,11 +552,19 @@ def sequence_kinds(blob, max_voxels=None, max_frames=None):
     return [heads[i]["kind"] for i in range(len(off) - 1)]
 
 
+def sequence_motion(blob, max_voxels=None, max_frames=None):
+    """-> per frame of a sequence container None, or (block_log2, mv (n_blocks, 3) int8 numpy) for a motion-compensated frame, from
+    the headers alone (pure host code), with the checks of ``sequence_kinds``."""
+    off = parse_sequence(blob, max_frames)
+    heads = _frame_heads(memoryview(blob), off, range(len(off) - 1), max_voxels)
+    return [heads[i]["motion"] for i in range(len(off) - 1)]
+
+
 SEQ_CHUNK = SegmentedCoder.BATCH_MAX                                     # frames whose transform and entropy stages share launches
 
 
 def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None, gop=1, up=0,
-                          inter="auto"):
+                          inter="auto", motion=0, block_log2=4, motion_weights=None):
     """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
     container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
     frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
@@ -514,14 +580,25 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     needs frame i - 1's reconstruction, which needs its integers -- so with ``gop`` > 1 the transform + quantization (and, where a
     frame is predicted from, the inverse) run frame by frame, for I and P frames alike; the entropy stage still goes through one
     set of launches per ``SEQ_CHUNK`` frames. With the default ``gop=1`` the result is byte for byte what it was without these
-    arguments."""
+    arguments.
+
+    ``motion`` = r > 0 (with ``gop`` > 1): motion compensation. For a candidate frame ``ops.motion_search`` finds, for
+    every occupied block of 2^``block_log2`` voxels a side (1 <= block_log2 <= J), the vector of [-r, r]^3 (r <= 3,
+    ``ops.motion_candidates``) under which frame i - 1's reconstruction predicts A best; the cost of a column is weighted by
+    ``motion_weights`` (D numbers >= 0; default 1 / step of the column as float32, so that cost counts quantization steps; 0 leaves
+    a column out). If every vector is zero the frame goes the way of ``motion=0``, byte for byte. Otherwise Rmc = A -
+    ``ops.predict_mc`` is a third candidate: ``inter="always"`` codes it as an RAHTM001 frame, ``inter="auto"`` codes the smallest of
+    bytes_A, bytes_R + 24 and bytes_Rmc + 40 + the field's bytes (3 per block, padded to 8), a tie going to the earlier of the
+    three. ``motion=0`` (the default) is byte for byte what it was without these arguments."""
     import torch
     dev = torch.device(device)
-    J, n_wide, gop, up = int(J), int(n_wide), int(gop), int(up)
+    J, n_wide, gop, up, motion, block_log2 = int(J), int(n_wide), int(gop), int(up), int(motion), int(block_log2)
     if not frames:
         raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
     if gop < 1 or not 0 <= up <= 3 or inter not in ("auto", "always"):
         raise ValueError('encode_sequence_bytes: gop >= 1, up in 0 .. 3, inter "auto" or "always"')
+    if not 0 <= motion <= 3 or (motion and not 1 <= block_log2 <= J):
+        raise ValueError("encode_sequence_bytes: motion in 0 .. 3, block_log2 in 1 .. J")
     VA = []
     for i, (V_int, attributes) in enumerate(frames):
         V, A = _frame_input(f"encode_sequence_bytes: frame {i}", V_int, attributes, J, n_wide, dev)
@@ -530,6 +607,10 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
         VA.append((V, A))
     D = int(VA[0][1].shape[1])
     steps = _step_list(step, D)
+    if motion and gop > 1:
+        cands = ops.motion_candidates(motion)
+        if motion_weights is None:
+            motion_weights = (1.0 / np.asarray(steps * (D if len(steps) == 1 else 1), np.float64)).astype(np.float32)
     parts = []                                                               # (the pieces of every frame: joined once, at the end)
     with torch.cuda.device(dev):
         for lo in range(0, len(VA), SEQ_CHUNK):
@@ -541,19 +622,41 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
                 geos, Qs, wraps = [], [], []
                 for i, (V, A) in enumerate(chunk, lo):
                     keys, geo, plan = _keys_geometry_plan(V, J, geometry)
-                    src = A
+                    src, field = A, None                                     # (field: (mv, block_first) of a compensated frame)
                     if i % gop:                                              # (ref: frame i - 1's keys and reconstruction)
                         R = ops.predict(keys, ref[0], ref[1], X=A, up=up)
-                        if inter == "always" or (int(plan.rate_curve(R, [steps], n_wide, seg_len)["bytes"][0]) + P_HEAD
-                                                 < int(plan.rate_curve(A, [steps], n_wide, seg_len)["bytes"][0])):
-                            src = R
+                        if motion:
+                            n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
+                            block_first = ops.motion_blocks(keys, J, block_log2, n_blocks)
+                            mv = ops.motion_search(keys, ref[0], ref[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
+                            if bool(mv.any()):                               # (all zero: the frame goes as it does without motion)
+                                field = (mv, block_first)
+                                Rmc = ops.predict_mc(keys, ref[0], ref[1], mv, block_first, J, block_log2, X=A, up=up)
+                        if field is None:
+                            if inter == "always" or (int(plan.rate_curve(R, [steps], n_wide, seg_len)["bytes"][0]) + P_HEAD
+                                                     < int(plan.rate_curve(A, [steps], n_wide, seg_len)["bytes"][0])):
+                                src = R
+                        elif inter == "always":
+                            src = Rmc
+                        else:                                                # the smallest; a tie goes to the earlier entry
+                            size = [int(plan.rate_curve(M, [steps], n_wide, seg_len)["bytes"][0]) for M in (A, R, Rmc)]
+                            size[1] += P_HEAD
+                            size[2] += M_HEAD + _motion_field_bytes(n_blocks)
+                            src = (A, R, Rmc)[size.index(min(size))]
+                            if src is not Rmc:
+                                field = None
                     Q = _quantize([plan], [src], steps, n_wide)[0]
                     if i + 1 < len(VA) and (i + 1) % gop:                    # the next frame may be predicted from this one
                         C = _reconstruct([plan], [Q], steps, n_wide)[0]
-                        ref = (keys, C if src is A else ops.predict(keys, ref[0], ref[1], X=C, up=up, add=True, out=C))
+                        if field is not None:
+                            C = ops.predict_mc(keys, ref[0], ref[1], field[0], field[1], J, block_log2, X=C, up=up, add=True, out=C)
+                        elif src is not A:
+                            C = ops.predict(keys, ref[0], ref[1], X=C, up=up, add=True, out=C)
+                        ref = (keys, C)
                     geos.append(geo)
                     Qs.append(Q)
-                    wraps.append([] if src is A else [P_MAGIC + np.array([1, up], np.int64).tobytes()])
+                    wraps.append([] if src is A else [P_MAGIC + np.array([1, up], np.int64).tobytes()] if field is None
+                                 else [_mframe_wrapper(up, block_log2, field[0].cpu().numpy())])
             atts = _attribute_parts(Qs, seg_len, dev)
             parts += [w + _frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att)
                       for (_, A), geo, att, w in zip(chunk, geos, atts, wraps)]
@@ -570,7 +673,8 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
     section or a segment outside its payload when that frame's group is decoded.
 
     A predicted frame (RAHTP001) comes back as (V_int, fl(R_rec + P)): R_rec is what ``decode_frame_bytes`` returns for its inner
-    frame, P is ``ops.predict`` of its reference's decoded attributes. The requested indices are closed under dependencies, back to
+    frame, P is ``ops.predict`` of its reference's decoded attributes (``ops.predict_mc`` under the frame's motion field for an
+    RAHTM001 frame, whose ``block_log2`` and block count are checked against the inner frame's geometry header with the rest). The requested indices are closed under dependencies, back to
     the nearest intra frame, and that set is decoded in ascending order; only the requested frames are returned. R_rec does not
     depend on the prediction, so the entropy decode and the inverse transform of a group stay batched, for I and P frames alike;
     only the additions run in frame order. A predicted frame at index 0, a ``ref_back`` below 1 or reaching before frame 0, ``up``
@@ -644,6 +748,12 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
             hd = by_index[i]
             if hd["kind"] == "P":
                 _, C_ref, ref_keys = done[hd["ref"]]
-                C = ops.predict(keys, ref_keys, C_ref, X=C, up=hd["up"], add=True, out=C)
+                if hd["motion"] is None:
+                    C = ops.predict(keys, ref_keys, C_ref, X=C, up=hd["up"], add=True, out=C)
+                else:
+                    m, mv = hd["motion"]
+                    block_first = ops.motion_blocks(keys, hd["h"]["J"], m, len(mv))
+                    C = ops.predict_mc(keys, ref_keys, C_ref, torch.from_numpy(mv.copy()).to(dev), block_first, hd["h"]["J"], m, X=C,
+                                       up=hd["up"], add=True, out=C)
             done[i] = (V, C, keys)
     return [done[i][:2] for i in idx]

@@ -1,0 +1,238 @@
+// motion.hip -- block motion search and the motion-compensated predictor of a sequence (include/raht.h, "Motion compensation";
+// DESIGN.md 19). A block is a cell of the octree level block_log2 above the voxels; its rows are one run of the sorted keys
+// (block_first: raht_region_cells). A candidate vector v moves every voxel of the block to the voxel x + v of the reference; the
+// prediction of the row is raht_predict's for THAT key (predict_device.h: the same resolve, the same run mean, the same bits).
+//
+//   raht_motion_search   memset of the cost table, then
+//     search   MS tile rows per workgroup step, one thread per row. The weighted columns of the tile's X rows are staged in LDS
+//              once (row stride odd: a lane per row reads conflict-free), then every candidate is walked against them: shift the
+//              key, resolve it in the reference keys (L2-resident, as in the predictor), form the run mean column by column,
+//              accumulate c in the order of the definition (product rounded before the sum: __fmul_rn / __fadd_rn), q = the
+//              fixed-point cost. Rows of a block are contiguous, so q is summed per block by a segmented scan inside the wave,
+//              the wave's segment tails add into an LDS slot per block of the tile, and the block's first row of the tile issues
+//              ONE 64-bit atomic per (block, candidate, workgroup) into the table. Two sets of slots alternate, so a candidate
+//              costs one barrier. Integer sums: the table does not depend on the order or on how a block is cut into tiles.
+//              Matrices too wide for the LDS budget (D > 243) read X through the cache instead.
+//     select   one thread per block: the smallest cost, the smallest k among equals.
+//   raht_predict_mc      predict_device.h's kernel with MvKey: the key is shifted by the block's vector before the resolve.
+#include <optional>
+
+#include "predict_device.h"
+
+namespace raht {
+
+constexpr int MS_THREADS = 256;                          // the largest tile: one thread per row
+constexpr int MS_MAX_GRID = 2048;                        // grids are capped and grid-strided
+constexpr size_t MS_LDS_BYTES = 65536 - 64;              // dynamic LDS a workgroup may ask for (the kernel's statics: 16 bytes)
+constexpr float MS_COST_CAP = 1048576.0f;                // 2^20 per row; q = floor(min(c, cap) * 2^10) <= 2^30
+constexpr int MS_MAX_K = 512;
+
+// the fixed-point cost of a row from its float32 cost: NaN and +inf take the cap (fminf(NaN, x) = x), the product is exact
+__device__ __forceinline__ unsigned long long ms_fixed(float c)
+{
+    const float m = fminf(c, MS_COST_CAP);
+    return m > 0.0f ? (unsigned long long)floorf(m * 1024.0f) : 0ull;
+}
+
+// dynamic LDS of a tile: acc[2][tile] uint64 | wcol[D] int32 | wval[D] float | xs[tile * x_stride] float (STAGED only)
+static inline size_t ms_lds_bytes(int tile, int D, int x_stride) { return (size_t)tile * 16 + (size_t)D * 8 + (size_t)tile * x_stride * 4; }
+
+// STAGED: blockDim.x rows per tile, their weighted columns in LDS. Otherwise X and the weights are read through the cache.
+template <bool STAGED>
+__global__ __launch_bounds__(MS_THREADS) void motion_search_kernel(const uint64_t *__restrict__ keys, int64_t n, int J,
+                                                                  const int64_t *__restrict__ block_first, int64_t n_blocks,
+                                                                  const uint64_t *__restrict__ ref_keys, int32_t n_ref, int shift,
+                                                                  const float *__restrict__ C_ref, int64_t ld_ref,
+                                                                  const float *__restrict__ X, int64_t ldx, int D,
+                                                                  const float *__restrict__ weights, const int32_t *__restrict__ cand, int K,
+                                                                  unsigned long long *__restrict__ table, int x_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ms_lds[];
+    __shared__ int n_weighted;
+    const int tile = (int)blockDim.x, tid = (int)threadIdx.x, lane = tid & 63;
+    unsigned long long *acc = (unsigned long long *)ms_lds;                      // [2][tile]
+    int32_t *wcol = (int32_t *)(acc + 2 * tile);                                 // [D] (STAGED)
+    float *wval = (float *)(wcol + (STAGED ? D : 0));                            // [D] (STAGED)
+    float *xs = wval + (STAGED ? D : 0);                                         // [tile][x_stride] (STAGED)
+
+    acc[tid] = 0;
+    acc[tile + tid] = 0;
+    if (tid == 0) {                                      // the weighted columns, ascending (D <= 243 when STAGED)
+        int nw = 0;
+        for (int ch = 0; ch < D; ++ch) {
+            const float w = weights[ch];
+            if (w != 0.0f) {
+                if (STAGED) { wcol[nw] = ch; wval[nw] = w; }
+                ++nw;
+            }
+        }
+        n_weighted = nw;
+    }
+    __syncthreads();
+    const int nw = n_weighted;
+    if (nw == 0) return;                                 // every cost is 0: the table stays as the memset left it
+
+    const int64_t n_tiles = (n + tile - 1) / tile;
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t r0 = t * tile;
+        const int rows = (int)min((int64_t)tile, n - r0);
+        const bool active = tid < rows;
+        __syncthreads();                                 // the previous step's readers are done with xs, its flushes with acc
+        if constexpr (STAGED) {
+            for (int e = tid; e < rows * nw; e += tile) {
+                const int r = e / nw, j = e - r * nw;
+                xs[r * x_stride + j] = X[(r0 + r) * ldx + wcol[j]];
+            }
+        }
+        // this row: its voxel, its block, the slot of its block in the tile (the block's first row of the tile)
+        VoxCoords vox = {0, 0, 0};
+        int64_t b = 0;
+        int slot = -1;
+        if (active) {
+            vox = vox_coords(keys[r0 + tid]);
+            b = pr_block_of(block_first, n_blocks, r0 + tid);
+            const int64_t first = block_first[b] - r0;   // (bounded for any block_first: 0 <= slot <= tid)
+            slot = (int)(first < 0 ? 0 : (first > tid ? tid : first));
+        }
+        const int slot_next = __shfl_down(slot, 1);
+        const bool tail = active && (lane == 63 || slot_next != slot);           // the last lane of its block in this wave
+        const bool head = active && slot == tid;                                 // the block's first row of the tile flushes
+        __syncthreads();                                 // xs is staged
+        for (int k = 0; k < K; ++k) {
+            unsigned long long q = 0;
+            if (active) {
+                uint64_t key;
+                int32_t lo = 0, len = 0;
+                if (pr_shift_key(vox, cand[3 * k], cand[3 * k + 1], cand[3 * k + 2], J, key)) len = pr_resolve(ref_keys, n_ref, shift, key, lo);
+                float c = 0.0f;
+                if constexpr (STAGED) {
+                    const float *x = xs + tid * x_stride;
+                    for (int j = 0; j < nw; ++j) {
+                        const float d = fabsf(__fsub_rn(x[j], pr_mean(C_ref, ld_ref, lo, len, wcol[j])));
+                        c = __fadd_rn(c, __fmul_rn(wval[j], d));
+                    }
+                } else {
+                    const float *x = X + (r0 + tid) * ldx;
+                    for (int ch = 0; ch < D; ++ch) {
+                        const float w = weights[ch];
+                        if (w == 0.0f) continue;
+                        const float d = fabsf(__fsub_rn(x[ch], pr_mean(C_ref, ld_ref, lo, len, ch)));
+                        c = __fadd_rn(c, __fmul_rn(w, d));
+                    }
+                }
+                q = ms_fixed(c);
+            }
+            // the sum of q over the lanes of this lane's block up to this lane: blocks are runs of lanes
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const unsigned long long u = __shfl_up(q, d);
+                const int s = __shfl_up(slot, d);
+                if (lane >= d && s == slot) q += u;
+            }
+            unsigned long long *a = acc + (k & 1) * tile;
+            if (tail && q) atomicAdd(a + slot, q);
+            __syncthreads();
+            if (head) {
+                const unsigned long long v = a[tid];
+                if (v) {
+                    atomicAdd(table + b * K + k, v);
+                    a[tid] = 0;                          // (this set is added to again two candidates on: a barrier lies between)
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void motion_select_kernel(const unsigned long long *__restrict__ table, int64_t n_blocks, int K,
+                                                                  int32_t *__restrict__ best_k, unsigned long long *__restrict__ best_cost)
+{
+    for (int64_t b = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x; b < n_blocks; b += (int64_t)gridDim.x * MS_THREADS) {
+        const unsigned long long *row = table + b * K;
+        unsigned long long best = row[0];
+        int32_t at = 0;
+        for (int k = 1; k < K; ++k) {
+            const unsigned long long v = row[k];
+            if (v < best) { best = v; at = k; }          // strictly smaller: the smallest k among equals stays
+        }
+        best_k[b] = at;
+        if (best_cost) best_cost[b] = best;
+    }
+}
+
+}  // namespace raht
+
+using namespace raht;
+
+// the rules of a frame's blocks, shared by both entry points
+static int motion_check_blocks(const char *who, int J, int block_log2, const void *block_first, int64_t n_blocks, int64_t N)
+{
+    if (!block_first) { set_error("%s: NULL block_first", who); return RAHT_ERR_INVALID; }
+    if (J < 1 || J > 21) { set_error("%s: J=%d outside 1 .. 21", who, J); return RAHT_ERR_INVALID; }
+    if (block_log2 < 1 || block_log2 > J) { set_error("%s: block_log2=%d outside 1 .. J", who, block_log2); return RAHT_ERR_INVALID; }
+    if (n_blocks < 1 || n_blocks > N) { set_error("%s: n_blocks must be 1 .. N", who); return RAHT_ERR_INVALID; }
+    return RAHT_OK;
+}
+
+extern "C" {
+
+int raht_motion_search(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                       const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref, const float *X,
+                       int64_t ldx, int D, const float *weights, const int32_t *cand, int K, int32_t *best_k, uint64_t *best_cost,
+                       uint64_t *cost_table, raht_stream_t stream)
+{
+    const char *who = "raht_motion_search";
+    if (!X || !weights || !cand || !best_k) { set_error("%s: NULL X, weights, candidates or best_k", who); return RAHT_ERR_INVALID; }
+    // (the predictor's rules: X stands in for the output, whose stride is then X's)
+    RAHT_RET(predict_check(who, keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, 0, X, ldx));
+    RAHT_RET(motion_check_blocks(who, J, block_log2, block_first, n_blocks, N));
+    if (K < 1 || K > MS_MAX_K) { set_error("%s: K=%d outside 1 .. %d", who, K, MS_MAX_K); return RAHT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    return guarded(who, [&]() -> int {
+        const size_t table_bytes = sizeof(uint64_t) * (size_t)n_blocks * (size_t)K;
+        std::optional<Scratch> ws;                       // (the caller's table, or one from the pool)
+        if (!cost_table) {
+            ws.emplace(table_bytes, s);
+            if (!ws->ok()) { set_error("%s: out of device memory", who); return RAHT_ERR_NOMEM; }
+        }
+        unsigned long long *table = cost_table ? (unsigned long long *)cost_table : ws->as<unsigned long long>();
+        RAHT_HIP_CHECK(hipMemsetAsync(table, 0, table_bytes, s));
+        // the largest tile whose rows fit the LDS budget; none: X through the cache
+        const int x_stride = D | 1;
+        int tile = 0;
+        if (D <= 4096)
+            for (int t = MS_THREADS; t >= 64 && !tile; t -= 64)
+                if (ms_lds_bytes(t, D, x_stride) <= MS_LDS_BYTES) tile = t;
+        const bool staged = tile != 0;
+        if (!staged) tile = MS_THREADS;
+        const int64_t tiles = ceil_div(N, tile);
+        const unsigned grid = (unsigned)(tiles > MS_MAX_GRID ? MS_MAX_GRID : tiles);
+        if (staged)
+            hipLaunchKernelGGL(motion_search_kernel<true>, dim3(grid), dim3(tile), ms_lds_bytes(tile, D, x_stride), s, keys_sorted, N, J,
+                               block_first, n_blocks, ref_keys_sorted, (int32_t)N_ref, shift, C_ref, ld_ref, X, ldx, D, weights, cand, K, table,
+                               x_stride);
+        else
+            hipLaunchKernelGGL(motion_search_kernel<false>, dim3(grid), dim3(tile), ms_lds_bytes(tile, 0, 0), s, keys_sorted, N, J,
+                               block_first, n_blocks, ref_keys_sorted, (int32_t)N_ref, shift, C_ref, ld_ref, X, ldx, D, weights, cand, K, table,
+                               0);
+        RAHT_HIP_CHECK(hipGetLastError());
+        const int64_t sel = ceil_div(n_blocks, MS_THREADS);
+        hipLaunchKernelGGL(motion_select_kernel, dim3((unsigned)(sel > MS_MAX_GRID ? MS_MAX_GRID : sel)), dim3(MS_THREADS), 0, s, table, n_blocks,
+                           K, best_k, (unsigned long long *)best_cost);
+        RAHT_HIP_CHECK(hipGetLastError());
+        return RAHT_OK;
+    });
+}
+
+int raht_predict_mc(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                    const int8_t *mv, const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref,
+                    const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched, raht_stream_t stream)
+{
+    const char *who = "raht_predict_mc";
+    if (!mv) { set_error("%s: NULL mv", who); return RAHT_ERR_INVALID; }
+    RAHT_RET(predict_check(who, keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, add, Y, ldy));
+    RAHT_RET(motion_check_blocks(who, J, block_log2, block_first, n_blocks, N));
+    return predict_enqueue(keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, add, Y, ldy, n_matched,
+                           MvKey{block_first, n_blocks, mv, J}, (hipStream_t)stream);
+}
+
+}  // extern "C"

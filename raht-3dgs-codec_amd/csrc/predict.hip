@@ -12,163 +12,8 @@
 //               cache (neighbouring voxels of a cell re-read them when shift > 0), two chunks per lane and round with their X
 //               loads issued first; padded matrices move element by element.
 //   Every row recomputes the mean of its run: no table of cell means is built (DESIGN.md 18 has the numbers).
-#include "raht_common.h"
-#include "raht_device.h"
-
-namespace raht {
-
-constexpr int PR_THREADS = 256;
-constexpr int PR_MAX_GRID = 2048;                        // grids are capped and grid-strided
-constexpr int PR_TILE_ROWS = PR_THREADS;                 // rows a workgroup resolves per step: one thread per row
-
-// first r in [a, b) with (ref[r] >> shift) >= c (UPPER: > c); b when there is none
-template <bool UPPER>
-__device__ __forceinline__ int32_t pr_bound(const uint64_t *__restrict__ ref, int32_t a, int32_t b, int shift, uint64_t c)
-{
-    while (a < b) {
-        const int32_t m = a + ((b - a) >> 1);
-        const uint64_t v = ref[m] >> shift;
-        if (UPPER ? v <= c : v < c) a = m + 1; else b = m;
-    }
-    return a;
-}
-
-// prediction of channel ch of a row whose run is [lo, lo + len): the sequential float32 sum, one IEEE division
-__device__ __forceinline__ float pr_mean(const float *__restrict__ C_ref, int64_t ld_ref, int32_t lo, int32_t len, int ch)
-{
-    if (len == 0) return 0.0f;
-    const float *p = C_ref + (int64_t)lo * ld_ref + ch;
-    float s = p[0];
-    for (int32_t r = 1; r < len; ++r) s = s + p[(int64_t)r * ld_ref];
-    return len > 1 ? __fdiv_rn(s, (float)len) : s;       // (s / 1.0f is s)
-}
-
-// MODE 0: Y = P, 1: Y = X - P, 2: Y = X + P
-template <int MODE> __device__ __forceinline__ float pr_apply(float x, float p) { return MODE == 0 ? p : (MODE == 1 ? x - p : x + p); }
-
-// the 16-byte chunk of a flat tile that starts at element e: four predictions applied to x
-template <int MODE>
-__device__ __forceinline__ RegChunk<float> pr_chunk(const float *__restrict__ C_ref, int64_t ld_ref, const int32_t *run_lo, const int32_t *run_len,
-                                                    uint32_t e, uint32_t D, const RegChunk<float> &x)
-{
-    uint32_t j = e / D, ch = e - j * D;
-    RegChunk<float> y;
-    if (ch + 4 <= D) {                                   // the chunk lies in one row: its run in 16-byte loads
-        const int32_t len = run_len[j];
-        RegChunk<float> s;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s.v[i] = 0.0f;
-        if (len > 0) {
-            const float *p = C_ref + (int64_t)run_lo[j] * ld_ref + ch;
-            s = ld_chunk<float>(p);
-            for (int32_t r = 1; r < len; ++r) {
-                const RegChunk<float> a = ld_chunk<float>(p + (int64_t)r * ld_ref);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s.v[i] = s.v[i] + a.v[i];
-            }
-            if (len > 1) {
-                const float d = (float)len;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s.v[i] = __fdiv_rn(s.v[i], d);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) y.v[i] = pr_apply<MODE>(x.v[i], s.v[i]);
-    } else {                                             // the chunk straddles rows (as many as four when D = 1)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            y.v[i] = pr_apply<MODE>(x.v[i], pr_mean(C_ref, ld_ref, run_lo[j], run_len[j], (int)ch));
-            if (++ch == D) { ch = 0; ++j; }
-        }
-    }
-    return y;
-}
-
-// FLAT: every row stride == D, the tile is one run of rows * D floats (X, Y element-aligned only). X and Y may be the same matrix:
-// a thread reads what it writes and nothing else of them.
-template <int MODE, bool FLAT>
-__global__ __launch_bounds__(PR_THREADS) void predict_kernel(const uint64_t *__restrict__ keys, int64_t n, const uint64_t *__restrict__ ref_keys,
-                                                             int32_t n_ref, int shift, const float *__restrict__ C_ref, int64_t ld_ref,
-                                                             const float *X, int64_t ldx, int D, float *Y, int64_t ldy,
-                                                             unsigned long long *__restrict__ n_matched)
-{
-    __shared__ int32_t run_lo[PR_TILE_ROWS], run_len[PR_TILE_ROWS];
-    __shared__ uint32_t hits;
-    if (threadIdx.x == 0) hits = 0;
-    uint32_t mine = 0;
-    const int64_t n_tiles = (n + PR_TILE_ROWS - 1) / PR_TILE_ROWS;
-    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const int64_t r0 = t * PR_TILE_ROWS;
-        const int rows = (int)min((int64_t)PR_TILE_ROWS, n - r0);
-        __syncthreads();                                 // the previous step's readers are done with the runs
-        if ((int)threadIdx.x < rows) {
-            const uint64_t c = keys[r0 + threadIdx.x] >> shift;
-            const int32_t lo = pr_bound<false>(ref_keys, 0, n_ref, shift, c);
-            // strictly ascending keys: a cell holds at most 8^up = 2^shift rows, so the run ends inside that window
-            const int32_t hi = pr_bound<true>(ref_keys, lo, (int32_t)min((int64_t)n_ref, (int64_t)lo + ((int64_t)1 << shift)), shift, c);
-            run_lo[threadIdx.x] = lo;
-            run_len[threadIdx.x] = hi - lo;
-            mine += hi > lo;
-        }
-        __syncthreads();
-        const uint32_t n_el = (uint32_t)rows * (uint32_t)D;
-        if constexpr (FLAT) {
-            const float *xt = MODE ? X + r0 * D : nullptr;
-            float *yt = Y + r0 * D;
-            const uint32_t n_chunks = n_el >> 2;
-            // two chunks per round, their loads of X first: 32 bytes of X and two reference chunks per lane in flight
-            for (uint32_t q = threadIdx.x; q < n_chunks; q += 2 * PR_THREADS) {
-                const uint32_t e0 = q << 2, e1 = (q + PR_THREADS) << 2;
-                const bool two = q + PR_THREADS < n_chunks;
-                RegChunk<float> x0 = {}, x1 = {};
-                if constexpr (MODE != 0) {
-                    x0 = ld_chunk<float, true>(xt + e0);
-                    if (two) x1 = ld_chunk<float, true>(xt + e1);
-                }
-                const RegChunk<float> y0 = pr_chunk<MODE>(C_ref, ld_ref, run_lo, run_len, e0, (uint32_t)D, x0);
-                if (two) {
-                    const RegChunk<float> y1 = pr_chunk<MODE>(C_ref, ld_ref, run_lo, run_len, e1, (uint32_t)D, x1);
-                    st_chunk<float, true>(yt + e0, y0);
-                    st_chunk<float, true>(yt + e1, y1);
-                } else {
-                    st_chunk<float, true>(yt + e0, y0);
-                }
-            }
-            // the last elements of the frame's last tile (rows * D no multiple of 4)
-            const uint32_t e = (n_chunks << 2) + threadIdx.x;
-            if (e < n_el) {
-                const uint32_t j = e / (uint32_t)D, ch = e - j * (uint32_t)D;
-                yt[e] = pr_apply<MODE>(MODE ? xt[e] : 0.0f, pr_mean(C_ref, ld_ref, run_lo[j], run_len[j], (int)ch));
-            }
-        } else {
-            for (int64_t e = threadIdx.x; e < (int64_t)rows * D; e += PR_THREADS) {      // (also the home of D >= 2^22: 64-bit indices)
-                const int64_t j = e / D, ch = e - j * D;
-                const float x = MODE ? X[(r0 + j) * ldx + ch] : 0.0f;
-                Y[(r0 + j) * ldy + ch] = pr_apply<MODE>(x, pr_mean(C_ref, ld_ref, run_lo[j], run_len[j], (int)ch));
-            }
-        }
-    }
-    if (n_matched) {                                     // an integer sum: whatever the order, the same number
-        if (mine) atomicAdd(&hits, mine);
-        __syncthreads();
-        if (threadIdx.x == 0 && hits) atomicAdd(n_matched, (unsigned long long)hits);
-    }
-}
-
-template <int MODE>
-static void predict_launch(bool flat, unsigned grid, hipStream_t s, const uint64_t *keys, int64_t N, const uint64_t *ref_keys, int64_t N_ref,
-                           int shift, const float *C_ref, int64_t ld_ref, const float *X, int64_t ldx, int D, float *Y, int64_t ldy,
-                           int64_t *n_matched)
-{
-    if (flat)
-        hipLaunchKernelGGL((predict_kernel<MODE, true>), dim3(grid), dim3(PR_THREADS), 0, s, keys, N, ref_keys, (int32_t)N_ref, shift, C_ref,
-                           ld_ref, X, ldx, D, Y, ldy, (unsigned long long *)n_matched);
-    else
-        hipLaunchKernelGGL((predict_kernel<MODE, false>), dim3(grid), dim3(PR_THREADS), 0, s, keys, N, ref_keys, (int32_t)N_ref, shift, C_ref,
-                           ld_ref, X, ldx, D, Y, ldy, (unsigned long long *)n_matched);
-}
-
-}  // namespace raht
+// The device code lives in predict_device.h, which motion.hip shares.
+#include "predict_device.h"
 
 using namespace raht;
 
@@ -178,24 +23,9 @@ int raht_predict(const uint64_t *keys_sorted, int64_t N, const uint64_t *ref_key
                  int64_t ld_ref, const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched,
                  raht_stream_t stream)
 {
-    if (!keys_sorted || !ref_keys_sorted || !C_ref || !Y) { set_error("raht_predict: NULL keys, reference or output"); return RAHT_ERR_INVALID; }
-    if (N < 1 || N >= ((int64_t)1 << 31) || N_ref < 1 || N_ref >= ((int64_t)1 << 31)) {
-        set_error("raht_predict: N and N_ref must be 1 .. 2^31 - 1");
-        return RAHT_ERR_INVALID;
-    }
-    if (shift != 0 && shift != 3 && shift != 6 && shift != 9) { set_error("raht_predict: shift=%d (0, 3, 6 or 9)", shift); return RAHT_ERR_INVALID; }
-    if (D < 1 || ld_ref < D || ldy < D || (X && ldx < D)) { set_error("raht_predict: D must be >= 1 and no row stride below it"); return RAHT_ERR_INVALID; }
-    if (add != 0 && add != 1) { set_error("raht_predict: add=%d (0 or 1)", add); return RAHT_ERR_INVALID; }
-    hipStream_t s = (hipStream_t)stream;
-    if (n_matched) RAHT_HIP_CHECK(hipMemsetAsync(n_matched, 0, sizeof(int64_t), s));
-    const int64_t tiles = ceil_div(N, PR_TILE_ROWS);
-    const unsigned grid = (unsigned)(tiles > PR_MAX_GRID ? PR_MAX_GRID : tiles);
-    const bool flat = ldy == D && (!X || ldx == D) && D < (1 << 22);      // (flat tiles index their elements with 32 bits)
-    if (!X) predict_launch<0>(flat, grid, s, keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, Y, ldy, n_matched);
-    else if (!add) predict_launch<1>(flat, grid, s, keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, Y, ldy, n_matched);
-    else predict_launch<2>(flat, grid, s, keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, Y, ldy, n_matched);
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    RAHT_RET(predict_check("raht_predict", keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, add, Y, ldy));
+    return predict_enqueue(keys_sorted, N, ref_keys_sorted, N_ref, shift, C_ref, ld_ref, X, ldx, D, add, Y, ldy, n_matched, SameKey(),
+                           (hipStream_t)stream);
 }
 
 }  // extern "C"

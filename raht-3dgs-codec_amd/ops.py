@@ -935,6 +935,133 @@ def predict(keys, ref_keys, C_ref, X=None, up=0, add=False, out=None, want_match
     return (out, matched) if want_matched else out
 
 
+# ---- motion compensation (raht_motion_search / raht_predict_mc) -----------------------------------------------------
+MOTION_MAX_CANDIDATES = 512
+
+
+def motion_candidates(radius):
+    """-> (K, 3) int32 numpy: every vector of [-radius, radius]^3, radius 1 .. 3, sorted by (dx^2 + dy^2 + dz^2, dx, dy, dz). Index 0
+    is (0, 0, 0), and the search gives a tie to the smaller index: to no motion first, to a shorter vector before a longer one."""
+    import numpy as np
+    r = int(radius)
+    if not 1 <= r <= 3:
+        raise ValueError("motion_candidates: radius must be 1 .. 3")
+    rng = range(-r, r + 1)
+    return np.array(sorted(((x, y, z) for x in rng for y in rng for z in rng), key=lambda v: (v[0] ** 2 + v[1] ** 2 + v[2] ** 2,) + v),
+                    np.int32)
+
+
+def _motion_frame(who, keys, J, block_log2):
+    k = _region_keys(keys, who)
+    J, m = int(J), int(block_log2)
+    if not 1 <= J <= 21 or not 1 <= m <= J:
+        raise ValueError(f"{who}: J must be 1 .. 21 and block_log2 1 .. J")
+    return k, J, m
+
+
+def _motion_block_first(who, block_first, k):
+    _need_cuda(block_first, "block_first")
+    if block_first.dtype != torch.int64 or block_first.dim() != 1 or not 2 <= block_first.shape[0] <= k.shape[0] + 1:
+        raise ValueError(f"{who}: block_first must hold n_blocks + 1 int64 rows, 1 <= n_blocks <= N")
+    return block_first.contiguous()
+
+
+@torch.no_grad()
+def motion_blocks(keys, J, block_log2, n_blocks):
+    """-> block_first (n_blocks + 1,) int64 on the keys' device: the first row of every occupied block (a cell of the octree level
+    ``block_log2`` above the voxels: ``key >> 3 block_log2``), ascending, then N. ``n_blocks``: the level count n_(J - block_log2)
+    of the frame's geometry header; ``RahtError`` when the keys hold another number. This is ``region_cells``' cell walk (one block,
+    ``block_log2 == J``, needs none). Synchronises."""
+    k, J, m = _motion_frame("motion_blocks", keys, J, block_log2)
+    if m == J:
+        if int(n_blocks) != 1:
+            raise ValueError("motion_blocks: block_log2 == J is one block")
+        return torch.tensor([0, k.shape[0]], dtype=torch.int64, device=k.device)
+    return region_cells(k, 3 * J, 3 * m, n_blocks)[1]
+
+
+@torch.no_grad()
+def motion_search(keys, ref_keys, C_ref, X, J, block_log2, block_first, candidates, weights, up=0, want_table=False):
+    """Block motion search (raht_motion_search): for every block of the frame, the candidate vector under which the
+    reference predicts the rows of ``X`` best. keys / ref_keys / C_ref / ``up``: as ``predict`` takes them; X: (N, D) float32;
+    block_first: ``motion_blocks``; candidates: (K, 3) integers within +-127, K <= 512 (``motion_candidates``); weights: D finite
+    floats >= 0 (checked here, on the host), a column of weight 0 is left out. The cost of a row under a vector v is
+    sum_ch w[ch] |X[i, ch] - P_v[i, ch]| in float32 (channels ascending, product rounded before the sum), capped at 2^20 and taken
+    to 2^-10 fixed point; a block's cost is the integer sum over its rows; the smallest cost wins, the smallest index among equals.
+    -> (mv (n_blocks, 3) int8, best_cost (n_blocks,) int64[, table (n_blocks, K) int64]) on the device; v points from the voxel to
+    its reference voxel. Enqueued only."""
+    import numpy as np
+    k, J, m = _motion_frame("motion_search", keys, J, block_log2)
+    r = _region_keys(ref_keys, "motion_search")
+    up = int(up)
+    if not 0 <= up <= 3:
+        raise ValueError("motion_search: up must be 0 .. 3")
+    _need_cuda(C_ref, "C_ref")
+    if C_ref.dim() != 2:
+        raise ValueError("motion_search: C_ref must be a matrix")
+    N, D = int(k.shape[0]), int(C_ref.shape[1])
+    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
+    X = _predict_rows(X, N, D, "X")
+    bf = _motion_block_first("motion_search", block_first, k)
+    n_blocks = int(bf.shape[0]) - 1
+    cand = np.asarray(candidates)
+    if cand.ndim != 2 or cand.shape[1] != 3 or not 1 <= cand.shape[0] <= MOTION_MAX_CANDIDATES or cand.dtype.kind not in "iu":
+        raise ValueError(f"motion_search: candidates must be (K, 3) integers, 1 <= K <= {MOTION_MAX_CANDIDATES}")
+    if np.abs(cand.astype(np.int64)).max() > 127:
+        raise ValueError("motion_search: a candidate outside +-127 (a vector is stored as int8)")
+    w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1)
+    if w.shape[0] != D or not bool(np.all(np.isfinite(w) & (w >= 0))):
+        raise ValueError("motion_search: weights must be D finite numbers >= 0")
+    dev = k.device
+    if len({t.device for t in (k, r, C_ref, X, bf)}) != 1:
+        raise ValueError("motion_search: all tensors must be on one device")
+    cand_d = torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev)
+    w_d = torch.from_numpy(w).to(dev)
+    K = int(cand.shape[0])
+    best_k = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+    best_cost = torch.empty(n_blocks, dtype=torch.int64, device=dev)
+    table = torch.empty((n_blocks, K), dtype=torch.int64, device=dev) if want_table else None
+    _call(_lib.lib().raht_motion_search, dev, _p(k), N, J, m, _p(bf), n_blocks, _p(r), int(r.shape[0]), 3 * up, _p(C_ref),
+          C_ref.stride(0), _p(X), X.stride(0), D, _p(w_d), _p(cand_d), K, _p(best_k), _p(best_cost), _p(table))
+    mv = cand_d.to(torch.int8)[best_k.long()]
+    return (mv, best_cost, table) if want_table else (mv, best_cost)
+
+
+@torch.no_grad()
+def predict_mc(keys, ref_keys, C_ref, mv, block_first, J, block_log2, X=None, up=0, add=False, out=None, want_matched=False):
+    """The motion-compensated predictor (raht_predict_mc): ``predict`` with the key of every row shifted by the vector
+    of its block before it is looked up in the reference -- P[i] is ``predict``'s P of the voxel x_i + mv[block(i)], 0 where that
+    voxel leaves the cube [0, 2^J)^3. mv: (n_blocks, 3) int8 on the device; block_first: ``motion_blocks``. Everything else, the three
+    modes and ``out`` / ``want_matched`` included, is ``predict``'s; with mv = 0 so are the bits. Enqueued only."""
+    k, J, m = _motion_frame("predict_mc", keys, J, block_log2)
+    r = _region_keys(ref_keys, "predict_mc")
+    up = int(up)
+    if not 0 <= up <= 3:
+        raise ValueError("predict_mc: up must be 0 .. 3")
+    _need_cuda(C_ref, "C_ref")
+    if C_ref.dim() != 2:
+        raise ValueError("predict_mc: C_ref must be a matrix")
+    N, D = int(k.shape[0]), int(C_ref.shape[1])
+    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
+    bf = _motion_block_first("predict_mc", block_first, k)
+    n_blocks = int(bf.shape[0]) - 1
+    _need_cuda(mv, "mv")
+    if mv.dtype != torch.int8 or tuple(mv.shape) != (n_blocks, 3):
+        raise ValueError(f"predict_mc: mv must be a ({n_blocks}, 3) int8 tensor")
+    mv = mv.contiguous()
+    if X is not None:
+        X = _predict_rows(X, N, D, "X")
+    elif add:
+        raise ValueError("predict_mc: add needs X")
+    out = torch.empty((N, D), dtype=torch.float32, device=k.device) if out is None else _predict_rows(out, N, D, "out")
+    if len({t.device for t in (k, r, C_ref, out, bf, mv) + (() if X is None else (X,))}) != 1:
+        raise ValueError("predict_mc: all tensors must be on one device")
+    matched = torch.empty(1, dtype=torch.int64, device=k.device) if want_matched else None
+    _call(_lib.lib().raht_predict_mc, k.device, _p(k), N, J, m, _p(bf), n_blocks, _p(mv), _p(r), int(r.shape[0]), 3 * up, _p(C_ref),
+          C_ref.stride(0), _p(X), 0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched))
+    return (out, matched) if want_matched else out
+
+
 @torch.no_grad()
 def voxel_keys(PC, vmin, width, J):
     """Unsorted 3J-bit Morton keys (int64) of the points of PC (n, >= 3) float32 for a given bounding box: the
