@@ -752,6 +752,11 @@ int raht_debug_sort_form(int onesweep, int rounds, int64_t fail_tile);
 int64_t raht_debug_live_blocks(void);
 /* Freed blocks the cache currently keeps (what raht_release_cached_memory() would return to HIP), on every device. */
 int64_t raht_debug_cached_blocks(void);
+/* The form raht_motion_search takes for rows of D floats: the rows of a workgroup's tile whose weighted columns are staged in LDS
+ * -- 256 for D <= 59, 192 for D <= 79, 128 for D <= 121, 64 for D <= 243 -- or 0 when no tile fits and X is read through the cache
+ * (256 rows per workgroup step then); 0 for D < 1 too. The entry point calls the same function. Host only, no GPU work; a testing
+ * hook: the tests assert the form they mean to exercise. */
+int raht_debug_motion_tile(int D);
 
 /* out[c] = sum over rows of (A[i, c] - B[i, c])^2, DEVICE double[D]: what the drivers' five PSNR columns are made of
  * (python/encode_3dgs.py:298-310: torch.mean((C - C_rec) ** 2) over all / quats / scales / opacity / colour columns -- each a

@@ -30,7 +30,7 @@ EXPORTS = [
     "raht_fwd_quant_mixed_multi", "raht_dequant_inv_mixed_sqdiff",
     "raht_fwd_batch", "raht_inv_batch", "raht_fwd_quant_batch", "raht_dequant_inv_batch",
     "raht_fwd_quant_mixed_batch", "raht_dequant_inv_mixed_batch", "raht_mixed_batch_stats",
-    "raht_rlgr_bound", "raht_rlgr_encode", "raht_rlgr_decode", "raht_rlgr_encode_channels", "raht_rlgr_decode_channels", "raht_transpose_i32", "raht_i32_equal", "raht_sqdiff_columns", "raht_merge_clusters", "raht_voxelize_merge", "raht_rlgr_seg_encode", "raht_rlgr_seg_decode", "raht_rlgr_seg_encode_strided", "raht_rlgr_seg_decode_strided", "raht_rlgr_seg_encode_batch", "raht_rlgr_seg_decode_batch", "raht_rlgr_seg_decode_batch_check", "raht_rlgr_seg_offsets_width", "raht_rlgr_seg_encode64", "raht_rlgr_seg_decode64", "raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_decode_batch64", "raht_rlgr_seg_encode_ragged", "raht_rlgr_seg_decode_ragged", "raht_debug_rlgr_decode_out", "raht_debug_rlgr_encode_out", "raht_rlgr_seg_rate", "raht_debug_height_stages_per_launch", "raht_debug_live_blocks", "raht_debug_cached_blocks", "raht_debug_sort_form",
+    "raht_rlgr_bound", "raht_rlgr_encode", "raht_rlgr_decode", "raht_rlgr_encode_channels", "raht_rlgr_decode_channels", "raht_transpose_i32", "raht_i32_equal", "raht_sqdiff_columns", "raht_merge_clusters", "raht_voxelize_merge", "raht_rlgr_seg_encode", "raht_rlgr_seg_decode", "raht_rlgr_seg_encode_strided", "raht_rlgr_seg_decode_strided", "raht_rlgr_seg_encode_batch", "raht_rlgr_seg_decode_batch", "raht_rlgr_seg_decode_batch_check", "raht_rlgr_seg_offsets_width", "raht_rlgr_seg_encode64", "raht_rlgr_seg_decode64", "raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_decode_batch64", "raht_rlgr_seg_encode_ragged", "raht_rlgr_seg_decode_ragged", "raht_debug_rlgr_decode_out", "raht_debug_rlgr_encode_out", "raht_rlgr_seg_rate", "raht_debug_height_stages_per_launch", "raht_debug_live_blocks", "raht_debug_cached_blocks", "raht_debug_sort_form", "raht_debug_motion_tile",
     "raht_xchg_bytes", "raht_xchg_alloc", "raht_xchg_open", "raht_xchg_close", "raht_xchg_free", "raht_xchg_gather", "raht_xchg_buffer", "raht_xchg_status",
     "raht_octree_counts", "raht_octree_encode", "raht_octree_decode", "raht_octree_symbols", "raht_octree_bytes", "raht_demorton",
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
@@ -168,6 +168,7 @@ def lib():
     L.raht_debug_cached_blocks.restype = i64
     L.raht_set_cached_memory_limit.argtypes = [i64]
     L.raht_debug_sort_form.argtypes = [i32, i32, i64]
+    L.raht_debug_motion_tile.argtypes = [i32]
     L.raht_rlgr_seg_encode_batch.argtypes = [i32, C.POINTER(vp), i64, i32, i64, i64, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), vp]
     L.raht_rlgr_seg_decode_batch.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), i64, i32, i32, i32, C.POINTER(vp), i64, i64, vp, vp]
     L.raht_rlgr_seg_decode_batch_check.argtypes = [i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), i64, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), i64, i64, vp, vp]

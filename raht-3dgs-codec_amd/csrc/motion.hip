@@ -37,6 +37,16 @@ __device__ __forceinline__ unsigned long long ms_fixed(float c)
 // dynamic LDS of a tile: acc[2][tile] uint64 | wcol[D] int32 | wval[D] float | xs[tile * x_stride] float (STAGED only)
 static inline size_t ms_lds_bytes(int tile, int D, int x_stride) { return (size_t)tile * 16 + (size_t)D * 8 + (size_t)tile * x_stride * 4; }
 
+// the rows of a staged tile for rows of D floats (row stride D | 1 in LDS): the largest of 256 / 192 / 128 / 64 whose rows fit the
+// LDS budget; 0: none fits, X is read through the cache (raht_debug_motion_tile)
+static int ms_tile_rows(int D)
+{
+    if (D < 1 || D > 4096) return 0;
+    for (int t = MS_THREADS; t >= 64; t -= 64)
+        if (ms_lds_bytes(t, D, D | 1) <= MS_LDS_BYTES) return t;
+    return 0;
+}
+
 // STAGED: blockDim.x rows per tile, their weighted columns in LDS. Otherwise X and the weights are read through the cache.
 template <bool STAGED>
 __global__ __launch_bounds__(MS_THREADS) void motion_search_kernel(const uint64_t *__restrict__ keys, int64_t n, int J,
@@ -175,6 +185,8 @@ static int motion_check_blocks(const char *who, int J, int block_log2, const voi
 
 extern "C" {
 
+int raht_debug_motion_tile(int D) { return ms_tile_rows(D); }
+
 int raht_motion_search(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
                        const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref, const float *X,
                        int64_t ldx, int D, const float *weights, const int32_t *cand, int K, int32_t *best_k, uint64_t *best_cost,
@@ -198,12 +210,9 @@ int raht_motion_search(const uint64_t *keys_sorted, int64_t N, int J, int block_
         RAHT_HIP_CHECK(hipMemsetAsync(table, 0, table_bytes, s));
         // the largest tile whose rows fit the LDS budget; none: X through the cache
         const int x_stride = D | 1;
-        int tile = 0;
-        if (D <= 4096)
-            for (int t = MS_THREADS; t >= 64 && !tile; t -= 64)
-                if (ms_lds_bytes(t, D, x_stride) <= MS_LDS_BYTES) tile = t;
-        const bool staged = tile != 0;
-        if (!staged) tile = MS_THREADS;
+        const int staged_rows = ms_tile_rows(D);
+        const bool staged = staged_rows != 0;
+        const int tile = staged ? staged_rows : MS_THREADS;
         const int64_t tiles = ceil_div(N, tile);
         const unsigned grid = (unsigned)(tiles > MS_MAX_GRID ? MS_MAX_GRID : tiles);
         if (staged)
