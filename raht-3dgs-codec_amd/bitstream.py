@@ -31,6 +31,7 @@ With ``motion`` > 0 the prediction may follow a MOTION FIELD: one
 sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
 """
+import itertools
 import math
 
 import numpy as np
@@ -78,11 +79,6 @@ def _keys_geometry_plan(V, J, geometry):
     keys = ops.get_morton_code(V, J)
     geo = OctreeCoder.encode(keys, J, entropy=geometry)                   # (also refuses rows that are not sorted and unique)
     return keys, geo, ops.RahtPlan.from_keys(keys, 3 * J)
-
-
-def _geometry_and_plan(V, J, geometry):
-    """sorted voxel coordinates -> (geometry section, plan over their keys)"""
-    return _keys_geometry_plan(V, J, geometry)[1:]
 
 
 def _quantize(plans, As, steps, n_wide):
@@ -140,7 +136,7 @@ def encode_frame_bytes(V_int, attributes, J, step, device="cuda", n_wide=0, seg_
     N, D = A.shape
     steps = _step_list(step, D)
     with torch.cuda.device(dev):
-        geo, plan = _geometry_and_plan(V, J, geometry)
+        _, geo, plan = _keys_geometry_plan(V, J, geometry)
         att = _attribute_parts(_quantize([plan], [A], steps, n_wide), seg_len, dev)[0]
     return b"".join(_frame_parts(J, N, D, n_wide, steps, vmin, width, geo, att))
 
@@ -179,7 +175,7 @@ def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scal
         raise ValueError("encode_frame_bytes_target: scale_range must be 0 < lo <= hi, rounds >= 1")
     K = SegmentedCoder.RATE_MAX
     with torch.cuda.device(dev):
-        geo, plan = _geometry_and_plan(V, J, geometry)
+        _, geo, plan = _keys_geometry_plan(V, J, geometry)
         # the frame around the attribute container: header, steps + box, the geometry section and the two length words
         budget = target - (len(MAGIC) + 40 + 8 * (len(base) + 4)) - (8 + len(geo)) - 8
         if budget < 0:
@@ -272,17 +268,39 @@ def decode_frame_bytes(blob, device="cuda", max_voxels=None):
 
 def _decode_frame(blob, h, dev, max_voxels):
     """a frame container and its parsed header -> (V_int, C_rec, keys)"""
+    return _decode_group([("", blob, h)], dev, max_voxels)[0]
+
+
+def _attribute_matrices(coders):
+    """coders with their containers uploaded -> ([Q (N_i, D) int32], failed): ``_attribute_parts`` read backwards. One frame, and
+    every frame of a group in which one needs 64-bit offsets, goes through ``SegmentedCoder.decode``; the others share one launch.
+    ``failed()`` -> the frames whose tables reached outside their payload (it synchronises: for after the inverse is enqueued)."""
+    if len(coders) == 1 or any(c.wide for c in coders):
+        return [c.decode(row_major=True) for c in coders], lambda: [j for j, c in enumerate(coders) if int(c.bad.item())]
+    return SegmentedCoder.decode_ragged(coders, row_major=True), lambda: SegmentedCoder.roundtrip_failed(coders)
+
+
+def _decode_group(group, dev, max_voxels):
+    """group: [(who, frame container, its parsed header)], one frame at least, all of one (D, n_wide, steps) -> [(V_int, C_rec,
+    keys)]: the geometry frame by frame, the entropy decode and the inverse transform of all frames together (``_attribute_matrices``,
+    ``_reconstruct``). ``who`` opens what a refusal of that frame says ("" for a frame that stands alone)."""
     import torch
-    (go, gl), (ao, al) = h["geometry"], h["attributes"]
+    keys, coders, Vs, plans = [], [], [], []
     with torch.cuda.device(dev):
-        keys = OctreeCoder.decode(blob[go: go + gl], dev, max_voxels)
-        V = ops.demorton(keys, h["J"])
-        plan = ops.RahtPlan.from_keys(keys, 3 * h["J"])
-        sc = SegmentedCoder.from_container(blob[ao: ao + al], dev, max_symbols=h["N"] * h["D"])
-        Q = sc.decode(row_major=True)
-        C_rec = _reconstruct([plan], [Q], h["steps"], h["n_wide"])[0]
-        _refuse_outside(int(sc.bad.item()))
-    return V, C_rec, keys
+        for who, fb, h in group:
+            (go, gl), (ao, al) = h["geometry"], h["attributes"]
+            try:
+                keys.append(OctreeCoder.decode(fb[go: go + gl], dev, max_voxels))
+                coders.append(SegmentedCoder.from_container(fb[ao: ao + al], dev, max_symbols=h["N"] * h["D"]))
+            except ValueError as e:
+                raise ValueError(f"{who}{e}") from None
+            Vs.append(ops.demorton(keys[-1], h["J"]))
+            plans.append(ops.RahtPlan.from_keys(keys[-1], 3 * h["J"]))
+        Qs, failed = _attribute_matrices(coders)
+        Cs = _reconstruct(plans, Qs, group[0][2]["steps"], group[0][2]["n_wide"])
+        for j in failed():
+            _refuse_outside(True, group[j][0])
+    return list(zip(Vs, Cs, keys))
 
 
 def region_runs(table, J, depth, n_roots):
@@ -437,20 +455,7 @@ def sequence_frame(blob, i, offsets=None):
     return memoryview(blob)[off[i]: off[i + 1]]
 
 
-def parse_pframe(fb):
-    """The wrapper of a predicted frame, checked (pure host code) -> (ref_back, up, the inner RAHTF001 container as a memoryview).
-    ``ValueError`` for another magic, a wrapper too short to hold a frame, ``ref_back < 1`` or ``up`` outside 0 .. 3; the inner
-    frame is ``parse_frame``'s to judge."""
-    if bytes(fb[:len(P_MAGIC)]) != P_MAGIC:
-        raise ValueError("not a RAHT predicted-frame wrapper")
-    if len(fb) < P_HEAD + MIN_FRAME_BYTES:
-        raise ValueError("predicted frame: truncated wrapper")
-    ref_back, up = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(P_MAGIC))]
-    if ref_back < 1:
-        raise ValueError(f"predicted frame: ref_back = {ref_back}, must be at least 1")
-    if not 0 <= up <= 3:
-        raise ValueError(f"predicted frame: up = {up} outside 0 .. 3")
-    return ref_back, up, memoryview(fb)[P_HEAD:]
+_WRAPPERS = {P_MAGIC: ("predicted frame", P_HEAD), M_MAGIC: ("motion-compensated frame", M_HEAD)}      # what a refusal says, the fixed part
 
 
 def _motion_field_bytes(n_blocks):
@@ -458,11 +463,44 @@ def _motion_field_bytes(n_blocks):
     return (3 * n_blocks + 7) // 8 * 8
 
 
-def _mframe_wrapper(up, block_log2, mv):
-    """the wrapper of a motion-compensated frame: everything before its inner frame (mv: (n_blocks, 3) int8 numpy)"""
-    field = np.ascontiguousarray(mv, np.int8).tobytes()
-    return (M_MAGIC + np.array([1, up, block_log2, len(field) // 3], np.int64).tobytes() + field
-            + bytes(_motion_field_bytes(len(field) // 3) - len(field)))
+def _parse_wrapper(fb, only=None):
+    """The wrapper of a predicted frame of either kind, checked as ``parse_pframe`` and ``parse_mframe`` say -> (ref_back, up, motion:
+    None or (block_log2, mv (n_blocks, 3) int8 numpy), the inner RAHTF001 container as a memoryview). None when ``fb`` opens with no
+    wrapper's magic (with ``only``: with another magic than that one)."""
+    magic = bytes(fb[:len(P_MAGIC)])
+    if magic not in _WRAPPERS or only not in (None, magic):
+        return None
+    what, head = _WRAPPERS[magic]
+    if len(fb) < head + MIN_FRAME_BYTES:
+        raise ValueError(f"{what}: truncated wrapper")
+    ref_back, up = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic))]
+    if ref_back < 1:
+        raise ValueError(f"{what}: ref_back = {ref_back}, must be at least 1")
+    if not 0 <= up <= 3:
+        raise ValueError(f"{what}: up = {up} outside 0 .. 3")
+    motion = None
+    if magic == M_MAGIC:
+        block_log2, n_blocks = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic) + 16)]
+        if not 1 <= block_log2 <= MAX_J:
+            raise ValueError(f"{what}: block_log2 = {block_log2} outside 1 .. {MAX_J}")
+        if n_blocks < 1 or n_blocks >= 2 ** 31 or len(fb) < head + _motion_field_bytes(n_blocks) + MIN_FRAME_BYTES:
+            raise ValueError(f"{what}: too short for a motion field of {n_blocks} blocks and a frame")
+        field = np.frombuffer(fb, np.int8, _motion_field_bytes(n_blocks), head)
+        if field[3 * n_blocks:].any():
+            raise ValueError(f"{what}: the padding behind the motion field is not zero")
+        motion = (block_log2, field[:3 * n_blocks].reshape(n_blocks, 3))
+        head += len(field)
+    return ref_back, up, motion, memoryview(fb)[head:]
+
+
+def parse_pframe(fb):
+    """The wrapper of a predicted frame, checked (pure host code) -> (ref_back, up, the inner RAHTF001 container as a memoryview).
+    ``ValueError`` for another magic, a wrapper too short to hold a frame, ``ref_back < 1`` or ``up`` outside 0 .. 3; the inner
+    frame is ``parse_frame``'s to judge."""
+    w = _parse_wrapper(fb, P_MAGIC)
+    if w is None:
+        raise ValueError("not a RAHT predicted-frame wrapper")
+    return w[0], w[1], w[3]
 
 
 def parse_mframe(fb):
@@ -470,23 +508,10 @@ def parse_mframe(fb):
     the inner RAHTF001 container as a memoryview). ``ValueError`` for another magic, ``ref_back < 1``, ``up`` outside 0 .. 3,
     ``block_log2`` outside 1 .. 21, a wrapper too short for its motion field plus a frame, padding that is not zero. Every int8
     vector is legal. Whether ``block_log2`` and ``n_blocks`` go with the inner frame is for the sequence's checks (``_frame_head``)."""
-    if bytes(fb[:len(M_MAGIC)]) != M_MAGIC:
+    w = _parse_wrapper(fb, M_MAGIC)
+    if w is None:
         raise ValueError("not a RAHT motion-compensated frame wrapper")
-    if len(fb) < M_HEAD + MIN_FRAME_BYTES:
-        raise ValueError("motion-compensated frame: truncated wrapper")
-    ref_back, up, block_log2, n_blocks = [int(x) for x in np.frombuffer(fb, np.int64, 4, len(M_MAGIC))]
-    if ref_back < 1:
-        raise ValueError(f"motion-compensated frame: ref_back = {ref_back}, must be at least 1")
-    if not 0 <= up <= 3:
-        raise ValueError(f"motion-compensated frame: up = {up} outside 0 .. 3")
-    if not 1 <= block_log2 <= MAX_J:
-        raise ValueError(f"motion-compensated frame: block_log2 = {block_log2} outside 1 .. {MAX_J}")
-    if n_blocks < 1 or n_blocks >= 2 ** 31 or len(fb) < M_HEAD + _motion_field_bytes(n_blocks) + MIN_FRAME_BYTES:
-        raise ValueError(f"motion-compensated frame: too short for a motion field of {n_blocks} blocks and a frame")
-    field = np.frombuffer(fb, np.int8, _motion_field_bytes(n_blocks), M_HEAD)
-    if field[3 * n_blocks:].any():
-        raise ValueError("motion-compensated frame: the padding behind the motion field is not zero")
-    return ref_back, up, block_log2, field[:3 * n_blocks].reshape(n_blocks, 3), memoryview(fb)[M_HEAD + len(field):]
+    return w[0], w[1], *w[2], w[3]
 
 
 def _frame_head(view, off, i, max_voxels):
@@ -496,19 +521,14 @@ def _frame_head(view, off, i, max_voxels):
     fb = view[off[i]: off[i + 1]]
     kind, ref, up, motion = "I", None, 0, None
     try:
-        magic = bytes(fb[:len(P_MAGIC)])
-        if magic in (P_MAGIC, M_MAGIC):
-            kind = "P"
-            if magic == M_MAGIC:
-                ref_back, up, block_log2, mv, fb = parse_mframe(fb)
-                motion = (block_log2, mv)
-            else:
-                ref_back, up, fb = parse_pframe(fb)
+        w = _parse_wrapper(fb)
+        if w is not None:
+            ref_back, up, motion, fb = w
             if i == 0:
                 raise ValueError("a predicted frame cannot open a sequence")
             if ref_back > i:
                 raise ValueError(f"predicted frame: ref_back = {ref_back} reaches before frame 0")
-            ref = i - ref_back
+            kind, ref = "P", i - ref_back
         h = parse_frame(fb, max_voxels)
         if motion is not None:
             if motion[0] > h["J"]:
@@ -542,22 +562,58 @@ def _frame_heads(view, off, idx, max_voxels):
     return heads
 
 
+def _sequence_heads(blob, max_voxels, max_frames):
+    """-> the head of every frame of a sequence container, in order"""
+    off = parse_sequence(blob, max_frames)
+    heads = _frame_heads(memoryview(blob), off, range(len(off) - 1), max_voxels)
+    return [heads[i] for i in range(len(off) - 1)]
+
+
 def sequence_kinds(blob, max_voxels=None, max_frames=None):
     """-> ["I" | "P"] per frame of a sequence container, from the headers alone (pure host code). Every frame's headers are checked
     on the way as ``decode_sequence_bytes`` checks them: ``ValueError`` naming the frame for a predicted frame at index 0, a
     ``ref_back`` below 1 or reaching before frame 0, ``up`` outside 0 .. 3, a truncated wrapper, a frame ``parse_frame`` refuses, a
     predicted frame whose J or D differs from its reference's."""
-    off = parse_sequence(blob, max_frames)
-    heads = _frame_heads(memoryview(blob), off, range(len(off) - 1), max_voxels)
-    return [heads[i]["kind"] for i in range(len(off) - 1)]
+    return [hd["kind"] for hd in _sequence_heads(blob, max_voxels, max_frames)]
 
 
 def sequence_motion(blob, max_voxels=None, max_frames=None):
     """-> per frame of a sequence container None, or (block_log2, mv (n_blocks, 3) int8 numpy) for a motion-compensated frame, from
     the headers alone (pure host code), with the checks of ``sequence_kinds``."""
-    off = parse_sequence(blob, max_frames)
-    heads = _frame_heads(memoryview(blob), off, range(len(off) - 1), max_voxels)
-    return [heads[i]["motion"] for i in range(len(off) - 1)]
+    return [hd["motion"] for hd in _sequence_heads(blob, max_voxels, max_frames)]
+
+
+class _Predictor:
+    """"This frame is predicted from that one": the frame's ``keys``, its reference ``ref`` = (keys, reconstruction), ``J``, ``up``
+    and ``motion`` -- None, or (block_log2, mv (n_blocks, 3) int8 on the device, block_first) of a motion-compensated frame. The
+    encoder's closed loop and the decoder add the prediction through the one ``restore``, with one argument list: that is what
+    keeps the loop free of drift. ``overhead``: the bytes of ``wrapper()``."""
+
+    def __init__(self, keys, ref, J, up, motion=None):
+        self.keys, self.ref, self.J, self.up, self.motion = keys, ref, J, up, motion
+        self.overhead = P_HEAD if motion is None else M_HEAD + _motion_field_bytes(len(motion[1]))
+
+    def _apply(self, X, add):
+        """X - P into a fresh matrix, or with ``add`` X + P in place"""
+        kw = dict(X=X, up=self.up, add=add, out=X if add else None)
+        if self.motion is None:
+            return ops.predict(self.keys, *self.ref, **kw)
+        block_log2, mv, block_first = self.motion
+        return ops.predict_mc(self.keys, *self.ref, mv, block_first, self.J, block_log2, **kw)
+
+    def residual(self, A):
+        return self._apply(A, False)
+
+    def restore(self, C):
+        return self._apply(C, True)
+
+    def wrapper(self):
+        """the bytes in front of the inner frame, with ref_back = 1 (a motion field comes to the host here)"""
+        if self.motion is None:
+            return P_MAGIC + np.array([1, self.up], np.int64).tobytes()
+        field = self.motion[1].cpu().numpy().tobytes()
+        return (M_MAGIC + np.array([1, self.up, self.motion[0], len(field) // 3], np.int64).tobytes() + field
+                + bytes(self.overhead - M_HEAD - len(field)))
 
 
 SEQ_CHUNK = SegmentedCoder.BATCH_MAX                                     # frames whose transform and entropy stages share launches
@@ -616,70 +672,62 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
         for lo in range(0, len(VA), SEQ_CHUNK):
             chunk = VA[lo: lo + SEQ_CHUNK]
             if gop == 1:
-                geos, plans = zip(*[_geometry_and_plan(V, J, geometry) for V, _ in chunk])
-                Qs, wraps = _quantize(list(plans), [A for _, A in chunk], steps, n_wide), [[]] * len(chunk)
+                _, geos, plans = zip(*[_keys_geometry_plan(V, J, geometry) for V, _ in chunk])
+                Qs, wraps = _quantize(list(plans), [A for _, A in chunk], steps, n_wide), [b""] * len(chunk)
             else:
                 geos, Qs, wraps = [], [], []
                 for i, (V, A) in enumerate(chunk, lo):
                     keys, geo, plan = _keys_geometry_plan(V, J, geometry)
-                    src, field = A, None                                     # (field: (mv, block_first) of a compensated frame)
-                    if i % gop:                                              # (ref: frame i - 1's keys and reconstruction)
-                        R = ops.predict(keys, ref[0], ref[1], X=A, up=up)
+                    # the ways to code the frame, each by its predictor: intra (None), predicted from frame i - 1 (ref: its keys and
+                    # reconstruction, carried from frame to frame), and under a motion field that is not all zero
+                    ways = [None]
+                    if i % gop:
+                        ways.append(_Predictor(keys, ref, J, up))
                         if motion:
                             n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
                             block_first = ops.motion_blocks(keys, J, block_log2, n_blocks)
                             mv = ops.motion_search(keys, ref[0], ref[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
-                            if bool(mv.any()):                               # (all zero: the frame goes as it does without motion)
-                                field = (mv, block_first)
-                                Rmc = ops.predict_mc(keys, ref[0], ref[1], mv, block_first, J, block_log2, X=A, up=up)
-                        if field is None:
-                            if inter == "always" or (int(plan.rate_curve(R, [steps], n_wide, seg_len)["bytes"][0]) + P_HEAD
-                                                     < int(plan.rate_curve(A, [steps], n_wide, seg_len)["bytes"][0])):
-                                src = R
-                        elif inter == "always":
-                            src = Rmc
-                        else:                                                # the smallest; a tie goes to the earlier entry
-                            size = [int(plan.rate_curve(M, [steps], n_wide, seg_len)["bytes"][0]) for M in (A, R, Rmc)]
-                            size[1] += P_HEAD
-                            size[2] += M_HEAD + _motion_field_bytes(n_blocks)
-                            src = (A, R, Rmc)[size.index(min(size))]
-                            if src is not Rmc:
-                                field = None
+                            if bool(mv.any()):
+                                ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, block_first)))
+                    if inter == "always" or len(ways) == 1:                  # the last way; its source alone is formed
+                        pred = ways[-1]
+                        src = A if pred is None else pred.residual(A)
+                    else:                                                    # the fewest bytes, wrapper included; the earliest among equals
+                        srcs = [A] + [p.residual(A) for p in ways[1:]]
+                        cost = [int(plan.rate_curve(X, [steps], n_wide, seg_len)["bytes"][0]) + (p.overhead if p else 0)
+                                for p, X in zip(ways, srcs)]
+                        pred, src = min(zip(ways, srcs, cost), key=lambda w: w[2])[:2]
                     Q = _quantize([plan], [src], steps, n_wide)[0]
                     if i + 1 < len(VA) and (i + 1) % gop:                    # the next frame may be predicted from this one
                         C = _reconstruct([plan], [Q], steps, n_wide)[0]
-                        if field is not None:
-                            C = ops.predict_mc(keys, ref[0], ref[1], field[0], field[1], J, block_log2, X=C, up=up, add=True, out=C)
-                        elif src is not A:
-                            C = ops.predict(keys, ref[0], ref[1], X=C, up=up, add=True, out=C)
-                        ref = (keys, C)
+                        ref = (keys, C if pred is None else pred.restore(C))
                     geos.append(geo)
                     Qs.append(Q)
-                    wraps.append([] if src is A else [P_MAGIC + np.array([1, up], np.int64).tobytes()] if field is None
-                                 else [_mframe_wrapper(up, block_log2, field[0].cpu().numpy())])
+                    wraps.append(b"" if pred is None else pred.wrapper())
             atts = _attribute_parts(Qs, seg_len, dev)
-            parts += [w + _frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att)
+            parts += [[w] + _frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att)
                       for (_, A), geo, att, w in zip(chunk, geos, atts, wraps)]
     return _pack_parts(parts)
 
 
 def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max_frames=None):
     """-> [(V_int (N_i, 3) int64, C_rec (N_i, D) float32)] for the frame indices ``frames`` (default: all, in order), each what
-    ``decode_frame_bytes(sequence_frame(blob, i))`` returns, bit for bit. The geometry is decoded frame by frame; consecutive chosen
-    frames with the same (D, seg_len, n_wide, steps) share one entropy launch (``SegmentedCoder.decode_ragged``) and one set of
-    inverse transform launches (a frame of exactly D voxels goes alone). ``max_voxels`` per frame and ``max_frames`` are checked
-    before anything is allocated from the numbers of the blob. ``ValueError`` for a corrupt container; a corrupt frame is named by
-    its index -- for a header or an attribute length table that does not add up before any device work, for a corrupt geometry
-    section or a segment outside its payload when that frame's group is decoded.
+    ``decode_frame_bytes(sequence_frame(blob, i))`` returns, bit for bit. The requested indices are closed under dependencies, back
+    to the nearest intra frame, and that set is decoded once, in ascending order; the requested frames are returned in the order
+    asked. The geometry is decoded frame by frame; consecutive frames of the set with the same (D, seg_len, n_wide, steps) share one
+    entropy launch (``SegmentedCoder.decode_ragged``) and one set of inverse transform launches (a frame of exactly D voxels goes
+    alone). ``max_voxels`` per frame and ``max_frames`` are checked before anything is allocated from the numbers of the blob.
+    ``ValueError`` for a corrupt container; a corrupt frame is named by its index -- for a header or an attribute length table that
+    does not add up before any device work, for a corrupt geometry section or a segment outside its payload when that frame's
+    group is decoded.
 
     A predicted frame (RAHTP001) comes back as (V_int, fl(R_rec + P)): R_rec is what ``decode_frame_bytes`` returns for its inner
     frame, P is ``ops.predict`` of its reference's decoded attributes (``ops.predict_mc`` under the frame's motion field for an
-    RAHTM001 frame, whose ``block_log2`` and block count are checked against the inner frame's geometry header with the rest). The requested indices are closed under dependencies, back to
-    the nearest intra frame, and that set is decoded in ascending order; only the requested frames are returned. R_rec does not
-    depend on the prediction, so the entropy decode and the inverse transform of a group stay batched, for I and P frames alike;
-    only the additions run in frame order. A predicted frame at index 0, a ``ref_back`` below 1 or reaching before frame 0, ``up``
-    outside 0 .. 3, a truncated wrapper, an inner frame ``parse_frame`` refuses or one whose J or D is not its reference's are
-    refused from the headers, before any device work."""
+    RAHTM001 frame, whose ``block_log2`` and block count are checked against the inner frame's geometry header with the rest).
+    R_rec does not depend on the prediction, so the entropy decode and the inverse transform of a group stay batched, for I and P
+    frames alike; only the additions run in frame order. A predicted frame at index 0, a ``ref_back`` below 1 or reaching before
+    frame 0, ``up`` outside 0 .. 3, a truncated wrapper, an inner frame ``parse_frame`` refuses or one whose J or D is not its
+    reference's are refused from the headers, before any device work."""
     import torch
     off = parse_sequence(blob, max_frames)
     n = len(off) - 1
@@ -692,68 +740,27 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
     if any(not 0 <= i < n for i in idx):
         raise ValueError(f"decode_sequence_bytes: frame indices must be in 0 .. {n - 1}")
     dev = torch.device(device)
-    view = memoryview(blob)
-    by_index = _frame_heads(view, off, idx, max_voxels)
-    inter = any(hd["kind"] == "P" for hd in by_index.values())
-    heads = []
-    for i in (sorted(by_index) if inter else idx):                           # (no predicted frame: the frames as they were asked for)
-        fb, h, S = by_index[i]["fb"], by_index[i]["h"], by_index[i]["seg_len"]
+    heads = _frame_heads(memoryview(blob), off, idx, max_voxels)
+
+    def same(i):
         # (a frame of exactly D voxels is a group of its own: decode_frame_bytes reads its square matrix as the encoder wrote it)
-        heads.append((i, fb, h, (h["D"], S, h["n_wide"], tuple(h["steps"])) + ((len(heads),) if h["N"] == h["D"] else ())))
-    out = []                                                                 # (V, C_rec or R_rec, keys) per head
+        h = heads[i]["h"]
+        return (h["D"], heads[i]["seg_len"], h["n_wide"], tuple(h["steps"])) + ((i,) if h["N"] == h["D"] else ())
+    done = {}                                                                # frame -> (V, C_rec or R_rec, keys)
+    for _, run in itertools.groupby(sorted(heads), key=same):
+        run = list(run)
+        for group in (run[lo: lo + SEQ_CHUNK] for lo in range(0, len(run), SEQ_CHUNK)):
+            named = [(f"sequence container: frame {i}: ", heads[i]["fb"], heads[i]["h"]) for i in group]
+            done.update(zip(group, _decode_group(named, dev, max_voxels)))
     with torch.cuda.device(dev):
-        lo = 0
-        while lo < len(heads):
-            hi = lo + 1
-            while hi < len(heads) and hi - lo < SEQ_CHUNK and heads[hi][3] == heads[lo][3]:
-                hi += 1
-            group = heads[lo:hi]
-            lo = hi
-            if len(group) == 1:
-                i, fb, h, _ = group[0]
-                try:
-                    out.append(_decode_frame(fb, h, dev, max_voxels))
-                except ValueError as e:
-                    raise ValueError(f"sequence container: frame {i}: {e}") from None
-                continue
-            Vs, plans, coders, ks = [], [], [], []
-            for i, fb, h, _ in group:
-                (go, gl), (ao, al) = h["geometry"], h["attributes"]
-                try:
-                    keys = OctreeCoder.decode(fb[go: go + gl], dev, max_voxels)
-                    coders.append(SegmentedCoder.from_container(fb[ao: ao + al], dev, max_symbols=h["N"] * h["D"]))
-                except ValueError as e:
-                    raise ValueError(f"sequence container: frame {i}: {e}") from None
-                Vs.append(ops.demorton(keys, h["J"]))
-                plans.append(ops.RahtPlan.from_keys(keys, 3 * h["J"]))
-                ks.append(keys)
-            _, _, n_wide, steps = group[0][3][:4]
-            steps = list(steps)
-            if any(c.wide for c in coders):                              # (64-bit offsets: such a frame goes alone)
-                Qs = [c.decode(row_major=True) for c in coders]
-                bad = [j for j, c in enumerate(coders) if int(c.bad.item()) != 0]
-            else:
-                Qs = SegmentedCoder.decode_ragged(coders, row_major=True)
-                bad = None
-            Cs = _reconstruct(plans, Qs, steps, n_wide)
-            if bad is None:
-                bad = SegmentedCoder.roundtrip_failed(coders)
-            if bad:
-                _refuse_outside(True, f"sequence container: frame {group[bad[0]][0]}: ")
-            out += list(zip(Vs, Cs, ks))
-        if not inter:
-            return [(V, C) for V, C, _ in out]
-        done = {}                                                            # frame -> (V, C_rec, keys), in ascending frame order
-        for (i, _, _, _), (V, C, keys) in zip(heads, out):
-            hd = by_index[i]
+        for i in sorted(done):                                               # ascending: a reference is whole before it is used
+            hd = heads[i]
             if hd["kind"] == "P":
-                _, C_ref, ref_keys = done[hd["ref"]]
-                if hd["motion"] is None:
-                    C = ops.predict(keys, ref_keys, C_ref, X=C, up=hd["up"], add=True, out=C)
-                else:
-                    m, mv = hd["motion"]
-                    block_first = ops.motion_blocks(keys, hd["h"]["J"], m, len(mv))
-                    C = ops.predict_mc(keys, ref_keys, C_ref, torch.from_numpy(mv.copy()).to(dev), block_first, hd["h"]["J"], m, X=C,
-                                       up=hd["up"], add=True, out=C)
-            done[i] = (V, C, keys)
+                (_, C, keys), (_, C_ref, ref_keys) = done[i], done[hd["ref"]]
+                motion, J = hd["motion"], hd["h"]["J"]
+                if motion is not None:
+                    block_first = ops.motion_blocks(keys, J, motion[0], len(motion[1]))
+                    motion = (motion[0], torch.from_numpy(motion[1].copy()).to(dev), block_first)
+                _Predictor(keys, (ref_keys, C_ref), J, hd["up"], motion).restore(C)
     return [done[i][:2] for i in idx]
+

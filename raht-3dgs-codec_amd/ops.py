@@ -905,6 +905,54 @@ def _predict_rows(M, n_rows, D, name):
     return M
 
 
+def _inter_args(who, keys, ref_keys, C_ref, up, X, blocks=None, result=None):
+    """What ``predict``, ``predict_mc`` and ``motion_search`` take in common, checked (``who`` opens a refusal) -> (device, the
+    entry point's arguments from the keys on, the tensors behind them -- to be held until the call is made --, out, matched).
+    blocks: (J, block_log2, block_first) of ``motion_search``, with mv as a fourth of ``predict_mc``. result: (add, out,
+    want_matched) of the two predictors, whose arguments end with out and matched; without it X is required and they end with D."""
+    if blocks is None:
+        k = _region_keys(keys, who)
+    else:
+        k, J, m = _motion_frame(who, keys, blocks[0], blocks[1])
+    r = _region_keys(ref_keys, who)
+    up = int(up)
+    if not 0 <= up <= 3:
+        raise ValueError(f"{who}: up must be 0 .. 3")
+    _need_cuda(C_ref, "C_ref")
+    if C_ref.dim() != 2:
+        raise ValueError(f"{who}: C_ref must be a matrix")
+    N, D = int(k.shape[0]), int(C_ref.shape[1])
+    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
+    live, args = [k, r, C_ref], [_p(k), N]
+    if blocks is not None:
+        _need_cuda(blocks[2], "block_first")
+        if blocks[2].dtype != torch.int64 or blocks[2].dim() != 1 or not 2 <= blocks[2].shape[0] <= N + 1:
+            raise ValueError(f"{who}: block_first must hold n_blocks + 1 int64 rows, 1 <= n_blocks <= N")
+        bf, n_blocks = blocks[2].contiguous(), int(blocks[2].shape[0]) - 1
+        live, args = live + [bf], args + [J, m, _p(bf), n_blocks]
+        if len(blocks) > 3:
+            _need_cuda(blocks[3], "mv")
+            if blocks[3].dtype != torch.int8 or tuple(blocks[3].shape) != (n_blocks, 3):
+                raise ValueError(f"{who}: mv must be a ({n_blocks}, 3) int8 tensor")
+            live.append(blocks[3].contiguous())
+            args.append(_p(live[-1]))
+    add, out, want_matched = result or (False, None, False)
+    if X is not None or result is None:
+        X = _predict_rows(X, N, D, "X")
+        live.append(X)
+    elif add:
+        raise ValueError(f"{who}: add needs X")
+    args += [_p(r), int(r.shape[0]), 3 * up, _p(C_ref), C_ref.stride(0), _p(X), 0 if X is None else X.stride(0), D]
+    matched = torch.empty(1, dtype=torch.int64, device=k.device) if want_matched else None
+    if result is not None:
+        out = torch.empty((N, D), dtype=torch.float32, device=k.device) if out is None else _predict_rows(out, N, D, "out")
+        live.append(out)
+        args += [int(bool(add)), _p(out), out.stride(0), _p(matched)]
+    if len({t.device for t in live}) != 1:
+        raise ValueError(f"{who}: all tensors must be on one device")
+    return k.device, args, live, out, matched
+
+
 @torch.no_grad()
 def predict(keys, ref_keys, C_ref, X=None, up=0, add=False, out=None, want_matched=False):
     """The inter-frame predictor (raht_predict). keys (N,), ref_keys (N_ref,): the sorted int64 Morton keys of the frame
@@ -913,25 +961,8 @@ def predict(keys, ref_keys, C_ref, X=None, up=0, add=False, out=None, want_match
     empty; ``up = 0``: the co-located voxel's row). -> P when ``X`` is None, X - P, or X + P with ``add``; into ``out`` when given
     (``out`` may be ``X``: in place). Column slices of wider matrices pass as they are. ``want_matched``: -> (result, n_matched), a
     (1,) int64 device tensor with the number of rows whose cell is not empty. Enqueued only."""
-    k, r = _region_keys(keys, "predict"), _region_keys(ref_keys, "predict")
-    up = int(up)
-    if not 0 <= up <= 3:
-        raise ValueError("predict: up must be 0 .. 3")
-    _need_cuda(C_ref, "C_ref")
-    if C_ref.dim() != 2:
-        raise ValueError("predict: C_ref must be a matrix")
-    N, D = int(k.shape[0]), int(C_ref.shape[1])
-    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
-    if X is not None:
-        X = _predict_rows(X, N, D, "X")
-    elif add:
-        raise ValueError("predict: add needs X")
-    out = torch.empty((N, D), dtype=torch.float32, device=k.device) if out is None else _predict_rows(out, N, D, "out")
-    if len({t.device for t in (k, r, C_ref, out) + (() if X is None else (X,))}) != 1:
-        raise ValueError("predict: all tensors must be on one device")
-    matched = torch.empty(1, dtype=torch.int64, device=k.device) if want_matched else None
-    _call(_lib.lib().raht_predict, k.device, _p(k), N, _p(r), int(r.shape[0]), 3 * up, _p(C_ref), C_ref.stride(0), _p(X),
-          0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched))
+    dev, args, _live, out, matched = _inter_args("predict", keys, ref_keys, C_ref, up, X, result=(add, out, want_matched))
+    _call(_lib.lib().raht_predict, dev, *args)
     return (out, matched) if want_matched else out
 
 
@@ -959,13 +990,6 @@ def _motion_frame(who, keys, J, block_log2):
     return k, J, m
 
 
-def _motion_block_first(who, block_first, k):
-    _need_cuda(block_first, "block_first")
-    if block_first.dtype != torch.int64 or block_first.dim() != 1 or not 2 <= block_first.shape[0] <= k.shape[0] + 1:
-        raise ValueError(f"{who}: block_first must hold n_blocks + 1 int64 rows, 1 <= n_blocks <= N")
-    return block_first.contiguous()
-
-
 @torch.no_grad()
 def motion_blocks(keys, J, block_log2, n_blocks):
     """-> block_first (n_blocks + 1,) int64 on the keys' device: the first row of every occupied block (a cell of the octree level
@@ -991,19 +1015,8 @@ def motion_search(keys, ref_keys, C_ref, X, J, block_log2, block_first, candidat
     -> (mv (n_blocks, 3) int8, best_cost (n_blocks,) int64[, table (n_blocks, K) int64]) on the device; v points from the voxel to
     its reference voxel. Enqueued only."""
     import numpy as np
-    k, J, m = _motion_frame("motion_search", keys, J, block_log2)
-    r = _region_keys(ref_keys, "motion_search")
-    up = int(up)
-    if not 0 <= up <= 3:
-        raise ValueError("motion_search: up must be 0 .. 3")
-    _need_cuda(C_ref, "C_ref")
-    if C_ref.dim() != 2:
-        raise ValueError("motion_search: C_ref must be a matrix")
-    N, D = int(k.shape[0]), int(C_ref.shape[1])
-    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
-    X = _predict_rows(X, N, D, "X")
-    bf = _motion_block_first("motion_search", block_first, k)
-    n_blocks = int(bf.shape[0]) - 1
+    dev, args, _live, _, _ = _inter_args("motion_search", keys, ref_keys, C_ref, up, X, blocks=(J, block_log2, block_first))
+    n_blocks, D = int(block_first.shape[0]) - 1, int(C_ref.shape[1])
     cand = np.asarray(candidates)
     if cand.ndim != 2 or cand.shape[1] != 3 or not 1 <= cand.shape[0] <= MOTION_MAX_CANDIDATES or cand.dtype.kind not in "iu":
         raise ValueError(f"motion_search: candidates must be (K, 3) integers, 1 <= K <= {MOTION_MAX_CANDIDATES}")
@@ -1012,17 +1025,13 @@ def motion_search(keys, ref_keys, C_ref, X, J, block_log2, block_first, candidat
     w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1)
     if w.shape[0] != D or not bool(np.all(np.isfinite(w) & (w >= 0))):
         raise ValueError("motion_search: weights must be D finite numbers >= 0")
-    dev = k.device
-    if len({t.device for t in (k, r, C_ref, X, bf)}) != 1:
-        raise ValueError("motion_search: all tensors must be on one device")
     cand_d = torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev)
     w_d = torch.from_numpy(w).to(dev)
     K = int(cand.shape[0])
     best_k = torch.empty(n_blocks, dtype=torch.int32, device=dev)
     best_cost = torch.empty(n_blocks, dtype=torch.int64, device=dev)
     table = torch.empty((n_blocks, K), dtype=torch.int64, device=dev) if want_table else None
-    _call(_lib.lib().raht_motion_search, dev, _p(k), N, J, m, _p(bf), n_blocks, _p(r), int(r.shape[0]), 3 * up, _p(C_ref),
-          C_ref.stride(0), _p(X), X.stride(0), D, _p(w_d), _p(cand_d), K, _p(best_k), _p(best_cost), _p(table))
+    _call(_lib.lib().raht_motion_search, dev, *args, _p(w_d), _p(cand_d), K, _p(best_k), _p(best_cost), _p(table))
     mv = cand_d.to(torch.int8)[best_k.long()]
     return (mv, best_cost, table) if want_table else (mv, best_cost)
 
@@ -1033,32 +1042,9 @@ def predict_mc(keys, ref_keys, C_ref, mv, block_first, J, block_log2, X=None, up
     of its block before it is looked up in the reference -- P[i] is ``predict``'s P of the voxel x_i + mv[block(i)], 0 where that
     voxel leaves the cube [0, 2^J)^3. mv: (n_blocks, 3) int8 on the device; block_first: ``motion_blocks``. Everything else, the three
     modes and ``out`` / ``want_matched`` included, is ``predict``'s; with mv = 0 so are the bits. Enqueued only."""
-    k, J, m = _motion_frame("predict_mc", keys, J, block_log2)
-    r = _region_keys(ref_keys, "predict_mc")
-    up = int(up)
-    if not 0 <= up <= 3:
-        raise ValueError("predict_mc: up must be 0 .. 3")
-    _need_cuda(C_ref, "C_ref")
-    if C_ref.dim() != 2:
-        raise ValueError("predict_mc: C_ref must be a matrix")
-    N, D = int(k.shape[0]), int(C_ref.shape[1])
-    C_ref = _predict_rows(C_ref, int(r.shape[0]), D, "C_ref")
-    bf = _motion_block_first("predict_mc", block_first, k)
-    n_blocks = int(bf.shape[0]) - 1
-    _need_cuda(mv, "mv")
-    if mv.dtype != torch.int8 or tuple(mv.shape) != (n_blocks, 3):
-        raise ValueError(f"predict_mc: mv must be a ({n_blocks}, 3) int8 tensor")
-    mv = mv.contiguous()
-    if X is not None:
-        X = _predict_rows(X, N, D, "X")
-    elif add:
-        raise ValueError("predict_mc: add needs X")
-    out = torch.empty((N, D), dtype=torch.float32, device=k.device) if out is None else _predict_rows(out, N, D, "out")
-    if len({t.device for t in (k, r, C_ref, out, bf, mv) + (() if X is None else (X,))}) != 1:
-        raise ValueError("predict_mc: all tensors must be on one device")
-    matched = torch.empty(1, dtype=torch.int64, device=k.device) if want_matched else None
-    _call(_lib.lib().raht_predict_mc, k.device, _p(k), N, J, m, _p(bf), n_blocks, _p(mv), _p(r), int(r.shape[0]), 3 * up, _p(C_ref),
-          C_ref.stride(0), _p(X), 0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched))
+    dev, args, _live, out, matched = _inter_args("predict_mc", keys, ref_keys, C_ref, up, X, blocks=(J, block_log2, block_first, mv),
+                                                 result=(add, out, want_matched))
+    _call(_lib.lib().raht_predict_mc, dev, *args)
     return (out, matched) if want_matched else out
 
 

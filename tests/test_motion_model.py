@@ -95,6 +95,14 @@ def test_kinds_motion_and_wrapper_of_hand_built_containers():
         ref_back, up, m, mv, inner = bitstream.parse_mframe(fb)
         assert (ref_back, up, m) == want == MM.parse_mframe(fb)[:3]
         assert np.array_equal(mv, MM.parse_mframe(fb)[3]) and isinstance(inner, memoryview) and bytes(inner) == f == MM.parse_mframe(fb)[4]
+    # the two public parsers and the sequence's own heads read one wrapper parser: the same ref_back and up, frame by frame
+    for i, hd in enumerate(bitstream._sequence_heads(seq, None, None)):
+        if hd["kind"] == "P":
+            parse = bitstream.parse_pframe if hd["motion"] is None else bitstream.parse_mframe
+            ref_back, up = parse(bitstream.sequence_frame(seq, i))[:2]
+            assert (hd["ref"], hd["up"]) == (i - ref_back, up), i
+        else:
+            assert (hd["ref"], hd["up"], hd["motion"]) == (None, 0, None), i
     with pytest.raises(ValueError, match="not a RAHT motion-compensated frame wrapper"):
         bitstream.parse_mframe(M.pframe(f))
     with pytest.raises(ValueError, match="not a RAHT predicted-frame wrapper"):
