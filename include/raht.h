@@ -841,6 +841,37 @@ int raht_region_cells(const uint64_t *keys_sorted, int64_t N, int nbits, int top
 int raht_region_assemble(const int32_t *src, int64_t ld_src, int64_t n_src_rows, int32_t *dst, int64_t ld_dst, int64_t n_dst_rows, int D,
                          const int64_t *runs, int n_runs, raht_stream_t stream);
 
+/* A SET of row ranges (python: bitstream.decode_cells_bytes, decode_sequence_region). The rows of R ascending,
+ * disjoint runs of depth-d cells, concatenated, are the region; its own coded order (the plan over the concatenated keys,
+ * truncated at top_level) keeps the first row of every cell in the root part and, in a finer bucket, holds range 0's rows of the
+ * bucket, then range 1's, and so on: one run of coded rows per (bucket, range).
+ *   raht_region_layout_set   : row_bounds (DEVICE int64[2 R]: lo_0, hi_0, lo_1, ..., ascending, 0 <= lo_r <= hi_r <= lo_(r+1) <= N;
+ *                              1 <= R <= RAHT_REGION_MAX_RANGES) -> table (DEVICE int64[(1 + 2 R) * RAHT_REGION_BUCKETS]): rows per
+ *                              bucket in the whole frame, then for every range in [0, lo_r) and in [lo_r, hi_r). One pass over the
+ *                              keys whatever R is; integer sums. For R = 1 it is raht_region_layout's table. The bounds are not
+ *                              read on the host: bounds that do not ascend give counts that mean nothing, and nothing else.
+ *                              Enqueues only (a memset and two launches).
+ *   raht_region_assemble_set : raht_region_assemble with the table in device memory: runs (DEVICE int64[3 * n_runs], n_runs <=
+ *                              RAHT_REGION_BUCKETS * RAHT_REGION_MAX_RANGES), destinations ascending and disjoint. runs_host (HOST,
+ *                              may be NULL): the caller's copy of the same table, held to raht_region_assemble's rules before
+ *                              anything is enqueued. Whatever the device table holds, the kernel clamps every source row into src
+ *                              and writes the n_dst_rows rows of dst only. One launch, enqueues only.
+ *   raht_region_needs        : the depth-d cells (top_level = 3 (J - d)) of ANOTHER frame that a prediction of these rows reaches
+ *                              into: cells (DEVICE uint64[capacity]) = the ascending, duplicate-free values of
+ *                              (k' >> w) << (w - top_level), w = max(top_level, 3 up), over the rows i with a match, k' being the
+ *                              shifted key of "Motion compensation" below under the field mv (block_first, n_blocks, block_log2 as
+ *                              raht_predict_mc takes them), or k[i] itself when mv is NULL (block_first is then not read). Where
+ *                              3 up > top_level a value stands for the aligned group of 8^(up - (J - d)) cells that starts with
+ *                              it; widening it is the caller's. *n_cells (HOST) = their number; every store is bounded by
+ *                              capacity, and a larger number is RAHT_ERR_INVALID (with *n_cells set). SYNCHRONISES `stream`. */
+#define RAHT_REGION_MAX_RANGES 512
+int raht_region_layout_set(const uint64_t *keys_sorted, int64_t N, int nbits, const int64_t *row_bounds, int R, int64_t *table,
+                           raht_stream_t stream);
+int raht_region_assemble_set(const int32_t *src, int64_t ld_src, int64_t n_src_rows, int32_t *dst, int64_t ld_dst, int64_t n_dst_rows, int D,
+                             const int64_t *runs, const int64_t *runs_host, int n_runs, raht_stream_t stream);
+int raht_region_needs(const uint64_t *keys_sorted, int64_t N, int J, int top_level, int up, const int64_t *block_first, int64_t n_blocks,
+                      const int8_t *mv, int block_log2, uint64_t *cells, int64_t capacity, int64_t *n_cells, raht_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Inter-frame prediction (csrc/predict.hip): a frame of a sequence predicted from the RECONSTRUCTION of another one, so that only
  * the residual is coded (python: bitstream.encode_sequence_bytes(..., gop, up, inter) / decode_sequence_bytes).

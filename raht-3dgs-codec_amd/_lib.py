@@ -34,6 +34,7 @@ EXPORTS = [
     "raht_xchg_bytes", "raht_xchg_alloc", "raht_xchg_open", "raht_xchg_close", "raht_xchg_free", "raht_xchg_gather", "raht_xchg_buffer", "raht_xchg_status",
     "raht_octree_counts", "raht_octree_encode", "raht_octree_decode", "raht_octree_symbols", "raht_octree_bytes", "raht_demorton",
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
+    "raht_region_layout_set", "raht_region_assemble_set", "raht_region_needs",
     "raht_predict", "raht_motion_search", "raht_predict_mc",
 ]
 
@@ -197,6 +198,9 @@ def lib():
     L.raht_region_layout.argtypes = [vp, i64, i32, i64, i64, vp, vp]
     L.raht_region_cells.argtypes = [vp, i64, i32, i32, i64, vp, vp, vp]
     L.raht_region_assemble.argtypes = [vp, i64, i64, vp, i64, i64, i32, C.POINTER(i64), i32, vp]
+    L.raht_region_layout_set.argtypes = [vp, i64, i32, vp, i32, vp, vp]
+    L.raht_region_assemble_set.argtypes = [vp, i64, i64, vp, i64, i64, i32, vp, C.POINTER(i64), i32, vp]
+    L.raht_region_needs.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp, i32, vp, i64, C.POINTER(i64), vp]
     L.raht_predict.argtypes = [vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp]
     L.raht_motion_search.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp]
     L.raht_predict_mc.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp]

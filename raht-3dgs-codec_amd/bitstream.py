@@ -15,7 +15,9 @@ with the transform and entropy stages of all frames in common launches (DESIGN.m
 Inside a sequence a frame may be PREDICTED from the reconstruction of an earlier one (``encode_sequence_bytes(..., gop, up,
 inter)``): a wrapper around an ordinary frame whose attributes are the residual ``A - P``, P being ``ops.predict`` of
 the reference's reconstruction (the mean of the reference voxels in the same cell ``up`` octree levels above the voxels; ``up = 0``:
-the co-located voxel). ``decode_frame_bytes`` / ``decode_region_bytes`` refuse the wrapper; ``decode_sequence_bytes`` resolves it.
+the co-located voxel). ``decode_frame_bytes`` / ``decode_region_bytes`` refuse the wrapper; ``decode_sequence_bytes`` resolves it,
+and ``decode_sequence_region`` resolves it for a range of cells of the frame, from the cells of the chain's frames that the
+prediction reaches into (``decode_cells_bytes``: a frame's region made of several cell ranges).
 
     RAHTP001 | int64 ref_back (>= 1: the reference is ref_back frames earlier; this version writes 1) | int64 up (0 .. 3) |
     a whole RAHTF001 frame
@@ -309,15 +311,26 @@ def region_runs(table, J, depth, n_roots):
     tree above ``depth`` (row 0 and every row of a bucket >= J - depth); ``runs`` holds one (coded row, row of the region's own coded
     matrix, count) per finer bucket that has rows in the region, coarse to fine. The region's matrix starts with its ``n_roots``
     root slots (one per occupied cell)."""
-    whole, before, inside = table
-    cut = int(J) - int(depth)
+    return region_runs_set(table, J, depth, n_roots)
+
+
+def region_runs_set(table, J, depth, n_roots):
+    """``region_runs`` for a region of R row ranges (ascending, disjoint runs of depth-``depth`` cells, concatenated), from the
+    table of ``ops.region_layout_set`` (host integers, (1 + 2 R, 22): whole frame, then per range the rows before it and inside
+    it) -> (n_top, runs). The tree above ``depth`` is the same first ``n_top`` coded rows. The region's own plan
+    (``RahtPlan.from_keys`` of the concatenated keys, truncated at the cells) keeps every cell's first row among its ``n_roots``
+    root slots, and in a finer bucket holds range 0's rows of the bucket, then range 1's, and so on: one run per (bucket, range),
+    buckets coarse to fine. Destinations ascend."""
+    whole, cut, R = table[0], int(J) - int(depth), (len(table) - 1) // 2
     n_top = int(sum(whole[cut:]))
     coded, dst, runs = n_top, int(n_roots), []
     for beta in range(cut - 1, -1, -1):
-        if inside[beta]:
-            runs.append((coded + int(before[beta]), dst, int(inside[beta])))
+        for r in range(R):
+            before, inside = int(table[1 + 2 * r][beta]), int(table[2 + 2 * r][beta])
+            if inside:
+                runs.append((coded + before, dst, inside))
+            dst += inside
         coded += int(whole[beta])
-        dst += int(inside[beta])
     return n_top, runs
 
 
@@ -341,31 +354,65 @@ def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys
     not decoded again. info: rows (a, b), n_cells (occupied cells in the range), segments_decoded / segments_total (per channel),
     byte_ranges ((offset, length) within ``blob``: everything outside them may be missing) and bytes_needed, geometry_decoded,
     keys. No N x D matrix is allocated: the only full-length arrays are the keys and the cell search's flags.
-    ``ValueError`` for a corrupt frame or arguments outside the ranges above."""
+    ``ValueError`` for a corrupt frame or arguments outside the ranges above. The one-range call of ``decode_cells_bytes``' core."""
     import torch
+    who = "decode_region_bytes"
     h = parse_frame(blob, max_voxels)
-    J, N, D, n_wide, steps = h["J"], h["N"], h["D"], h["n_wide"], h["steps"]
     try:
         depth, (c0, c1) = int(depth), (int(c) for c in cells)
     except (TypeError, ValueError):
-        raise ValueError("decode_region_bytes: depth is an integer, cells a pair of integers") from None
-    if not 1 <= depth <= J - 1:
-        raise ValueError(f"decode_region_bytes: depth must be 1 .. J - 1 = {J - 1}")
+        raise ValueError(f"{who}: depth is an integer, cells a pair of integers") from None
+    _region_depth(who, h, depth)
     if not 0 <= c0 < c1 <= 8 ** depth:
-        raise ValueError(f"decode_region_bytes: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
-    dev = torch.device(device)
+        raise ValueError(f"{who}: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
+    V, C_rec, info, _ = _decode_cells(who, blob, h, depth, [(c0, c1)], torch.device(device), max_voxels, keys)
+    info["rows"] = info["rows"][0]
+    return V, C_rec, info
+
+
+def decode_cells_bytes(blob, depth, ranges, device="cuda", max_voxels=None, keys=None):
+    """``decode_region_bytes`` for a SET of cell ranges. ranges: a non-empty ascending list of disjoint pairs
+    ``(c0, c1)`` of depth-``depth`` cell indices (0 <= c0 < c1 <= 8^depth, every c0 at or above the c1 before it), 512 at most ->
+    (V_int, C_rec, info) for the concatenation of the ranges' rows: bit for bit the concatenation of ``decode_region_bytes`` over
+    each range. The geometry is decoded once, the tree above ``depth`` once, and one plan over the concatenated keys serves all
+    ranges. info: as ``decode_region_bytes``', with rows a list of (a, b), one per range."""
+    import torch
+    who = "decode_cells_bytes"
+    h = parse_frame(blob, max_voxels)
+    try:
+        depth, ranges = int(depth), [(int(c0), int(c1)) for c0, c1 in ranges]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: depth is an integer, ranges a list of pairs of integers") from None
+    _region_depth(who, h, depth)
+    if not 1 <= len(ranges) <= ops.REGION_MAX_RANGES:
+        raise ValueError(f"{who}: 1 .. {ops.REGION_MAX_RANGES} ranges")
+    if any(not c0 < c1 for c0, c1 in ranges) or any(p[1] > q[0] for p, q in zip(ranges, ranges[1:])) or ranges[0][0] < 0 or ranges[-1][1] > 8 ** depth:
+        raise ValueError(f"{who}: ranges must be ascending, disjoint pairs 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
+    return _decode_cells(who, blob, h, depth, ranges, torch.device(device), max_voxels, keys)[:3]
+
+
+def _region_depth(who, h, depth):
+    if not 1 <= depth <= h["J"] - 1:
+        raise ValueError(f"{who}: depth must be 1 .. J - 1 = {h['J'] - 1}")
+
+
+def _decode_cells(who, blob, h, depth, ranges, dev, max_voxels, keys):
+    """THE region decoder: the frame ``blob`` with its parsed header ``h``, checked ``depth`` and cell ``ranges`` -> (V_int, C_rec,
+    info, the region's keys), the rows of the ranges concatenated. ``who`` opens a refusal."""
+    import torch
+    J, N, D, n_wide, steps = h["J"], h["N"], h["D"], h["n_wide"], h["steps"]
     (go, gl), (ao, al) = h["geometry"], h["attributes"]
     view = memoryview(blob)
     n_d = OctreeCoder.parse(view[go: go + gl], max_voxels)["counts"][depth]
     att = view[ao: ao + al]
     _, _, S, _, _, _, pay = SegmentedCoder._parse(att, N * D)
     nseg = (N + S - 1) // S
-    ranges = [(0, ao + pay)]                                              # frame header, geometry section, attribute header + table
+    byte_ranges = [(0, ao + pay)]                                         # frame header, geometry section, attribute header + table
     if keys is not None:
         if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dtype != torch.int64 or tuple(keys.shape) != (N,):
-            raise ValueError(f"decode_region_bytes: keys must be the ({N},) int64 CUDA tensor an earlier call returned")
+            raise ValueError(f"{who}: keys must be the ({N},) int64 CUDA tensor an earlier call returned")
         keys = keys.contiguous()
-    tl = 3 * (J - depth)
+    tl, R = 3 * (J - depth), len(ranges)
     with torch.cuda.device(dev):
         decoded = keys is None
         if decoded:
@@ -373,37 +420,47 @@ def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys
         try:
             cell_keys, cell_first = ops.region_cells(keys, 3 * J, tl, n_d)
         except ops.RahtError as e:
-            raise ValueError(f"decode_region_bytes: the keys are not this frame's ({e})") from None
-        j = torch.searchsorted(cell_keys, torch.tensor([c0, c1], dtype=torch.int64, device=dev))
-        j0, j1, a, b = torch.cat([j, cell_first[j]]).tolist()
-        info = dict(rows=(a, b), n_cells=j1 - j0, segments_decoded=0, segments_total=nseg, byte_ranges=ranges,
-                    bytes_needed=ranges[0][1], geometry_decoded=decoded, keys=keys)
-        if j0 == j1:
-            return (torch.empty((0, 3), dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev), info)
-        n_top, runs = region_runs(ops.region_layout(keys, 3 * J, a, b).tolist(), J, depth, j1 - j0)
+            raise ValueError(f"{who}: the keys are not this frame's ({e})") from None
+        j = torch.searchsorted(cell_keys, torch.tensor([c for r in ranges for c in r], dtype=torch.int64, device=dev))
+        bounds = cell_first[j]                                               # lo_0, hi_0, lo_1, ...: the rows of every range
+        host = torch.cat([j, bounds]).tolist()
+        js, rows = list(zip(host[0: 2 * R: 2], host[1: 2 * R: 2])), list(zip(host[2 * R:: 2], host[2 * R + 1:: 2]))
+        n_roots, n = sum(j1 - j0 for j0, j1 in js), sum(b - a for a, b in rows)
+        info = dict(rows=rows, n_cells=n_roots, segments_decoded=0, segments_total=nseg, byte_ranges=byte_ranges,
+                    bytes_needed=byte_ranges[0][1], geometry_decoded=decoded, keys=keys)
+        if n_roots == 0:
+            return (torch.empty((0, 3), dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev), info,
+                    torch.empty(0, dtype=torch.int64, device=dev))
+        n_top, runs = region_runs_set(ops.region_layout_set(keys, 3 * J, bounds).tolist(), J, depth, n_roots)
         if n_top != n_d:
-            raise ValueError("decode_region_bytes: the keys are not this frame's")
+            raise ValueError(f"{who}: the keys are not this frame's")
         seg_ids, compact = region_segments(n_top, runs, S)
         sc, att_ranges = SegmentedCoder.from_container_segments(att, seg_ids, dev, max_symbols=N * D)
         Qc = sc.decode(row_major=True)
         # the tree above `depth`: a weighted plan over the occupied cells; its inverse gives every cell's low-pass row
         top = ops.RahtPlan.from_keys(cell_keys, 3 * depth, leaf_weights=cell_first[1:] - cell_first[:-1])
-        roots = top.dequant_inverse(Qc[:n_top], steps)[j0:j1]
+        if R == 1:
+            pick = slice(*js[0])
+            kr = keys[rows[0][0]: rows[0][1]]
+        else:                                                                # the selected cells' rows of the top plan's inverse, gathered
+            pick = torch.cat([torch.arange(j0, j1, device=dev) for j0, j1 in js])
+            kr = torch.cat([keys[a:b] for a, b in rows])
+        roots = top.dequant_inverse(Qc[:n_top], steps)[pick]
         # the region: a plan truncated at the cells over its own rows, its coded matrix put together from the decoded runs
-        plan = ops.RahtPlan.from_keys(keys[a:b], 3 * J, top_level=tl)
-        Qr = ops.region_assemble(Qc, [(compact(r), d, n) for r, d, n in runs], b - a)
-        wide = top.dequant_inverse(Qc[:n_top, :n_wide], steps[:n_wide], dtype=torch.float64)[j0:j1].contiguous() if n_wide else None
+        plan = ops.RahtPlan.from_keys(kr, 3 * J, top_level=tl)
+        Qr = ops.region_assemble_set(Qc, [(compact(r), d, c) for r, d, c in runs], n)
+        wide = top.dequant_inverse(Qc[:n_top, :n_wide], steps[:n_wide], dtype=torch.float64)[pick].contiguous() if n_wide else None
         C_rec = _reconstruct([plan], [Qr], steps, n_wide, roots=roots.contiguous(), roots_wide=wide)[0]
-        V = ops.demorton(keys[a:b], J)
+        V = ops.demorton(kr, J)
         _refuse_outside(int(sc.bad.item()))
-    ranges = [(0, ao)]                                                    # frame header, geometry section, the attributes' length word
+    byte_ranges = [(0, ao)]                                               # frame header, geometry section, the attributes' length word
     for off, ln in att_ranges:                                            # the first: header + table (+ the slots that follow them)
-        if ranges[-1][0] + ranges[-1][1] == ao + off:
-            ranges[-1] = (ranges[-1][0], ranges[-1][1] + ln)
+        if byte_ranges[-1][0] + byte_ranges[-1][1] == ao + off:
+            byte_ranges[-1] = (byte_ranges[-1][0], byte_ranges[-1][1] + ln)
         else:
-            ranges.append((ao + off, ln))
-    info.update(segments_decoded=len(seg_ids), byte_ranges=ranges, bytes_needed=sum(ln for _, ln in ranges))
-    return V, C_rec, info
+            byte_ranges.append((ao + off, ln))
+    info.update(segments_decoded=len(seg_ids), byte_ranges=byte_ranges, bytes_needed=sum(ln for _, ln in byte_ranges))
+    return V, C_rec, info, kr
 
 
 def pack_sequence(frame_blobs):
@@ -764,3 +821,129 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
                 _Predictor(keys, (ref_keys, C_ref), J, hd["up"], motion).restore(C)
     return [done[i][:2] for i in idx]
 
+
+
+def _merge_cells(cells, group, limit=ops.REGION_MAX_RANGES):
+    """ascending, duplicate-free first cells of aligned groups of ``group`` cells (a device tensor) -> the ascending list of
+    disjoint ranges (c0, c1) they cover, neighbours merged. More than ``limit`` ranges are brought down to it by closing the
+    narrowest gaps between them: a needed set may hold more cells than it must, never fewer."""
+    import torch
+    if cells.shape[0] == 0:
+        return []
+    brk = cells[1:] != cells[:-1] + group
+    one = torch.ones(1, dtype=torch.bool, device=cells.device)
+    lo, hi = cells[torch.cat([one, brk])].tolist(), (cells[torch.cat([brk, one])] + group).tolist()
+    if len(lo) > limit:
+        gaps = np.asarray(lo[1:]) - np.asarray(hi[:-1])
+        keep = np.sort(np.argsort(gaps, kind="stable")[len(gaps) - (limit - 1):])      # the limit - 1 widest gaps stay open
+        lo, hi = [lo[0]] + [lo[g + 1] for g in keep], [hi[g] for g in keep] + [hi[-1]]
+    return list(zip(lo, hi))
+
+
+def _region_motion(block_first, mv, rows, dev):
+    """The motion field of a region: ``block_first`` (n_blocks + 1 rows of the whole frame) and ``mv`` of a frame, ``rows`` = [(a,
+    b)] of the region's ranges, ascending -> (block_first, mv) over the rows of the region matrix (the ranges concatenated), as
+    ``ops.predict_mc`` takes them: the blocks that have rows in a range, range by range, each with its first row in the region. A
+    block that two ranges cut is listed once per range."""
+    import torch
+    lo = torch.tensor([a for a, _ in rows], dtype=torch.int64, device=dev)
+    hi = torch.tensor([b for _, b in rows], dtype=torch.int64, device=dev)
+    k0 = torch.searchsorted(block_first, lo, right=True) - 1                 # the block of row a; the first block that starts at b or later
+    k1 = torch.searchsorted(block_first[:-1], hi, right=False)
+    idx, first, base = [], [], 0
+    for (a, b), b0, b1 in zip(rows, k0.tolist(), k1.tolist()):
+        if b > a:
+            idx.append(torch.arange(b0, b1, device=dev))
+            first.append(torch.clamp(block_first[b0:b1] - a, min=0) + base)
+            base += b - a
+    first.append(torch.tensor([base], dtype=torch.int64, device=dev))
+    return torch.cat(first), mv[torch.cat(idx)].contiguous()
+
+
+def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None, max_frames=None, keys=None):
+    """The voxels of the depth-``depth`` cells ``cells = (c0, c1)`` of frame ``i`` of a sequence container, whatever its kind, from
+    the bytes they depend on -> (V_int (n, 3) int64, C_rec (n, D) float32, info): rows [a, b) of
+    ``decode_sequence_bytes(blob, [i])[0]``, bit for bit. The argument rules are ``decode_region_bytes``'; for an intra frame so is
+    the work.
+
+    A predicted frame is resolved along its chain i -> ref(i) -> ... -> the intra frame (``ref_back`` of every wrapper is
+    honoured). Every chain frame f has a NEEDED SET S_f, an ascending list of disjoint ranges of depth-``depth`` cells: S_i =
+    [cells]; for f predicted from g, S_g holds every cell with a reference voxel that the predictor of f can resolve for a row of f
+    inside S_f (``ops.region_needs``: the cell of the row's key, shifted by its block's vector under a motion field; a row whose
+    shifted voxel leaves the cube asks for nothing), widened to the aligned group of cells an ``up``-cell covers where ``up > J -
+    depth``, neighbours merged. The geometry of a chain frame is decoded whole, its attributes for S_f only
+    (``decode_cells_bytes``' core); then the chain is replayed from the intra frame on with the one predictor on the region
+    matrices -- the keys and the reconstruction of S_g as the reference, and under a motion field the blocks that have rows in S_f.
+
+    ``keys``: {frame index: keys} as an earlier call returned in ``info["keys"]``; the frames in it skip the geometry decode.
+    info: chain (the frame indices, intra first), frames ({f: ranges (S_f), rows, n_cells, segments_decoded, segments_total,
+    byte_ranges ((offset, length) within the SEQUENCE blob), bytes_needed, geometry_decoded}; a frame nothing is needed of has no
+    ranges and the bytes of an empty region: its headers, which the walk along the chain reads), bytes_needed (the sum over the
+    chain), byte_ranges (the sequence header's bytes, then every chain frame's: everything outside them may be missing), keys.
+    ``ValueError`` as ``decode_sequence_bytes`` raises it, a frame named by its index; what the headers show is refused before any
+    device work."""
+    import torch
+    who = "decode_sequence_region"
+    off = parse_sequence(blob, max_frames)
+    n = len(off) - 1
+    try:
+        i, depth, (c0, c1) = int(i), int(depth), (int(c) for c in cells)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: i and depth are integers, cells a pair of integers") from None
+    if not 0 <= i < n:
+        raise ValueError(f"{who}: the frame index must be in 0 .. {n - 1}")
+    heads = _frame_heads(memoryview(blob), off, [i], max_voxels)
+    _region_depth(who, heads[i]["h"], depth)                                 # (a chain has one J: _frame_heads)
+    if not 0 <= c0 < c1 <= 8 ** depth:
+        raise ValueError(f"{who}: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
+    if keys is not None and not isinstance(keys, dict):
+        raise ValueError(f'{who}: keys is the dict an earlier call returned in info["keys"]')
+    dev = torch.device(device)
+    chain = sorted(heads)
+    J = heads[i]["h"]["J"]
+    tl = 3 * (J - depth)
+    part, frames, keys_out = {}, {}, {}                                      # part: frame -> (V, C, region keys, region motion)
+    S = [(c0, c1)]
+    with torch.cuda.device(dev):
+        for f in reversed(chain):                                            # down the chain: what is needed of every frame
+            hd = heads[f]
+            h, fb = hd["h"], hd["fb"]
+            base = off[f + 1] - len(fb)                                      # where the inner frame starts in the sequence blob
+            if not S:                                                        # nothing but what the walk along the chain reads: as an empty region
+                ao, al = h["attributes"]
+                head = base - off[f] + ao + SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[6]
+                frames[f] = dict(ranges=[], rows=0, n_cells=0, segments_decoded=0,
+                                 segments_total=(h["N"] + hd["seg_len"] - 1) // hd["seg_len"], byte_ranges=[(off[f], head)],
+                                 bytes_needed=head, geometry_decoded=False)
+                continue
+            try:
+                V, C, info, kr = _decode_cells(who, fb, h, depth, S, dev, max_voxels, None if keys is None else keys.get(f))
+            except ValueError as e:
+                raise ValueError(f"sequence container: frame {f}: {e}") from None
+            keys_out[f] = info["keys"]
+            ranges = [(base + o, ln) for o, ln in info["byte_ranges"]]
+            ranges[0] = (off[f], ranges[0][1] + base - off[f])               # (the wrapper of a predicted frame lies in front)
+            frames[f] = dict(ranges=S, rows=int(kr.shape[0]), n_cells=info["n_cells"], segments_decoded=info["segments_decoded"],
+                             segments_total=info["segments_total"], byte_ranges=ranges, bytes_needed=sum(ln for _, ln in ranges),
+                             geometry_decoded=info["geometry_decoded"])
+            motion = None
+            if hd["kind"] == "P" and kr.shape[0]:
+                if hd["motion"] is not None:
+                    m, mv = hd["motion"]
+                    motion = (m,) + _region_motion(ops.motion_blocks(info["keys"], J, m, len(mv)), torch.from_numpy(mv.copy()).to(dev),
+                                                   info["rows"], dev)[::-1]
+                need = ops.region_needs(kr, J, tl, hd["up"], *((None, None, 0) if motion is None else (motion[2], motion[1], motion[0])))
+                S = _merge_cells(need, 8 ** max(hd["up"] - (J - depth), 0))
+            else:
+                S = []
+            part[f] = (V, C, kr, motion)
+        for f in chain:                                                      # and up again: a reference is whole before it is used
+            hd = heads[f]
+            g = hd["ref"]
+            if f in part and g in part and part[f][2].shape[0] and part[g][2].shape[0]:
+                _, C, kr, motion = part[f]
+                _Predictor(kr, (part[g][2], part[g][1]), J, hd["up"], motion).restore(C)
+    byte_ranges = [(0, off[0])] + [r for f in chain for r in frames[f]["byte_ranges"]]
+    info = dict(chain=chain, frames=frames, bytes_needed=sum(fr["bytes_needed"] for fr in frames.values()), byte_ranges=byte_ranges,
+                keys=keys_out)
+    return part[i][0], part[i][1], info

@@ -9,7 +9,16 @@
 //   cells     the first row of every occupied cell of a depth (flag, the library's scan, scatter): the keys and leaf weights of
 //             the plan of the tree above that depth, and the row range of a range of cells.
 //   assemble  the region's runs out of the matrix the selected segments decode to, into the region's own coded order.
+//
+// A SET of row ranges (a region that a motion field has dilated is not one Morton range) has the same three steps in one pass each:
+//   layout_set    the 2R ascending bounds cut the rows into 2R + 1 intervals (gap, range, gap, ...). A wave counts the buckets of
+//                 the interval it is in with ballots, keeps the counts in its lanes while it stays there, and adds them to the
+//                 interval's bins when it leaves; a second launch turns the bins into the table (a prefix sum over the intervals).
+//   assemble_set  the run table lies in device memory; a destination row finds its run by binary search over the destinations.
+//   needs         the cells of another frame that a prediction of these rows reaches into: flag / scan / scatter of the rows whose
+//                 (shifted) cell differs from the row before, and under a motion field a sort and a second pass over that list.
 #include "raht_common.h"
+#include "predict_device.h"
 
 namespace raht {
 
@@ -103,6 +112,159 @@ __global__ __launch_bounds__(REG_THREADS) void region_assemble_kernel(const int3
     }
 }
 
+// the interval of row i among nb ascending bounds: how many bounds are <= i (0 .. nb); odd: inside range (t - 1) / 2
+__device__ __forceinline__ int region_interval(const int64_t *bounds, int nb, int64_t i)
+{
+    int a = 0, b = nb;
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if (bounds[m] <= i) a = m + 1; else b = m;
+    }
+    return a;
+}
+
+// bins: (nb + 1) x RAHT_REGION_BUCKETS, zeroed by the caller. Whatever the bounds hold, an interval index is 0 .. nb.
+__global__ __launch_bounds__(REG_THREADS) void region_layout_set_kernel(const uint64_t *__restrict__ keys, int64_t n,
+                                                                        const int64_t *__restrict__ bounds, int nb,
+                                                                        unsigned long long *__restrict__ bins)
+{
+    __shared__ int64_t sb[2 * RAHT_REGION_MAX_RANGES];
+    for (int k = threadIdx.x; k < nb; k += REG_THREADS) sb[k] = bounds[k];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    uint32_t acc = 0;                                    // lane b: this wave's rows of bucket b in the interval `cur`
+    int cur = -1;
+    for (int64_t i0 = (int64_t)blockIdx.x * REG_THREADS; i0 < n; i0 += (int64_t)gridDim.x * REG_THREADS) {
+        const int64_t i = i0 + threadIdx.x;
+        int b = -1, t = -1;
+        if (i < n) {
+            b = i ? region_bucket(keys[i], keys[i - 1]) : RAHT_REGION_BUCKETS - 1;
+            t = region_interval(sb, nb, i);
+        }
+        uint64_t todo = __ballot(i < n);
+        while (todo) {                                   // one round per interval the wave's 64 rows touch: nearly always one
+            const int tt = __shfl(t, __ffsll((unsigned long long)todo) - 1);
+            const uint64_t m_t = __ballot(t == tt);
+            if (tt != cur) {
+                if (cur >= 0 && lane < RAHT_REGION_BUCKETS && acc) atomicAdd(&bins[(int64_t)cur * RAHT_REGION_BUCKETS + lane], (unsigned long long)acc);
+                acc = 0;
+                cur = tt;
+            }
+            for (int k = 0; k < RAHT_REGION_BUCKETS; ++k) {
+                const uint64_t m = __ballot(b == k);
+                if (lane == k) acc += (uint32_t)__popcll(m & m_t);
+            }
+            todo &= ~m_t;
+        }
+    }
+    if (cur >= 0 && lane < RAHT_REGION_BUCKETS && acc) atomicAdd(&bins[(int64_t)cur * RAHT_REGION_BUCKETS + lane], (unsigned long long)acc);
+}
+
+// bins -> table: the whole frame, then per range the rows before it (a running sum over the intervals) and inside it
+__global__ void region_layout_set_table_kernel(const unsigned long long *__restrict__ bins, int R, int64_t *__restrict__ table)
+{
+    const int b = threadIdx.x;
+    if (b >= RAHT_REGION_BUCKETS) return;
+    int64_t run = 0;
+    for (int r = 0; r < R; ++r) {
+        run += (int64_t)bins[(int64_t)(2 * r) * RAHT_REGION_BUCKETS + b];
+        const int64_t inside = (int64_t)bins[(int64_t)(2 * r + 1) * RAHT_REGION_BUCKETS + b];
+        table[(int64_t)(1 + 2 * r) * RAHT_REGION_BUCKETS + b] = run;
+        table[(int64_t)(2 + 2 * r) * RAHT_REGION_BUCKETS + b] = inside;
+        run += inside;
+    }
+    table[b] = run + (int64_t)bins[(int64_t)(2 * R) * RAHT_REGION_BUCKETS + b];
+}
+
+// region_assemble_kernel with the runs in device memory (3 int64 per run: source row, destination row, count). A destination row
+// belongs to the last run that starts at or before it; every source row is clamped into src, so that no table reads outside it.
+__global__ __launch_bounds__(REG_THREADS) void region_assemble_set_kernel(const int32_t *__restrict__ src, int64_t ld_src, int64_t n_src_rows,
+                                                                          int32_t *__restrict__ dst, int64_t ld_dst, int D,
+                                                                          const int64_t *__restrict__ runs, int n_runs, int64_t n_dst_rows)
+{
+    __shared__ int64_t from[REG_TILE_ROWS];
+    const int64_t n_tiles = (n_dst_rows + REG_TILE_ROWS - 1) / REG_TILE_ROWS;
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t r0 = t * REG_TILE_ROWS;
+        const int rows = (int)min((int64_t)REG_TILE_ROWS, n_dst_rows - r0);
+        __syncthreads();                                 // the previous step's readers are done with `from`
+        if ((int)threadIdx.x < rows) {
+            const int64_t r = r0 + threadIdx.x;
+            int a = 0, b = n_runs;                       // first run whose destination is > r
+            while (a < b) {
+                const int m = (a + b) >> 1;
+                if (runs[3 * (int64_t)m + 1] <= r) a = m + 1; else b = m;
+            }
+            int64_t f = -1;
+            if (a > 0) {
+                const int64_t *run = runs + 3 * (int64_t)(a - 1);
+                const int64_t off = r - run[1];
+                if (off < run[2]) f = max(min(max(run[0], (int64_t)0) + off, n_src_rows - 1), (int64_t)0);      // (max: a sum that wrapped)
+            }
+            from[threadIdx.x] = f;
+        }
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < (uint32_t)rows * (uint32_t)D; e += REG_THREADS) {
+            const uint32_t j = e / (uint32_t)D, c = e - j * (uint32_t)D;
+            const int64_t f = from[j];
+            dst[(r0 + j) * ld_dst + c] = f >= 0 ? src[f * ld_src + c] : 0;
+        }
+    }
+}
+
+constexpr uint64_t NEEDS_NONE = ~0ull;                   // the cell of a row without a match (no cell index has 64 bits)
+
+// the cell a prediction of row i reaches into: the key KEY resolves the row for, cut to its `wide`-bit cell and written as the
+// first cell of that group at top_level (wide >= top_level)
+template <typename KEY>
+__device__ __forceinline__ uint64_t needs_cell(const uint64_t *__restrict__ keys, int64_t i, int top_level, int wide, const KEY &key_of)
+{
+    uint64_t k;
+    if (!key_of(i, keys[i], k)) return NEEDS_NONE;
+    return (k >> wide) << (wide - top_level);
+}
+
+template <typename KEY>
+__global__ __launch_bounds__(REG_THREADS) void region_needs_flag_kernel(const uint64_t *__restrict__ keys, int64_t n, int top_level, int wide,
+                                                                        const KEY key_of, uint32_t *__restrict__ flag)
+{
+    for (int64_t i = (int64_t)blockIdx.x * REG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * REG_THREADS) {
+        const uint64_t c = needs_cell(keys, i, top_level, wide, key_of);
+        flag[i] = (c != NEEDS_NONE && (i == 0 || needs_cell(keys, i - 1, top_level, wide, key_of) != c)) ? 1u : 0u;
+    }
+}
+
+// every store is bounded by cap
+template <typename KEY>
+__global__ __launch_bounds__(REG_THREADS) void region_needs_scatter_kernel(const uint64_t *__restrict__ keys, int64_t n, int top_level, int wide,
+                                                                           const KEY key_of, const uint32_t *__restrict__ flag,
+                                                                           const uint32_t *__restrict__ pos, int64_t cap,
+                                                                           uint64_t *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * REG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * REG_THREADS) {
+        if (!flag[i]) continue;
+        const int64_t j = (int64_t)pos[i];
+        if (j < cap) out[j] = needs_cell(keys, i, top_level, wide, key_of);
+    }
+}
+
+// the second pass, over the sorted list: an entry that differs from the one before it
+__global__ __launch_bounds__(REG_THREADS) void region_needs_first_kernel(const uint64_t *__restrict__ list, int64_t n, uint32_t *__restrict__ flag)
+{
+    for (int64_t i = (int64_t)blockIdx.x * REG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * REG_THREADS)
+        flag[i] = (i == 0 || list[i] != list[i - 1]) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(REG_THREADS) void region_needs_pick_kernel(const uint64_t *__restrict__ list, int64_t n, const uint32_t *__restrict__ flag,
+                                                                        const uint32_t *__restrict__ pos, int64_t cap, uint64_t *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * REG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * REG_THREADS) {
+        if (!flag[i]) continue;
+        const int64_t j = (int64_t)pos[i];
+        if (j < cap) out[j] = list[i];
+    }
+}
+
 static inline unsigned region_grid(int64_t items, int64_t per_block)
 {
     const int64_t g = ceil_div(items, per_block);
@@ -116,6 +278,20 @@ static int region_check_keys(const char *what, const void *keys, int64_t N, int 
     if (N < 1 || N >= ((int64_t)1 << 31)) { set_error("%s: N must be 1 .. 2^31 - 1", what); return RAHT_ERR_INVALID; }
     if (nbits < 1 || nbits > 63) { set_error("%s: nbits=%d (1..63)", what, nbits); return RAHT_ERR_INVALID; }
     return RAHT_OK;
+}
+
+// raht_region_needs for checked arguments: the rows' cells with neighbouring repeats dropped -> first (capacity cap), their number
+template <typename KEY>
+static int region_needs_first(const uint64_t *keys, int64_t N, int top_level, int wide, const KEY &key_of, uint32_t *flag, uint32_t *pos,
+                              uint32_t *total, uint64_t *first, int64_t cap, uint32_t *found, hipStream_t s)
+{
+    const dim3 grid(region_grid(N, REG_THREADS * 4)), blk(REG_THREADS);
+    hipLaunchKernelGGL(region_needs_flag_kernel<KEY>, grid, blk, 0, s, keys, N, top_level, wide, key_of, flag);
+    RAHT_RET(exclusive_scan_u32(flag, pos, N, total, s));
+    hipLaunchKernelGGL(region_needs_scatter_kernel<KEY>, grid, blk, 0, s, keys, N, top_level, wide, key_of, (const uint32_t *)flag,
+                       (const uint32_t *)pos, cap, first);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return read_back_u32(found, total, 1, nullptr, nullptr, 0, s);
 }
 
 }  // namespace raht
@@ -196,6 +372,102 @@ int raht_region_assemble(const int32_t *src, int64_t ld_src, int64_t n_src_rows,
                        ld_src, dst, ld_dst, D, rr, n_dst_rows);
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
+}
+
+int raht_region_layout_set(const uint64_t *keys_sorted, int64_t N, int nbits, const int64_t *row_bounds, int R, int64_t *table,
+                           raht_stream_t stream)
+{
+    RAHT_RET(region_check_keys("raht_region_layout_set", keys_sorted, N, nbits));
+    if (!row_bounds || !table) { set_error("raht_region_layout_set: NULL row_bounds or table"); return RAHT_ERR_INVALID; }
+    if (R < 1 || R > RAHT_REGION_MAX_RANGES) { set_error("raht_region_layout_set: R=%d (1..%d)", R, RAHT_REGION_MAX_RANGES); return RAHT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_bins = (size_t)(2 * R + 1) * RAHT_REGION_BUCKETS;
+    Scratch ws(sizeof(unsigned long long) * n_bins, s);  // (returns to the pool stream-ordered, behind the two launches)
+    if (!ws.ok()) { set_error("raht_region_layout_set: out of device memory"); return RAHT_ERR_NOMEM; }
+    unsigned long long *bins = ws.as<unsigned long long>();
+    RAHT_HIP_CHECK(hipMemsetAsync(bins, 0, sizeof(unsigned long long) * n_bins, s));
+    hipLaunchKernelGGL(region_layout_set_kernel, dim3(region_grid(N, REG_THREADS * 4)), dim3(REG_THREADS), 0, s, keys_sorted, N, row_bounds,
+                       2 * R, bins);
+    hipLaunchKernelGGL(region_layout_set_table_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)bins, R, table);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+int raht_region_assemble_set(const int32_t *src, int64_t ld_src, int64_t n_src_rows, int32_t *dst, int64_t ld_dst, int64_t n_dst_rows, int D,
+                             const int64_t *runs, const int64_t *runs_host, int n_runs, raht_stream_t stream)
+{
+    if (!src || !dst || (n_runs > 0 && !runs)) { set_error("raht_region_assemble_set: NULL argument"); return RAHT_ERR_INVALID; }
+    if (D < 1 || ld_src < D || ld_dst < D) { set_error("raht_region_assemble_set: bad D/ld"); return RAHT_ERR_INVALID; }
+    if (n_src_rows < 1 || n_dst_rows < 1 || n_src_rows >= ((int64_t)1 << 31) || n_dst_rows >= ((int64_t)1 << 31)) {
+        set_error("raht_region_assemble_set: both matrices hold 1 .. 2^31 - 1 rows");
+        return RAHT_ERR_INVALID;
+    }
+    if (n_runs < 0 || n_runs > RAHT_REGION_BUCKETS * RAHT_REGION_MAX_RANGES) {
+        set_error("raht_region_assemble_set: n_runs must be 0 .. %d", RAHT_REGION_BUCKETS * RAHT_REGION_MAX_RANGES);
+        return RAHT_ERR_INVALID;
+    }
+    int64_t dst_end = 0;                                 // the caller's host copy of the table, when there is one: raht_region_assemble's rules
+    for (int k = 0; runs_host && k < n_runs; ++k) {
+        const int64_t sr = runs_host[3 * k], dr = runs_host[3 * k + 1], cnt = runs_host[3 * k + 2];
+        if (cnt < 0 || sr < 0 || sr > n_src_rows - cnt || dr < dst_end || dr > n_dst_rows - cnt) {
+            set_error("raht_region_assemble_set: run %d (%lld, %lld, %lld) leaves a matrix or overlaps the run before it", k, (long long)sr,
+                      (long long)dr, (long long)cnt);
+            return RAHT_ERR_INVALID;
+        }
+        dst_end = dr + cnt;
+    }
+    hipLaunchKernelGGL(region_assemble_set_kernel, dim3(region_grid(n_dst_rows, REG_TILE_ROWS)), dim3(REG_THREADS), 0, (hipStream_t)stream, src,
+                       ld_src, n_src_rows, dst, ld_dst, D, runs, n_runs, n_dst_rows);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
+}
+
+int raht_region_needs(const uint64_t *keys_sorted, int64_t N, int J, int top_level, int up, const int64_t *block_first, int64_t n_blocks,
+                      const int8_t *mv, int block_log2, uint64_t *cells, int64_t capacity, int64_t *n_cells, raht_stream_t stream)
+{
+    if (J < 1 || J > 21) { set_error("raht_region_needs: J=%d (1..21)", J); return RAHT_ERR_INVALID; }
+    RAHT_RET(region_check_keys("raht_region_needs", keys_sorted, N, 3 * J));
+    if (!cells || !n_cells || capacity < 1) { set_error("raht_region_needs: NULL output or no capacity"); return RAHT_ERR_INVALID; }
+    if (top_level % 3 || top_level < 3 || top_level > 3 * J - 3) {
+        set_error("raht_region_needs: top_level=%d must be a multiple of 3 in [3, 3 J - 3]", top_level);
+        return RAHT_ERR_INVALID;
+    }
+    if (up < 0 || up > 3) { set_error("raht_region_needs: up=%d (0..3)", up); return RAHT_ERR_INVALID; }
+    if (mv && (!block_first || n_blocks < 1 || n_blocks > N || block_log2 < 1 || block_log2 > J)) {
+        set_error("raht_region_needs: a motion field needs block_first, 1 <= n_blocks <= N and block_log2 in 1 .. J");
+        return RAHT_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int wide = 3 * up > top_level ? 3 * up : top_level;
+    return guarded("raht_region_needs", [&]() -> int {
+        // without a field the rows' cells ascend: the first pass is the answer. Under one they do not: its list is sorted and passed again.
+        Scratch ws((mv ? 2 * sizeof(uint64_t) + sizeof(uint32_t) : 0) * (size_t)N + sizeof(uint32_t) * (2 * (size_t)N + 2), s);
+        if (!ws.ok()) { set_error("raht_region_needs: out of device memory"); return RAHT_ERR_NOMEM; }
+        uint64_t *first = mv ? ws.as<uint64_t>() : cells, *sorted = mv ? first + N : nullptr;
+        uint32_t *flag = mv ? (uint32_t *)(sorted + N) : ws.as<uint32_t>(), *pos = flag + N, *total = pos + N, *idx = total + 2;
+        uint32_t found = 0;
+        if (mv)
+            RAHT_RET(region_needs_first(keys_sorted, N, top_level, wide, MvKey{block_first, n_blocks, mv, J}, flag, pos, total, first, N, &found, s));
+        else
+            RAHT_RET(region_needs_first(keys_sorted, N, top_level, wide, SameKey{}, flag, pos, total, first, capacity, &found, s));
+        if (mv && found) {
+            const int64_t M = (int64_t)found;            // (<= N: one flag per row)
+            RAHT_RET(sort_keys_u32idx(first, M, 3 * J - top_level, sorted, idx, s));
+            const dim3 grid(region_grid(M, REG_THREADS * 4)), blk(REG_THREADS);
+            hipLaunchKernelGGL(region_needs_first_kernel, grid, blk, 0, s, (const uint64_t *)sorted, M, flag);
+            RAHT_RET(exclusive_scan_u32(flag, pos, M, total, s));
+            hipLaunchKernelGGL(region_needs_pick_kernel, grid, blk, 0, s, (const uint64_t *)sorted, M, (const uint32_t *)flag,
+                               (const uint32_t *)pos, capacity, cells);
+            RAHT_HIP_CHECK(hipGetLastError());
+            RAHT_RET(read_back_u32(&found, total, 1, nullptr, nullptr, 0, s));
+        }
+        *n_cells = (int64_t)found;
+        if ((int64_t)found > capacity) {
+            set_error("raht_region_needs: %u cells, the caller's buffer holds %lld", found, (long long)capacity);
+            return RAHT_ERR_INVALID;
+        }
+        return RAHT_OK;
+    });
 }
 
 }  // extern "C"

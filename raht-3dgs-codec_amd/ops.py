@@ -897,6 +897,87 @@ def region_assemble(src, runs, n_dst_rows):
     return dst
 
 
+REGION_MAX_RANGES = 512                                      # RAHT_REGION_MAX_RANGES
+
+
+@torch.no_grad()
+def region_layout_set(keys_sorted, nbits, row_bounds):
+    """``region_layout`` for R row ranges in one pass over the keys (raht_region_layout_set). row_bounds: (2 R,) int64 on the keys'
+    device, lo_0, hi_0, lo_1, ... ascending, R <= 512 -> (1 + 2 R, 22) int64 device tensor: rows per bucket in the whole frame, then
+    per range in [0, lo_r) and in [lo_r, hi_r). With R = 1 it is ``region_layout``'s table. Enqueued only."""
+    k = _region_keys(keys_sorted, "region_layout_set")
+    _need_cuda(row_bounds, "row_bounds")
+    if row_bounds.dtype != torch.int64 or row_bounds.dim() != 1 or row_bounds.shape[0] % 2 or row_bounds.device != k.device:
+        raise ValueError("region_layout_set: row_bounds must be a 1-D int64 tensor of 2 R entries on the keys' device")
+    R = int(row_bounds.shape[0]) // 2
+    if not 1 <= R <= REGION_MAX_RANGES:
+        raise ValueError(f"region_layout_set: 1 .. {REGION_MAX_RANGES} ranges")
+    rb = row_bounds.contiguous()
+    table = torch.empty((1 + 2 * R, REGION_BUCKETS), dtype=torch.int64, device=k.device)
+    _call(_lib.lib().raht_region_layout_set, k.device, _p(k), k.shape[0], int(nbits), _p(rb), R, _p(table))
+    return table
+
+
+@torch.no_grad()
+def region_assemble_set(src, runs, n_dst_rows):
+    """``region_assemble`` with any number of runs up to 22 * 512 (raht_region_assemble_set). runs: ``(src_row, dst_row, count)``
+    triples, destinations ascending and disjoint -- as a host list or array they are checked here (``RahtError`` for a run that
+    leaves a matrix or overlaps the one before it) and uploaded; as a (n, 3) int64 tensor on ``src``'s device they are the caller's
+    word, and the kernel clamps every source row into ``src``. -> (n_dst_rows, D) int32, rows no run covers 0. One launch."""
+    import numpy as np
+    _need_cuda(src, "src")
+    if src.dtype != torch.int32 or src.dim() != 2 or src.stride(1) != 1 or src.shape[0] < 1:
+        raise ValueError("region_assemble_set: src must be a non-empty int32 matrix with contiguous rows")
+    D = int(src.shape[1])
+    if isinstance(runs, torch.Tensor) and runs.is_cuda:
+        if runs.dtype != torch.int64 or runs.dim() != 2 or runs.shape[1] != 3 or runs.device != src.device:
+            raise ValueError("region_assemble_set: a device table is (n, 3) int64 on src's device")
+        table, host = runs.contiguous(), None
+    else:
+        flat = np.ascontiguousarray(np.asarray(runs, np.int64).reshape(-1, 3))
+        host = flat.ctypes.data_as(C.POINTER(C.c_int64))
+        table = torch.from_numpy(flat).to(src.device)
+    dst = torch.empty((int(n_dst_rows), D), dtype=torch.int32, device=src.device)
+    _call(_lib.lib().raht_region_assemble_set, src.device, _p(src), src.stride(0), src.shape[0], _p(dst), D, int(n_dst_rows), D,
+          C.c_void_p(table.data_ptr()) if table.shape[0] else None, host, int(table.shape[0]))
+    return dst
+
+
+@torch.no_grad()
+def region_needs(keys, J, top_level, up, block_first=None, mv=None, block_log2=0, capacity=None):
+    """The cells, ``top_level / 3`` octree levels above the voxels, of a reference frame that the predictor of the rows ``keys``
+    (strictly ascending int64 Morton keys on the GPU) reaches into (raht_region_needs) -> (n,) int64 on the device,
+    ascending and without repeats: ``k' >> top_level`` of every row with a match, k' the row's key shifted by the vector of its
+    block (mv (n_blocks, 3) int8, block_first (n_blocks + 1,) int64 rows of ``keys``, as ``predict_mc`` takes them), or the key
+    itself without a field. Where ``3 up > top_level`` an entry is the first cell of the aligned group of cells that the
+    ``up``-cell covers; widening it to the group is the caller's. ``capacity``: the entries the result may have (default: as many
+    as there can be); ``RahtError`` for more. Synchronises."""
+    J, tl, up = int(J), int(top_level), int(up)
+    if mv is None:
+        k = _region_keys(keys, "region_needs")
+        bf, field, n_blocks, m = None, None, 0, 0
+    else:
+        k, J, m = _motion_frame("region_needs", keys, J, block_log2)
+        _need_cuda(block_first, "block_first")
+        _need_cuda(mv, "mv")
+        if block_first.dtype != torch.int64 or block_first.dim() != 1 or not 2 <= block_first.shape[0] <= k.shape[0] + 1:
+            raise ValueError("region_needs: block_first must hold n_blocks + 1 int64 rows, 1 <= n_blocks <= N")
+        n_blocks = int(block_first.shape[0]) - 1
+        if mv.dtype != torch.int8 or tuple(mv.shape) != (n_blocks, 3):
+            raise ValueError(f"region_needs: mv must be a ({n_blocks}, 3) int8 tensor")
+        bf, field = block_first.contiguous(), mv.contiguous()
+    if capacity is None:
+        capacity = min(int(k.shape[0]), 8 ** max(J - tl // 3, 0))
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError("region_needs: capacity must be at least 1")
+    cells = torch.empty(capacity, dtype=torch.int64, device=k.device)
+    n = C.c_int64(0)
+    _call(_lib.lib().raht_region_needs, k.device, _p(k), k.shape[0], J, tl, up, _p(bf), n_blocks, _p(field), m, _p(cells), capacity,
+          C.byref(n))
+    return cells[: n.value]
+
+
 def _predict_rows(M, n_rows, D, name):
     """a float32 CUDA matrix of the predictor, as it is: (n_rows, D), unit column stride, a row stride of at least D"""
     _need_cuda(M, name)
