@@ -76,6 +76,12 @@ int raht_version(void);
  *
  * V: N x 3 (x, y, z) coordinates holding integers, already Morton-sorted and duplicate-free, in
  * v_dtype. Vint = floor((V - minV) / (width / 2^depth)); key = sum_k (z_k + 2 y_k + 4 x_k) << 3k.
+ * The arithmetic is IEEE float64 for EVERY element type (RAHT_F32, RAHT_I32 and RAHT_I64 coordinates are
+ * converted to double first, as RAHT_param.py:21-24 promotes them): subtract, divide, floor, bit for bit
+ * what the reference computes on the CPU, also on and next to voxel faces and for a width that is no
+ * power of two. depth is 1..21 (up to 63-bit keys). Any coordinate whose index is not in [0, 2^depth) is
+ * RAHT_ERR_BOUNDS, and so is any non-finite one (NaN, +-inf) and any value no int64 holds: the real value
+ * is tested before it is converted. The error text names the first offending row.
  * Instead of the reference's per-level List / Flags / weights the plan stores three arrays of
  * length N derived from the sorted keys:
  *     lvl[i] = msb(key[i] ^ key[i-1])    the one binary level at which row i is a right sibling

@@ -129,7 +129,7 @@ def raht_param(V, minV, width, depth, ref_quirks=True):
     rc = lib().orc_param_build(_ptr(V), V.shape[0], _ptr(minV), float(width), int(depth),
                                1 if ref_quirks else 0, C.byref(h))
     if rc:
-        raise ValueError("orc_param_build failed")
+        raise ValueError("orc_param_build: a coordinate is non-finite or outside [0, 2^depth)" if rc == -3 else "orc_param_build failed")
     return Param(h)
 
 

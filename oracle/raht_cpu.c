@@ -49,16 +49,18 @@ int raht_cpu_plan_create(const void *V, int v_dtype, int64_t N, const double min
         }
     }
     const double Q = width / (double)((uint64_t)1 << depth);
-    const int64_t hi = (int64_t)1 << depth;
+    const double hi = (double)((int64_t)1 << depth);
     int64_t *Vi = (int64_t *)malloc(sizeof(int64_t) * 3 * (size_t)N);
     uint64_t *mc = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)N);
     if (!Vi || !mc) { free(Vd); free(Vi); free(mc); return RAHT_ERR_NOMEM; }
     int rc = RAHT_OK;
     for (int64_t i = 0; i < N && rc == RAHT_OK; ++i)
         for (int a = 0; a < 3; ++a) {
-            const int64_t q = (int64_t)floor((Vd[3 * i + a] - minV[a]) / Q);     /* RAHT_param.py:205-206 */
-            if (q < 0 || q >= hi) { set_err("coordinate out of [0, 2^%d) at row %lld", depth, (long long)i); rc = RAHT_ERR_BOUNDS; break; }
-            Vi[3 * i + a] = q;
+            const double q = floor((Vd[3 * i + a] - minV[a]) / Q);               /* RAHT_param.py:205-206 */
+            /* the real value is tested, and only a value in range is converted (raht_plan_create's rule: NaN, infinities and
+             * values no int64 holds are out of bounds) */
+            if (!(q >= 0 && q < hi)) { set_err("coordinate out of [0, 2^%d) at row %lld", depth, (long long)i); rc = RAHT_ERR_BOUNDS; break; }
+            Vi[3 * i + a] = (int64_t)q;
         }
     if (rc == RAHT_OK) {
         orc_morton(Vi, N, depth, mc);

@@ -84,12 +84,19 @@ int orc_param_build(const double *V, int64_t N, const double minV[3], double wid
                     int ref_quirks, orc_param **out)
 {
     if (N < 1 || depth < 1 || depth > 21) return -1;
+    /* :205-212  Q, Vint, Morton (digit = z + 2y + 4x). The real value is tested BEFORE it is converted, as raht_plan_create and
+     * raht_cpu_plan_create do: a NaN, an infinity or a value no int64 holds has no defined conversion (RAHT_param.py:26-27
+     * raises OutOfBounds for all of them) */
+    const double Q = width / (double)((uint64_t)1 << depth);
+    const double hi = (double)((uint64_t)1 << depth);
+    for (int64_t n = 0; n < 3 * N; ++n) {
+        const double q = floor((V[n] - minV[n % 3]) / Q);
+        if (!(q >= 0 && q < hi)) return -3;
+    }
     orc_param *p = (orc_param *)calloc(1, sizeof(orc_param));
     p->N = N;
     p->order_len = -1;
 
-    /* :205-212  Q, Vint, Morton (digit = z + 2y + 4x) */
-    const double Q = width / (double)((uint64_t)1 << depth);
     int64_t *Vint = (int64_t *)malloc(sizeof(int64_t) * 3 * (size_t)N);
     for (int64_t n = 0; n < N; ++n)
         for (int a = 0; a < 3; ++a)

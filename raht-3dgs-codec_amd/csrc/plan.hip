@@ -74,12 +74,19 @@ __global__ void keys_from_coords_kernel(const VT *__restrict__ V, int64_t N, dou
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    // RAHT_param.py:205-206  Vint = floor((V - minV) / Q)
-    const int64_t x = (int64_t)floor(((double)V[3 * i + 0] - m0) / Q);
-    const int64_t y = (int64_t)floor(((double)V[3 * i + 1] - m1) / Q);
-    const int64_t z = (int64_t)floor(((double)V[3 * i + 2] - m2) / Q);
-    const int64_t hi = (int64_t)1 << depth;
-    if (x < 0 || y < 0 || z < 0 || x >= hi || y >= hi || z >= hi) report(err, RAHT_ERR_BOUNDS, i);
+    // RAHT_param.py:205-206  Vint = floor((V - minV) / Q), in float64 for every element type (:21-24 promotes)
+    const double x = floor(((double)V[3 * i + 0] - m0) / Q);
+    const double y = floor(((double)V[3 * i + 1] - m1) / Q);
+    const double z = floor(((double)V[3 * i + 2] - m2) / Q);
+    const double hi = (double)((int64_t)1 << depth);
+    // The REAL value is range-checked and only a value in range is converted: the conversion to int64 has no NaN test (a NaN
+    // came out as voxel 0, in range), and an infinity or a value no int64 holds saturates to whatever the instruction gives.
+    // Written so that a NaN fails: RAHT_param.py:26-27 raises OutOfBounds for it.
+    if (!(x >= 0 && x < hi && y >= 0 && y < hi && z >= 0 && z < hi)) {
+        report(err, RAHT_ERR_BOUNDS, i);
+        keys[i] = 0;
+        return;
+    }
     keys[i] = morton3((uint64_t)x, (uint64_t)y, (uint64_t)z);
 }
 

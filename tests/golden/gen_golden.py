@@ -571,3 +571,63 @@ def merge_cases():
 
 if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "merge_prepare"):
     merge_cases()
+
+
+def coord_cases():
+    """Plan construction from coordinates that are NOT float64 voxel indices under a zero origin: the clouds of
+    tests/plan_coord_cases.py that carry a fixture name (shifted origin, widths that are no power of two, points on and next to
+    voxel faces, one float32 input) through the reference's RAHT_param (RAHT_param.py:6-83) and RAHT_param_reorder_fast (:190-279),
+    then RAHT2_optimized on three seeded float64 columns. Written to tests/golden/coords/ (a directory of its own: every
+    tests/golden/*.npz outside the named families is fed to the transform tests with a zero origin and width 2^J).
+
+    Neither function hands out its Morton codes, so they are restated here from each one's own quantization line -- :24 (minV and V
+    promoted to float64) and :206 (the dtypes as they come: a float32 minV is NOT promoted) -- and the reference's get_morton_code;
+    the generator asserts that both give the same codes and the same List / Flags / weights. The float32 input is one for which
+    float32 arithmetic is exact (integers under an origin of halves and quarters), so that both agree. The lists, order_RAGFT and T
+    recorded are RAHT_param_reorder_fast's (``lists_from``).
+
+    Depth 21 (63-bit keys, the ~3000-voxel cloud deep_j21) is recorded too: the reference takes it -- its mask table's 1 << 63
+    wraps to INT64_MIN minus 2^j, whose low 63 bits are the mask that is meant, and both functions agree with each other."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests import plan_coord_cases as pc
+    out_dir = os.path.join(HERE, "coords")
+    os.makedirs(out_dir, exist_ok=True)
+    tdt = {"f32": torch.float32, "f64": torch.float64}
+
+    def codes(Vt, mt, width, J, promote):
+        Q = width / (2 ** J)
+        if promote:
+            Vint = torch.floor((Vt.to(torch.float64) - mt.to(torch.float64)) / Q).to(torch.int64)      # RAHT_param.py:21-24
+        else:
+            Vint = torch.floor((Vt - mt) / Q).to(torch.int64)                                          # RAHT_param.py:205-206
+        return get_morton_code(Vint, J).numpy().astype(np.uint64)
+
+    for case in pc.FIXTURES:
+        name, dt = case.fixture
+        V = case.cast(dt)
+        N, J, width = V.shape[0], case.J, case.width
+        assert N <= 2000 or case is pc.DEEP
+        Vt = torch.from_numpy(V)
+        mt = torch.tensor(case.minV, dtype=tdt[dt])
+        assert mt.to(torch.float64).tolist() == list(case.minV)
+        List, Flags, weights, order = RAHT_param_reorder_fast(Vt, mt, width, J)
+        L2, F2, W2 = RAHT_param(Vt, mt, width, J)
+        mc = codes(Vt, mt, width, J, True)
+        assert np.array_equal(mc, codes(Vt, mt, width, J, False)), name
+        assert len(L2) == len(List) and len(F2) == len(Flags) and len(W2) == len(weights), name
+        for a, b in zip(L2 + F2 + W2, List + Flags + weights):
+            assert torch.equal(a.long(), b.long()), name
+        C = np.random.default_rng(N * 1000 + J).standard_normal((N, 3)).astype(np.float32).astype(np.float64)   # float32 values: one input for both precisions
+        T, w = RAHT2_optimized(torch.from_numpy(C), List, Flags, weights)
+        np.savez_compressed(
+            os.path.join(out_dir, name + ".npz"),
+            V=V, minV=np.asarray(case.minV, np.float64), width=np.float64(width), J=np.int32(J), C=C, morton=mc,
+            level_len=np.array([len(l) for l in List], dtype=np.int64), list_cat=torch.cat(List).numpy().astype(np.int32),
+            flags_cat=np.packbits(torch.cat(Flags).numpy().astype(np.uint8)), weights_cat=torch.cat(weights).numpy().astype(np.int32),
+            order=order.numpy().astype(np.int64), order_is_none=np.bool_(False), T=T.numpy(), w=w.numpy().reshape(-1),
+            lists_from=np.array("RAHT_param_reorder_fast"), case=np.array(case.name))
+        print(f"coords/{name}: N={N} J={J} width={width} dtype={V.dtype} levels={len(Flags)}")
+
+
+if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "coords"):
+    coord_cases()
