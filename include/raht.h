@@ -817,6 +817,41 @@ int raht_octree_bytes(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_o
 int raht_demorton(const uint64_t *keys, int64_t N, int J, int64_t *V, raht_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Predicted octree geometry (csrc/octree_inter.hip): a frame's occupancy stream coded against the REFERENCE frame's occupancy of
+ * the same cells (python: geometry.OctreeCoder.encode / decode with ref_keys; bitstream.encode_sequence_bytes(...,
+ * geometry_inter)). Where part of a scene stands still most residual bytes are 0.
+ *
+ * The frame: N strictly ascending keys k < 8^J. The reference: N_ref >= 1 strictly ascending keys r of the same J.
+ *   pred[v]  for the node v of level g (0 <= g < J) with cell key c, s = 3 (J - g): the reference's occupancy byte of the same
+ *            cell -- bit d set <=> some r[i] has r[i] >> (s - 3) == 8 c + d; 0 where the reference has no voxel in the cell
+ *   res[v]   = occ[v] ^ pred[v], in the order of the occupancy stream (level 0 first, ascending key inside a level)
+ *   predicted section : "OCTP0001" | int64 J, N, mode, n_nodes, seg_len, N_ref, n_used | int64 n_0 ... n_J | body
+ *                       The body is laid out as in "OCTG0001". mode 0: the n_nodes residual bytes (n_used = 0). mode 1:
+ *                       byte_of_rank[256], the uint32 length of every RLGR segment, the streams in 4-byte slots; the ranks follow
+ *                       the rule of raht_octree_symbols applied to res. Byte 0 is an ordinary value here (normally rank 0), so the
+ *                       header carries n_used, the number of byte values that occur (1 .. 256): a symbol >= n_used is an error.
+ *
+ *   raht_octree_encode_inter : res[n_nodes] from the keys, the counts of raht_octree_counts and the reference's keys. The
+ *                              bottom-up walk of raht_octree_encode, every level's bytes XORed with pred. Enqueues only.
+ *   raht_octree_decode_inter : keys[counts[J]] from res. Top-down: at level g pred of the level's node keys, occ = res ^ pred, then
+ *                              the expansion of raht_octree_decode, under its rules: counts (HOST) from a header size everything,
+ *                              EVERY store is bounded by them whatever the bytes say; a reconstructed byte of 0, or popcounts
+ *                              that do not add up to the next count, set *bad. Enqueues only.
+ *   raht_octree_bytes_used   : raht_octree_bytes with the number of ranks in use taken from the header (n_used, 1 .. 256), not from
+ *                              the position of byte 0. The encoder's side is raht_octree_symbols unchanged.
+ * No atomics; deterministic. The reference's keys are not checked here (a sequence coder hands in keys that raht_octree_counts
+ * has seen): keys out of order give a pred that means nothing, possibly another one in the decoder -- *bad then -- but no search
+ * leaves [0, N_ref). RAHT_ERR_INVALID with nothing enqueued: J outside 1 .. 21, N or N_ref outside 1 .. 2^31 - 1,
+ * NULL pointers, counts that fail the rules of raht_octree_decode (encode: counts[J] != N), n_used outside 1 .. 256.
+ * All pointers DEVICE unless marked HOST. */
+int raht_octree_encode_inter(const uint64_t *keys_sorted, int64_t N, int J, const int64_t *counts, const uint64_t *ref_keys,
+                             int64_t N_ref, uint8_t *res, raht_stream_t stream);
+int raht_octree_decode_inter(const uint8_t *res, const int64_t *counts, int J, const uint64_t *ref_keys, int64_t N_ref, uint64_t *keys,
+                             int32_t *bad, raht_stream_t stream);
+int raht_octree_bytes_used(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_of_rank, int n_used, uint8_t *res, int32_t *bad,
+                           raht_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Regions of a frame (csrc/region.hip): where the rows of a run of octree cells lie in the frame's coded order, so that a decoder
  * can rebuild them from the segments that hold them (python: bitstream.decode_region_bytes).
  *

@@ -33,6 +33,7 @@ EXPORTS = [
     "raht_rlgr_bound", "raht_rlgr_encode", "raht_rlgr_decode", "raht_rlgr_encode_channels", "raht_rlgr_decode_channels", "raht_transpose_i32", "raht_i32_equal", "raht_sqdiff_columns", "raht_merge_clusters", "raht_voxelize_merge", "raht_rlgr_seg_encode", "raht_rlgr_seg_decode", "raht_rlgr_seg_encode_strided", "raht_rlgr_seg_decode_strided", "raht_rlgr_seg_encode_batch", "raht_rlgr_seg_decode_batch", "raht_rlgr_seg_decode_batch_check", "raht_rlgr_seg_offsets_width", "raht_rlgr_seg_encode64", "raht_rlgr_seg_decode64", "raht_rlgr_seg_encode_batch64", "raht_rlgr_seg_decode_batch64", "raht_rlgr_seg_encode_ragged", "raht_rlgr_seg_decode_ragged", "raht_debug_rlgr_decode_out", "raht_debug_rlgr_encode_out", "raht_rlgr_seg_rate", "raht_debug_height_stages_per_launch", "raht_debug_live_blocks", "raht_debug_cached_blocks", "raht_debug_sort_form", "raht_debug_motion_tile",
     "raht_xchg_bytes", "raht_xchg_alloc", "raht_xchg_open", "raht_xchg_close", "raht_xchg_free", "raht_xchg_gather", "raht_xchg_buffer", "raht_xchg_status",
     "raht_octree_counts", "raht_octree_encode", "raht_octree_decode", "raht_octree_symbols", "raht_octree_bytes", "raht_demorton",
+    "raht_octree_encode_inter", "raht_octree_decode_inter", "raht_octree_bytes_used",
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
     "raht_region_layout_set", "raht_region_assemble_set", "raht_region_needs",
     "raht_predict", "raht_motion_search", "raht_predict_mc",
@@ -195,6 +196,9 @@ def lib():
     L.raht_octree_symbols.argtypes = [vp, i64, vp, vp, vp]
     L.raht_octree_bytes.argtypes = [vp, i64, vp, vp, vp, vp]
     L.raht_demorton.argtypes = [vp, i64, i32, vp, vp]
+    L.raht_octree_encode_inter.argtypes = [vp, i64, i32, C.POINTER(i64), vp, i64, vp, vp]
+    L.raht_octree_decode_inter.argtypes = [vp, C.POINTER(i64), i32, vp, i64, vp, vp, vp]
+    L.raht_octree_bytes_used.argtypes = [vp, i64, vp, i32, vp, vp, vp]
     L.raht_region_layout.argtypes = [vp, i64, i32, i64, i64, vp, vp]
     L.raht_region_cells.argtypes = [vp, i64, i32, i32, i64, vp, vp, vp]
     L.raht_region_assemble.argtypes = [vp, i64, i64, vp, i64, i64, i32, C.POINTER(i64), i32, vp]

@@ -29,6 +29,10 @@ With ``motion`` > 0 the prediction may follow a MOTION FIELD: one
     RAHTM001 | int64 ref_back | int64 up | int64 block_log2 | int64 n_blocks | int8 mv[n_blocks][3] | zero bytes up to a
     multiple of 8 | a whole RAHTF001 frame
 
+With ``geometry_inter`` the GEOMETRY of such a frame may be predicted as well: its geometry section is then an
+``OCTP0001`` one, coded against the keys of the frame its wrapper names; ``sequence_geometry`` tells which frames do that, and the
+decoders of a single frame take those keys as ``ref_keys``.
+
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
 sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
@@ -222,7 +226,8 @@ def encode_frame_bytes_target(V_int, attributes, J, target_bytes, step=1.0, scal
 
 def parse_frame(blob, max_voxels=None):
     """The header of a frame container, checked against the blob (pure Python, nothing allocated on a device) -> dict: J, N, D,
-    n_wide, steps, vmin, width, geometry (offset, length), attributes (offset, length). ``ValueError`` when it does not add up."""
+    n_wide, steps, vmin, width, geometry (offset, length), attributes (offset, length), geometry_ref (None, or the voxel count of
+    the frame a predicted geometry section is coded against). ``ValueError`` when it does not add up."""
     m = len(MAGIC)
     if bytes(blob[:m]) != MAGIC:
         raise ValueError("not a RAHT frame container")
@@ -258,19 +263,25 @@ def parse_frame(blob, max_voxels=None):
     if bytes(blob[ao: ao + am]) != SegmentedCoder.MAGIC or [int(x) for x in np.frombuffer(blob, np.int64, 2, ao + am)] != [N, D]:
         raise ValueError("frame container: the attribute container is not the one the header announces")
     return dict(J=J, N=N, D=D, n_wide=n_wide, steps=steps, vmin=nums[n_steps: n_steps + 3], width=nums[n_steps + 3],
-                geometry=(go, gl), attributes=(ao, al))
+                geometry=(go, gl), attributes=(ao, al), geometry_ref=g.get("N_ref"))
 
 
-def decode_frame_bytes(blob, device="cuda", max_voxels=None):
+def decode_frame_bytes(blob, device="cuda", max_voxels=None, ref_keys=None):
     """-> (V_int (N, 3) int64, C_rec (N, D) float32), CUDA tensors on ``device``, from the bytes alone. ``max_voxels``: refuse
-    frames that announce more voxels than this before anything is allocated for them. ``ValueError`` for a corrupt frame."""
+    frames that announce more voxels than this before anything is allocated for them. ``ref_keys``: the keys of the reference
+    frame, for the inner frame of a sequence's predicted frame whose geometry is predicted too (``sequence_geometry``); without
+    them such a frame is refused before any device work. ``ValueError`` for a corrupt frame."""
     import torch
-    return _decode_frame(blob, parse_frame(blob, max_voxels), torch.device(device), max_voxels)[:2]
+    h = parse_frame(blob, max_voxels)
+    _need_ref_keys("decode_frame_bytes", blob, h, ref_keys)
+    return _decode_group([("", blob, h, ref_keys)], torch.device(device), max_voxels)[0][:2]
 
 
-def _decode_frame(blob, h, dev, max_voxels):
-    """a frame container and its parsed header -> (V_int, C_rec, keys)"""
-    return _decode_group([("", blob, h)], dev, max_voxels)[0]
+def _need_ref_keys(who, blob, h, ref_keys):
+    """a frame whose geometry is predicted from another frame's is refused here when the keys of that frame are not at hand"""
+    if h["geometry_ref"] is not None:
+        go, gl = h["geometry"]
+        OctreeCoder.check_ref_keys(OctreeCoder.parse(blob[go: go + gl]), ref_keys, who)
 
 
 def _attribute_matrices(coders):
@@ -283,16 +294,18 @@ def _attribute_matrices(coders):
 
 
 def _decode_group(group, dev, max_voxels):
-    """group: [(who, frame container, its parsed header)], one frame at least, all of one (D, n_wide, steps) -> [(V_int, C_rec,
-    keys)]: the geometry frame by frame, the entropy decode and the inverse transform of all frames together (``_attribute_matrices``,
-    ``_reconstruct``). ``who`` opens what a refusal of that frame says ("" for a frame that stands alone)."""
+    """group: [(who, frame container, its parsed header, ref)], one frame at least, all of one (D, n_wide, steps) -> [(V_int,
+    C_rec, keys)]: the geometry frame by frame, the entropy decode and the inverse transform of all frames together
+    (``_attribute_matrices``, ``_reconstruct``). ``who`` opens what a refusal of that frame says ("" for a frame that stands alone).
+    ``ref``: for a frame with a predicted geometry section the keys of its reference frame, or the position in this group of that
+    frame (an earlier one)."""
     import torch
     keys, coders, Vs, plans = [], [], [], []
     with torch.cuda.device(dev):
-        for who, fb, h in group:
+        for who, fb, h, ref in group:
             (go, gl), (ao, al) = h["geometry"], h["attributes"]
             try:
-                keys.append(OctreeCoder.decode(fb[go: go + gl], dev, max_voxels))
+                keys.append(OctreeCoder.decode(fb[go: go + gl], dev, max_voxels, keys[ref] if isinstance(ref, int) else ref))
                 coders.append(SegmentedCoder.from_container(fb[ao: ao + al], dev, max_symbols=h["N"] * h["D"]))
             except ValueError as e:
                 raise ValueError(f"{who}{e}") from None
@@ -346,14 +359,15 @@ def region_segments(n_top, runs, seg_len):
     return ids, compact
 
 
-def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys=None):
+def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys=None, ref_keys=None):
     """The voxels of the octree cells ``cells = (c0, c1)`` (Morton indices at ``depth``, 1 <= depth <= J - 1, 0 <= c0 < c1 <=
     8^depth) of a frame, from the geometry and the attribute segments they depend on -> (V_int (n, 3) int64, C_rec (n, D) float32,
     info): rows [a, b) of what ``decode_frame_bytes`` returns, up to the rounding of the tree above ``depth``, which the two
     decoders compute in different launches. ``keys``: ``info["keys"]`` of an earlier call on the same frame; the geometry is then
     not decoded again. info: rows (a, b), n_cells (occupied cells in the range), segments_decoded / segments_total (per channel),
     byte_ranges ((offset, length) within ``blob``: everything outside them may be missing) and bytes_needed, geometry_decoded,
-    keys. No N x D matrix is allocated: the only full-length arrays are the keys and the cell search's flags.
+    keys. No N x D matrix is allocated: the only full-length arrays are the keys and the cell search's flags. ``ref_keys``: the
+    reference frame's keys, for a frame whose geometry section is predicted (``decode_frame_bytes``); ``keys`` makes them needless.
     ``ValueError`` for a corrupt frame or arguments outside the ranges above. The one-range call of ``decode_cells_bytes``' core."""
     import torch
     who = "decode_region_bytes"
@@ -365,12 +379,12 @@ def decode_region_bytes(blob, depth, cells, device="cuda", max_voxels=None, keys
     _region_depth(who, h, depth)
     if not 0 <= c0 < c1 <= 8 ** depth:
         raise ValueError(f"{who}: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
-    V, C_rec, info, _ = _decode_cells(who, blob, h, depth, [(c0, c1)], torch.device(device), max_voxels, keys)
+    V, C_rec, info, _ = _decode_cells(who, blob, h, depth, [(c0, c1)], torch.device(device), max_voxels, keys, ref_keys)
     info["rows"] = info["rows"][0]
     return V, C_rec, info
 
 
-def decode_cells_bytes(blob, depth, ranges, device="cuda", max_voxels=None, keys=None):
+def decode_cells_bytes(blob, depth, ranges, device="cuda", max_voxels=None, keys=None, ref_keys=None):
     """``decode_region_bytes`` for a SET of cell ranges. ranges: a non-empty ascending list of disjoint pairs
     ``(c0, c1)`` of depth-``depth`` cell indices (0 <= c0 < c1 <= 8^depth, every c0 at or above the c1 before it), 512 at most ->
     (V_int, C_rec, info) for the concatenation of the ranges' rows: bit for bit the concatenation of ``decode_region_bytes`` over
@@ -388,7 +402,7 @@ def decode_cells_bytes(blob, depth, ranges, device="cuda", max_voxels=None, keys
         raise ValueError(f"{who}: 1 .. {ops.REGION_MAX_RANGES} ranges")
     if any(not c0 < c1 for c0, c1 in ranges) or any(p[1] > q[0] for p, q in zip(ranges, ranges[1:])) or ranges[0][0] < 0 or ranges[-1][1] > 8 ** depth:
         raise ValueError(f"{who}: ranges must be ascending, disjoint pairs 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
-    return _decode_cells(who, blob, h, depth, ranges, torch.device(device), max_voxels, keys)[:3]
+    return _decode_cells(who, blob, h, depth, ranges, torch.device(device), max_voxels, keys, ref_keys)[:3]
 
 
 def _region_depth(who, h, depth):
@@ -396,10 +410,12 @@ def _region_depth(who, h, depth):
         raise ValueError(f"{who}: depth must be 1 .. J - 1 = {h['J'] - 1}")
 
 
-def _decode_cells(who, blob, h, depth, ranges, dev, max_voxels, keys):
+def _decode_cells(who, blob, h, depth, ranges, dev, max_voxels, keys, ref_keys=None):
     """THE region decoder: the frame ``blob`` with its parsed header ``h``, checked ``depth`` and cell ``ranges`` -> (V_int, C_rec,
     info, the region's keys), the rows of the ranges concatenated. ``who`` opens a refusal."""
     import torch
+    if keys is None:
+        _need_ref_keys(who, blob, h, ref_keys)
     J, N, D, n_wide, steps = h["J"], h["N"], h["D"], h["n_wide"], h["steps"]
     (go, gl), (ao, al) = h["geometry"], h["attributes"]
     view = memoryview(blob)
@@ -416,7 +432,7 @@ def _decode_cells(who, blob, h, depth, ranges, dev, max_voxels, keys):
     with torch.cuda.device(dev):
         decoded = keys is None
         if decoded:
-            keys = OctreeCoder.decode(view[go: go + gl], dev, max_voxels)
+            keys = OctreeCoder.decode(view[go: go + gl], dev, max_voxels, ref_keys)
         try:
             cell_keys, cell_first = ops.region_cells(keys, 3 * J, tl, n_d)
         except ops.RahtError as e:
@@ -587,6 +603,8 @@ def _frame_head(view, off, i, max_voxels):
                 raise ValueError(f"predicted frame: ref_back = {ref_back} reaches before frame 0")
             kind, ref = "P", i - ref_back
         h = parse_frame(fb, max_voxels)
+        if h["geometry_ref"] is not None and ref is None:
+            raise ValueError("a geometry section predicted from another frame in a frame without a wrapper")
         if motion is not None:
             if motion[0] > h["J"]:
                 raise ValueError(f"motion-compensated frame: block_log2 = {motion[0]} outside 1 .. J = {h['J']}")
@@ -603,7 +621,8 @@ def _frame_head(view, off, i, max_voxels):
 
 def _frame_heads(view, off, idx, max_voxels):
     """the heads of the frames ``idx`` and of every frame they depend on, back to the nearest intra frame -> {i: head}; a predicted
-    frame whose J or D is not its reference's is refused here, before any device work"""
+    frame whose J or D is not its reference's, or whose geometry is predicted from another voxel count than its reference's, is
+    refused here, before any device work"""
     heads = {}
     for i in idx:                                                            # (in the order asked for: the first bad frame is the one named)
         while i is not None and i not in heads:
@@ -616,6 +635,9 @@ def _frame_heads(view, off, idx, max_voxels):
             if (h["J"], h["D"]) != (r["J"], r["D"]):
                 raise ValueError(f"sequence container: frame {i}: a predicted frame of J = {h['J']}, D = {h['D']} against a reference "
                                  f"(frame {hd['ref']}) of J = {r['J']}, D = {r['D']}")
+            if h["geometry_ref"] not in (None, r["N"]):
+                raise ValueError(f"sequence container: frame {i}: a geometry section predicted from {h['geometry_ref']} voxels, the "
+                                 f"reference (frame {hd['ref']}) has {r['N']}")
     return heads
 
 
@@ -638,6 +660,13 @@ def sequence_motion(blob, max_voxels=None, max_frames=None):
     """-> per frame of a sequence container None, or (block_log2, mv (n_blocks, 3) int8 numpy) for a motion-compensated frame, from
     the headers alone (pure host code), with the checks of ``sequence_kinds``."""
     return [hd["motion"] for hd in _sequence_heads(blob, max_voxels, max_frames)]
+
+
+def sequence_geometry(blob, max_voxels=None, max_frames=None):
+    """-> ["intra" | "predicted"] per frame of a sequence container: how its geometry section is coded, from the headers alone
+    (pure host code), with the checks of ``sequence_kinds`` and two more: a predicted geometry section in a frame without a
+    wrapper, or one predicted from another voxel count than its reference frame's, is refused, the frame named."""
+    return ["intra" if hd["h"]["geometry_ref"] is None else "predicted" for hd in _sequence_heads(blob, max_voxels, max_frames)]
 
 
 class _Predictor:
@@ -677,7 +706,7 @@ SEQ_CHUNK = SegmentedCoder.BATCH_MAX                                     # frame
 
 
 def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None, gop=1, up=0,
-                          inter="auto", motion=0, block_log2=4, motion_weights=None):
+                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off"):
     """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
     container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
     frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
@@ -702,7 +731,14 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     a column out). If every vector is zero the frame goes the way of ``motion=0``, byte for byte. Otherwise Rmc = A -
     ``ops.predict_mc`` is a third candidate: ``inter="always"`` codes it as an RAHTM001 frame, ``inter="auto"`` codes the smallest of
     bytes_A, bytes_R + 24 and bytes_Rmc + 40 + the field's bytes (3 per block, padded to 8), a tie going to the earlier of the
-    three. ``motion=0`` (the default) is byte for byte what it was without these arguments."""
+    three. ``motion=0`` (the default) is byte for byte what it was without these arguments.
+
+    ``geometry_inter`` (with ``gop`` > 1): "always" -- a frame that is coded as a predicted frame of either kind carries
+    a predicted geometry section (``OctreeCoder.encode(keys, J, ref_keys=the keys of frame i - 1)``, the frame its wrapper names;
+    under a motion field too: the reference is not shifted); "auto" -- both sections are coded and the smaller is kept, a tie going
+    to the intra one. Frames coded intra never carry one. Under ``inter="auto"`` the cost of a way to code the frame is then its
+    attribute bytes + its wrapper + the geometry section it would carry. "off" (the default) is byte for byte what it was without
+    this argument."""
     import torch
     dev = torch.device(device)
     J, n_wide, gop, up, motion, block_log2 = int(J), int(n_wide), int(gop), int(up), int(motion), int(block_log2)
@@ -712,6 +748,8 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
         raise ValueError('encode_sequence_bytes: gop >= 1, up in 0 .. 3, inter "auto" or "always"')
     if not 0 <= motion <= 3 or (motion and not 1 <= block_log2 <= J):
         raise ValueError("encode_sequence_bytes: motion in 0 .. 3, block_log2 in 1 .. J")
+    if geometry_inter not in ("off", "always", "auto"):
+        raise ValueError('encode_sequence_bytes: geometry_inter "off", "always" or "auto"')
     VA = []
     for i, (V_int, attributes) in enumerate(frames):
         V, A = _frame_input(f"encode_sequence_bytes: frame {i}", V_int, attributes, J, n_wide, dev)
@@ -737,8 +775,12 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
                     keys, geo, plan = _keys_geometry_plan(V, J, geometry)
                     # the ways to code the frame, each by its predictor: intra (None), predicted from frame i - 1 (ref: its keys and
                     # reconstruction, carried from frame to frame), and under a motion field that is not all zero
-                    ways = [None]
+                    ways, geo_p = [None], geo                                # geo_p: the section of a frame that is coded predicted
                     if i % gop:
+                        if geometry_inter != "off":
+                            geo_p = OctreeCoder.encode(keys, J, entropy=geometry, ref_keys=ref[0])
+                            if geometry_inter == "auto" and len(geo_p) >= len(geo):
+                                geo_p = geo
                         ways.append(_Predictor(keys, ref, J, up))
                         if motion:
                             n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
@@ -751,14 +793,14 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
                         src = A if pred is None else pred.residual(A)
                     else:                                                    # the fewest bytes, wrapper included; the earliest among equals
                         srcs = [A] + [p.residual(A) for p in ways[1:]]
-                        cost = [int(plan.rate_curve(X, [steps], n_wide, seg_len)["bytes"][0]) + (p.overhead if p else 0)
+                        cost = [int(plan.rate_curve(X, [steps], n_wide, seg_len)["bytes"][0]) + (p.overhead + len(geo_p) if p else len(geo))
                                 for p, X in zip(ways, srcs)]
                         pred, src = min(zip(ways, srcs, cost), key=lambda w: w[2])[:2]
                     Q = _quantize([plan], [src], steps, n_wide)[0]
                     if i + 1 < len(VA) and (i + 1) % gop:                    # the next frame may be predicted from this one
                         C = _reconstruct([plan], [Q], steps, n_wide)[0]
                         ref = (keys, C if pred is None else pred.restore(C))
-                    geos.append(geo)
+                    geos.append(geo if pred is None else geo_p)
                     Qs.append(Q)
                     wraps.append(b"" if pred is None else pred.wrapper())
             atts = _attribute_parts(Qs, seg_len, dev)
@@ -771,7 +813,8 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
     """-> [(V_int (N_i, 3) int64, C_rec (N_i, D) float32)] for the frame indices ``frames`` (default: all, in order), each what
     ``decode_frame_bytes(sequence_frame(blob, i))`` returns, bit for bit. The requested indices are closed under dependencies, back
     to the nearest intra frame, and that set is decoded once, in ascending order; the requested frames are returned in the order
-    asked. The geometry is decoded frame by frame; consecutive frames of the set with the same (D, seg_len, n_wide, steps) share one
+    asked. The geometry is decoded frame by frame (a predicted geometry section against the keys of the frame's reference, which is
+    decoded before it); consecutive frames of the set with the same (D, seg_len, n_wide, steps) share one
     entropy launch (``SegmentedCoder.decode_ragged``) and one set of inverse transform launches (a frame of exactly D voxels goes
     alone). ``max_voxels`` per frame and ``max_frames`` are checked before anything is allocated from the numbers of the blob.
     ``ValueError`` for a corrupt container; a corrupt frame is named by its index -- for a header or an attribute length table that
@@ -804,10 +847,17 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
         h = heads[i]["h"]
         return (h["D"], heads[i]["seg_len"], h["n_wide"], tuple(h["steps"])) + ((i,) if h["N"] == h["D"] else ())
     done = {}                                                                # frame -> (V, C_rec or R_rec, keys)
+
+    def geo_ref(i, group):
+        # what a predicted geometry section is decoded against: the reference's keys, or its place in the group it shares with i
+        r = heads[i]["ref"]
+        if heads[i]["h"]["geometry_ref"] is None:
+            return None
+        return group.index(r) if r in group else done[r][2]
     for _, run in itertools.groupby(sorted(heads), key=same):
         run = list(run)
         for group in (run[lo: lo + SEQ_CHUNK] for lo in range(0, len(run), SEQ_CHUNK)):
-            named = [(f"sequence container: frame {i}: ", heads[i]["fb"], heads[i]["h"]) for i in group]
+            named = [(f"sequence container: frame {i}: ", heads[i]["fb"], heads[i]["h"], geo_ref(i, group)) for i in group]
             done.update(zip(group, _decode_group(named, dev, max_voxels)))
     with torch.cuda.device(dev):
         for i in sorted(done):                                               # ascending: a reference is whole before it is used
@@ -875,6 +925,10 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
     (``decode_cells_bytes``' core); then the chain is replayed from the intra frame on with the one predictor on the region
     matrices -- the keys and the reconstruction of S_g as the reference, and under a motion field the blocks that have rows in S_f.
 
+    A chain frame whose geometry section is predicted needs the WHOLE keys of its reference before its own can be
+    decoded: the reference's geometry is then decoded (and ``geometry_decoded`` set) even where nothing else is needed of that
+    frame -- its section lies inside the bytes listed for it either way -- unless ``keys`` holds the predicted frame already.
+
     ``keys``: {frame index: keys} as an earlier call returned in ``info["keys"]``; the frames in it skip the geometry decode.
     info: chain (the frame indices, intra first), frames ({f: ranges (S_f), rows, n_cells, segments_decoded, segments_total,
     byte_ranges ((offset, length) within the SEQUENCE blob), bytes_needed, geometry_decoded}; a frame nothing is needed of has no
@@ -904,6 +958,27 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
     tl = 3 * (J - depth)
     part, frames, keys_out = {}, {}, {}                                      # part: frame -> (V, C, region keys, region motion)
     S = [(c0, c1)]
+    given, decoded = keys or {}, set()                                       # decoded: the frames whose geometry this call decodes
+
+    def whole_keys(f):
+        # the keys of chain frame f: handed in, decoded before, or decoded here -- a predicted section after its reference's
+        todo = [f]
+        while todo[-1] not in keys_out and given.get(todo[-1]) is None and heads[todo[-1]]["h"]["geometry_ref"] is not None:
+            todo.append(heads[todo[-1]]["ref"])
+        for g in reversed(todo):
+            if g not in keys_out:
+                if given.get(g) is not None:
+                    keys_out[g] = given[g]
+                    continue
+                (go, gl), fb = heads[g]["h"]["geometry"], heads[g]["fb"]
+                rk = keys_out[heads[g]["ref"]] if heads[g]["h"]["geometry_ref"] is not None else None
+                try:
+                    keys_out[g] = OctreeCoder.decode(fb[go: go + gl], dev, max_voxels, rk)
+                except ValueError as e:
+                    raise ValueError(f"sequence container: frame {g}: {e}") from None
+                decoded.add(g)
+        return keys_out[f]
+
     with torch.cuda.device(dev):
         for f in reversed(chain):                                            # down the chain: what is needed of every frame
             hd = heads[f]
@@ -916,16 +991,16 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
                                  segments_total=(h["N"] + hd["seg_len"] - 1) // hd["seg_len"], byte_ranges=[(off[f], head)],
                                  bytes_needed=head, geometry_decoded=False)
                 continue
+            kf = whole_keys(f)
             try:
-                V, C, info, kr = _decode_cells(who, fb, h, depth, S, dev, max_voxels, None if keys is None else keys.get(f))
+                V, C, info, kr = _decode_cells(who, fb, h, depth, S, dev, max_voxels, kf)
             except ValueError as e:
                 raise ValueError(f"sequence container: frame {f}: {e}") from None
-            keys_out[f] = info["keys"]
             ranges = [(base + o, ln) for o, ln in info["byte_ranges"]]
             ranges[0] = (off[f], ranges[0][1] + base - off[f])               # (the wrapper of a predicted frame lies in front)
             frames[f] = dict(ranges=S, rows=int(kr.shape[0]), n_cells=info["n_cells"], segments_decoded=info["segments_decoded"],
                              segments_total=info["segments_total"], byte_ranges=ranges, bytes_needed=sum(ln for _, ln in ranges),
-                             geometry_decoded=info["geometry_decoded"])
+                             geometry_decoded=False)
             motion = None
             if hd["kind"] == "P" and kr.shape[0]:
                 if hd["motion"] is not None:
@@ -943,6 +1018,8 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
             if f in part and g in part and part[f][2].shape[0] and part[g][2].shape[0]:
                 _, C, kr, motion = part[f]
                 _Predictor(kr, (part[g][2], part[g][1]), J, hd["up"], motion).restore(C)
+    for f in decoded:
+        frames[f]["geometry_decoded"] = True
     byte_ranges = [(0, off[0])] + [r for f in chain for r in frames[f]["byte_ranges"]]
     info = dict(chain=chain, frames=frames, bytes_needed=sum(fr["bytes_needed"] for fr in frames.values()), byte_ranges=byte_ranges,
                 keys=keys_out)

@@ -14,57 +14,14 @@
 //            the header's counts size every level, and every write index is bounded by them whatever the bytes say.
 //   symbols  256-bin histogram (per-wave LDS bins, one global atomic per non-empty bin per workgroup), the rank table on the
 //            device (descending count, ties by ascending byte), byte -> int32 rank for the segmented RLGR coder; and back.
-#include "raht_common.h"
-#include "raht_device.h"
+// The level walks themselves (kernels and host loops) live in octree_device.h: octree_inter.hip runs them too.
+#include "octree_device.h"
 
 #include <cstring>
 
 namespace raht {
 
-constexpr int OCT_THREADS = 256;                         // one workgroup size everywhere in this file
-constexpr int OCT_ITEMS = 8;                             // consecutive nodes per thread
-constexpr int OCT_CHUNK = OCT_THREADS * OCT_ITEMS;       // nodes per workgroup step
-constexpr int OCT_MAX_GRID = 2048;                       // grids are capped and grid-strided
-constexpr int OCT_SELF_PREFIX = 2048;                    // up to this many chunks a workgroup sums the chunks before it by itself
-constexpr int OCT_MAX_J = 21;
 constexpr int OCT_HIST_GRID = 512;
-
-struct OctCounts { int64_t n[OCT_MAX_J + 1]; };
-
-// exclusive prefix of v over the workgroup (256 threads) and the workgroup's total; reusable inside a loop
-__device__ __forceinline__ uint32_t oct_block_scan(uint32_t v, uint32_t *total)
-{
-    __shared__ uint32_t wsum[OCT_THREADS / RAHT_WAVE];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < RAHT_WAVE; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, RAHT_WAVE);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();                                     // the previous call's readers are done with wsum
-    if (lane == RAHT_WAVE - 1) wsum[wid] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < OCT_THREADS / RAHT_WAVE; ++w) {
-        const uint32_t c = wsum[w];
-        if (w < wid) base += c;
-        tot += c;
-    }
-    *total = tot;
-    return base + inc - v;
-}
-
-// number of items of the chunks before chunk c: blk already scanned, or summed here
-__device__ __forceinline__ uint32_t oct_before(const uint32_t *blk, int64_t c, int scanned)
-{
-    if (scanned) return blk[c];
-    uint32_t part = 0, tot;
-    for (int64_t b = threadIdx.x; b < c; b += OCT_THREADS) part += blk[b];
-    (void)oct_block_scan(part, &tot);
-    return tot;
-}
 
 // ---- counts ------------------------------------------------------------------------------------------------------------------
 // hist[c], c < J: rows that share exactly c leading digits with their predecessor (row 0: c = 0); hist[31] != 0: bad input
@@ -101,172 +58,6 @@ __global__ __launch_bounds__(OCT_THREADS) void oct_counts_kernel(const uint64_t 
     if (err) atomicOr(&bins[31], 1u);
     __syncthreads();
     if (threadIdx.x < 32 && bins[threadIdx.x]) atomicAdd(&hist[threadIdx.x], bins[threadIdx.x]);
-}
-
-// ---- encode: one level up ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool oct_is_head(int64_t i, int64_t n, uint64_t x, uint64_t prev)
-{
-    return i < n && (i == 0 || (x >> 3) != (prev >> 3));
-}
-
-__device__ __forceinline__ void oct_load_chunk(const uint64_t *cur, int64_t n, int64_t base, uint64_t (&x)[OCT_ITEMS], uint64_t &prev)
-{
-#pragma unroll
-    for (int k = 0; k < OCT_ITEMS; ++k) x[k] = (base + k < n) ? cur[base + k] : 0ull;
-    prev = (base > 0 && base < n) ? cur[base - 1] : 0ull;
-}
-
-__device__ __forceinline__ uint32_t oct_count_heads(int64_t n, int64_t base, const uint64_t (&x)[OCT_ITEMS], uint64_t prev)
-{
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < OCT_ITEMS; ++k) c += oct_is_head(base + k, n, x[k], k ? x[k - 1] : prev) ? 1u : 0u;
-    return c;
-}
-
-// chunk c of level g + 1 (cur, n keys) -> its parents' keys and occupancy bytes at rank `before` + (rank inside the chunk).
-// A head's run may reach into the items of the following threads: those (at most 7) keys are read again.
-__device__ __forceinline__ void oct_up_chunk(const uint64_t *cur, int64_t n, int64_t c, uint32_t before, uint64_t *parent,
-                                             uint8_t *occ, int64_t n_parent)
-{
-    const int64_t base = c * OCT_CHUNK + (int64_t)threadIdx.x * OCT_ITEMS;
-    uint64_t x[OCT_ITEMS], prev;
-    oct_load_chunk(cur, n, base, x, prev);
-    uint32_t tot;
-    int64_t pos = (int64_t)before + oct_block_scan(oct_count_heads(n, base, x, prev), &tot);
-    bool open = false;
-    uint32_t byte = 0;
-    uint64_t pk = 0;
-#pragma unroll
-    for (int k = 0; k < OCT_ITEMS; ++k) {
-        if (oct_is_head(base + k, n, x[k], k ? x[k - 1] : prev)) {
-            if (open) {
-                if (pos < n_parent) { occ[pos] = (uint8_t)byte; parent[pos] = pk; }
-                ++pos;
-            }
-            open = true;
-            byte = 0;
-            pk = x[k] >> 3;
-        }
-        if (open && base + k < n) byte |= 1u << (uint32_t)(x[k] & 7ull);
-    }
-    if (open) {
-        for (int64_t j = base + OCT_ITEMS; j < n && j < base + OCT_ITEMS + 7; ++j) {
-            const uint64_t y = cur[j];
-            if ((y >> 3) != pk) break;
-            byte |= 1u << (uint32_t)(y & 7ull);
-        }
-        if (pos < n_parent) { occ[pos] = (uint8_t)byte; parent[pos] = pk; }
-    }
-}
-
-__global__ __launch_bounds__(OCT_THREADS) void oct_head_count_kernel(const uint64_t *__restrict__ cur, int64_t n, int64_t nchunks,
-                                                                     uint32_t *__restrict__ blk)
-{
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int64_t base = c * OCT_CHUNK + (int64_t)threadIdx.x * OCT_ITEMS;
-        uint64_t x[OCT_ITEMS], prev;
-        oct_load_chunk(cur, n, base, x, prev);
-        uint32_t tot;
-        (void)oct_block_scan(oct_count_heads(n, base, x, prev), &tot);
-        if (threadIdx.x == 0) blk[c] = tot;
-    }
-}
-
-__global__ __launch_bounds__(OCT_THREADS) void oct_level_up_kernel(const uint64_t *__restrict__ cur, int64_t n, int64_t nchunks,
-                                                                   const uint32_t *__restrict__ blk, int scanned,
-                                                                   uint64_t *__restrict__ parent, uint8_t *__restrict__ occ,
-                                                                   int64_t n_parent)
-{
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) oct_up_chunk(cur, n, c, oct_before(blk, c, scanned), parent, occ, n_parent);
-}
-
-// the coarse levels: steps g = g_first, g_first - 1, ... 0 (each reads level g + 1, at most one chunk) in one workgroup
-__global__ __launch_bounds__(OCT_THREADS) void oct_top_up_kernel(const uint64_t *src, uint64_t *a, uint64_t *b, int g_first,
-                                                                 const OctCounts cn, uint8_t *occ)
-{
-    int64_t off = 0;
-    for (int g = 0; g < g_first; ++g) off += cn.n[g];
-    const uint64_t *cur = src;
-    uint64_t *dst = a, *other = b;
-    for (int g = g_first; g >= 0; --g) {
-        oct_up_chunk(cur, cn.n[g + 1], 0, 0u, dst, occ + off, cn.n[g]);
-        __syncthreads();                                 // this level's parent keys are the next step's input
-        cur = dst;
-        uint64_t *t = dst; dst = other; other = t;
-        if (g > 0) off -= cn.n[g - 1];
-    }
-}
-
-// ---- decode: one level down --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t oct_load_bytes(const uint8_t *occ, int64_t n, int64_t base, uint32_t (&o)[OCT_ITEMS])
-{
-    uint32_t c = 0;
-#pragma unroll
-    for (int k = 0; k < OCT_ITEMS; ++k) {
-        o[k] = (base + k < n) ? (uint32_t)occ[base + k] : 0u;
-        c += (uint32_t)__popc(o[k]);
-    }
-    return c;
-}
-
-// chunk c of level g (n parents: keys `parent`, or the root when parent == NULL; bytes occ) -> the keys of its children. Every
-// store is bounded by n_child; a zero byte, or a level whose popcounts do not add up to n_child, raises *bad.
-__device__ __forceinline__ void oct_down_chunk(const uint64_t *parent, const uint8_t *occ, int64_t n, int64_t c, int64_t nchunks,
-                                               uint32_t before, uint64_t *child, int64_t n_child, int32_t *bad)
-{
-    const int64_t base = c * OCT_CHUNK + (int64_t)threadIdx.x * OCT_ITEMS;
-    uint32_t o[OCT_ITEMS], tot;
-    const uint32_t cnt = oct_load_bytes(occ, n, base, o);
-    int64_t pos = (int64_t)before + oct_block_scan(cnt, &tot);
-    bool zero = false;
-#pragma unroll
-    for (int k = 0; k < OCT_ITEMS; ++k) {
-        if (base + k < n) {
-            const uint64_t pk = parent ? parent[base + k] : 0ull;
-            zero |= o[k] == 0u;
-            for (uint32_t m = o[k]; m; m &= m - 1u) {
-                if (pos < n_child) child[pos] = (pk << 3) | (uint64_t)(__ffs((int)m) - 1);
-                ++pos;
-            }
-        }
-    }
-    if (zero) *bad = 1;
-    if (c == nchunks - 1 && threadIdx.x == 0 && (int64_t)before + (int64_t)tot != n_child) *bad = 1;
-}
-
-__global__ __launch_bounds__(OCT_THREADS) void oct_pop_count_kernel(const uint8_t *__restrict__ occ, int64_t n, int64_t nchunks,
-                                                                    uint32_t *__restrict__ blk)
-{
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        uint32_t o[OCT_ITEMS], tot;
-        (void)oct_block_scan(oct_load_bytes(occ, n, c * OCT_CHUNK + (int64_t)threadIdx.x * OCT_ITEMS, o), &tot);
-        if (threadIdx.x == 0) blk[c] = tot;
-    }
-}
-
-__global__ __launch_bounds__(OCT_THREADS) void oct_level_down_kernel(const uint64_t *__restrict__ parent, const uint8_t *__restrict__ occ,
-                                                                     int64_t n, int64_t nchunks, const uint32_t *__restrict__ blk,
-                                                                     int scanned, uint64_t *__restrict__ child, int64_t n_child,
-                                                                     int32_t *bad)
-{
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x)
-        oct_down_chunk(parent, occ, n, c, nchunks, oct_before(blk, c, scanned), child, n_child, bad);
-}
-
-// steps g = 0 .. g_end - 1 (each at most one chunk of parents) in one workgroup; step g writes into (g & 1) ? b : a
-__global__ __launch_bounds__(OCT_THREADS) void oct_top_down_kernel(const uint8_t *occ, int g_end, const OctCounts cn, uint64_t *a,
-                                                                   uint64_t *b, int32_t *bad)
-{
-    int64_t off = 0;
-    const uint64_t *cur = nullptr;
-    for (int g = 0; g < g_end; ++g) {
-        uint64_t *dst = (g & 1) ? b : a;
-        oct_down_chunk(cur, occ + off, cn.n[g], 0, 1, 0u, dst, cn.n[g + 1], bad);
-        __syncthreads();
-        cur = dst;
-        off += cn.n[g];
-    }
 }
 
 // ---- byte <-> rank -----------------------------------------------------------------------------------------------------------
@@ -383,37 +174,6 @@ __global__ __launch_bounds__(OCT_THREADS) void oct_demorton_kernel(const uint64_
     }
 }
 
-// ---- host --------------------------------------------------------------------------------------------------------------------
-static inline unsigned oct_grid(int64_t items, int64_t per_block, int cap = OCT_MAX_GRID)
-{
-    const int64_t g = ceil_div(items, per_block);
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-// the plausibility rules of a count list (the header of a geometry section comes off the wire)
-static int oct_check_counts(const char *what, const int64_t *counts, int J, int64_t *n_nodes)
-{
-    if (J < 1 || J > OCT_MAX_J) { set_error("%s: J must be 1 .. 21", what); return RAHT_ERR_INVALID; }
-    if (!counts) { set_error("%s: NULL counts", what); return RAHT_ERR_INVALID; }
-    if (counts[0] != 1) { set_error("%s: counts[0] must be 1 (the root)", what); return RAHT_ERR_INVALID; }
-    int64_t tot = 0;
-    for (int g = 0; g < J; ++g) {
-        if (counts[g + 1] < counts[g] || counts[g + 1] > 8 * counts[g] || counts[g + 1] >= ((int64_t)1 << 31)) {
-            set_error("%s: counts[%d] = %lld does not go with counts[%d] = %lld (n_g <= n_g+1 <= 8 n_g, below 2^31)", what, g + 1,
-                      (long long)counts[g + 1], g, (long long)counts[g]);
-            return RAHT_ERR_INVALID;
-        }
-        tot += counts[g];
-    }
-    *n_nodes = tot;
-    return RAHT_OK;
-}
-
-static void oct_fill(OctCounts &cn, const int64_t *counts, int J)
-{
-    for (int g = 0; g <= OCT_MAX_J; ++g) cn.n[g] = g <= J ? counts[g] : 0;
-}
-
 }  // namespace raht
 
 using namespace raht;
@@ -454,31 +214,7 @@ int raht_octree_encode(const uint64_t *keys_sorted, int64_t N, int J, const int6
     if (counts[J] != N) { set_error("raht_octree_encode: counts[J] must be N"); return RAHT_ERR_INVALID; }
     hipStream_t s = (hipStream_t)stream;
     return guarded("raht_octree_encode", [&]() -> int {
-        Scratch ka(sizeof(uint64_t) * (size_t)counts[J - 1], s), kb(sizeof(uint64_t) * (size_t)(J > 1 ? counts[J - 2] : 1), s);
-        Scratch blk(sizeof(uint32_t) * (size_t)ceil_div(N, OCT_CHUNK), s);
-        if (!ka.ok() || !kb.ok() || !blk.ok()) { set_error("raht_octree_encode: out of device memory"); return RAHT_ERR_NOMEM; }
-        OctCounts cn;
-        oct_fill(cn, counts, J);
-        uint64_t *bufs[2] = {ka.as<uint64_t>(), kb.as<uint64_t>()};
-        const uint64_t *src = keys_sorted;
-        int w = 0, g = J - 1;
-        int64_t off = n_nodes;
-        for (; g >= 0 && counts[g + 1] > OCT_CHUNK; --g) {
-            const int64_t n = counts[g + 1], nchunks = ceil_div(n, OCT_CHUNK);
-            const int scanned = nchunks > OCT_SELF_PREFIX;
-            off -= counts[g];
-            hipLaunchKernelGGL(oct_head_count_kernel, dim3(oct_grid(nchunks, 1)), dim3(OCT_THREADS), 0, s, src, n, nchunks,
-                               blk.as<uint32_t>());
-            if (scanned) RAHT_RET(exclusive_scan_u32(blk.as<uint32_t>(), blk.as<uint32_t>(), nchunks, nullptr, s));
-            hipLaunchKernelGGL(oct_level_up_kernel, dim3(oct_grid(nchunks, 1)), dim3(OCT_THREADS), 0, s, src, n, nchunks,
-                               (const uint32_t *)blk.as<uint32_t>(), scanned, bufs[w], occ + off, counts[g]);
-            src = bufs[w];
-            w ^= 1;
-        }
-        if (g >= 0)
-            hipLaunchKernelGGL(oct_top_up_kernel, dim3(1), dim3(OCT_THREADS), 0, s, src, bufs[w], bufs[w ^ 1], g, cn, occ);
-        RAHT_HIP_CHECK(hipGetLastError());
-        return RAHT_OK;
+        return oct_encode_levels("raht_octree_encode", keys_sorted, N, J, counts, n_nodes, occ, OctNoHook(), s);
     });
 }
 
@@ -489,33 +225,7 @@ int raht_octree_decode(const uint8_t *occ, const int64_t *counts, int J, uint64_
     RAHT_RET(oct_check_counts("raht_octree_decode", counts, J, &n_nodes));
     hipStream_t s = (hipStream_t)stream;
     return guarded("raht_octree_decode", [&]() -> int {
-        const int64_t N = counts[J];
-        Scratch tmp(sizeof(uint64_t) * (size_t)counts[J - 1], s);
-        Scratch blk(sizeof(uint32_t) * (size_t)ceil_div(N, OCT_CHUNK), s);
-        if (!tmp.ok() || !blk.ok()) { set_error("raht_octree_decode: out of device memory"); return RAHT_ERR_NOMEM; }
-        OctCounts cn;
-        oct_fill(cn, counts, J);
-        // step g writes level g + 1; the last step (g = J - 1) writes `keys`, the steps before it alternate
-        uint64_t *even = ((J - 1) & 1) ? tmp.as<uint64_t>() : keys, *odd = ((J - 1) & 1) ? keys : tmp.as<uint64_t>();
-        int g_end = 1;
-        while (g_end < J && counts[g_end] <= OCT_CHUNK) ++g_end;
-        hipLaunchKernelGGL(oct_top_down_kernel, dim3(1), dim3(OCT_THREADS), 0, s, occ, g_end, cn, even, odd, bad);
-        int64_t off = 0;
-        for (int g = 0; g < g_end; ++g) off += counts[g];
-        for (int g = g_end; g < J; ++g) {
-            const int64_t n = counts[g], nchunks = ceil_div(n, OCT_CHUNK);
-            const int scanned = nchunks > OCT_SELF_PREFIX;
-            const uint64_t *parent = ((g - 1) & 1) ? odd : even;
-            uint64_t *child = (g & 1) ? odd : even;
-            hipLaunchKernelGGL(oct_pop_count_kernel, dim3(oct_grid(nchunks, 1)), dim3(OCT_THREADS), 0, s, occ + off, n, nchunks,
-                               blk.as<uint32_t>());
-            if (scanned) RAHT_RET(exclusive_scan_u32(blk.as<uint32_t>(), blk.as<uint32_t>(), nchunks, nullptr, s));
-            hipLaunchKernelGGL(oct_level_down_kernel, dim3(oct_grid(nchunks, 1)), dim3(OCT_THREADS), 0, s, parent, occ + off, n, nchunks,
-                               (const uint32_t *)blk.as<uint32_t>(), scanned, child, counts[g + 1], bad);
-            off += n;
-        }
-        RAHT_HIP_CHECK(hipGetLastError());
-        return RAHT_OK;
+        return oct_decode_levels("raht_octree_decode", occ, counts, J, keys, bad, OctNoHook(), s);
     });
 }
 
@@ -546,28 +256,44 @@ int raht_octree_symbols(const uint8_t *occ, int64_t n_nodes, uint8_t *byte_of_ra
     });
 }
 
-int raht_octree_bytes(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_of_rank, uint8_t *occ, int32_t *bad, raht_stream_t stream)
+// ranks -> bytes under a table from a header; n_used < 0: the ranks in use end where byte 0 stands
+static int oct_bytes_run(const char *what, const int32_t *sym, int64_t n_nodes, const uint8_t *byte_of_rank, int n_used, uint8_t *out,
+                         int32_t *bad, raht_stream_t stream)
 {
-    if (!sym || !byte_of_rank || !occ || !bad) { set_error("raht_octree_bytes: NULL argument"); return RAHT_ERR_INVALID; }
-    if (n_nodes < 1 || n_nodes >= ((int64_t)1 << 31)) { set_error("raht_octree_bytes: n_nodes must be 1 .. 2^31 - 1"); return RAHT_ERR_INVALID; }
-    if ((uintptr_t)sym & 3) { set_error("raht_octree_bytes: sym must be 4-byte aligned"); return RAHT_ERR_INVALID; }
+    if (!sym || !byte_of_rank || !out || !bad) { set_error("%s: NULL argument", what); return RAHT_ERR_INVALID; }
+    if (n_nodes < 1 || n_nodes >= ((int64_t)1 << 31)) { set_error("%s: n_nodes must be 1 .. 2^31 - 1", what); return RAHT_ERR_INVALID; }
+    if ((uintptr_t)sym & 3) { set_error("%s: sym must be 4-byte aligned", what); return RAHT_ERR_INVALID; }
     OctTable tb;
     bool seen[256] = {};
     tb.used = 256;
     for (int r = 0; r < 256; ++r) {
         const uint8_t b = byte_of_rank[r];
-        if (seen[b]) { set_error("raht_octree_bytes: byte_of_rank is not a permutation of 0 .. 255"); return RAHT_ERR_INVALID; }
+        if (seen[b]) { set_error("%s: byte_of_rank is not a permutation of 0 .. 255", what); return RAHT_ERR_INVALID; }
         seen[b] = true;
         tb.byte_of[r] = b;
-        if (b == 0) tb.used = (uint32_t)r;       // no node has an empty occupancy byte: byte 0 leads the unused ranks
+        if (b == 0 && n_used < 0) tb.used = (uint32_t)r;   // no node has an empty occupancy byte: byte 0 leads the unused ranks
     }
+    if (n_used >= 0) tb.used = (uint32_t)n_used;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = (((uintptr_t)occ & 3) | ((uintptr_t)sym & 15)) == 0;
+    const bool vec = (((uintptr_t)out & 3) | ((uintptr_t)sym & 15)) == 0;
     const dim3 gm(oct_grid(n_nodes, OCT_THREADS * 4)), blk(OCT_THREADS);
-    if (vec) hipLaunchKernelGGL(oct_bytes_kernel<true>, gm, blk, 0, s, sym, n_nodes, tb, occ, bad);
-    else hipLaunchKernelGGL(oct_bytes_kernel<false>, gm, blk, 0, s, sym, n_nodes, tb, occ, bad);
+    if (vec) hipLaunchKernelGGL(oct_bytes_kernel<true>, gm, blk, 0, s, sym, n_nodes, tb, out, bad);
+    else hipLaunchKernelGGL(oct_bytes_kernel<false>, gm, blk, 0, s, sym, n_nodes, tb, out, bad);
     RAHT_HIP_CHECK(hipGetLastError());
     return RAHT_OK;
+}
+
+int raht_octree_bytes(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_of_rank, uint8_t *occ, int32_t *bad, raht_stream_t stream)
+{
+    return oct_bytes_run("raht_octree_bytes", sym, n_nodes, byte_of_rank, -1, occ, bad, stream);
+}
+
+// the residual bytes of a predicted section (octree_inter.hip): byte 0 is an ordinary value there, the header says how many ranks are in use
+int raht_octree_bytes_used(const int32_t *sym, int64_t n_nodes, const uint8_t *byte_of_rank, int n_used, uint8_t *res, int32_t *bad,
+                           raht_stream_t stream)
+{
+    if (n_used < 1 || n_used > 256) { set_error("raht_octree_bytes_used: n_used must be 1 .. 256"); return RAHT_ERR_INVALID; }
+    return oct_bytes_run("raht_octree_bytes_used", sym, n_nodes, byte_of_rank, n_used, res, bad, stream);
 }
 
 int raht_demorton(const uint64_t *keys, int64_t N, int J, int64_t *V, raht_stream_t stream)
