@@ -396,7 +396,19 @@ int raht_debug_run_stage(const raht_plan *plan, int inverse, int stage, const fl
  * python/encode_3dgs.py:204 floor(x/step+0.5), :210 index_select(0, order_RAGFT), :215 int32;
  * :261 x*step, :267-268 gather by argsort(order_RAGFT)).
  *   Q[k, c] = (int32) floor(T[order[k], c] / step_c + 0.5)        T[order[k], c] = Q[k, c] * step_c
- * steps: HOST array of n_steps values, n_steps == 1 (one step for all channels) or == D. */
+ * steps: HOST array of n_steps values, n_steps == 1 (one step for all channels) or == D.
+ *
+ * THE OUT-OF-RANGE RULE, for this and every other entry point that quantizes (raht_fwd_quant*, raht_quant_rows*, the mixed, multi and
+ * batch forms, raht_rlgr_seg_rate): for a coefficient x and a step s of type T (float or double) all arithmetic is in T -- q = x / s
+ * (IEEE division), r = floor(q + 0.5) -- and the integer is
+ *   r          if -2^31 <= r <= 2^31 - 1  (float: q + 0.5f rounds to even from 2^23 on, as float32 arithmetic does)
+ *   INT32_MAX  if r > 2^31 - 1, +inf included   (x = +inf, or a quotient that overflows T)
+ *   INT32_MIN  if r < -2^31, -inf included
+ *   0          if r is NaN                       (x is NaN)
+ * The reference leaves these cases to the platform's conversion (encode_3dgs.py:215), which differs between the CPU and a GPU; here
+ * the device kernels, the host twins, the oracle and the torch helper of the unfused drivers (ops.to_int32) return the same integers,
+ * bit for bit (tests/test_gpu_quant_edges.py, tests/test_quant_edges_model.py). A saturated integer is not reported: a caller keeps a
+ * column whole by keeping |x| / s below 2^31 -- for the DC term of a column, |mean| * sqrt(N) / s < 2^31. */
 int raht_quant_reorder(const raht_plan *plan, const float *T, int64_t ldt, int D, const float *steps,
                        int n_steps, int32_t *Q, int64_t ldq, raht_stream_t stream);
 int raht_dequant_unreorder(const raht_plan *plan, const int32_t *Q, int64_t ldq, int D,
@@ -717,7 +729,8 @@ int raht_rlgr_seg_decode_ragged(int k, const uint8_t *const *in, const int64_t *
  * RAHT_ERR_INVALID (nothing enqueued, no device touched): T, steps or seg_bytes NULL; an unknown dtype; N < 1, D < 1, ldt < D, k < 1,
  * n_steps not 1 or D; a (N, D, seg_len) raht_rlgr_seg_encode_strided refuses (seg_len < 64, 2^31 segments, a worst case of 4 GiB);
  * flag_signed not 0 or 1; a step that is not finite and positive, or, float32, outside [2^-100, 2^100] (the range in which the
- * float32 quantizer's division needs no scaling). Quotients beyond int32 are undefined, as in every quantizer of this library.
+ * float32 quantizer's division needs no scaling). Quotients beyond int32 saturate, as in every quantizer of this library (the out-of-range rule at raht_quant_reorder);
+ * the squared error is that of the saturated integer.
  * Device memory: the k * n_steps steps, nothing else. Enqueues only: `steps` goes to the device with an asynchronous copy on
  * `stream`, which has read pageable memory by the time the call returns; a table in page-locked memory must stay unchanged
  * until the stream has passed this call. */

@@ -225,7 +225,7 @@ int raht_cpu_quant_reorder(const raht_cpu_plan *plan, const float *T, int64_t ld
     if (!plan || !T || !Q || D < 1 || ldt < D || ldq < D || !steps_ok(steps, n_steps, D)) { set_err("raht_cpu_quant_reorder: bad argument"); return RAHT_ERR_INVALID; }
     const int64_t *order = orc_param_order(plan->p);
     for (int64_t k = 0; k < plan->N; ++k) for (int c = 0; c < D; ++c)
-        Q[k * ldq + c] = (int32_t)floorf(T[order[k] * ldt + c] / steps[n_steps == 1 ? 0 : c] + 0.5f);
+        Q[k * ldq + c] = orc_saturate_i32((double)floorf(T[order[k] * ldt + c] / steps[n_steps == 1 ? 0 : c] + 0.5f));
     return RAHT_OK;
 }
 int raht_cpu_dequant_unreorder(const raht_cpu_plan *plan, const int32_t *Q, int64_t ldq, int D, const float *steps, int n_steps, float *T, int64_t ldt, raht_stream_t stream)
@@ -243,7 +243,7 @@ int raht_cpu_quant_reorder_f64(const raht_cpu_plan *plan, const double *T, int64
     if (!plan || !T || !Q || D < 1 || ldt < D || ldq < D || !steps_ok(steps, n_steps, D)) { set_err("raht_cpu_quant_reorder_f64: bad argument"); return RAHT_ERR_INVALID; }
     const int64_t *order = orc_param_order(plan->p);
     for (int64_t k = 0; k < plan->N; ++k) for (int c = 0; c < D; ++c)
-        Q[k * ldq + c] = (int32_t)floor(T[order[k] * ldt + c] / steps[n_steps == 1 ? 0 : c] + 0.5);
+        Q[k * ldq + c] = orc_saturate_i32(floor(T[order[k] * ldt + c] / steps[n_steps == 1 ? 0 : c] + 0.5));
     return RAHT_OK;
 }
 int raht_cpu_dequant_unreorder_f64(const raht_cpu_plan *plan, const int32_t *Q, int64_t ldq, int D, const double *steps, int n_steps, double *T, int64_t ldt, raht_stream_t stream)

@@ -294,7 +294,7 @@ int orc_quant_reorder(const double *T, int64_t N, int D, double step, const int6
     for (int64_t k = 0; k < N; ++k) {
         const double *src = T + order[k] * D;                   /* :210 index_select(0, order) */
         for (int c = 0; c < D; ++c)
-            Q[k * D + c] = (int32_t)floor(src[c] / step + 0.5); /* :204, :215 */
+            Q[k * D + c] = orc_saturate_i32(floor(src[c] / step + 0.5)); /* :204, :215 */
     }
     return 0;
 }

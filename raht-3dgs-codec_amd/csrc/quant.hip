@@ -89,7 +89,7 @@ struct RowPos {                    // explicit rows of the integer matrix (NULL:
 };
 
 // the true IEEE division in both precisions (this file is built with -fno-fast-math)
-__device__ __forceinline__ int32_t quantize_div(float x, float step) { return (int32_t)floorf(x / step + 0.5f); }    // :204, :215
+__device__ __forceinline__ int32_t quantize_div(float x, float step) { return saturate_i32(floorf(x / step + 0.5f)); }    // :204, :215
 __device__ __forceinline__ int32_t quantize_div(double x, double step) { return quantize_one_f64(x, step); }
 
 template <typename T, bool QUANT, typename Index>

@@ -84,7 +84,16 @@ __device__ __forceinline__ void st_ints(int32_t *__restrict__ p, const int32_t (
     for (int i = 0; i < VN; ++i) t.v[i] = v[i];
     *(IntPack<VN> *)p = t;
 }
-__device__ __forceinline__ int32_t quantize_one_f64(double x, double step) { return (int32_t)floor(x / step + 0.5); }   // encode_3dgs.py:204
+// THE out-of-range rule of every quantizer (include/raht.h): r = floor(x / step + 0.5) in the matrix's own type becomes r
+// itself within [-2^31, 2^31 - 1], INT32_MAX above (+inf included), INT32_MIN below (-inf included) and 0 when it is NaN. That is
+// what v_cvt_i32_f32 / v_cvt_i32_f64, which these conversions compile to, do with such an operand; the language leaves it open, so
+// tests/test_gpu_quant_edges.py pins the rule on every quantizing path of every build. An explicit clamp (max, min, conversion, two
+// compares, two selects per element) was measured at +1.2 % on the mixed and +1.8 % on the float32 fused step of the 3 M x 59
+// frame, against 0.2 to 0.5 % between repeated runs (profiles/quant_edges.json): the bare conversion stays.
+__device__ __forceinline__ int32_t saturate_i32(float r) { return (int32_t)r; }
+__device__ __forceinline__ int32_t saturate_i32(double r) { return (int32_t)r; }
+
+__device__ __forceinline__ int32_t quantize_one_f64(double x, double step) { return saturate_i32(floor(x / step + 0.5)); }   // encode_3dgs.py:204
 
 __device__ __forceinline__ int32_t quantize_one(float x, float sp, float r, int fast_div)
 {
@@ -95,11 +104,14 @@ __device__ __forceinline__ int32_t quantize_one(float x, float sp, float r, int 
         // within [2^-100, 2^100]); r is the refined reciprocal of the step (refined_rcp)
         const float q0 = x * r;
         const float q1 = __builtin_fmaf(__builtin_fmaf(-sp, q0, x), r, q0);
-        q = __builtin_fmaf(__builtin_fmaf(-sp, q1, x), r, q1);
+        const float q2 = __builtin_fmaf(__builtin_fmaf(-sp, q1, x), r, q1);
+        // a first product of 2^32 or more saturates whatever its last bits are, and an infinite one (x = +-inf, |x / step| >= 2^128)
+        // must not be refined: fma(-sp, inf, x) = -inf, then -inf * r + inf = NaN where the division gives +-inf
+        q = fabsf(q0) < 0x1p32f ? q2 : q0;
     } else {
         q = x / sp;
     }
-    return (int32_t)floorf(q + 0.5f);                     // encode_3dgs.py:204
+    return saturate_i32(floorf(q + 0.5f));                // encode_3dgs.py:204
 }
 
 // v_rcp_f32 + one Newton step: exactly how hipcc's own float division refines 1 / step per quotient

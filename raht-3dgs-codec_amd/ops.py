@@ -85,6 +85,16 @@ def _qmat(Q):
     return Q.to(torch.int32).contiguous()
 
 
+def to_int32(R):
+    """The integers of R = floor(x / step + 0.5) (float32 or float64, any device) by THE out-of-range rule of every quantizer
+    (include/raht.h): R itself within [-2^31, 2^31 - 1], INT32_MAX above (+inf included), INT32_MIN below (-inf included), 0 for NaN.
+    A bare ``.to(torch.int32)`` of such values differs between the CPU and the GPU. Clamped in R's own type, so that only values in
+    range are converted: the largest float32 below 2^31 is 2^31 - 128, whatever lies above it takes INT32_MAX by a select."""
+    f64 = R.dtype == torch.float64
+    q = torch.nan_to_num(R, nan=0.0).clamp_(-2147483648.0, 2147483647.0 if f64 else 2147483520.0).to(torch.int32)
+    return q if f64 else q.masked_fill_(R >= 2147483648.0, 2147483647)
+
+
 def step_list(steps, D=None):
     """A quantization step argument as a list of Python floats: [step] for a scalar (Python or numpy number, 0-d array or tensor),
     else the entries of a list, tuple, numpy array or tensor (which comes to the host once). With ``D``: one entry or D."""

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import rlgr as rlgr_mod
-from .ops import RAHT_param_reorder_fast, plan_of, raht_fn, sqdiff_columns, step_list
+from .ops import RAHT_param_reorder_fast, plan_of, raht_fn, sqdiff_columns, step_list, to_int32
 
 CSV_HEADER = ("Frame,Quantization_Step,Rate_bpp,"
               "RAHT_prelude_time,RAHT_transform_time,Quant_time,"
@@ -132,7 +132,7 @@ def encode_frame(V_int, attributes, J, steps, frame=1, device="cuda:0", dtype=to
             _sync()
             r["Quant_time"] = time.time() - t0
             t0 = time.time()
-            coeff_reordered = Coeff_enc.index_select(0, order_RAGFT).to(torch.int32)   # :210, :215
+            coeff_reordered = to_int32(Coeff_enc.index_select(0, order_RAGFT))        # :210, :215
             _sync()
             r["Coeff_reorder_enc_time"] = time.time() - t0
             r["RAHT_transform_time"] = t_transform
@@ -491,7 +491,7 @@ def encode_ply_frame(V_int, Crgb, J, steps=(1, 2, 4, 6, 8, 12, 16, 20, 24, 32, 6
         Y_hat = Coeff_enc[:, 0] * step
         mse = (torch.linalg.norm(Coeff[:, 0].double() - Y_hat.double()) ** 2) / (N * 255 ** 2)     # :150-151
         r["psnr"] = float(-10 * torch.log10(mse))
-        q_dev = Coeff_enc.index_select(0, order_RAGFT).to(torch.int32)              # :156-157
+        q_dev = to_int32(Coeff_enc.index_select(0, order_RAGFT))                    # :156-157
         q_cpu = rlgr_mod.to_host(rlgr_mod.transpose_on_device(q_dev))
         streams, r["Entropy_enc_time"] = rlgr_mod.encode_channels(q_cpu, 1, nthreads=nthreads, channel_major=True)   # :164-176
         q_back, r["Entropy_dec_time"] = rlgr_mod.decode_channels(streams, N, 1, nthreads=nthreads, channel_major=True)

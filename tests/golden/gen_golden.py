@@ -531,6 +531,34 @@ if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "rlgr_ra
     rlgr_random_cases()
 
 
+def rlgr_extreme_cases():
+    """The reference coder's streams for tests/rlgr_inputs.extreme_sequences (INT32_MIN and INT32_MAX in runs, alternating,
+    isolated, first and last), as lengths and SHA-256 digests like rlgr_random.npz, and whether the reference coder reads each
+    of its own streams back to the input (``round_trips``): where it does not, the tests pin the product coder to its own round
+    trip for that sequence."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref"))
+    import rlgr
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests.rlgr_inputs import digest, extreme_sequences
+    names, xs, bs, ok = [], [], [], []
+    for name, x in extreme_sequences():
+        m = rlgr.membuf()
+        m.rlgrWrite([int(v) for v in x], 1)
+        m.close()
+        b = np.array(m.get_buffer(), dtype=np.uint8)
+        _, back = rlgr.membuf(b.tolist()).rlgrRead(len(x), 1)
+        names.append(name); xs.append(x); bs.append(b); ok.append(list(back) == x.tolist())
+    np.savez_compressed(os.path.join(HERE, "rlgr_extreme.npz"), names=np.array(names),
+                        x_sha256=np.stack([digest(x) for x in xs]), x_len=np.array([len(x) for x in xs], np.int64),
+                        sha256=np.stack([digest(b) for b in bs]), bytes_len=np.array([len(b) for b in bs], np.int64),
+                        round_trips=np.array(ok, dtype=bool))
+    print("rlgr_extreme:", {n: (len(b), r) for n, b, r in zip(names, bs, ok)})
+
+
+if __name__ == "__main__" and os.environ.get("GOLDEN_ONLY", "") in ("", "rlgr_extreme"):
+    rlgr_extreme_cases()
+
+
 def merge_cases():
     """The reference's ``prepare_cluster_data`` (cuda/merge_cluster_cuda/__init__.py:30-75, pure torch, runs on the CPU; only
     its ``_C`` import is CUDA-only and merely warns) on seeded label sets: labels -> (cluster_indices, cluster_offsets).

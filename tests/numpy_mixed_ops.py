@@ -9,7 +9,7 @@ them with NaN, so a driver that reads them fails the tests."""
 import numpy as np
 import torch
 
-from tests.numpy_ops import NumpyLocalOps
+from tests.numpy_ops import NumpyLocalOps, _quantize
 
 
 def _steps(step, D):
@@ -23,7 +23,7 @@ class NumpyMixedLocalOps(NumpyLocalOps):
     # (the float columns' row quantizers, with per-channel steps as well)
     @staticmethod
     def quant_rows(X, step, pos, Q):
-        Q[pos] = torch.floor(X.to(torch.float64) / _steps(step, X.shape[1]) + 0.5).to(torch.int32)
+        Q[pos] = _quantize(X.to(torch.float64), _steps(step, X.shape[1]))
         return Q
 
     @staticmethod
@@ -34,7 +34,7 @@ class NumpyMixedLocalOps(NumpyLocalOps):
     @staticmethod
     def quant_rows_f64(X, step, pos, Q):
         assert X.dtype == torch.float64
-        Q[pos] = torch.floor(X / _steps(step, X.shape[1]) + 0.5).to(torch.int32)
+        Q[pos] = _quantize(X, _steps(step, X.shape[1]))
         return Q
 
     @staticmethod
@@ -53,7 +53,7 @@ class NumpyMixedLocalOps(NumpyLocalOps):
             roots_wide.copy_(R[:, :n_wide])
             roots.copy_(R.to(roots.dtype))
             roots[:, :n_wide] = float("nan")                 # unspecified in the product: nobody may read them
-        Q = torch.floor(T[plan.order_RAGFT] / _steps(step, T.shape[1]) + 0.5).to(torch.int32)
+        Q = _quantize(T[plan.order_RAGFT], _steps(step, T.shape[1]))
         if roots is not None:
             Q[plan.inv_order[plan.root_rows]] = np.iinfo(np.int32).min      # left to the caller's top stage
         return Q

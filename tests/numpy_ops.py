@@ -6,6 +6,34 @@ import numpy as np
 import torch
 
 
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def quantize_model(x, step, dtype):
+    """THE quantizer of every path (include/raht.h), as plain numpy: for coefficients ``x`` and steps ``step`` (broadcast against
+    each other) all arithmetic is in ``dtype`` (float32 or float64): q = x / step (IEEE division), r = floor(q + 0.5). The result
+    is r itself within [-2^31, 2^31 - 1], INT32_MAX above (+inf included), INT32_MIN below (-inf included) and 0 for NaN.
+    The clamp runs in float64, where every float32 and every |r| < 2^63 is exact, and only values in range are converted.
+    -> int32 array. In range this is ``floor(x / step + 0.5).astype(int32)`` bit for bit."""
+    dt = np.dtype(dtype)
+    assert dt in (np.dtype(np.float32), np.dtype(np.float64)), dt
+    x, s = np.asarray(x), np.asarray(step)
+    assert x.dtype == dt or x.dtype.kind != "f", (x.dtype, dt)             # (no silent rounding of the coefficients)
+    with np.errstate(all="ignore"):
+        r = np.floor(x.astype(dt) / s.astype(dt) + dt.type(0.5))
+    assert r.dtype == dt
+    r = r.astype(np.float64)
+    r = np.where(np.isnan(r), 0.0, np.clip(r, float(INT32_MIN), float(INT32_MAX)))
+    return r.astype(np.int32)
+
+
+def _quantize(X, step):
+    """quantize_model on a float64 CPU tensor -> int32 tensor"""
+    assert X.dtype == torch.float64
+    st = step.numpy() if torch.is_tensor(step) else step
+    return torch.from_numpy(quantize_model(X.numpy(), st, np.float64))
+
+
 def _msb(x):
     m = np.zeros(x.shape, dtype=np.int64)
     t = x.copy()
@@ -113,8 +141,7 @@ class NumpyPlan:
 
     def forward_quant(self, C, step, roots=None):
         T = self.forward(C, roots=roots)
-        Q = torch.floor(T[self.order_RAGFT] / step + 0.5).to(torch.int32)
-        return Q
+        return _quantize(T[self.order_RAGFT], step)
 
     def dequant_inverse(self, Q, step, roots=None):
         T = torch.empty((self.N, Q.shape[1]), dtype=torch.float64)
@@ -132,7 +159,7 @@ class NumpyLocalOps:
     # a few rows at explicit positions (ops.quant_rows / dequant_rows / rows_gather / rows_scatter)
     @staticmethod
     def quant_rows(X, step, pos, Q):
-        Q[pos] = torch.floor(X.to(torch.float64) / torch.as_tensor(step, dtype=torch.float64) + 0.5).to(torch.int32)
+        Q[pos] = _quantize(X.to(torch.float64), torch.as_tensor(step, dtype=torch.float64))
         return Q
 
     @staticmethod

@@ -39,6 +39,37 @@ def random_sequences():
     return xs
 
 
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def extreme_sequences():
+    """The two limits of int32, which a saturated quantizer writes (include/raht.h) and the seeded draws above never hold:
+    -> [(name, int32 array)], every sequence 200 symbols long (more than three segments of 64, ending inside one): runs of
+    each limit of 1, 2, 63, 64 and 65 symbols starting at symbol 0 (so that they end before, on and behind a segment border of
+    64), followed by small symbols; the two alternating; each isolated inside a long zero run; each as the first and as the
+    last symbol."""
+    n = 200
+    small = (np.arange(n) % 7 - 3).astype(np.int32)
+    out = []
+    for tag, v in (("min", INT32_MIN), ("max", INT32_MAX)):
+        for run in (1, 2, 63, 64, 65):
+            x = small.copy()
+            x[:run] = v
+            out.append((f"run{run}_{tag}", x))
+        x = np.zeros(n, dtype=np.int32)
+        x[131] = v
+        out.append((f"isolated_{tag}", x))
+        x = np.zeros(n, dtype=np.int32)                          # (run1_*: first before small symbols; here: before a zero run)
+        x[0] = v
+        out.append((f"first_{tag}", x))
+        x = small.copy()
+        x[-1] = v
+        out.append((f"last_{tag}", x))
+    x = np.where(np.arange(n) % 2 == 0, INT32_MIN, INT32_MAX).astype(np.int32)
+    out.append(("alternating", x))
+    return out
+
+
 def digest(a):
     """SHA-256 of an array's little-endian bytes, as 32 uint8."""
     a = np.ascontiguousarray(a)

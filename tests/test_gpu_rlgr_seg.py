@@ -346,3 +346,34 @@ def test_one_frame_decode_reads_the_same_symbols_from_any_payload_alignment():
     assert rc == 0, L.raht_last_error()
     assert torch.equal(outs[0], Q) and torch.equal(outs[1], Q)
     assert int(bad.item()) == 0
+
+
+def test_the_limits_of_int32_in_every_segment_position():
+    """INT32_MIN and INT32_MAX, which a saturated quantizer writes (include/raht.h) and 70 000 uniform draws meet with probability
+    1e-5: tests/rlgr_inputs.extreme_sequences as the channels of one frame at seg_len = 64, so that the runs end before, on and
+    behind a segment border. Every segment against the host coder (pinned to the reference coder's streams for the same
+    sequences by tests/test_rlgr.py), then the GPU decode, row-major and channel-major."""
+    import torch
+    from raht_3dgs_codec_amd import rlgr
+    from .rlgr_inputs import extreme_sequences
+    Q = np.stack([x for _, x in extreme_sequences()]).astype(np.int32)
+    D, N = Q.shape
+    S = 64
+    sc = rlgr.SegmentedCoder(N, D, S)
+    Qd = torch.from_numpy(Q).cuda()
+    total = sc.encode(Qd)
+    lens, offs = sc.seg_bytes.cpu().numpy(), sc.seg_off.cpu().numpy()
+    blob = sc.out[:total].cpu().numpy()
+    for c in range(D):
+        for s in range(sc.nseg):
+            m = rlgr.membuf()
+            m.rlgrWrite(Q[c, s * S: (s + 1) * S], 1)
+            ref = m.get_array()
+            g = c * sc.nseg + s
+            assert lens[g] == ref.shape[0], (c, s, lens[g], ref.shape[0])
+            assert np.array_equal(blob[offs[g]: offs[g] + lens[g]], ref), (c, s)
+    assert torch.equal(sc.decode(), Qd) and int(sc.bad.item()) == 0
+    rows = Qd.t().contiguous()                                                      # (N, D): what forward_quant hands the coder
+    sc2 = rlgr.SegmentedCoder(N, D, S)
+    assert sc2.encode(rows) == total and torch.equal(sc2.seg_bytes, sc.seg_bytes)
+    assert torch.equal(sc2.decode(row_major=True), rows)

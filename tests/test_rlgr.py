@@ -152,6 +152,40 @@ def test_random_streams_round_trip_and_match_the_reference_build_when_present():
     assert checked == 300
 
 
+# the reference coder's streams for tests/rlgr_inputs.extreme_sequences (tests/golden/gen_golden.py::rlgr_extreme_cases)
+EXTREME = load_golden("rlgr_extreme")
+
+
+def test_the_limits_of_int32_match_the_reference_coder(rl, oracle):
+    """INT32_MIN and INT32_MAX -- what a saturated quantizer writes (include/raht.h) -- in runs of 1, 2, 63, 64 and 65, alternating,
+    isolated in a zero run, first and last: the host coder's streams are the reference coder's (stored lengths and digests; its
+    build, where present, is asked too), and they decode to the input. The reference coder read every one of its own streams back
+    to the input when the fixture was made (``round_trips`` all true), so no sequence is pinned to the product alone."""
+    from .rlgr_inputs import digest, extreme_sequences
+    seqs = extreme_sequences()
+    assert [n for n, _ in seqs] == EXTREME["names"].tolist()
+    assert np.array_equal(np.stack([digest(x) for _, x in seqs]), EXTREME["x_sha256"]), "inputs differ from the digested ones"
+    assert EXTREME["round_trips"].all()
+    ref = _reference_build()
+    for i, (name, x) in enumerate(seqs):
+        assert (x == -2 ** 31).any() or (x == 2 ** 31 - 1).any(), name
+        m = rl.membuf()
+        m.rlgrWrite(x, 1)
+        got = m.get_array()
+        assert len(got) == int(EXTREME["bytes_len"][i]) and np.array_equal(digest(got), EXTREME["sha256"][i]), name
+        assert np.array_equal(got, oracle.rlgr_encode(x.astype(np.int64), 1)), name
+        _, back = rl.membuf(got).rlgrRead(len(x), 1)
+        assert back == x.tolist(), name
+        assert np.array_equal(oracle.rlgr_decode(got, len(x), 1), x), name
+        streams, _ = rl.encode_channels(x.reshape(1, -1), 1, nthreads=1, channel_major=True)
+        assert streams[0].tobytes() == got.tobytes(), name
+        back2, _ = rl.decode_channels(streams, len(x), 1, nthreads=1, channel_major=True)
+        assert np.array_equal(back2.reshape(-1), x), name
+        if ref is not None:
+            a = ref.membuf(); a.rlgrWrite(x.tolist(), 1); a.close()
+            assert bytes(bytearray(a.get_buffer())) == got.tobytes(), name
+
+
 def test_channel_coder_keeps_one_arena_and_checks_round_trips():
     """ChannelCoder (the pipeline's glue-free path): same bytes as encode_channels, decode into a caller's array, threaded
     equality with the position of the first difference."""
