@@ -997,6 +997,40 @@ int raht_predict_mc(const uint64_t *keys_sorted, int64_t N, int J, int block_log
                     const int8_t *mv, const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref,
                     const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched, raht_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Two references (csrc/predict_bi.hip): the predictor of a B frame, which lies between two coded frames and is a reference of
+ * none (python: ops.predict_bi, bitstream.encode_sequence_bytes(..., bframes)).
+ *
+ * The frame's keys k[0 .. N), two references (k0', C0') and (k1', C1') of the same depth and D, shift = 3 up as above, and
+ * optionally one motion field per reference, mv0 and mv1 (DEVICE int8[3 * n_blocks] over the FRAME's blocks: J, block_log2,
+ * block_first, n_blocks as raht_predict_mc takes them; a NULL field is all zero, and with both NULL none of the four is read).
+ * For reference r, m_r[i, ch] is exactly raht_predict's P (raht_predict_mc's under mv_r) against that reference -- the sequential
+ * float32 sum over the run in row order, one IEEE division -- and len_r the run's length, 0 for an empty cell or a shifted voxel
+ * outside the cube. Then
+ *     P = m0                      where len1 == 0
+ *     P = m1                      where len0 == 0        (+0.0f where both are 0)
+ *     P = fl(0.5f * fl(m0 + m1))  where both have a run: the sum is rounded, then the product; neither is contracted with what
+ *                                 follows (a sum that overflows, overflows)
+ * and Y = fl(X - P) (add = 0), fl(X + P) (add = 1) or P (X NULL): one float32 operation per element, also where P = 0. A row
+ * with a run in one reference only has raht_predict(_mc)'s bits for that reference; two identical references give raht_predict's
+ * bits for finite |m| < FLT_MAX / 2.
+ *   raht_predict_bi : Y may be X (a lane reads only what it writes); neither reference may overlap Y. n_matched (DEVICE int64[3],
+ *                     may be NULL) = the rows with a run in reference 0, in reference 1, in both. One launch (and a memset when
+ *                     n_matched is given); enqueues only, never synchronises.
+ * RAHT_ERR_INVALID, with nothing enqueued: raht_predict's rules for either reference, and with a field raht_predict_mc's rules
+ * for J, block_log2, block_first and n_blocks.
+ *
+ *   B frame : "RAHTB001" | int64 ref_back (>= 1) | int64 ref_fwd (>= 1) | int64 up | int64 block_log2 (0: no fields, else 1 .. J) |
+ *             int64 n_blocks (0 iff block_log2 == 0) | with fields: int8 mv0[n_blocks][3], zero bytes up to a multiple of 8, int8
+ *             mv1[n_blocks][3], padded likewise | a whole "RAHTF001" frame container whose attributes are the residual X - P.
+ *             Frame i is predicted from the frames i - ref_back (reference 0) and i + ref_fwd (reference 1), neither of which is a
+ *             B frame; only inside a sequence container, never at index 0, never reaching past the last frame. A predicted
+ *             geometry section is coded against reference 0's keys. */
+int raht_predict_bi(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                    const int8_t *mv0, const int8_t *mv1, const uint64_t *ref0_keys_sorted, int64_t N_ref0, const float *C_ref0,
+                    int64_t ld_ref0, const uint64_t *ref1_keys_sorted, int64_t N_ref1, const float *C_ref1, int64_t ld_ref1, int shift,
+                    const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched, raht_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

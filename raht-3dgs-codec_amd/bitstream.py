@@ -33,6 +33,15 @@ With ``geometry_inter`` the GEOMETRY of such a frame may be predicted as well (D
 ``OCTP0001`` one, coded against the keys of the frame its wrapper names; ``sequence_geometry`` tells which frames do that, and the
 decoders of a single frame take those keys as ``ref_keys``.
 
+With ``bframes`` > 0 a frame between two coded frames may be a B FRAME: predicted from both (``ops.predict_bi``:
+the mean of the two one-reference predictions where both references have voxels in the cell, the one that has where only one
+has), optionally under one motion field per reference, and never a reference itself -- ``decode_sequence_bytes(blob,
+frames=anchors)`` never touches its bytes. ``sequence_plan`` has the structure, ``sequence_refs`` reads it back.
+
+    RAHTB001 | int64 ref_back (>= 1) | int64 ref_fwd (>= 1: reference 1 is ref_fwd frames LATER) | int64 up | int64 block_log2
+    (0: no fields) | int64 n_blocks (0 iff block_log2 == 0) | with fields: int8 mv0[n_blocks][3], zero bytes up to a multiple of 8,
+    int8 mv1[n_blocks][3], padded likewise | a whole RAHTF001 frame
+
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
 sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
@@ -53,6 +62,8 @@ P_MAGIC = b"RAHTP001"
 P_HEAD = len(P_MAGIC) + 16                                     # what a predicted frame's wrapper adds to its inner frame
 M_MAGIC = b"RAHTM001"
 M_HEAD = len(M_MAGIC) + 32                                     # ... and a motion-compensated frame's, before its motion field
+B_MAGIC = b"RAHTB001"
+B_HEAD = len(B_MAGIC) + 40                                     # ... and a B frame's, before its two motion fields
 MIN_FRAME_BYTES = len(MAGIC) + 40 + 8 * 5 + 2 * (8 + 48)      # header, one step + box, two sections of 48 bytes at least
 
 
@@ -528,7 +539,8 @@ def sequence_frame(blob, i, offsets=None):
     return memoryview(blob)[off[i]: off[i + 1]]
 
 
-_WRAPPERS = {P_MAGIC: ("predicted frame", P_HEAD), M_MAGIC: ("motion-compensated frame", M_HEAD)}      # what a refusal says, the fixed part
+_WRAPPERS = {P_MAGIC: ("predicted frame", P_HEAD), M_MAGIC: ("motion-compensated frame", M_HEAD),      # what a refusal says, the fixed part
+             B_MAGIC: ("B frame", B_HEAD)}
 
 
 def _motion_field_bytes(n_blocks):
@@ -537,22 +549,43 @@ def _motion_field_bytes(n_blocks):
 
 
 def _parse_wrapper(fb, only=None):
-    """The wrapper of a predicted frame of either kind, checked as ``parse_pframe`` and ``parse_mframe`` say -> (ref_back, up, motion:
-    None or (block_log2, mv (n_blocks, 3) int8 numpy), the inner RAHTF001 container as a memoryview). None when ``fb`` opens with no
-    wrapper's magic (with ``only``: with another magic than that one)."""
+    """The wrapper of a predicted frame of any kind, checked as ``parse_pframe``, ``parse_mframe`` and ``parse_bframe`` say ->
+    (ref_back, up, motion: None or (block_log2, mv (n_blocks, 3) int8 numpy) -- (block_log2, mv0, mv1) in a B frame --, the inner
+    RAHTF001 container as a memoryview, ref_fwd: None but in a B frame). None when ``fb`` opens with no wrapper's magic (with
+    ``only``: with another magic than that one)."""
     magic = bytes(fb[:len(P_MAGIC)])
     if magic not in _WRAPPERS or only not in (None, magic):
         return None
     what, head = _WRAPPERS[magic]
     if len(fb) < head + MIN_FRAME_BYTES:
         raise ValueError(f"{what}: truncated wrapper")
-    ref_back, up = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic))]
+    ref_fwd = None
+    if magic == B_MAGIC:
+        ref_back, ref_fwd, up = [int(x) for x in np.frombuffer(fb, np.int64, 3, len(magic))]
+        if ref_fwd < 1:
+            raise ValueError(f"{what}: ref_fwd = {ref_fwd}, must be at least 1")
+    else:
+        ref_back, up = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic))]
     if ref_back < 1:
         raise ValueError(f"{what}: ref_back = {ref_back}, must be at least 1")
     if not 0 <= up <= 3:
         raise ValueError(f"{what}: up = {up} outside 0 .. 3")
     motion = None
-    if magic == M_MAGIC:
+    if magic == B_MAGIC:
+        block_log2, n_blocks = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic) + 24)]
+        if (block_log2 == 0) != (n_blocks == 0):
+            raise ValueError(f"{what}: block_log2 = {block_log2} with n_blocks = {n_blocks} (both 0 without motion fields, neither with)")
+        if block_log2:
+            if not 1 <= block_log2 <= MAX_J:
+                raise ValueError(f"{what}: block_log2 = {block_log2} outside 1 .. {MAX_J}")
+            if n_blocks < 1 or n_blocks >= 2 ** 31 or len(fb) < head + 2 * _motion_field_bytes(n_blocks) + MIN_FRAME_BYTES:
+                raise ValueError(f"{what}: too short for two motion fields of {n_blocks} blocks and a frame")
+            fields = np.frombuffer(fb, np.int8, 2 * _motion_field_bytes(n_blocks), head).reshape(2, -1)
+            if fields[:, 3 * n_blocks:].any():
+                raise ValueError(f"{what}: the padding behind a motion field is not zero")
+            motion = (block_log2, fields[0, :3 * n_blocks].reshape(n_blocks, 3), fields[1, :3 * n_blocks].reshape(n_blocks, 3))
+            head += fields.size
+    elif magic == M_MAGIC:
         block_log2, n_blocks = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic) + 16)]
         if not 1 <= block_log2 <= MAX_J:
             raise ValueError(f"{what}: block_log2 = {block_log2} outside 1 .. {MAX_J}")
@@ -563,7 +596,7 @@ def _parse_wrapper(fb, only=None):
             raise ValueError(f"{what}: the padding behind the motion field is not zero")
         motion = (block_log2, field[:3 * n_blocks].reshape(n_blocks, 3))
         head += len(field)
-    return ref_back, up, motion, memoryview(fb)[head:]
+    return ref_back, up, motion, memoryview(fb)[head:], ref_fwd
 
 
 def parse_pframe(fb):
@@ -587,54 +620,83 @@ def parse_mframe(fb):
     return w[0], w[1], *w[2], w[3]
 
 
+def parse_bframe(fb):
+    """The wrapper of a B frame, checked (pure host code) -> (ref_back, ref_fwd, up, block_log2, mv0, mv1, the inner RAHTF001
+    container as a memoryview); block_log2 is 0 and mv0, mv1 are None without motion fields, (n_blocks, 3) int8 numpy with them.
+    ``ValueError`` for another magic, ``ref_back`` or ``ref_fwd`` below 1, ``up`` outside 0 .. 3, ``block_log2`` and ``n_blocks`` of
+    which one is 0 and the other not, ``block_log2`` outside 1 .. 21, a wrapper too short for its fields plus a frame, padding that
+    is not zero. What depends on the sequence or on the inner frame is for the sequence's checks (``_frame_head``)."""
+    w = _parse_wrapper(fb, B_MAGIC)
+    if w is None:
+        raise ValueError("not a RAHT B-frame wrapper")
+    return w[0], w[4], w[1], *(w[2] or (0, None, None)), w[3]
+
+
 def _frame_head(view, off, i, max_voxels):
-    """frame i of a sequence from its headers alone -> dict: kind ("I" / "P"), ref (the frame it is predicted from, or None), up,
-    motion (None, or (block_log2, mv) of a motion-compensated frame), fb (its RAHTF001 container: the inner one of a predicted
-    frame), h (``parse_frame`` of it), seg_len. ``ValueError`` naming i."""
+    """frame i of a sequence from its headers alone -> dict: kind ("I" / "P" / "B"), ref (the frame it is predicted from -- a B
+    frame's reference 0 --, or None), ref1 (a B frame's reference 1, or None), up, motion (None, (block_log2, mv) of a
+    motion-compensated frame, (block_log2, mv0, mv1) of a B frame with fields), fb (its RAHTF001 container: the inner one of a
+    predicted frame), h (``parse_frame`` of it), seg_len. ``ValueError`` naming i."""
     fb = view[off[i]: off[i + 1]]
-    kind, ref, up, motion = "I", None, 0, None
+    kind, ref, ref1, up, motion = "I", None, None, 0, None
     try:
         w = _parse_wrapper(fb)
         if w is not None:
-            ref_back, up, motion, fb = w
+            ref_back, up, motion, fb, ref_fwd = w
+            what = "predicted frame" if ref_fwd is None else "B frame"
             if i == 0:
-                raise ValueError("a predicted frame cannot open a sequence")
+                raise ValueError(f"a {what} cannot open a sequence")
             if ref_back > i:
-                raise ValueError(f"predicted frame: ref_back = {ref_back} reaches before frame 0")
+                raise ValueError(f"{what}: ref_back = {ref_back} reaches before frame 0")
             kind, ref = "P", i - ref_back
+            if ref_fwd is not None:
+                if i + ref_fwd > len(off) - 2:
+                    raise ValueError(f"{what}: ref_fwd = {ref_fwd} reaches past the last frame")
+                kind, ref1 = "B", i + ref_fwd
         h = parse_frame(fb, max_voxels)
         if h["geometry_ref"] is not None and ref is None:
             raise ValueError("a geometry section predicted from another frame in a frame without a wrapper")
         if motion is not None:
+            what = "B frame" if kind == "B" else "motion-compensated frame"
             if motion[0] > h["J"]:
-                raise ValueError(f"motion-compensated frame: block_log2 = {motion[0]} outside 1 .. J = {h['J']}")
+                raise ValueError(f"{what}: block_log2 = {motion[0]} outside 1 .. J = {h['J']}")
             go, gl = h["geometry"]
             n_level = OctreeCoder.parse(fb[go: go + gl], max_voxels)["counts"][h["J"] - motion[0]]
             if len(motion[1]) != n_level:
-                raise ValueError(f"motion-compensated frame: a motion field of {len(motion[1])} blocks, the geometry has {n_level}")
+                raise ValueError(f"{what}: a motion field of {len(motion[1])} blocks, the geometry has {n_level}")
         ao, al = h["attributes"]
         S = SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[2]
     except ValueError as e:
         raise ValueError(f"sequence container: frame {i}: {e}") from None
-    return dict(kind=kind, ref=ref, up=up, motion=motion, fb=fb, h=h, seg_len=S)
+    return dict(kind=kind, ref=ref, ref1=ref1, up=up, motion=motion, fb=fb, h=h, seg_len=S)
 
 
 def _frame_heads(view, off, idx, max_voxels):
-    """the heads of the frames ``idx`` and of every frame they depend on, back to the nearest intra frame -> {i: head}; a predicted
-    frame whose J or D is not its reference's, or whose geometry is predicted from another voxel count than its reference's, is
-    refused here, before any device work"""
+    """the heads of the frames ``idx`` and of every frame they depend on -- under both references of a B frame --, back to the
+    nearest intra frames -> {i: head}; a predicted frame whose J or D is not its reference's, whose reference is a B frame, or whose
+    geometry is predicted from another voxel count than its reference's (a B frame's: reference 0's), is refused here, before any
+    device work"""
     heads = {}
     for i in idx:                                                            # (in the order asked for: the first bad frame is the one named)
-        while i is not None and i not in heads:
-            heads[i] = _frame_head(view, off, i, max_voxels)
-            i = heads[i]["ref"]
+        todo = [i]
+        while todo:
+            i = todo.pop()
+            if i is not None and i not in heads:
+                heads[i] = _frame_head(view, off, i, max_voxels)
+                todo += [heads[i]["ref1"], heads[i]["ref"]]                  # (reference 0's chain first)
     for i in sorted(heads):
         hd = heads[i]
-        if hd["ref"] is not None:
-            h, r = hd["h"], heads[hd["ref"]]["h"]
+        for g in (hd["ref"], hd["ref1"]):
+            if g is None:
+                continue
+            h, r = hd["h"], heads[g]["h"]
+            if heads[g]["kind"] == "B":
+                raise ValueError(f"sequence container: frame {i}: its reference (frame {g}) is a B frame, which is no frame's reference")
             if (h["J"], h["D"]) != (r["J"], r["D"]):
                 raise ValueError(f"sequence container: frame {i}: a predicted frame of J = {h['J']}, D = {h['D']} against a reference "
-                                 f"(frame {hd['ref']}) of J = {r['J']}, D = {r['D']}")
+                                 f"(frame {g}) of J = {r['J']}, D = {r['D']}")
+        if hd["ref"] is not None:
+            h, r = hd["h"], heads[hd["ref"]]["h"]
             if h["geometry_ref"] not in (None, r["N"]):
                 raise ValueError(f"sequence container: frame {i}: a geometry section predicted from {h['geometry_ref']} voxels, the "
                                  f"reference (frame {hd['ref']}) has {r['N']}")
@@ -649,16 +711,24 @@ def _sequence_heads(blob, max_voxels, max_frames):
 
 
 def sequence_kinds(blob, max_voxels=None, max_frames=None):
-    """-> ["I" | "P"] per frame of a sequence container, from the headers alone (pure host code). Every frame's headers are checked
+    """-> ["I" | "P" | "B"] per frame of a sequence container, from the headers alone (pure host code). Every frame's headers are checked
     on the way as ``decode_sequence_bytes`` checks them: ``ValueError`` naming the frame for a predicted frame at index 0, a
     ``ref_back`` below 1 or reaching before frame 0, ``up`` outside 0 .. 3, a truncated wrapper, a frame ``parse_frame`` refuses, a
-    predicted frame whose J or D differs from its reference's."""
+    predicted frame whose J or D differs from its reference's; for a B frame (RAHTB001) also a ``ref_fwd`` below 1 or reaching past
+    the last frame, ``block_log2`` / ``n_blocks`` that do not go together or with the inner frame, and a reference that is a B frame."""
     return [hd["kind"] for hd in _sequence_heads(blob, max_voxels, max_frames)]
 
 
+def sequence_refs(blob, max_voxels=None, max_frames=None):
+    """-> per frame of a sequence container the tuple of the frame indices it is predicted from: () for an intra frame, (r,) for a
+    predicted one, (r0, r1) for a B frame; from the headers alone (pure host code), with the checks of ``sequence_kinds``."""
+    return [tuple(r for r in (hd["ref"], hd["ref1"]) if r is not None) for hd in _sequence_heads(blob, max_voxels, max_frames)]
+
+
 def sequence_motion(blob, max_voxels=None, max_frames=None):
-    """-> per frame of a sequence container None, or (block_log2, mv (n_blocks, 3) int8 numpy) for a motion-compensated frame, from
-    the headers alone (pure host code), with the checks of ``sequence_kinds``."""
+    """-> per frame of a sequence container None, (block_log2, mv (n_blocks, 3) int8 numpy) for a motion-compensated frame, or
+    (block_log2, mv0, mv1) for a B frame with motion fields, from the headers alone (pure host code), with the checks of
+    ``sequence_kinds``."""
     return [hd["motion"] for hd in _sequence_heads(blob, max_voxels, max_frames)]
 
 
@@ -675,13 +745,23 @@ class _Predictor:
     encoder's closed loop and the decoder add the prediction through the one ``restore``, with one argument list: that is what
     keeps the loop free of drift. ``overhead``: the bytes of ``wrapper()``."""
 
-    def __init__(self, keys, ref, J, up, motion=None):
-        self.keys, self.ref, self.J, self.up, self.motion = keys, ref, J, up, motion
-        self.overhead = P_HEAD if motion is None else M_HEAD + _motion_field_bytes(len(motion[1]))
+    def __init__(self, keys, ref, J, up, motion=None, back=1, ref1=None, fwd=None):
+        """back: how many frames earlier ``ref`` lies. A B frame has a second reference ``ref1``, ``fwd`` frames later; its ``motion``
+        is None or (block_log2, mv0, mv1, block_first)."""
+        self.keys, self.ref, self.J, self.up, self.motion, self.back, self.ref1, self.fwd = keys, ref, J, up, motion, back, ref1, fwd
+        if ref1 is not None:
+            self.overhead = B_HEAD + (0 if motion is None else 2 * _motion_field_bytes(len(motion[1])))
+        else:
+            self.overhead = P_HEAD if motion is None else M_HEAD + _motion_field_bytes(len(motion[1]))
 
     def _apply(self, X, add):
         """X - P into a fresh matrix, or with ``add`` X + P in place"""
         kw = dict(X=X, up=self.up, add=add, out=X if add else None)
+        if self.ref1 is not None:
+            if self.motion is not None:
+                block_log2, mv0, mv1, block_first = self.motion
+                kw.update(J=self.J, block_log2=block_log2, block_first=block_first, mv0=mv0, mv1=mv1)
+            return ops.predict_bi(self.keys, self.ref, self.ref1, **kw)
         if self.motion is None:
             return ops.predict(self.keys, *self.ref, **kw)
         block_log2, mv, block_first = self.motion
@@ -694,19 +774,45 @@ class _Predictor:
         return self._apply(C, True)
 
     def wrapper(self):
-        """the bytes in front of the inner frame, with ref_back = 1 (a motion field comes to the host here)"""
+        """the bytes in front of the inner frame (a motion field comes to the host here)"""
+        if self.ref1 is not None:
+            fields, n_blocks = b"", 0
+            if self.motion is not None:
+                n_blocks = len(self.motion[1])
+                pad = bytes(_motion_field_bytes(n_blocks) - 3 * n_blocks)
+                fields = b"".join(mv.cpu().numpy().tobytes() + pad for mv in self.motion[1:3])
+            block_log2 = 0 if self.motion is None else self.motion[0]
+            return B_MAGIC + np.array([self.back, self.fwd, self.up, block_log2, n_blocks], np.int64).tobytes() + fields
         if self.motion is None:
-            return P_MAGIC + np.array([1, self.up], np.int64).tobytes()
+            return P_MAGIC + np.array([self.back, self.up], np.int64).tobytes()
         field = self.motion[1].cpu().numpy().tobytes()
-        return (M_MAGIC + np.array([1, self.up, self.motion[0], len(field) // 3], np.int64).tobytes() + field
+        return (M_MAGIC + np.array([self.back, self.up, self.motion[0], len(field) // 3], np.int64).tobytes() + field
                 + bytes(self.overhead - M_HEAD - len(field)))
 
 
 SEQ_CHUNK = SegmentedCoder.BATCH_MAX                                     # frames whose transform and entropy stages share launches
 
 
+def sequence_plan(n, gop, bframes=0):
+    """The structure ``encode_sequence_bytes(..., gop, bframes)`` gives a sequence of ``n`` frames (pure host code) -> per frame
+    ("I" | "P" | "B", refs): what the frame may be coded as at most, and the frames it is then predicted from. A GOP covers the
+    frames g0 .. g1 - 1, g1 = min(g0 + gop, n); its ANCHORS are g0 + k (bframes + 1) and its last frame: g0 is "I" with no
+    reference, every other anchor "P" from the anchor before it; every other frame is a "B" candidate between its neighbouring
+    anchors (a, c), a < i < c."""
+    n, gop, b = int(n), int(gop), int(bframes)
+    if n < 1 or gop < 1 or b < 0:
+        raise ValueError("sequence_plan: n >= 1, gop >= 1, bframes >= 0")
+    plan = []
+    for g0 in range(0, n, gop):
+        g1 = min(g0 + gop, n)
+        anchors = sorted(set(range(g0, g1, b + 1)) | {g1 - 1})
+        for a, c in zip([None] + anchors, anchors):
+            plan += [("B", (a, c))] * (0 if a is None else c - a - 1) + [("I", ()) if a is None else ("P", (a,))]
+    return plan
+
+
 def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None, gop=1, up=0,
-                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off"):
+                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off", bframes=0):
     """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
     container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
     frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
@@ -738,14 +844,24 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     under a motion field too: the reference is not shifted); "auto" -- both sections are coded and the smaller is kept, a tie going
     to the intra one. Frames coded intra never carry one. Under ``inter="auto"`` the cost of a way to code the frame is then its
     attribute bytes + its wrapper + the geometry section it would carry. "off" (the default) is byte for byte what it was without
-    this argument."""
+    this argument.
+
+    ``bframes`` = b > 0 (with ``gop`` > 1): B frames (``sequence_plan`` has the structure). The anchors of a GOP --
+    every (b + 1)-th frame and its last -- are coded as above, each from the anchor BEFORE it (its wrapper carries that
+    ``ref_back``). A frame between two anchors a < i < c is coded after both are reconstructed and is no frame's reference: the
+    ways are intra, predicted from a, that under a motion field, B from (a, c) -- R = A - ``ops.predict_bi`` of the two
+    reconstructions, an RAHTB001 frame -- and B under two fields (two independent ``ops.motion_search`` calls, one per reference;
+    taken when either field is not all zero). ``inter="always"`` takes the last way, ``inter="auto"`` the fewest bytes (attribute
+    bytes + wrapper + geometry section), the earliest among equals. A predicted geometry section of such a frame is coded against
+    a's keys. No reconstruction is formed for these frames, and the transform + quantization of the ones between two anchors go
+    through one set of launches. ``bframes=0`` (the default) is byte for byte what it was without this argument."""
     import torch
     dev = torch.device(device)
-    J, n_wide, gop, up, motion, block_log2 = int(J), int(n_wide), int(gop), int(up), int(motion), int(block_log2)
+    J, n_wide, gop, up, motion, block_log2, bframes = int(J), int(n_wide), int(gop), int(up), int(motion), int(block_log2), int(bframes)
     if not frames:
         raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
-    if gop < 1 or not 0 <= up <= 3 or inter not in ("auto", "always"):
-        raise ValueError('encode_sequence_bytes: gop >= 1, up in 0 .. 3, inter "auto" or "always"')
+    if gop < 1 or not 0 <= up <= 3 or inter not in ("auto", "always") or bframes < 0:
+        raise ValueError('encode_sequence_bytes: gop >= 1, up in 0 .. 3, inter "auto" or "always", bframes >= 0')
     if not 0 <= motion <= 3 or (motion and not 1 <= block_log2 <= J):
         raise ValueError("encode_sequence_bytes: motion in 0 .. 3, block_log2 in 1 .. J")
     if geometry_inter not in ("off", "always", "auto"):
@@ -762,50 +878,88 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
         cands = ops.motion_candidates(motion)
         if motion_weights is None:
             motion_weights = (1.0 / np.asarray(steps * (D if len(steps) == 1 else 1), np.float64)).astype(np.float32)
+    n = len(VA)
     parts = []                                                               # (the pieces of every frame: joined once, at the end)
+    coded = {}                                                               # frame -> (geometry section, Q, wrapper) until its entropy stage
+
+    def flush():
+        # the entropy stage of the next SEQ_CHUNK frames in display order (of the rest at the end), once all of them are coded
+        while len(parts) < n and all(i in coded for i in range(len(parts), min(len(parts) + SEQ_CHUNK, n))):
+            idx = range(len(parts), min(len(parts) + SEQ_CHUNK, n))
+            geos, Qs, wraps = zip(*[coded.pop(i) for i in idx])
+            atts = _attribute_parts(list(Qs), seg_len, dev)
+            parts.extend([w] + _frame_parts(J, VA[i][1].shape[0], D, n_wide, steps, vmin, width, geo, att)
+                         for i, geo, att, w in zip(idx, geos, atts, wraps))
+
+    def choose(i, A, a, c=None):
+        """How frame i is coded, its reference 0 frame ``a`` (None: intra only) and, for a B candidate, its reference 1 frame ``c``
+        -> (plan, source of the transform, geometry section, wrapper, predictor or None). The ways, each by its predictor: intra
+        (None), predicted from a's reconstruction, that under a motion field that is not all zero, from both references, and
+        that under two fields of which one is not all zero."""
+        keys, geo, plan = _keys_geometry_plan(VA[i][0], J, geometry)
+        ways, geo_p = [None], geo                                            # geo_p: the section of a frame that is coded predicted
+        if a is not None:
+            ref, ref1 = recon[a], None if c is None else recon[c]
+            if geometry_inter != "off":
+                geo_p = OctreeCoder.encode(keys, J, entropy=geometry, ref_keys=ref[0])
+                if geometry_inter == "auto" and len(geo_p) >= len(geo):
+                    geo_p = geo
+            ways.append(_Predictor(keys, ref, J, up, back=i - a))
+            if motion:
+                n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
+                block_first = ops.motion_blocks(keys, J, block_log2, n_blocks)
+                mv = ops.motion_search(keys, ref[0], ref[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
+                moved = bool(mv.any())
+                if moved:
+                    ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, block_first), back=i - a))
+            if ref1 is not None:
+                ways.append(_Predictor(keys, ref, J, up, back=i - a, ref1=ref1, fwd=c - i))
+                if motion:                                                   # (two independent searches, one per reference)
+                    mv1 = ops.motion_search(keys, ref1[0], ref1[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
+                    if moved or bool(mv1.any()):
+                        ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, mv1, block_first), back=i - a, ref1=ref1, fwd=c - i))
+        if inter == "always" or len(ways) == 1:                              # the last way; its source alone is formed
+            pred = ways[-1]
+            src = A if pred is None else pred.residual(A)
+        else:                                                                # the fewest bytes, wrapper included; the earliest among equals
+            srcs = [A] + [p.residual(A) for p in ways[1:]]
+            cost = [int(plan.rate_curve(X, [steps], n_wide, seg_len)["bytes"][0]) + (p.overhead + len(geo_p) if p else len(geo))
+                    for p, X in zip(ways, srcs)]
+            pred, src = min(zip(ways, srcs, cost), key=lambda w: w[2])[:2]
+        return keys, plan, src, geo if pred is None else geo_p, b"" if pred is None else pred.wrapper(), pred
+
     with torch.cuda.device(dev):
-        for lo in range(0, len(VA), SEQ_CHUNK):
-            chunk = VA[lo: lo + SEQ_CHUNK]
-            if gop == 1:
+        if gop == 1:
+            for lo in range(0, n, SEQ_CHUNK):
+                chunk = VA[lo: lo + SEQ_CHUNK]
                 _, geos, plans = zip(*[_keys_geometry_plan(V, J, geometry) for V, _ in chunk])
-                Qs, wraps = _quantize(list(plans), [A for _, A in chunk], steps, n_wide), [b""] * len(chunk)
-            else:
-                geos, Qs, wraps = [], [], []
-                for i, (V, A) in enumerate(chunk, lo):
-                    keys, geo, plan = _keys_geometry_plan(V, J, geometry)
-                    # the ways to code the frame, each by its predictor: intra (None), predicted from frame i - 1 (ref: its keys and
-                    # reconstruction, carried from frame to frame), and under a motion field that is not all zero
-                    ways, geo_p = [None], geo                                # geo_p: the section of a frame that is coded predicted
-                    if i % gop:
-                        if geometry_inter != "off":
-                            geo_p = OctreeCoder.encode(keys, J, entropy=geometry, ref_keys=ref[0])
-                            if geometry_inter == "auto" and len(geo_p) >= len(geo):
-                                geo_p = geo
-                        ways.append(_Predictor(keys, ref, J, up))
-                        if motion:
-                            n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
-                            block_first = ops.motion_blocks(keys, J, block_log2, n_blocks)
-                            mv = ops.motion_search(keys, ref[0], ref[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
-                            if bool(mv.any()):
-                                ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, block_first)))
-                    if inter == "always" or len(ways) == 1:                  # the last way; its source alone is formed
-                        pred = ways[-1]
-                        src = A if pred is None else pred.residual(A)
-                    else:                                                    # the fewest bytes, wrapper included; the earliest among equals
-                        srcs = [A] + [p.residual(A) for p in ways[1:]]
-                        cost = [int(plan.rate_curve(X, [steps], n_wide, seg_len)["bytes"][0]) + (p.overhead + len(geo_p) if p else len(geo))
-                                for p, X in zip(ways, srcs)]
-                        pred, src = min(zip(ways, srcs, cost), key=lambda w: w[2])[:2]
-                    Q = _quantize([plan], [src], steps, n_wide)[0]
-                    if i + 1 < len(VA) and (i + 1) % gop:                    # the next frame may be predicted from this one
-                        C = _reconstruct([plan], [Q], steps, n_wide)[0]
-                        ref = (keys, C if pred is None else pred.restore(C))
-                    geos.append(geo if pred is None else geo_p)
-                    Qs.append(Q)
-                    wraps.append(b"" if pred is None else pred.wrapper())
-            atts = _attribute_parts(Qs, seg_len, dev)
-            parts += [[w] + _frame_parts(J, A.shape[0], D, n_wide, steps, vmin, width, geo, att)
-                      for (_, A), geo, att, w in zip(chunk, geos, atts, wraps)]
+                Qs = _quantize(list(plans), [A for _, A in chunk], steps, n_wide)
+                coded.update({lo + k: (geo, Q, b"") for k, (geo, Q) in enumerate(zip(geos, Qs))})
+                flush()
+        else:
+            # anchors in display order, each predicted from the anchor before it in its GOP; the B candidates between two anchors
+            # after the second of them. recon: anchor -> (keys, reconstruction), kept while a frame to come is predicted from it.
+            order = sequence_plan(n, gop, bframes)
+            last_use = {r: i for i, (_, refs) in enumerate(order) for r in refs}
+            recon, prev = {}, None                                           # prev: the anchor before this one
+            for i, (kind, refs) in enumerate(order):
+                if kind == "B":
+                    continue
+                keys, plan, src, geo, wrap, pred = choose(i, VA[i][1], refs[0] if refs else None)
+                Q = _quantize([plan], [src], steps, n_wide)[0]
+                if i in last_use:                                            # a frame to come is predicted from this one
+                    C = _reconstruct([plan], [Q], steps, n_wide)[0]
+                    recon[i] = (keys, C if pred is None else pred.restore(C))
+                coded[i] = (geo, Q, wrap)
+                between = [] if prev is None else [j for j in range(prev + 1, i) if order[j][0] == "B"]
+                if between:                                                  # no frame is predicted from these: one set of transform launches
+                    ways = [choose(j, VA[j][1], *order[j][1]) for j in between]
+                    Qs = _quantize([w[1] for w in ways], [w[2] for w in ways], steps, n_wide)
+                    coded.update({j: (w[3], Q, w[4]) for j, w, Q in zip(between, ways, Qs)})
+                for r in [r for r in recon if last_use[r] <= i]:             # (a B candidate lies before its second anchor)
+                    del recon[r]
+                prev = i
+                flush()
     return _pack_parts(parts)
 
 
@@ -860,15 +1014,17 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
             named = [(f"sequence container: frame {i}: ", heads[i]["fb"], heads[i]["h"], geo_ref(i, group)) for i in group]
             done.update(zip(group, _decode_group(named, dev, max_voxels)))
     with torch.cuda.device(dev):
-        for i in sorted(done):                                               # ascending: a reference is whole before it is used
+        # a reference is whole before it is used: the anchors ascending, then the B frames, which are no frame's reference
+        for i in sorted(done, key=lambda i: (heads[i]["kind"] == "B", i)):
             hd = heads[i]
-            if hd["kind"] == "P":
+            if hd["kind"] != "I":
                 (_, C, keys), (_, C_ref, ref_keys) = done[i], done[hd["ref"]]
                 motion, J = hd["motion"], hd["h"]["J"]
                 if motion is not None:
                     block_first = ops.motion_blocks(keys, J, motion[0], len(motion[1]))
-                    motion = (motion[0], torch.from_numpy(motion[1].copy()).to(dev), block_first)
-                _Predictor(keys, (ref_keys, C_ref), J, hd["up"], motion).restore(C)
+                    motion = (motion[0], *(torch.from_numpy(mv.copy()).to(dev) for mv in motion[1:]), block_first)
+                ref1 = done[hd["ref1"]][2:0:-1] if hd["kind"] == "B" else None
+                _Predictor(keys, (ref_keys, C_ref), J, hd["up"], motion, ref1=ref1).restore(C)
     return [done[i][:2] for i in idx]
 
 
@@ -947,6 +1103,8 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
     if not 0 <= i < n:
         raise ValueError(f"{who}: the frame index must be in 0 .. {n - 1}")
     heads = _frame_heads(memoryview(blob), off, [i], max_voxels)
+    if heads[i]["kind"] == "B":
+        raise ValueError(f"{who}: frame {i} is a B frame: a region of a frame with two references is not supported, decode it whole")
     _region_depth(who, heads[i]["h"], depth)                                 # (a chain has one J: _frame_heads)
     if not 0 <= c0 < c1 <= 8 ** depth:
         raise ValueError(f"{who}: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")

@@ -173,16 +173,6 @@ __global__ __launch_bounds__(MS_THREADS) void motion_select_kernel(const unsigne
 
 using namespace raht;
 
-// the rules of a frame's blocks, shared by both entry points
-static int motion_check_blocks(const char *who, int J, int block_log2, const void *block_first, int64_t n_blocks, int64_t N)
-{
-    if (!block_first) { set_error("%s: NULL block_first", who); return RAHT_ERR_INVALID; }
-    if (J < 1 || J > 21) { set_error("%s: J=%d outside 1 .. 21", who, J); return RAHT_ERR_INVALID; }
-    if (block_log2 < 1 || block_log2 > J) { set_error("%s: block_log2=%d outside 1 .. J", who, block_log2); return RAHT_ERR_INVALID; }
-    if (n_blocks < 1 || n_blocks > N) { set_error("%s: n_blocks must be 1 .. N", who); return RAHT_ERR_INVALID; }
-    return RAHT_OK;
-}
-
 extern "C" {
 
 int raht_debug_motion_tile(int D) { return ms_tile_rows(D); }

@@ -1,7 +1,7 @@
-// predict_device.h -- the inter-frame predictor's device code, shared by predict.hip (the co-located predictor) and motion.hip
-// (the motion-compensated one and the motion search): the resolve of a key to its run in the reference, the run mean, and the
-// predictor kernel, whose KEY functor says for which key a row is resolved (include/raht.h, "Inter-frame prediction" and "Motion
-// compensation").
+// predict_device.h -- the inter-frame predictor's device code, shared by predict.hip (the co-located predictor), motion.hip
+// (the motion-compensated one and the motion search) and predict_bi.hip (the two-reference one): the resolve of a key to its run in
+// the reference, the run mean, and the predictor kernel, whose KEY functor says for which key a row is resolved (include/raht.h,
+// "Inter-frame prediction", "Motion compensation" and "Two references").
 // Row i of the current frame lies in the cell c = key[i] >> shift; its prediction is the mean of the reference rows of that cell,
 // which are ONE run [lo, hi) of the reference's sorted keys: summed in float32 in row order from the run's first row, divided once
 // by the run's length, 0 for an empty run. The order of the sum is part of the definition (a run holds at most 8^up <= 512 rows),
@@ -136,6 +136,39 @@ __device__ __forceinline__ RegChunk<float> pr_chunk(const float *__restrict__ C_
     return y;
 }
 
+// pr_chunk's mean without the apply, for the two-reference predictor (predict_bi.hip): the means of channels ch .. ch + 3 of ONE
+// row whose run is [lo, lo + len), the bits of pr_mean per channel; +0 for an empty run
+__device__ __forceinline__ RegChunk<float> pr_chunk_mean(const float *__restrict__ C_ref, int64_t ld_ref, int32_t lo, int32_t len, uint32_t ch)
+{
+    RegChunk<float> s;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s.v[i] = 0.0f;
+    if (len > 0) {
+        const float *p = C_ref + (int64_t)lo * ld_ref + ch;
+        s = ld_chunk<float>(p);
+        for (int32_t r = 1; r < len; ++r) {
+            const RegChunk<float> a = ld_chunk<float>(p + (int64_t)r * ld_ref);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s.v[i] = s.v[i] + a.v[i];
+        }
+        if (len > 1) {
+            const float d = (float)len;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s.v[i] = __fdiv_rn(s.v[i], d);
+        }
+    }
+    return s;
+}
+
+// the two-reference prediction from the two means (each +0 for an empty run): the one that has a run, or fl(0.5 fl(m0 + m1)) --
+// the sum rounded, then the product, neither contracted with what is done with the result
+__device__ __forceinline__ float pr_bi(float m0, int32_t len0, float m1, int32_t len1)
+{
+    if (len1 == 0) return m0;
+    if (len0 == 0) return m1;
+    return __fmul_rn(0.5f, __fadd_rn(m0, m1));
+}
+
 // FLAT: every row stride == D, the tile is one run of rows * D floats (X, Y element-aligned only). X and Y may be the same matrix:
 // a thread reads what it writes and nothing else of them.
 template <int MODE, bool FLAT, typename KEY>
@@ -231,6 +264,16 @@ static inline int predict_check(const char *who, const void *keys, int64_t N, co
     if (shift != 0 && shift != 3 && shift != 6 && shift != 9) { set_error("%s: shift=%d (0, 3, 6 or 9)", who, shift); return RAHT_ERR_INVALID; }
     if (D < 1 || ld_ref < D || ldy < D || (X && ldx < D)) { set_error("%s: D must be >= 1 and no row stride below it", who); return RAHT_ERR_INVALID; }
     if (add != 0 && add != 1) { set_error("%s: add=%d (0 or 1)", who, add); return RAHT_ERR_INVALID; }
+    return RAHT_OK;
+}
+
+// the rules of a frame's blocks, shared by every entry point that takes a motion field
+static inline int motion_check_blocks(const char *who, int J, int block_log2, const void *block_first, int64_t n_blocks, int64_t N)
+{
+    if (!block_first) { set_error("%s: NULL block_first", who); return RAHT_ERR_INVALID; }
+    if (J < 1 || J > 21) { set_error("%s: J=%d outside 1 .. 21", who, J); return RAHT_ERR_INVALID; }
+    if (block_log2 < 1 || block_log2 > J) { set_error("%s: block_log2=%d outside 1 .. J", who, block_log2); return RAHT_ERR_INVALID; }
+    if (n_blocks < 1 || n_blocks > N) { set_error("%s: n_blocks must be 1 .. N", who); return RAHT_ERR_INVALID; }
     return RAHT_OK;
 }
 

@@ -1140,6 +1140,41 @@ def predict_mc(keys, ref_keys, C_ref, mv, block_first, J, block_log2, X=None, up
 
 
 @torch.no_grad()
+def predict_bi(keys, ref0, ref1, X=None, up=0, add=False, out=None, want_matched=False, J=None, block_log2=0, block_first=None,
+               mv0=None, mv1=None):
+    """The two-reference predictor of a B frame (raht_predict_bi). ref0, ref1: (ref_keys, C_ref) as ``predict`` takes
+    them, of one D. With m_r = ``predict``'s P against reference r (``predict_mc``'s under ``mv_r``: (n_blocks, 3) int8 over the
+    FRAME's blocks, with ``J``, ``block_log2`` and ``block_first`` of ``motion_blocks``; a field that is None is all zero), P is m0
+    where reference 1 has no run for the row, m1 where reference 0 has none, 0 where neither has, and fl(0.5 fl(m0 + m1)) where
+    both have. -> P when ``X`` is None, X - P, or X + P with ``add``; into ``out`` when given (``out`` may be ``X``). Column slices
+    pass as they are. ``want_matched``: -> (result, n_matched), a (3,) int64 device tensor: the rows with a run in reference 0, in
+    reference 1, in both. Enqueued only."""
+    who = "predict_bi"
+    try:
+        (rk0, C0), (rk1, C1) = ref0, ref1
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: ref0 and ref1 are (ref_keys, C_ref) pairs") from None
+    fields = [f for f in (mv0, mv1) if f is not None]
+    if fields and (J is None or block_first is None):
+        raise ValueError(f"{who}: a motion field needs J, block_log2 and block_first")
+    blocks0 = (J, block_log2, block_first, fields[0]) if fields else None
+    blocks1 = (J, block_log2, block_first, fields[-1]) if fields else None
+    dev, _, live0, out, _ = _inter_args(who, keys, rk0, C0, up, X, blocks=blocks0, result=(add, out, False))
+    _, _, live1, _, _ = _inter_args(who, keys, rk1, C1, up, X, blocks=blocks1, result=(add, out, False))
+    (k, r0, C0), (r1, C1) = live0[:3], live1[1:3]
+    if C1.shape[1] != C0.shape[1] or C1.device != dev:
+        raise ValueError(f"{who}: both references must have the same D and lie on one device")
+    N, D = int(k.shape[0]), int(C0.shape[1])
+    bf = live0[3] if fields else None
+    f0, f1 = (None if f is None else f.contiguous() for f in (mv0, mv1))
+    matched = torch.empty(3, dtype=torch.int64, device=dev) if want_matched else None
+    _call(_lib.lib().raht_predict_bi, dev, _p(k), N, int(J) if fields else 0, int(block_log2) if fields else 0, _p(bf),
+          int(bf.shape[0]) - 1 if fields else 0, _p(f0), _p(f1), _p(r0), int(r0.shape[0]), _p(C0), C0.stride(0), _p(r1), int(r1.shape[0]),
+          _p(C1), C1.stride(0), 3 * int(up), _p(X), 0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched))
+    return (out, matched) if want_matched else out
+
+
+@torch.no_grad()
 def voxel_keys(PC, vmin, width, J):
     """Unsorted 3J-bit Morton keys (int64) of the points of PC (n, >= 3) float32 for a given bounding box: the
     voxelizer's first phase (reference python/voxelize_pc.py:92-100)."""
