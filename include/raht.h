@@ -988,11 +988,38 @@ int raht_predict(const uint64_t *keys_sorted, int64_t N, const uint64_t *ref_key
  *                       bytes up to a multiple of 8 | a whole "RAHTF001" frame container whose attributes are the residual
  *                       X - P_mv. Every int8 value is legal (a vector that leaves the cube predicts 0). n_blocks is the inner
  *                       geometry header's n_(J - block_log2). The rules of a predicted frame hold: only inside a sequence
- *                       container, never at index 0; the reconstruction is the inner frame's plus P_mv of the reference's. */
+ *                       container, never at index 0; the reconstruction is the inner frame's plus P_mv of the reference's.
+ *
+ * Hierarchical search (python: ops.motion_search_around / ops.motion_pyramid / ops.motion_search_hier,
+ * bitstream.encode_sequence_bytes(..., motion_levels)): vectors beyond the reach of an exhaustive search, at a cost
+ * that does not grow with the cube of the reach. Inputs: the frame's (k, X), a reference (k', C') of the same J and D,
+ * block_log2 = m, weights w, up, a number of levels L with 0 <= L <= min(3, m - 1) and J - L >= 1, and a top radius r in 1 .. 3.
+ * Pyramid. Level 0 of a frame (k, C) is the frame. Level l has as keys the distinct values of k >> 3 l, ascending, at depth J - l;
+ * its row for a cell is the run mean of C over the cell's rows -- the sequential float32 sum in row order and one IEEE division,
+ * the bits raht_predict(cell_keys << 3 l, k, C, X = NULL, shift = 3 l) returns. The frame's blocks are the same cells at every
+ * level: at level l they have block_log2 = m - l and n_blocks is unchanged.
+ * Search. v_L = raht_motion_search on level L of both frames with every vector of [-r, r]^3 (ordered by squared length, then
+ * dx, dy, dz: index 0 is no motion), w and shift 0. For l = L - 1 .. 0: v_l = raht_motion_search_around on level l of both frames
+ * with base = 2 v_(l+1), the 27 vectors of [-1, 1]^3 in that order, w, shift 0 above level 0 and the caller's 3 up at level 0.
+ * The result is v_0; its reach is r 2^L + 2^L - 1 <= 31 per component. L = 0 is raht_motion_search.
+ * Search around a base. base (DEVICE int8[3 * n_blocks]): the vector of the pair (block b, candidate k) is base[b] + cand[k],
+ * formed in integers. The cost of the pair is the cost above under that vector: shifted key, resolve, run mean, fl order, cap,
+ * 2^-10 fixed point, integer block sums. A pair with a component outside -127 .. 127 is INVALID: its table entry is 2^64 - 1
+ * after the call and it is never selected. best_k[b] = the smallest k among the valid pairs of the smallest cost, best_cost[b]
+ * that cost, mv[b] = base[b] + cand[best_k[b]]; a block with no valid pair gets best_k = -1, best_cost = 2^64 - 1 and mv = 0.
+ * With base = 0 the table and the selection are raht_motion_search's; with a constant base v the table is raht_motion_search's
+ * for the candidates v + cand[k].
+ *   raht_motion_search_around : raht_motion_search's arguments, base, and mv (DEVICE int8[3 * n_blocks], written by the library).
+ *                               A memset of the table and two launches; enqueues only, never synchronises.
+ * RAHT_ERR_INVALID, with nothing enqueued: every rule of raht_motion_search, a NULL base, a NULL mv. */
 int raht_motion_search(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
                        const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref, const float *X,
                        int64_t ldx, int D, const float *weights, const int32_t *cand, int K, int32_t *best_k, uint64_t *best_cost,
                        uint64_t *cost_table, raht_stream_t stream);
+int raht_motion_search_around(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                              const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref, const float *X,
+                              int64_t ldx, int D, const float *weights, const int8_t *base, const int32_t *cand, int K, int32_t *best_k,
+                              uint64_t *best_cost, int8_t *mv, uint64_t *cost_table, raht_stream_t stream);
 int raht_predict_mc(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
                     const int8_t *mv, const uint64_t *ref_keys_sorted, int64_t N_ref, int shift, const float *C_ref, int64_t ld_ref,
                     const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched, raht_stream_t stream);

@@ -29,6 +29,9 @@ With ``motion`` > 0 the prediction may follow a MOTION FIELD: one
     RAHTM001 | int64 ref_back | int64 up | int64 block_log2 | int64 n_blocks | int8 mv[n_blocks][3] | zero bytes up to a
     multiple of 8 | a whole RAHTF001 frame
 
+With ``motion_levels`` > 0 the field is found coarse to fine (``ops.motion_search_hier``) and may hold vectors of up
+to 31 voxels a component; the container and the decoders are the same.
+
 With ``geometry_inter`` the GEOMETRY of such a frame may be predicted as well: its geometry section is then an
 ``OCTP0001`` one, coded against the keys of the frame its wrapper names; ``sequence_geometry`` tells which frames do that, and the
 decoders of a single frame take those keys as ``ref_keys``.
@@ -812,7 +815,7 @@ def sequence_plan(n, gop, bframes=0):
 
 
 def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None, gop=1, up=0,
-                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off", bframes=0):
+                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off", bframes=0, motion_levels=0):
     """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
     container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
     frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
@@ -854,16 +857,26 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     taken when either field is not all zero). ``inter="always"`` takes the last way, ``inter="auto"`` the fewest bytes (attribute
     bytes + wrapper + geometry section), the earliest among equals. A predicted geometry section of such a frame is coded against
     a's keys. No reconstruction is formed for these frames, and the transform + quantization of the ones between two anchors go
-    through one set of launches. ``bframes=0`` (the default) is byte for byte what it was without this argument."""
+    through one set of launches. ``bframes=0`` (the default) is byte for byte what it was without this argument.
+
+    ``motion_levels`` = L > 0 (with ``motion`` = r > 0): every motion search -- against reference 0 and, for a B
+    candidate, against reference 1 -- is the coarse-to-fine ``ops.motion_search_hier(levels=L, radius=r)``: vectors of up to
+    r 2^L + 2^L - 1 voxels a component at the cost of a few radius-1 searches. L <= min(3, block_log2 - 1) and J - L >= 1. The
+    coarse levels of a reconstruction are built once and kept beside it for every frame that is searched against it. The format
+    and the decoders are the same: a field is a field. ``motion_levels=0`` (the default) is byte for byte what it was without
+    this argument."""
     import torch
     dev = torch.device(device)
     J, n_wide, gop, up, motion, block_log2, bframes = int(J), int(n_wide), int(gop), int(up), int(motion), int(block_log2), int(bframes)
+    motion_levels = int(motion_levels)
     if not frames:
         raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
     if gop < 1 or not 0 <= up <= 3 or inter not in ("auto", "always") or bframes < 0:
         raise ValueError('encode_sequence_bytes: gop >= 1, up in 0 .. 3, inter "auto" or "always", bframes >= 0')
     if not 0 <= motion <= 3 or (motion and not 1 <= block_log2 <= J):
         raise ValueError("encode_sequence_bytes: motion in 0 .. 3, block_log2 in 1 .. J")
+    if motion_levels < 0 or (motion_levels and (not motion or motion_levels > min(3, block_log2 - 1) or J - motion_levels < 1)):
+        raise ValueError("encode_sequence_bytes: motion_levels in 0 .. min(3, block_log2 - 1) with J - motion_levels >= 1, and only with motion")
     if geometry_inter not in ("off", "always", "auto"):
         raise ValueError('encode_sequence_bytes: geometry_inter "off", "always" or "auto"')
     VA = []
@@ -891,6 +904,17 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
             parts.extend([w] + _frame_parts(J, VA[i][1].shape[0], D, n_wide, steps, vmin, width, geo, att)
                          for i, geo, att, w in zip(idx, geos, atts, wraps))
 
+    def search(keys, counts, r, A, block_first):
+        """the motion field of a frame against the reconstruction of frame ``r``: exhaustive, or coarse to fine with the coarse
+        levels of that reconstruction built at their first use and kept until it is dropped"""
+        ref = recon[r]
+        if not motion_levels:
+            return ops.motion_search(keys, ref[0], ref[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
+        mv, _, info = ops.motion_search_hier(keys, ref[0], ref[1], A, J, block_log2, block_first, motion_levels, motion, motion_weights, up=up,
+                                             counts=counts, ref_counts=level_counts[r], ref_pyramid=pyramids.get(r))
+        pyramids[r] = info["ref_pyramid"]
+        return mv
+
     def choose(i, A, a, c=None):
         """How frame i is coded, its reference 0 frame ``a`` (None: intra only) and, for a B candidate, its reference 1 frame ``c``
         -> (plan, source of the transform, geometry section, wrapper, predictor or None). The ways, each by its predictor: intra
@@ -898,6 +922,9 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
         that under two fields of which one is not all zero."""
         keys, geo, plan = _keys_geometry_plan(VA[i][0], J, geometry)
         ways, geo_p = [None], geo                                            # geo_p: the section of a frame that is coded predicted
+        counts = OctreeCoder.parse(geo)["counts"] if motion_levels else None
+        if motion_levels and i in last_use:                                  # a reference to be: its coarse levels need their counts
+            level_counts[i] = counts
         if a is not None:
             ref, ref1 = recon[a], None if c is None else recon[c]
             if geometry_inter != "off":
@@ -908,14 +935,14 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
             if motion:
                 n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
                 block_first = ops.motion_blocks(keys, J, block_log2, n_blocks)
-                mv = ops.motion_search(keys, ref[0], ref[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
+                mv = search(keys, counts, a, A, block_first)
                 moved = bool(mv.any())
                 if moved:
                     ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, block_first), back=i - a))
             if ref1 is not None:
                 ways.append(_Predictor(keys, ref, J, up, back=i - a, ref1=ref1, fwd=c - i))
                 if motion:                                                   # (two independent searches, one per reference)
-                    mv1 = ops.motion_search(keys, ref1[0], ref1[1], A, J, block_log2, block_first, cands, motion_weights, up=up)[0]
+                    mv1 = search(keys, counts, c, A, block_first)
                     if moved or bool(mv1.any()):
                         ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, mv1, block_first), back=i - a, ref1=ref1, fwd=c - i))
         if inter == "always" or len(ways) == 1:                              # the last way; its source alone is formed
@@ -942,6 +969,7 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
             order = sequence_plan(n, gop, bframes)
             last_use = {r: i for i, (_, refs) in enumerate(order) for r in refs}
             recon, prev = {}, None                                           # prev: the anchor before this one
+            level_counts, pyramids = {}, {}                                  # (motion_levels) anchor -> its level counts, its coarse levels
             for i, (kind, refs) in enumerate(order):
                 if kind == "B":
                     continue
@@ -958,6 +986,8 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
                     coded.update({j: (w[3], Q, w[4]) for j, w, Q in zip(between, ways, Qs)})
                 for r in [r for r in recon if last_use[r] <= i]:             # (a B candidate lies before its second anchor)
                     del recon[r]
+                    level_counts.pop(r, None)
+                    pyramids.pop(r, None)
                 prev = i
                 flush()
     return _pack_parts(parts)

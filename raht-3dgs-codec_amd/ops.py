@@ -1105,26 +1105,127 @@ def motion_search(keys, ref_keys, C_ref, X, J, block_log2, block_first, candidat
     to 2^-10 fixed point; a block's cost is the integer sum over its rows; the smallest cost wins, the smallest index among equals.
     -> (mv (n_blocks, 3) int8, best_cost (n_blocks,) int64[, table (n_blocks, K) int64]) on the device; v points from the voxel to
     its reference voxel. Enqueued only."""
-    import numpy as np
     dev, args, _live, _, _ = _inter_args("motion_search", keys, ref_keys, C_ref, up, X, blocks=(J, block_log2, block_first))
-    n_blocks, D = int(block_first.shape[0]) - 1, int(C_ref.shape[1])
-    cand = np.asarray(candidates)
-    if cand.ndim != 2 or cand.shape[1] != 3 or not 1 <= cand.shape[0] <= MOTION_MAX_CANDIDATES or cand.dtype.kind not in "iu":
-        raise ValueError(f"motion_search: candidates must be (K, 3) integers, 1 <= K <= {MOTION_MAX_CANDIDATES}")
-    if np.abs(cand.astype(np.int64)).max() > 127:
-        raise ValueError("motion_search: a candidate outside +-127 (a vector is stored as int8)")
-    w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1)
-    if w.shape[0] != D or not bool(np.all(np.isfinite(w) & (w >= 0))):
-        raise ValueError("motion_search: weights must be D finite numbers >= 0")
-    cand_d = torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev)
-    w_d = torch.from_numpy(w).to(dev)
-    K = int(cand.shape[0])
+    n_blocks = int(block_first.shape[0]) - 1
+    cand_d, w_d, K = _search_host_args("motion_search", candidates, weights, int(C_ref.shape[1]), dev)
     best_k = torch.empty(n_blocks, dtype=torch.int32, device=dev)
     best_cost = torch.empty(n_blocks, dtype=torch.int64, device=dev)
     table = torch.empty((n_blocks, K), dtype=torch.int64, device=dev) if want_table else None
     _call(_lib.lib().raht_motion_search, dev, *args, _p(w_d), _p(cand_d), K, _p(best_k), _p(best_cost), _p(table))
     mv = cand_d.to(torch.int8)[best_k.long()]
     return (mv, best_cost, table) if want_table else (mv, best_cost)
+
+
+def _search_host_args(who, candidates, weights, D, dev):
+    """the candidates and weights of a search, checked on the host -> (cand (K, 3) int32, weights (D,) float32 on ``dev``, K)"""
+    import numpy as np
+    cand = np.asarray(candidates)
+    if cand.ndim != 2 or cand.shape[1] != 3 or not 1 <= cand.shape[0] <= MOTION_MAX_CANDIDATES or cand.dtype.kind not in "iu":
+        raise ValueError(f"{who}: candidates must be (K, 3) integers, 1 <= K <= {MOTION_MAX_CANDIDATES}")
+    if np.abs(cand.astype(np.int64)).max() > 127:
+        raise ValueError(f"{who}: a candidate outside +-127 (a vector is stored as int8)")
+    w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1)
+    if w.shape[0] != D or not bool(np.all(np.isfinite(w) & (w >= 0))):
+        raise ValueError(f"{who}: weights must be D finite numbers >= 0")
+    return torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev), torch.from_numpy(w).to(dev), int(cand.shape[0])
+
+
+# ---- hierarchical motion search (raht_motion_search_around; DESIGN.md 23) -------------------------------------------------------------
+MOTION_MAX_LEVELS = 3
+
+
+@torch.no_grad()
+def motion_search_around(keys, ref_keys, C_ref, X, J, block_log2, block_first, base, candidates, weights, up=0, want_table=False):
+    """``motion_search`` around a base (raht_motion_search_around). base: (n_blocks, 3) int8 on the device; the vector
+    of the pair (block b, candidate k) is ``base[b] + candidates[k]``, and its cost is ``motion_search``'s under that vector. A pair
+    with a component outside +-127 is invalid: its table entry is -1 (2^64 - 1) and it is never chosen. -> (mv (n_blocks, 3) int8:
+    base + the chosen candidate, written by the library; best_cost (n_blocks,) int64; best_k (n_blocks,) int32: the smallest k among
+    the valid pairs of the smallest cost[, table (n_blocks, K) int64]). A block with no valid pair has best_k = -1, best_cost = -1
+    and mv = 0. With a zero base the table and the choice are ``motion_search``'s. Enqueued only."""
+    who = "motion_search_around"
+    dev, args, _live, _, _ = _inter_args(who, keys, ref_keys, C_ref, up, X, blocks=(J, block_log2, block_first))
+    n_blocks = int(block_first.shape[0]) - 1
+    _need_cuda(base, "base")
+    if base.dtype != torch.int8 or tuple(base.shape) != (n_blocks, 3) or base.device != dev:
+        raise ValueError(f"{who}: base must be a ({n_blocks}, 3) int8 tensor on the keys' device")
+    base = base.contiguous()
+    cand_d, w_d, K = _search_host_args(who, candidates, weights, int(C_ref.shape[1]), dev)
+    best_k = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+    best_cost = torch.empty(n_blocks, dtype=torch.int64, device=dev)
+    mv = torch.empty((n_blocks, 3), dtype=torch.int8, device=dev)
+    table = torch.empty((n_blocks, K), dtype=torch.int64, device=dev) if want_table else None
+    _call(_lib.lib().raht_motion_search_around, dev, *args, _p(w_d), _p(base), _p(cand_d), K, _p(best_k), _p(best_cost), _p(mv), _p(table))
+    return (mv, best_cost, best_k, table) if want_table else (mv, best_cost, best_k)
+
+
+def _level_counts(who, k, J, levels, counts):
+    """the number of occupied cells at depth J - l for l = 1 .. levels: from ``counts`` (a geometry header's level counts, indexed
+    by depth 0 .. J), or counted from the keys (which synchronises)"""
+    if counts is None:
+        return [int(torch.unique_consecutive(k >> (3 * l)).numel()) for l in range(1, levels + 1)]
+    if len(counts) != J + 1:
+        raise ValueError(f"{who}: counts must hold the J + 1 level counts of the frame")
+    return [int(counts[J - l]) for l in range(1, levels + 1)]
+
+
+def _hier_levels(who, J, block_log2, levels):
+    J, L = int(J), int(levels)
+    if not 0 <= L <= MOTION_MAX_LEVELS or J - L < 1 or (block_log2 is not None and L > int(block_log2) - 1):
+        raise ValueError(f"{who}: levels must be 0 .. min({MOTION_MAX_LEVELS}, block_log2 - 1) with J - levels >= 1")
+    return J, L
+
+
+@torch.no_grad()
+def motion_pyramid(keys, C, J, levels, counts=None):
+    """The coarse levels of a frame for the hierarchical search -> per level l = 1 .. ``levels`` (keys_l (n_l,) int64:
+    the distinct values of ``keys >> 3 l``, ascending -- keys of depth J - l --, C_l (n_l, D) float32: the mean of ``C`` over the rows
+    of every cell, as ``predict`` forms it: summed in row order in float32, divided once). counts: the frame's level counts (a
+    geometry header's, indexed by depth 0 .. J); None: counted from the keys. The cell walk is ``region_cells``, the means are
+    ``predict(keys_l << 3 l, keys, C, up=l)``. Synchronises."""
+    who = "motion_pyramid"
+    k = _region_keys(keys, who)
+    J, L = _hier_levels(who, J, None, levels)
+    if k.dtype == torch.uint64:
+        k = k.view(torch.int64)
+    out = []
+    for l, n_l in zip(range(1, L + 1), _level_counts(who, k, J, L, counts)):
+        cells = region_cells(k, 3 * J, 3 * l, n_l)[0]
+        out.append((cells, predict(cells << (3 * l), k, C, up=l)))
+    return out
+
+
+@torch.no_grad()
+def motion_search_hier(keys, ref_keys, C_ref, X, J, block_log2, block_first, levels, radius, weights, up=0, counts=None, ref_counts=None,
+                       ref_pyramid=None):
+    """Coarse-to-fine block motion search. With L = ``levels`` (0 .. min(3, block_log2 - 1), J - L >= 1) and r =
+    ``radius`` (1 .. 3): level L of both frames (``motion_pyramid``) is searched with ``motion_candidates(r)`` and ``up = 0``; then
+    every level l below it is searched around twice the vectors of level l + 1 with ``motion_candidates(1)`` -- ``up = 0`` above
+    level 0, the caller's ``up`` at level 0. The frame's blocks are the same cells at every level (block_log2 - l at level l). The
+    reach is r 2^L + 2^L - 1 voxels; ``levels = 0`` is ``motion_search``. counts / ref_counts: the level counts of the frame and of
+    the reference (None: counted from the keys). ref_pyramid: ``info["ref_pyramid"]`` of an earlier call against the same reference,
+    which is then not built again. -> (mv (n_blocks, 3) int8, best_cost (n_blocks,) int64 -- of level 0 --, info: "mv": the vectors
+    per level 0 .. L, "pyramid" and "ref_pyramid": the levels 1 .. L of the frame and of the reference). Synchronises when L > 0."""
+    who = "motion_search_hier"
+    J, L = _hier_levels(who, J, block_log2, levels)
+    m, top = int(block_log2), motion_candidates(radius)
+    if L == 0:
+        mv, cost = motion_search(keys, ref_keys, C_ref, X, J, m, block_first, top, weights, up=up)
+        return mv, cost, dict(mv=[mv], pyramid=[], ref_pyramid=[])
+    n_blocks = int(block_first.shape[0]) - 1
+    pyramid = motion_pyramid(keys, X, J, L, counts)
+    if ref_pyramid is None:
+        ref_pyramid = motion_pyramid(ref_keys, C_ref, J, L, ref_counts)
+    elif len(ref_pyramid) != L:
+        raise ValueError(f"{who}: ref_pyramid must hold the levels 1 .. {L} of the reference")
+    cur, ref = [(keys, X)] + list(pyramid), [(ref_keys, C_ref)] + list(ref_pyramid)
+    firsts = [block_first] + [motion_blocks(cur[l][0], J - l, m - l, n_blocks) for l in range(1, L + 1)]
+    mv, cost = motion_search(cur[L][0], ref[L][0], ref[L][1], cur[L][1], J - L, m - L, firsts[L], top, weights, up=0)
+    per_level, around = [mv], motion_candidates(1)
+    for l in range(L - 1, -1, -1):
+        mv, cost, _ = motion_search_around(cur[l][0], ref[l][0], ref[l][1], cur[l][1], J - l, m - l, firsts[l], mv * 2, around, weights,
+                                           up=up if l == 0 else 0)
+        per_level.insert(0, mv)
+    return mv, cost, dict(mv=per_level, pyramid=pyramid, ref_pyramid=ref_pyramid)
 
 
 @torch.no_grad()
