@@ -609,7 +609,22 @@ int raht_xchg_status(void *base, int world, int64_t slot_bytes, raht_stream_t st
  *   seg_bytes: DEVICE uint32[D * nseg], nseg = ceil(N / seg_len): exact stream length of segment c * nseg + s
  *   seg_off  : DEVICE uint32[D * nseg + 1]: its offset in `out` (slots padded to 4 bytes); the last entry = bytes used
  *   out      : DEVICE, 4-byte aligned, cap bytes. RAHT_ERR_NOMEM (and *total_bytes = what is needed) when cap is too small.
- * raht_rlgr_seg_encode synchronises the stream (it returns the size); raht_rlgr_seg_decode does not. */
+ * raht_rlgr_seg_encode synchronises the stream (it returns the size); raht_rlgr_seg_decode does not.
+ *
+ * DAMAGED PAYLOADS (every raht_rlgr_seg_decode* entry point below as well). The tables and the bytes come off the wire. A table
+ * entry that reaches outside `in` is reported: that segment decodes as zeros, nothing of it is read, and its frame's bit of
+ * *bad_dev is set. A PAYLOAD that is not what the encoder wrote -- cut short, a flipped bit, another segment's bytes, a length
+ * that is shorter or (inside `in`) longer than the stream -- is not an error and is not reported: *bad_dev speaks of tables only
+ * (with expect[], bits 16 + j report a frame that differs from what was expected, as for any other difference). The decoder
+ * then still writes exactly the n symbols of that segment and nothing else -- every store is at a symbol i < n of the segment's
+ * own place in Q, so every other segment holds what its own bytes say -- and reads only inside in[0, in_bytes): the words of the
+ * segment's 4-byte slot and, through the aligned 32-byte pieces of the batch decoders, other words of the same container. Bits
+ * past a segment's length read as zeros: the bytes behind it, in its last word and beyond, never count (an empty stream is
+ * the pattern 0, 0, -1, -1, -1, 0, ..., not zeros). The symbols are the same on every entry point, in either layout, for either
+ * table width, whatever the payload's alignment and whatever frames share the launch. They are the symbols the reference's
+ * decoder (membuf.cpp:258-338) gives for the segment's bytes followed by zeros, with its runs stopped at symbol n, as long as
+ * the decoder's state fits 32 bits: every Golomb-Rice value below 2^32, every symbol an int32, no run header doubled at k >= 31.
+ * Past that the symbols are some definite garbage, still the same everywhere and inside the same bounds. */
 int raht_rlgr_seg_encode(const int32_t *Q, int64_t N, int D, int64_t chan_stride, int seg_len, int flag_signed,
                          uint32_t *seg_bytes, uint32_t *seg_off, uint8_t *out, int64_t cap, int64_t *total_bytes,
                          raht_stream_t stream);
