@@ -1073,6 +1073,57 @@ int raht_predict_bi(const uint64_t *keys_sorted, int64_t N, int J, int block_log
                     int64_t ld_ref0, const uint64_t *ref1_keys_sorted, int64_t N_ref1, const float *C_ref1, int64_t ld_ref1, int shift,
                     const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched, raht_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Block modes (csrc/mode_search.hip, csrc/predict_bi.hip): every occupied block of a B frame picks its own predictor (python:
+ * ops.mode_search, ops.predict_bi(..., modes), bitstream.encode_sequence_bytes(..., block_modes)).
+ *
+ * The frame, its two references, shift and the optional fields mv0, mv1 are raht_predict_bi's; the blocks (J, block_log2,
+ * block_first, n_blocks) are raht_motion_search's and are needed with or without fields. With m_r and len_r as above, the
+ * prediction of a row under the mode of its block is
+ *     mode 0 : raht_predict_bi's P -- the mean where both references have a run, the one that has where one has, +0 where none has
+ *     mode 1 : m0 -- raht_predict's P (raht_predict_mc's under mv0) against reference 0, +0 where it has no run: reference 1 is
+ *              not looked at
+ *     mode 2 : m1, likewise against reference 1
+ *     mode 3 : +0
+ * Cost. The cost of a row under a mode is raht_motion_search's row cost against that mode's P: weights w[D] (DEVICE float32,
+ * finite and >= 0: the caller's contract), c = 0.0f; for ch ascending with w[ch] != 0: t = fl(X[i, ch] - P[i, ch]); t = |t|;
+ * t = fl(w[ch] t); c = fl(c + t); q = (uint64) floorf(fminf(c, 1048576.0f) * 1024.0f) -- NaN and +inf take the cap. cost[b][mode] =
+ * the sum of q over the rows of block b: integers, independent of order and of how rows are cut into tiles. With every weight 0
+ * the table is 0.
+ * Selection. mode[b] = the smallest mode among those with the smallest cost[b][mode]; best_cost[b] = that cost. Two references
+ * that predict the same choose mode 0 everywhere.
+ *   raht_mode_search      : mode (DEVICE uint8[n_blocks]), best_cost (DEVICE uint64[n_blocks], may be NULL) and, when the caller
+ *                           passes one, the whole table cost_table (DEVICE uint64[n_blocks * 4]; NULL: scratch of the library's
+ *                           pool). One pass over the frame: a row resolves its key once per reference and walks the weighted
+ *                           columns once for all four costs. A memset of the table and two launches; enqueues only, never
+ *                           synchronises.
+ *   raht_predict_bi_modes : raht_predict_bi under mode (DEVICE uint8[n_blocks]; a value above 3 predicts as 3): Y = X - P
+ *                           (add = 0), X + P (add = 1) or P (X NULL), one float32 operation per element also where P = +0; Y may
+ *                           be X. With every mode 0 the bits are raht_predict_bi's, with every mode 1 (2) raht_predict's or
+ *                           raht_predict_mc's against reference 0 (1). n_matched (DEVICE int64[3], may be NULL) = the rows whose
+ *                           prediction uses a run of reference 0, of reference 1, of both. One launch (and a memset when
+ *                           n_matched is given); enqueues only, never synchronises.
+ * RAHT_ERR_INVALID, with nothing enqueued: raht_predict's rules for either reference, raht_predict_mc's rules for J, block_log2,
+ * block_first and n_blocks (fields or none), a NULL mode, and for the search a NULL X or NULL weights. Whatever block_first, the
+ * fields and the modes hold, no store leaves a buffer.
+ *
+ *   B frame with modes : "RAHTB002" | int64 ref_back (>= 1) | int64 ref_fwd (>= 1) | int64 up | int64 block_log2 (1 .. J) | int64
+ *             n_blocks (>= 1) | int64 flags (bit 0: two motion fields follow; every other bit 0) | with bit 0: int8
+ *             mv0[n_blocks][3], zero bytes up to a multiple of 8, int8 mv1[n_blocks][3], padded likewise | uint8 mode[n_blocks]
+ *             (0 .. 3), zero bytes up to a multiple of 8 | a whole "RAHTF001" frame container whose attributes are the residual
+ *             X - P under the modes. n_blocks is the inner geometry header's n_(J - block_log2). Everything else is the B
+ *             frame's; "RAHTB001" stays what a B frame whose modes are all 0 is written as. */
+int raht_mode_search(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                     const int8_t *mv0, const int8_t *mv1, const uint64_t *ref0_keys_sorted, int64_t N_ref0, const float *C_ref0,
+                     int64_t ld_ref0, const uint64_t *ref1_keys_sorted, int64_t N_ref1, const float *C_ref1, int64_t ld_ref1, int shift,
+                     const float *X, int64_t ldx, int D, const float *weights, uint8_t *mode, uint64_t *best_cost, uint64_t *cost_table,
+                     raht_stream_t stream);
+int raht_predict_bi_modes(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                          const uint8_t *mode, const int8_t *mv0, const int8_t *mv1, const uint64_t *ref0_keys_sorted, int64_t N_ref0,
+                          const float *C_ref0, int64_t ld_ref0, const uint64_t *ref1_keys_sorted, int64_t N_ref1, const float *C_ref1,
+                          int64_t ld_ref1, int shift, const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched,
+                          raht_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

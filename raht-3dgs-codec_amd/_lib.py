@@ -37,6 +37,7 @@ EXPORTS = [
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
     "raht_region_layout_set", "raht_region_assemble_set", "raht_region_needs",
     "raht_predict", "raht_motion_search", "raht_motion_search_around", "raht_predict_mc", "raht_predict_bi",
+    "raht_mode_search", "raht_predict_bi_modes",
 ]
 
 
@@ -210,6 +211,9 @@ def lib():
     L.raht_motion_search_around.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.raht_predict_mc.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp]
     L.raht_predict_bi.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, vp, vp]
+    L.raht_mode_search.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, vp]
+    L.raht_predict_bi_modes.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64,
+                                        vp, vp]
     _lib = L
     return L
 

@@ -45,6 +45,14 @@ frames=anchors)`` never touches its bytes. ``sequence_plan`` has the structure, 
     (0: no fields) | int64 n_blocks (0 iff block_log2 == 0) | with fields: int8 mv0[n_blocks][3], zero bytes up to a multiple of 8,
     int8 mv1[n_blocks][3], padded likewise | a whole RAHTF001 frame
 
+With ``block_modes`` every occupied block of a B frame picks its own predictor (``ops.mode_search``): 0 the rule
+above, 1 reference 0 alone, 2 reference 1 alone, 3 none. A frame in which some block chooses another mode than 0 is written with
+its modes (``sequence_modes`` reads them back); one in which none does stays an RAHTB001 frame.
+
+    RAHTB002 | int64 ref_back | int64 ref_fwd | int64 up | int64 block_log2 (1 .. J) | int64 n_blocks (>= 1) | int64 flags (bit 0:
+    two motion fields follow; all other bits 0) | with bit 0: int8 mv0[n_blocks][3], zero bytes up to a multiple of 8, int8 mv1
+    likewise | uint8 mode[n_blocks] (0 .. 3), zero bytes up to a multiple of 8 | a whole RAHTF001 frame
+
 ``n_wide = 0``: ``forward_quant`` / ``dequant_inverse`` (float32; the float64 steps of the header are cast to float32 on both
 sides, as ``ops._step_array`` does). ``n_wide = 3``: ``forward_quant_mixed`` / ``dequant_inverse_mixed`` (float64 steps), for 59-column
 frames whose first three columns are xyz. ``vmin`` / ``width`` are metadata (the voxel grid's box; 0 when not given).
@@ -67,6 +75,8 @@ M_MAGIC = b"RAHTM001"
 M_HEAD = len(M_MAGIC) + 32                                     # ... and a motion-compensated frame's, before its motion field
 B_MAGIC = b"RAHTB001"
 B_HEAD = len(B_MAGIC) + 40                                     # ... and a B frame's, before its two motion fields
+B2_MAGIC = b"RAHTB002"
+B2_HEAD = len(B2_MAGIC) + 48                                   # ... and that of a B frame with block modes, before its fields and modes
 MIN_FRAME_BYTES = len(MAGIC) + 40 + 8 * 5 + 2 * (8 + 48)      # header, one step + box, two sections of 48 bytes at least
 
 
@@ -543,7 +553,7 @@ def sequence_frame(blob, i, offsets=None):
 
 
 _WRAPPERS = {P_MAGIC: ("predicted frame", P_HEAD), M_MAGIC: ("motion-compensated frame", M_HEAD),      # what a refusal says, the fixed part
-             B_MAGIC: ("B frame", B_HEAD)}
+             B_MAGIC: ("B frame", B_HEAD), B2_MAGIC: ("B frame", B2_HEAD)}
 
 
 def _motion_field_bytes(n_blocks):
@@ -551,19 +561,25 @@ def _motion_field_bytes(n_blocks):
     return (3 * n_blocks + 7) // 8 * 8
 
 
+def _mode_bytes(n_blocks):
+    """the bytes of the block modes in their wrapper: one per block, zero-padded to a multiple of 8"""
+    return (n_blocks + 7) // 8 * 8
+
+
 def _parse_wrapper(fb, only=None):
-    """The wrapper of a predicted frame of any kind, checked as ``parse_pframe``, ``parse_mframe`` and ``parse_bframe`` say ->
-    (ref_back, up, motion: None or (block_log2, mv (n_blocks, 3) int8 numpy) -- (block_log2, mv0, mv1) in a B frame --, the inner
-    RAHTF001 container as a memoryview, ref_fwd: None but in a B frame). None when ``fb`` opens with no wrapper's magic (with
-    ``only``: with another magic than that one)."""
+    """The wrapper of a predicted frame of any kind, checked as ``parse_pframe``, ``parse_mframe``, ``parse_bframe`` and
+    ``parse_bframe2`` say -> (ref_back, up, motion: None or (block_log2, mv (n_blocks, 3) int8 numpy) -- (block_log2, mv0, mv1) in a
+    B frame --, the inner RAHTF001 container as a memoryview, ref_fwd: None but in a B frame, modes: None but in an RAHTB002 frame,
+    there (block_log2, mode (n_blocks,) uint8 numpy)). None when ``fb`` opens with no wrapper's magic (with ``only``: with another
+    magic than that one)."""
     magic = bytes(fb[:len(P_MAGIC)])
     if magic not in _WRAPPERS or only not in (None, magic):
         return None
     what, head = _WRAPPERS[magic]
     if len(fb) < head + MIN_FRAME_BYTES:
         raise ValueError(f"{what}: truncated wrapper")
-    ref_fwd = None
-    if magic == B_MAGIC:
+    ref_fwd, modes = None, None
+    if magic in (B_MAGIC, B2_MAGIC):
         ref_back, ref_fwd, up = [int(x) for x in np.frombuffer(fb, np.int64, 3, len(magic))]
         if ref_fwd < 1:
             raise ValueError(f"{what}: ref_fwd = {ref_fwd}, must be at least 1")
@@ -574,7 +590,29 @@ def _parse_wrapper(fb, only=None):
     if not 0 <= up <= 3:
         raise ValueError(f"{what}: up = {up} outside 0 .. 3")
     motion = None
-    if magic == B_MAGIC:
+    if magic == B2_MAGIC:
+        block_log2, n_blocks, flags = [int(x) for x in np.frombuffer(fb, np.int64, 3, len(magic) + 24)]
+        if not 1 <= block_log2 <= MAX_J:
+            raise ValueError(f"{what}: block_log2 = {block_log2} outside 1 .. {MAX_J}")
+        if flags & ~1:
+            raise ValueError(f"{what}: unknown flag bits ({flags:#x})")
+        n_fields = 2 * (flags & 1)
+        if n_blocks < 1 or n_blocks >= 2 ** 31 or len(fb) < head + n_fields * _motion_field_bytes(n_blocks) + _mode_bytes(n_blocks) + MIN_FRAME_BYTES:
+            raise ValueError(f"{what}: too short for {n_fields} motion fields and the modes of {n_blocks} blocks and a frame")
+        if n_fields:
+            fields = np.frombuffer(fb, np.int8, 2 * _motion_field_bytes(n_blocks), head).reshape(2, -1)
+            if fields[:, 3 * n_blocks:].any():
+                raise ValueError(f"{what}: the padding behind a motion field is not zero")
+            motion = (block_log2, fields[0, :3 * n_blocks].reshape(n_blocks, 3), fields[1, :3 * n_blocks].reshape(n_blocks, 3))
+            head += fields.size
+        mode = np.frombuffer(fb, np.uint8, _mode_bytes(n_blocks), head)
+        if mode[n_blocks:].any():
+            raise ValueError(f"{what}: the padding behind the block modes is not zero")
+        if mode[:n_blocks].max() > 3:
+            raise ValueError(f"{what}: a block mode of {int(mode[:n_blocks].max())}, outside 0 .. 3")
+        modes = (block_log2, mode[:n_blocks])
+        head += len(mode)
+    elif magic == B_MAGIC:
         block_log2, n_blocks = [int(x) for x in np.frombuffer(fb, np.int64, 2, len(magic) + 24)]
         if (block_log2 == 0) != (n_blocks == 0):
             raise ValueError(f"{what}: block_log2 = {block_log2} with n_blocks = {n_blocks} (both 0 without motion fields, neither with)")
@@ -599,7 +637,7 @@ def _parse_wrapper(fb, only=None):
             raise ValueError(f"{what}: the padding behind the motion field is not zero")
         motion = (block_log2, field[:3 * n_blocks].reshape(n_blocks, 3))
         head += len(field)
-    return ref_back, up, motion, memoryview(fb)[head:], ref_fwd
+    return ref_back, up, motion, memoryview(fb)[head:], ref_fwd, modes
 
 
 def parse_pframe(fb):
@@ -635,17 +673,31 @@ def parse_bframe(fb):
     return w[0], w[4], w[1], *(w[2] or (0, None, None)), w[3]
 
 
+def parse_bframe2(fb):
+    """The wrapper of a B frame with block modes (RAHTB002), checked (pure host code) -> (ref_back, ref_fwd, up,
+    block_log2, mv0, mv1, modes (n_blocks,) uint8 numpy, the inner RAHTF001 container as a memoryview); mv0, mv1 are None without
+    motion fields (flag bit 0), (n_blocks, 3) int8 numpy with them. ``ValueError`` for another magic, ``ref_back`` or ``ref_fwd``
+    below 1, ``up`` outside 0 .. 3, ``block_log2`` outside 1 .. 21, an unknown flag bit, ``n_blocks`` below 1, a wrapper too short for
+    its fields and modes plus a frame, padding that is not zero, a mode above 3. What depends on the sequence or on the inner frame
+    is for the sequence's checks (``_frame_head``)."""
+    w = _parse_wrapper(fb, B2_MAGIC)
+    if w is None:
+        raise ValueError("not a RAHT B-frame wrapper with block modes")
+    mv0, mv1 = w[2][1:] if w[2] else (None, None)
+    return w[0], w[4], w[1], w[5][0], mv0, mv1, w[5][1], w[3]
+
+
 def _frame_head(view, off, i, max_voxels):
     """frame i of a sequence from its headers alone -> dict: kind ("I" / "P" / "B"), ref (the frame it is predicted from -- a B
     frame's reference 0 --, or None), ref1 (a B frame's reference 1, or None), up, motion (None, (block_log2, mv) of a
     motion-compensated frame, (block_log2, mv0, mv1) of a B frame with fields), fb (its RAHTF001 container: the inner one of a
     predicted frame), h (``parse_frame`` of it), seg_len. ``ValueError`` naming i."""
     fb = view[off[i]: off[i + 1]]
-    kind, ref, ref1, up, motion = "I", None, None, 0, None
+    kind, ref, ref1, up, motion, modes = "I", None, None, 0, None, None
     try:
         w = _parse_wrapper(fb)
         if w is not None:
-            ref_back, up, motion, fb, ref_fwd = w
+            ref_back, up, motion, fb, ref_fwd, modes = w
             what = "predicted frame" if ref_fwd is None else "B frame"
             if i == 0:
                 raise ValueError(f"a {what} cannot open a sequence")
@@ -659,19 +711,21 @@ def _frame_head(view, off, i, max_voxels):
         h = parse_frame(fb, max_voxels)
         if h["geometry_ref"] is not None and ref is None:
             raise ValueError("a geometry section predicted from another frame in a frame without a wrapper")
-        if motion is not None:
+        for blocks, of in ((motion, "a motion field"), (modes, "block modes")):
+            if blocks is None:
+                continue
             what = "B frame" if kind == "B" else "motion-compensated frame"
-            if motion[0] > h["J"]:
-                raise ValueError(f"{what}: block_log2 = {motion[0]} outside 1 .. J = {h['J']}")
+            if blocks[0] > h["J"]:
+                raise ValueError(f"{what}: block_log2 = {blocks[0]} outside 1 .. J = {h['J']}")
             go, gl = h["geometry"]
-            n_level = OctreeCoder.parse(fb[go: go + gl], max_voxels)["counts"][h["J"] - motion[0]]
-            if len(motion[1]) != n_level:
-                raise ValueError(f"{what}: a motion field of {len(motion[1])} blocks, the geometry has {n_level}")
+            n_level = OctreeCoder.parse(fb[go: go + gl], max_voxels)["counts"][h["J"] - blocks[0]]
+            if len(blocks[1]) != n_level:
+                raise ValueError(f"{what}: {of} of {len(blocks[1])} blocks, the geometry has {n_level}")
         ao, al = h["attributes"]
         S = SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[2]
     except ValueError as e:
         raise ValueError(f"sequence container: frame {i}: {e}") from None
-    return dict(kind=kind, ref=ref, ref1=ref1, up=up, motion=motion, fb=fb, h=h, seg_len=S)
+    return dict(kind=kind, ref=ref, ref1=ref1, up=up, motion=motion, modes=modes, fb=fb, h=h, seg_len=S)
 
 
 def _frame_heads(view, off, idx, max_voxels):
@@ -735,6 +789,14 @@ def sequence_motion(blob, max_voxels=None, max_frames=None):
     return [hd["motion"] for hd in _sequence_heads(blob, max_voxels, max_frames)]
 
 
+def sequence_modes(blob, max_voxels=None, max_frames=None):
+    """-> per frame of a sequence container None, or the block modes (n_blocks,) uint8 numpy of a B frame that carries them
+    (RAHTB002) -- over the blocks of the wrapper's ``block_log2``, which ``parse_bframe2`` returns --, from the
+    headers alone (pure host code), with the checks of ``sequence_kinds`` and those of the modes: a mode above 3, an unknown flag
+    bit, padding that is not zero, a block count that is not the inner frame's."""
+    return [None if hd["modes"] is None else hd["modes"][1] for hd in _sequence_heads(blob, max_voxels, max_frames)]
+
+
 def sequence_geometry(blob, max_voxels=None, max_frames=None):
     """-> ["intra" | "predicted"] per frame of a sequence container: how its geometry section is coded, from the headers alone
     (pure host code), with the checks of ``sequence_kinds`` and two more: a predicted geometry section in a frame without a
@@ -748,11 +810,15 @@ class _Predictor:
     encoder's closed loop and the decoder add the prediction through the one ``restore``, with one argument list: that is what
     keeps the loop free of drift. ``overhead``: the bytes of ``wrapper()``."""
 
-    def __init__(self, keys, ref, J, up, motion=None, back=1, ref1=None, fwd=None):
+    def __init__(self, keys, ref, J, up, motion=None, back=1, ref1=None, fwd=None, modes=None):
         """back: how many frames earlier ``ref`` lies. A B frame has a second reference ``ref1``, ``fwd`` frames later; its ``motion``
-        is None or (block_log2, mv0, mv1, block_first)."""
+        is None or (block_log2, mv0, mv1, block_first), and its ``modes`` None or (block_log2, mode (n_blocks,) uint8 on the device,
+        block_first) over the same blocks."""
         self.keys, self.ref, self.J, self.up, self.motion, self.back, self.ref1, self.fwd = keys, ref, J, up, motion, back, ref1, fwd
-        if ref1 is not None:
+        self.modes = modes
+        if modes is not None:
+            self.overhead = B2_HEAD + (0 if motion is None else 2 * _motion_field_bytes(len(modes[1]))) + _mode_bytes(len(modes[1]))
+        elif ref1 is not None:
             self.overhead = B_HEAD + (0 if motion is None else 2 * _motion_field_bytes(len(motion[1])))
         else:
             self.overhead = P_HEAD if motion is None else M_HEAD + _motion_field_bytes(len(motion[1]))
@@ -764,6 +830,9 @@ class _Predictor:
             if self.motion is not None:
                 block_log2, mv0, mv1, block_first = self.motion
                 kw.update(J=self.J, block_log2=block_log2, block_first=block_first, mv0=mv0, mv1=mv1)
+            if self.modes is not None:
+                block_log2, mode, block_first = self.modes
+                kw.update(J=self.J, block_log2=block_log2, block_first=block_first, modes=mode)
             return ops.predict_bi(self.keys, self.ref, self.ref1, **kw)
         if self.motion is None:
             return ops.predict(self.keys, *self.ref, **kw)
@@ -777,13 +846,18 @@ class _Predictor:
         return self._apply(C, True)
 
     def wrapper(self):
-        """the bytes in front of the inner frame (a motion field comes to the host here)"""
+        """the bytes in front of the inner frame (a motion field and the block modes come to the host here)"""
         if self.ref1 is not None:
             fields, n_blocks = b"", 0
             if self.motion is not None:
                 n_blocks = len(self.motion[1])
                 pad = bytes(_motion_field_bytes(n_blocks) - 3 * n_blocks)
                 fields = b"".join(mv.cpu().numpy().tobytes() + pad for mv in self.motion[1:3])
+            if self.modes is not None:
+                block_log2, n_blocks = self.modes[0], len(self.modes[1])
+                mode = self.modes[1].cpu().numpy().tobytes() + bytes(_mode_bytes(n_blocks) - n_blocks)
+                head = np.array([self.back, self.fwd, self.up, block_log2, n_blocks, int(self.motion is not None)], np.int64)
+                return B2_MAGIC + head.tobytes() + fields + mode
             block_log2 = 0 if self.motion is None else self.motion[0]
             return B_MAGIC + np.array([self.back, self.fwd, self.up, block_log2, n_blocks], np.int64).tobytes() + fields
         if self.motion is None:
@@ -815,7 +889,8 @@ def sequence_plan(n, gop, bframes=0):
 
 
 def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048, geometry="rlgr", vmin=None, width=None, gop=1, up=0,
-                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off", bframes=0, motion_levels=0):
+                          inter="auto", motion=0, block_log2=4, motion_weights=None, geometry_inter="off", bframes=0, motion_levels=0,
+                          block_modes=False):
     """frames: a list of (V_int, attributes) as ``encode_frame_bytes`` takes them, any voxel count per frame, one D -> the sequence
     container; frame i of it is ``encode_frame_bytes(*frames[i], J, step, ...)`` byte for byte. Keys, geometry section and plan
     frame by frame; the transform + quantization of up to ``SEQ_CHUNK`` frames in one set of launches (``forward_quant_mixed_batch``
@@ -864,11 +939,19 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     r 2^L + 2^L - 1 voxels a component at the cost of a few radius-1 searches. L <= min(3, block_log2 - 1) and J - L >= 1. The
     coarse levels of a reconstruction are built once and kept beside it for every frame that is searched against it. The format
     and the decoders are the same: a field is a field. ``motion_levels=0`` (the default) is byte for byte what it was without
-    this argument."""
+    this argument.
+
+    ``block_modes=True`` (with ``bframes`` > 0 and ``gop`` > 1): every occupied block of 2^``block_log2`` voxels a side
+    of a B candidate picks its own predictor. After the B ways above, ``ops.mode_search`` is run on the last of them -- the one under
+    two fields if there is one, else the one without -- with ``motion_weights`` (default 1 / step per column): mode 0 is that way's
+    own rule, 1 reference 0 alone, 2 reference 1 alone, 3 no prediction. If any block chooses another mode than 0, a further way
+    is added whose predictor carries the modes; it is written as an RAHTB002 frame, and its overhead is that wrapper, the padded
+    mode bytes included. ``inter="always"`` takes this last way, ``inter="auto"`` the fewest bytes as above. Where every block
+    chooses 0 nothing is added. ``block_modes=False`` (the default) is byte for byte what it was without this argument."""
     import torch
     dev = torch.device(device)
     J, n_wide, gop, up, motion, block_log2, bframes = int(J), int(n_wide), int(gop), int(up), int(motion), int(block_log2), int(bframes)
-    motion_levels = int(motion_levels)
+    motion_levels, block_modes = int(motion_levels), bool(block_modes)
     if not frames:
         raise ValueError("encode_sequence_bytes: a sequence has one frame at least")
     if gop < 1 or not 0 <= up <= 3 or inter not in ("auto", "always") or bframes < 0:
@@ -879,6 +962,8 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
         raise ValueError("encode_sequence_bytes: motion_levels in 0 .. min(3, block_log2 - 1) with J - motion_levels >= 1, and only with motion")
     if geometry_inter not in ("off", "always", "auto"):
         raise ValueError('encode_sequence_bytes: geometry_inter "off", "always" or "auto"')
+    if block_modes and (bframes < 1 or gop < 2 or not 1 <= block_log2 <= J):
+        raise ValueError("encode_sequence_bytes: block_modes needs bframes > 0, gop > 1 and block_log2 in 1 .. J")
     VA = []
     for i, (V_int, attributes) in enumerate(frames):
         V, A = _frame_input(f"encode_sequence_bytes: frame {i}", V_int, attributes, J, n_wide, dev)
@@ -889,8 +974,8 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
     steps = _step_list(step, D)
     if motion and gop > 1:
         cands = ops.motion_candidates(motion)
-        if motion_weights is None:
-            motion_weights = (1.0 / np.asarray(steps * (D if len(steps) == 1 else 1), np.float64)).astype(np.float32)
+    if (motion or block_modes) and gop > 1 and motion_weights is None:
+        motion_weights = (1.0 / np.asarray(steps * (D if len(steps) == 1 else 1), np.float64)).astype(np.float32)
     n = len(VA)
     parts = []                                                               # (the pieces of every frame: joined once, at the end)
     coded = {}                                                               # frame -> (geometry section, Q, wrapper) until its entropy stage
@@ -945,6 +1030,16 @@ def encode_sequence_bytes(frames, J, step, device="cuda", n_wide=0, seg_len=2048
                     mv1 = search(keys, counts, c, A, block_first)
                     if moved or bool(mv1.any()):
                         ways.append(_Predictor(keys, ref, J, up, (block_log2, mv, mv1, block_first), back=i - a, ref1=ref1, fwd=c - i))
+                if block_modes:                                              # the blocks of the last B way choose among its predictors
+                    last = ways[-1]
+                    if not motion:
+                        n_blocks = OctreeCoder.parse(geo)["counts"][J - block_log2]
+                        block_first = ops.motion_blocks(keys, J, block_log2, n_blocks)
+                    mv0, mv1 = (None, None) if last.motion is None else last.motion[1:3]
+                    mode = ops.mode_search(keys, ref, ref1, A, J, block_log2, block_first, motion_weights, up=up, mv0=mv0, mv1=mv1)[0]
+                    if bool(mode.any()):
+                        ways.append(_Predictor(keys, ref, J, up, last.motion, back=i - a, ref1=ref1, fwd=c - i,
+                                               modes=(block_log2, mode, block_first)))
         if inter == "always" or len(ways) == 1:                              # the last way; its source alone is formed
             pred = ways[-1]
             src = A if pred is None else pred.residual(A)
@@ -1054,7 +1149,11 @@ def decode_sequence_bytes(blob, frames=None, device="cuda", max_voxels=None, max
                     block_first = ops.motion_blocks(keys, J, motion[0], len(motion[1]))
                     motion = (motion[0], *(torch.from_numpy(mv.copy()).to(dev) for mv in motion[1:]), block_first)
                 ref1 = done[hd["ref1"]][2:0:-1] if hd["kind"] == "B" else None
-                _Predictor(keys, (ref_keys, C_ref), J, hd["up"], motion, ref1=ref1).restore(C)
+                modes = hd["modes"]
+                if modes is not None:                                        # (an RAHTB002 frame: the modes lie over the fields' blocks)
+                    block_first = motion[-1] if motion is not None else ops.motion_blocks(keys, J, modes[0], len(modes[1]))
+                    modes = (modes[0], torch.from_numpy(modes[1].copy()).to(dev), block_first)
+                _Predictor(keys, (ref_keys, C_ref), J, hd["up"], motion, ref1=ref1, modes=modes).restore(C)
     return [done[i][:2] for i in idx]
 
 

@@ -26,31 +26,7 @@
 
 namespace raht {
 
-constexpr int MS_THREADS = 256;                          // the largest tile: one thread per row
-constexpr int MS_MAX_GRID = 2048;                        // grids are capped and grid-strided
-constexpr size_t MS_LDS_BYTES = 65536 - 64;              // dynamic LDS a workgroup may ask for (the kernel's statics: 16 bytes)
-constexpr float MS_COST_CAP = 1048576.0f;                // 2^20 per row; q = floor(min(c, cap) * 2^10) <= 2^30
-constexpr int MS_MAX_K = 512;
-
-// the fixed-point cost of a row from its float32 cost: NaN and +inf take the cap (fminf(NaN, x) = x), the product is exact
-__device__ __forceinline__ unsigned long long ms_fixed(float c)
-{
-    const float m = fminf(c, MS_COST_CAP);
-    return m > 0.0f ? (unsigned long long)floorf(m * 1024.0f) : 0ull;
-}
-
-// dynamic LDS of a tile: acc[2][tile] uint64 | wcol[D] int32 | wval[D] float | xs[tile * x_stride] float (STAGED only)
-static inline size_t ms_lds_bytes(int tile, int D, int x_stride) { return (size_t)tile * 16 + (size_t)D * 8 + (size_t)tile * x_stride * 4; }
-
-// the rows of a staged tile for rows of D floats (row stride D | 1 in LDS): the largest of 256 / 192 / 128 / 64 whose rows fit the
-// LDS budget; 0: none fits, X is read through the cache (raht_debug_motion_tile)
-static int ms_tile_rows(int D)
-{
-    if (D < 1 || D > 4096) return 0;
-    for (int t = MS_THREADS; t >= 64; t -= 64)
-        if (ms_lds_bytes(t, D, D | 1) <= MS_LDS_BYTES) return t;
-    return 0;
-}
+constexpr int MS_MAX_K = 512;                            // (the tile, the LDS budget, the row cost and the block sums: predict_device.h)
 
 // a component of a vector base + cand that the int8 field can hold (-128 is not a vector: the rule is symmetric)
 __device__ __forceinline__ bool ms_in_range(int64_t v) { return v >= -127 && v <= 127; }
@@ -157,23 +133,7 @@ __global__ __launch_bounds__(MS_THREADS) void motion_search_kernel(const uint64_
                     q = ms_fixed(c);
                 }
             }
-            // the sum of q over the lanes of this lane's block up to this lane: blocks are runs of lanes
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned long long u = __shfl_up(q, d);
-                const int s = __shfl_up(slot, d);
-                if (lane >= d && s == slot) q += u;
-            }
-            unsigned long long *a = acc + (k & 1) * tile;
-            if (tail && q) atomicAdd(a + slot, q);
-            __syncthreads();
-            if (head) {
-                const unsigned long long v = a[tid];
-                if (v) {
-                    atomicAdd(table + b * K + k, v);
-                    a[tid] = 0;                          // (this set is added to again two candidates on: a barrier lies between)
-                }
-            }
+            ms_block_add(q, slot, lane, tid, tail, head, acc + (k & 1) * tile, table + b * K + k);
         }
     }
 }

@@ -11,16 +11,31 @@
 //               the cache, two chunks per lane and round with their X loads issued before the runs are walked; padded matrices
 //               and chunks that straddle rows move element by element. X and Y may be the same matrix: a lane reads only what it
 //               writes.
+//   raht_predict_bi_modes   the same launch under a mode per block of the frame (include/raht.h, "Block modes"): the
+//     resolve step reads the mode of the row's block and leaves the run of a reference the mode does not use empty -- what the move
+//     step does with an empty run is the rule above, so mode 0 has raht_predict_bi's bits, modes 1 and 2 the one-reference
+//     predictors', and mode 3 predicts +0. The counters count the runs that are used.
 #include "predict_device.h"
 
 namespace raht {
 
-// a reference: its sorted keys and its reconstruction
-struct PrRef {
-    const uint64_t *keys;
-    int32_t n;
-    const float *C;
-    int64_t ld;
+// The predictors a row may use. AllRefs: both references (raht_predict_bi).
+struct AllRefs {
+    __device__ __forceinline__ void operator()(int64_t, bool &use0, bool &use1) const { use0 = use1 = true; }
+};
+
+// BlockModes: by the mode of the row's block (raht_predict_bi_modes) -- 0: both, 1: reference 0 only, 2: reference 1 only, 3 and
+// above: neither. A reference that is not used is not resolved: its run stays empty, and pr_bi gives the other mean, or +0.
+struct BlockModes {
+    const int64_t *block_first;
+    int64_t n_blocks;
+    const uint8_t *mode;
+    __device__ __forceinline__ void operator()(int64_t row, bool &use0, bool &use1) const
+    {
+        const uint8_t m = mode[pr_block_of(block_first, n_blocks, row)];
+        use0 = m == 0 || m == 1;
+        use1 = m == 0 || m == 2;
+    }
 };
 
 // the prediction of channel ch of a row whose runs are r = (lo0, len0, lo1, len1)
@@ -53,11 +68,13 @@ __device__ __forceinline__ RegChunk<float> pr_bi_chunk(const PrRef &r0, const Pr
 }
 
 // MODE, FLAT: as predict_kernel's. KEY0 / KEY1: the key a row is resolved for in reference 0 / 1 (SameKey or MvKey).
-// n_matched: three counters -- rows with a run in reference 0, in reference 1, in both.
-template <int MODE, bool FLAT, typename KEY0, typename KEY1>
+// USE: the references a row's prediction may use (AllRefs or BlockModes).
+// n_matched: three counters -- rows whose prediction uses a run of reference 0, of reference 1, of both.
+template <int MODE, bool FLAT, typename KEY0, typename KEY1, typename USE>
 __global__ __launch_bounds__(PR_THREADS) void predict_bi_kernel(const uint64_t *__restrict__ keys, int64_t n, const PrRef r0, const PrRef r1,
                                                                 int shift, const float *X, int64_t ldx, int D, float *Y, int64_t ldy,
-                                                                unsigned long long *__restrict__ n_matched, const KEY0 key0, const KEY1 key1)
+                                                                unsigned long long *__restrict__ n_matched, const KEY0 key0, const KEY1 key1,
+                                                                const USE use)
 {
     __shared__ int4 runs[PR_TILE_ROWS];
     __shared__ uint32_t hits[3];
@@ -73,8 +90,10 @@ __global__ __launch_bounds__(PR_THREADS) void predict_bi_kernel(const uint64_t *
             const uint64_t own = keys[row];
             uint64_t key;
             int4 r = make_int4(0, 0, 0, 0);
-            if (key0(row, own, key)) r.y = pr_resolve(r0.keys, r0.n, shift, key, r.x);
-            if (key1(row, own, key)) r.w = pr_resolve(r1.keys, r1.n, shift, key, r.z);
+            bool use0, use1;
+            use(row, use0, use1);
+            if (use0 && key0(row, own, key)) r.y = pr_resolve(r0.keys, r0.n, shift, key, r.x);
+            if (use1 && key1(row, own, key)) r.w = pr_resolve(r1.keys, r1.n, shift, key, r.z);
             runs[threadIdx.x] = r;
             mine0 += r.y > 0;
             mine1 += r.w > 0;
@@ -143,27 +162,60 @@ struct BiLaunch {
     unsigned long long *n_matched;
 };
 
-template <int MODE, bool FLAT, typename KEY0, typename KEY1>
-static void predict_bi_launch(const BiLaunch &a, const KEY0 &key0, const KEY1 &key1)
+template <int MODE, bool FLAT, typename KEY0, typename KEY1, typename USE>
+static void predict_bi_launch(const BiLaunch &a, const KEY0 &key0, const KEY1 &key1, const USE &use)
 {
-    hipLaunchKernelGGL((predict_bi_kernel<MODE, FLAT, KEY0, KEY1>), dim3(a.grid), dim3(PR_THREADS), 0, a.s, a.keys, a.N, a.r0, a.r1, a.shift,
-                       a.X, a.ldx, a.D, a.Y, a.ldy, a.n_matched, key0, key1);
+    hipLaunchKernelGGL((predict_bi_kernel<MODE, FLAT, KEY0, KEY1, USE>), dim3(a.grid), dim3(PR_THREADS), 0, a.s, a.keys, a.N, a.r0, a.r1,
+                       a.shift, a.X, a.ldx, a.D, a.Y, a.ldy, a.n_matched, key0, key1, use);
 }
 
-// the kernel of a call's mode and layout, for the key functors of its two references
-template <typename KEY0, typename KEY1>
-static void predict_bi_modes(const BiLaunch &a, const KEY0 &key0, const KEY1 &key1)
+// the kernel of a call's use (P, X - P, X + P) and layout, for the key functors of its two references
+template <typename KEY0, typename KEY1, typename USE>
+static void predict_bi_uses(const BiLaunch &a, const KEY0 &key0, const KEY1 &key1, const USE &use)
 {
     const int mode = !a.X ? 0 : (a.add ? 2 : 1);
     if (a.flat) {
-        if (mode == 0) predict_bi_launch<0, true>(a, key0, key1);
-        else if (mode == 1) predict_bi_launch<1, true>(a, key0, key1);
-        else predict_bi_launch<2, true>(a, key0, key1);
+        if (mode == 0) predict_bi_launch<0, true>(a, key0, key1, use);
+        else if (mode == 1) predict_bi_launch<1, true>(a, key0, key1, use);
+        else predict_bi_launch<2, true>(a, key0, key1, use);
     } else {
-        if (mode == 0) predict_bi_launch<0, false>(a, key0, key1);
-        else if (mode == 1) predict_bi_launch<1, false>(a, key0, key1);
-        else predict_bi_launch<2, false>(a, key0, key1);
+        if (mode == 0) predict_bi_launch<0, false>(a, key0, key1, use);
+        else if (mode == 1) predict_bi_launch<1, false>(a, key0, key1, use);
+        else predict_bi_launch<2, false>(a, key0, key1, use);
     }
+}
+
+// both entry points, checked: the memset of the counters and the one launch
+template <typename USE>
+static int predict_bi_enqueue(const uint64_t *keys_sorted, int64_t N, int J, const int64_t *block_first, int64_t n_blocks, const int8_t *mv0,
+                              const int8_t *mv1, const PrRef &r0, const PrRef &r1, int shift, const float *X, int64_t ldx, int D, int add,
+                              float *Y, int64_t ldy, int64_t *n_matched, const USE &use, hipStream_t s)
+{
+    if (n_matched) RAHT_HIP_CHECK(hipMemsetAsync(n_matched, 0, 3 * sizeof(int64_t), s));
+    const int64_t tiles = ceil_div(N, PR_TILE_ROWS);
+    BiLaunch a;
+    a.grid = (unsigned)(tiles > PR_MAX_GRID ? PR_MAX_GRID : tiles);
+    a.flat = ldy == D && (!X || ldx == D) && D < (1 << 22);                 // (flat tiles index their elements with 32 bits)
+    a.s = s;
+    a.keys = keys_sorted;
+    a.N = N;
+    a.r0 = r0;
+    a.r1 = r1;
+    a.shift = shift;
+    a.X = X;
+    a.ldx = ldx;
+    a.D = D;
+    a.add = add;
+    a.Y = Y;
+    a.ldy = ldy;
+    a.n_matched = (unsigned long long *)n_matched;
+    const MvKey f0{block_first, n_blocks, mv0, J}, f1{block_first, n_blocks, mv1, J};
+    if (mv0 && mv1) predict_bi_uses(a, f0, f1, use);
+    else if (mv0) predict_bi_uses(a, f0, SameKey(), use);
+    else if (mv1) predict_bi_uses(a, SameKey(), f1, use);
+    else predict_bi_uses(a, SameKey(), SameKey(), use);
+    RAHT_HIP_CHECK(hipGetLastError());
+    return RAHT_OK;
 }
 
 }  // namespace raht
@@ -181,32 +233,25 @@ int raht_predict_bi(const uint64_t *keys_sorted, int64_t N, int J, int block_log
     RAHT_RET(predict_check(who, keys_sorted, N, ref0_keys_sorted, N_ref0, shift, C_ref0, ld_ref0, X, ldx, D, add, Y, ldy));
     RAHT_RET(predict_check(who, keys_sorted, N, ref1_keys_sorted, N_ref1, shift, C_ref1, ld_ref1, X, ldx, D, add, Y, ldy));
     if (mv0 || mv1) RAHT_RET(motion_check_blocks(who, J, block_log2, block_first, n_blocks, N));
-    hipStream_t s = (hipStream_t)stream;
-    if (n_matched) RAHT_HIP_CHECK(hipMemsetAsync(n_matched, 0, 3 * sizeof(int64_t), s));
-    const int64_t tiles = ceil_div(N, PR_TILE_ROWS);
-    BiLaunch a;
-    a.grid = (unsigned)(tiles > PR_MAX_GRID ? PR_MAX_GRID : tiles);
-    a.flat = ldy == D && (!X || ldx == D) && D < (1 << 22);                 // (flat tiles index their elements with 32 bits)
-    a.s = s;
-    a.keys = keys_sorted;
-    a.N = N;
-    a.r0 = PrRef{ref0_keys_sorted, (int32_t)N_ref0, C_ref0, ld_ref0};
-    a.r1 = PrRef{ref1_keys_sorted, (int32_t)N_ref1, C_ref1, ld_ref1};
-    a.shift = shift;
-    a.X = X;
-    a.ldx = ldx;
-    a.D = D;
-    a.add = add;
-    a.Y = Y;
-    a.ldy = ldy;
-    a.n_matched = (unsigned long long *)n_matched;
-    const MvKey f0{block_first, n_blocks, mv0, J}, f1{block_first, n_blocks, mv1, J};
-    if (mv0 && mv1) predict_bi_modes(a, f0, f1);
-    else if (mv0) predict_bi_modes(a, f0, SameKey());
-    else if (mv1) predict_bi_modes(a, SameKey(), f1);
-    else predict_bi_modes(a, SameKey(), SameKey());
-    RAHT_HIP_CHECK(hipGetLastError());
-    return RAHT_OK;
+    return predict_bi_enqueue(keys_sorted, N, J, block_first, n_blocks, mv0, mv1, PrRef{ref0_keys_sorted, (int32_t)N_ref0, C_ref0, ld_ref0},
+                              PrRef{ref1_keys_sorted, (int32_t)N_ref1, C_ref1, ld_ref1}, shift, X, ldx, D, add, Y, ldy, n_matched, AllRefs(),
+                              (hipStream_t)stream);
+}
+
+int raht_predict_bi_modes(const uint64_t *keys_sorted, int64_t N, int J, int block_log2, const int64_t *block_first, int64_t n_blocks,
+                          const uint8_t *mode, const int8_t *mv0, const int8_t *mv1, const uint64_t *ref0_keys_sorted, int64_t N_ref0,
+                          const float *C_ref0, int64_t ld_ref0, const uint64_t *ref1_keys_sorted, int64_t N_ref1, const float *C_ref1,
+                          int64_t ld_ref1, int shift, const float *X, int64_t ldx, int D, int add, float *Y, int64_t ldy, int64_t *n_matched,
+                          raht_stream_t stream)
+{
+    const char *who = "raht_predict_bi_modes";
+    if (!mode) { set_error("%s: NULL mode", who); return RAHT_ERR_INVALID; }
+    RAHT_RET(predict_check(who, keys_sorted, N, ref0_keys_sorted, N_ref0, shift, C_ref0, ld_ref0, X, ldx, D, add, Y, ldy));
+    RAHT_RET(predict_check(who, keys_sorted, N, ref1_keys_sorted, N_ref1, shift, C_ref1, ld_ref1, X, ldx, D, add, Y, ldy));
+    RAHT_RET(motion_check_blocks(who, J, block_log2, block_first, n_blocks, N));      // (the modes lie over the blocks, fields or none)
+    return predict_bi_enqueue(keys_sorted, N, J, block_first, n_blocks, mv0, mv1, PrRef{ref0_keys_sorted, (int32_t)N_ref0, C_ref0, ld_ref0},
+                              PrRef{ref1_keys_sorted, (int32_t)N_ref1, C_ref1, ld_ref1}, shift, X, ldx, D, add, Y, ldy, n_matched,
+                              BlockModes{block_first, n_blocks, mode}, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // predict_device.h -- the inter-frame predictor's device code, shared by predict.hip (the co-located predictor), motion.hip
-// (the motion-compensated one and the motion search) and predict_bi.hip (the two-reference one): the resolve of a key to its run in
-// the reference, the run mean, and the predictor kernel, whose KEY functor says for which key a row is resolved (include/raht.h,
-// "Inter-frame prediction", "Motion compensation" and "Two references").
+// (the motion-compensated one and the motion search), predict_bi.hip (the two-reference one) and mode_search.hip (the per-block
+// choice among a B frame's predictors): the resolve of a key to its run in the reference, the run mean, the predictor kernel, whose
+// KEY functor says for which key a row is resolved, and the row cost and block sums of the searches (include/raht.h, "Inter-frame
+// prediction", "Motion compensation", "Two references" and "Block modes").
 // Row i of the current frame lies in the cell c = key[i] >> shift; its prediction is the mean of the reference rows of that cell,
 // which are ONE run [lo, hi) of the reference's sorted keys: summed in float32 in row order from the run's first row, divided once
 // by the run's length, 0 for an empty run. The order of the sum is part of the definition (a run holds at most 8^up <= 512 rows),
@@ -167,6 +168,66 @@ __device__ __forceinline__ float pr_bi(float m0, int32_t len0, float m1, int32_t
     if (len1 == 0) return m0;
     if (len0 == 0) return m1;
     return __fmul_rn(0.5f, __fadd_rn(m0, m1));
+}
+
+// a reference of the two-reference kernels (predict_bi.hip, mode_search.hip): its sorted keys and its reconstruction
+struct PrRef {
+    const uint64_t *keys;
+    int32_t n;
+    const float *C;
+    int64_t ld;
+};
+
+// ---- what the search kernels share (motion.hip: the motion search, mode_search.hip: the mode search) ----------------------------
+constexpr int MS_THREADS = 256;                          // the largest tile: one thread per row
+constexpr int MS_MAX_GRID = 2048;                        // grids are capped and grid-strided
+constexpr size_t MS_LDS_BYTES = 65536 - 64;              // dynamic LDS a workgroup may ask for (the kernels' statics: 16 bytes)
+constexpr float MS_COST_CAP = 1048576.0f;                // 2^20 per row; q = floor(min(c, cap) * 2^10) <= 2^30
+
+// the fixed-point cost of a row from its float32 cost: NaN and +inf take the cap (fminf(NaN, x) = x), the product is exact
+__device__ __forceinline__ unsigned long long ms_fixed(float c)
+{
+    const float m = fminf(c, MS_COST_CAP);
+    return m > 0.0f ? (unsigned long long)floorf(m * 1024.0f) : 0ull;
+}
+
+// dynamic LDS of a tile: acc[2][tile] uint64 | wcol[D] int32 | wval[D] float | xs[tile * x_stride] float (STAGED only)
+static inline size_t ms_lds_bytes(int tile, int D, int x_stride) { return (size_t)tile * 16 + (size_t)D * 8 + (size_t)tile * x_stride * 4; }
+
+// the rows of a staged tile for rows of D floats (row stride D | 1 in LDS): the largest of 256 / 192 / 128 / 64 whose rows fit the
+// LDS budget; 0: none fits, X is read through the cache (raht_debug_motion_tile)
+static inline int ms_tile_rows(int D)
+{
+    if (D < 1 || D > 4096) return 0;
+    for (int t = MS_THREADS; t >= 64; t -= 64)
+        if (ms_lds_bytes(t, D, D | 1) <= MS_LDS_BYTES) return t;
+    return 0;
+}
+
+// One column of a cost table, summed per block over a tile whose rows are lanes: q is this row's cost, slot the tile row at which
+// its block begins (blocks are runs of lanes), tail / head: the last lane of its block in this wave / the block's first row of the
+// tile. A segmented scan inside the wave, the wave's segment tails add into the LDS slot of their block (acc: one zeroed uint64
+// per tile row), and after the barrier the head adds the slot to *cell -- ONE 64-bit atomic per (block, column, workgroup) -- and
+// zeroes it. Every thread of the workgroup calls this; consecutive columns alternate between two sets of slots, so a column
+// costs one barrier.
+__device__ __forceinline__ void ms_block_add(unsigned long long q, int slot, int lane, int tid, bool tail, bool head, unsigned long long *acc,
+                                             unsigned long long *cell)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long u = __shfl_up(q, d);
+        const int s = __shfl_up(slot, d);
+        if (lane >= d && s == slot) q += u;
+    }
+    if (tail && q) atomicAdd(acc + slot, q);
+    __syncthreads();
+    if (head) {
+        const unsigned long long v = acc[tid];
+        if (v) {
+            atomicAdd(cell, v);
+            acc[tid] = 0;                                // (this set is added to again two columns on: a barrier lies between)
+        }
+    }
 }
 
 // FLAT: every row stride == D, the tile is one run of rows * D floats (X, Y element-aligned only). X and Y may be the same matrix:

@@ -1124,10 +1124,16 @@ def _search_host_args(who, candidates, weights, D, dev):
         raise ValueError(f"{who}: candidates must be (K, 3) integers, 1 <= K <= {MOTION_MAX_CANDIDATES}")
     if np.abs(cand.astype(np.int64)).max() > 127:
         raise ValueError(f"{who}: a candidate outside +-127 (a vector is stored as int8)")
+    return torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev), _search_weights(who, weights, D, dev), int(cand.shape[0])
+
+
+def _search_weights(who, weights, D, dev):
+    """the weights of a search, checked on the host -> (D,) float32 on ``dev``"""
+    import numpy as np
     w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1)
     if w.shape[0] != D or not bool(np.all(np.isfinite(w) & (w >= 0))):
         raise ValueError(f"{who}: weights must be D finite numbers >= 0")
-    return torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev), torch.from_numpy(w).to(dev), int(cand.shape[0])
+    return torch.from_numpy(w).to(dev)
 
 
 # ---- hierarchical motion search (raht_motion_search_around; DESIGN.md 23) -------------------------------------------------------------
@@ -1242,37 +1248,89 @@ def predict_mc(keys, ref_keys, C_ref, mv, block_first, J, block_log2, X=None, up
 
 @torch.no_grad()
 def predict_bi(keys, ref0, ref1, X=None, up=0, add=False, out=None, want_matched=False, J=None, block_log2=0, block_first=None,
-               mv0=None, mv1=None):
+               mv0=None, mv1=None, modes=None):
     """The two-reference predictor of a B frame (raht_predict_bi). ref0, ref1: (ref_keys, C_ref) as ``predict`` takes
     them, of one D. With m_r = ``predict``'s P against reference r (``predict_mc``'s under ``mv_r``: (n_blocks, 3) int8 over the
     FRAME's blocks, with ``J``, ``block_log2`` and ``block_first`` of ``motion_blocks``; a field that is None is all zero), P is m0
     where reference 1 has no run for the row, m1 where reference 0 has none, 0 where neither has, and fl(0.5 fl(m0 + m1)) where
     both have. -> P when ``X`` is None, X - P, or X + P with ``add``; into ``out`` when given (``out`` may be ``X``). Column slices
     pass as they are. ``want_matched``: -> (result, n_matched), a (3,) int64 device tensor: the rows with a run in reference 0, in
-    reference 1, in both. Enqueued only."""
+    reference 1, in both. Enqueued only.
+
+    ``modes`` (raht_predict_bi_modes): (n_blocks,) uint8 on the device, one per block of the frame (``J``,
+    ``block_log2`` and ``block_first`` are then needed with or without fields) -- 0: the rule above, 1: m0 alone (0 where reference
+    0 has no run), 2: m1 alone, 3: P = 0. All 0 gives the bits of the call without modes, all 1 or all 2 those of ``predict`` /
+    ``predict_mc`` against that reference; n_matched then counts the runs the prediction uses."""
     who = "predict_bi"
-    try:
-        (rk0, C0), (rk1, C1) = ref0, ref1
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: ref0 and ref1 are (ref_keys, C_ref) pairs") from None
+    (rk0, C0), (rk1, C1) = _ref_pairs(who, ref0, ref1)
     fields = [f for f in (mv0, mv1) if f is not None]
     if fields and (J is None or block_first is None):
         raise ValueError(f"{who}: a motion field needs J, block_log2 and block_first")
-    blocks0 = (J, block_log2, block_first, fields[0]) if fields else None
-    blocks1 = (J, block_log2, block_first, fields[-1]) if fields else None
+    if modes is not None and (J is None or block_first is None):
+        raise ValueError(f"{who}: modes need J, block_log2 and block_first")
+    framed = bool(fields) or modes is not None                               # (the blocks are read under a field or under modes)
+    blocks0 = (J, block_log2, block_first, *fields[:1]) if framed else None
+    blocks1 = (J, block_log2, block_first, *fields[-1:]) if framed else None
     dev, _, live0, out, _ = _inter_args(who, keys, rk0, C0, up, X, blocks=blocks0, result=(add, out, False))
     _, _, live1, _, _ = _inter_args(who, keys, rk1, C1, up, X, blocks=blocks1, result=(add, out, False))
     (k, r0, C0), (r1, C1) = live0[:3], live1[1:3]
     if C1.shape[1] != C0.shape[1] or C1.device != dev:
         raise ValueError(f"{who}: both references must have the same D and lie on one device")
     N, D = int(k.shape[0]), int(C0.shape[1])
-    bf = live0[3] if fields else None
+    bf = live0[3] if framed else None
+    n_blocks = int(bf.shape[0]) - 1 if framed else 0
     f0, f1 = (None if f is None else f.contiguous() for f in (mv0, mv1))
     matched = torch.empty(3, dtype=torch.int64, device=dev) if want_matched else None
-    _call(_lib.lib().raht_predict_bi, dev, _p(k), N, int(J) if fields else 0, int(block_log2) if fields else 0, _p(bf),
-          int(bf.shape[0]) - 1 if fields else 0, _p(f0), _p(f1), _p(r0), int(r0.shape[0]), _p(C0), C0.stride(0), _p(r1), int(r1.shape[0]),
-          _p(C1), C1.stride(0), 3 * int(up), _p(X), 0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched))
+    head = [_p(k), N, int(J) if framed else 0, int(block_log2) if framed else 0, _p(bf), n_blocks]
+    tail = [_p(f0), _p(f1), _p(r0), int(r0.shape[0]), _p(C0), C0.stride(0), _p(r1), int(r1.shape[0]), _p(C1), C1.stride(0), 3 * int(up),
+            _p(X), 0 if X is None else X.stride(0), D, int(bool(add)), _p(out), out.stride(0), _p(matched)]
+    if modes is None:
+        _call(_lib.lib().raht_predict_bi, dev, *head, *tail)
+    else:
+        _need_cuda(modes, "modes")
+        if modes.dtype != torch.uint8 or tuple(modes.shape) != (n_blocks,) or modes.device != dev:
+            raise ValueError(f"{who}: modes must be a ({n_blocks},) uint8 tensor on the keys' device")
+        modes = modes.contiguous()
+        _call(_lib.lib().raht_predict_bi_modes, dev, *head, _p(modes), *tail)
     return (out, matched) if want_matched else out
+
+
+def _ref_pairs(who, ref0, ref1):
+    try:
+        (rk0, C0), (rk1, C1) = ref0, ref1
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: ref0 and ref1 are (ref_keys, C_ref) pairs") from None
+    return (rk0, C0), (rk1, C1)
+
+
+# ---- block modes of a B frame (raht_mode_search / raht_predict_bi_modes; DESIGN.md 24) ------------------------------------------------
+@torch.no_grad()
+def mode_search(keys, ref0, ref1, X, J, block_log2, block_first, weights, up=0, mv0=None, mv1=None, want_table=False):
+    """The per-block choice among a B frame's predictors (raht_mode_search). keys, ref0, ref1, ``up``, mv0, mv1: as
+    ``predict_bi`` takes them; X: (N, D) float32; block_first: ``motion_blocks``; weights: D finite floats >= 0 (checked here, on the
+    host), a column of weight 0 is left out. A block is predicted in one of four ways -- 0: ``predict_bi``'s rule, 1: from reference
+    0 alone (``predict`` / ``predict_mc`` under mv0; 0 where it has no run), 2: from reference 1 alone, 3: not at all. The cost of a
+    row under a mode is ``motion_search``'s row cost against that mode's prediction, a block's cost the integer sum over its rows;
+    the smallest cost wins, the smallest mode among equals. -> (mode (n_blocks,) uint8, best_cost (n_blocks,) int64[, table
+    (n_blocks, 4) int64]) on the device. One pass over the frame. Enqueued only."""
+    who = "mode_search"
+    (rk0, C0), (rk1, C1) = _ref_pairs(who, ref0, ref1)
+    dev, _, live0, _, _ = _inter_args(who, keys, rk0, C0, up, X, blocks=(J, block_log2, block_first, *(() if mv0 is None else (mv0,))))
+    _, _, live1, _, _ = _inter_args(who, keys, rk1, C1, up, X, blocks=(J, block_log2, block_first, *(() if mv1 is None else (mv1,))))
+    (k, r0, C0, bf), (r1, C1) = live0[:4], live1[1:3]
+    if C1.shape[1] != C0.shape[1] or C1.device != dev:
+        raise ValueError(f"{who}: both references must have the same D and lie on one device")
+    X = live0[-1]
+    N, D, n_blocks = int(k.shape[0]), int(C0.shape[1]), int(bf.shape[0]) - 1
+    f0, f1 = (None if f is None else f.contiguous() for f in (mv0, mv1))
+    w_d = _search_weights(who, weights, D, dev)
+    mode = torch.empty(n_blocks, dtype=torch.uint8, device=dev)
+    best_cost = torch.empty(n_blocks, dtype=torch.int64, device=dev)
+    table = torch.empty((n_blocks, 4), dtype=torch.int64, device=dev) if want_table else None
+    _call(_lib.lib().raht_mode_search, dev, _p(k), N, int(J), int(block_log2), _p(bf), n_blocks, _p(f0), _p(f1), _p(r0), int(r0.shape[0]),
+          _p(C0), C0.stride(0), _p(r1), int(r1.shape[0]), _p(C1), C1.stride(0), 3 * int(up), _p(X), X.stride(0), D, _p(w_d), _p(mode),
+          _p(best_cost), _p(table))
+    return (mode, best_cost, table) if want_table else (mode, best_cost)
 
 
 @torch.no_grad()
