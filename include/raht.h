@@ -941,6 +941,23 @@ int raht_region_assemble_set(const int32_t *src, int64_t ld_src, int64_t n_src_r
 int raht_region_needs(const uint64_t *keys_sorted, int64_t N, int J, int top_level, int up, const int64_t *block_first, int64_t n_blocks,
                       const int8_t *mv, int block_log2, uint64_t *cells, int64_t capacity, int64_t *n_cells, raht_stream_t stream);
 
+/* The needed sets of a B frame (python: bitstream.decode_sequence_cells): for the rows keys_sorted of a frame with two
+ * references -- or of a region of one --, the cells of reference 0 (cells0) and of reference 1 (cells1) that the two-reference
+ * predictor ("Two references" and "Block modes" below) can reach into, from ONE pass over the keys. cells_r (DEVICE
+ * uint64[capacity]) holds raht_region_needs' entries for reference r -- (k' >> w) << (w - top_level), w = max(top_level, 3 up),
+ * ascending and duplicate-free -- over the rows whose voxel, shifted by the vector mv_r of the row's block, stays in the cube AND
+ * whose block's mode uses reference r: mode 0 uses both references, 1 reference 0 alone, 2 reference 1 alone, 3 neither; a mode byte
+ * above 3 counts as 3. mv0, mv1 (DEVICE int8[3 n_blocks]) and mode (DEVICE uint8[n_blocks]) may each be NULL: a zero field, every
+ * block in mode 0. block_first (DEVICE int64[n_blocks], rows of keys_sorted), n_blocks and block_log2 are required as soon as one of
+ * the three is given, under raht_region_needs' rules, and are not read otherwise. n_cells (HOST int64[2]) = the two counts; every
+ * store is bounded by capacity, and a larger count in either list is RAHT_ERR_INVALID (with both counts set). With mode NULL and
+ * mv1 == mv0 both lists are raht_region_needs' under that field, with all three NULL its answer without one. SYNCHRONISES `stream`.
+ * RAHT_ERR_INVALID, with nothing enqueued, for what raht_region_needs refuses; more than 2^31 - 1 candidate cells (N >= 2^30 rows)
+ * are refused as well. */
+int raht_region_needs_bi(const uint64_t *keys_sorted, int64_t N, int J, int top_level, int up, const int64_t *block_first, int64_t n_blocks,
+                         int block_log2, const int8_t *mv0, const int8_t *mv1, const uint8_t *mode, uint64_t *cells0, uint64_t *cells1,
+                         int64_t capacity, int64_t *n_cells, raht_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Inter-frame prediction (csrc/predict.hip): a frame of a sequence predicted from the RECONSTRUCTION of another one, so that only
  * the residual is coded (python: bitstream.encode_sequence_bytes(..., gop, up, inter) / decode_sequence_bytes).

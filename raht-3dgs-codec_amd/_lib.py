@@ -35,7 +35,7 @@ EXPORTS = [
     "raht_octree_counts", "raht_octree_encode", "raht_octree_decode", "raht_octree_symbols", "raht_octree_bytes", "raht_demorton",
     "raht_octree_encode_inter", "raht_octree_decode_inter", "raht_octree_bytes_used",
     "raht_region_layout", "raht_region_cells", "raht_region_assemble",
-    "raht_region_layout_set", "raht_region_assemble_set", "raht_region_needs",
+    "raht_region_layout_set", "raht_region_assemble_set", "raht_region_needs", "raht_region_needs_bi",
     "raht_predict", "raht_motion_search", "raht_motion_search_around", "raht_predict_mc", "raht_predict_bi",
     "raht_mode_search", "raht_predict_bi_modes",
 ]
@@ -206,6 +206,7 @@ def lib():
     L.raht_region_layout_set.argtypes = [vp, i64, i32, vp, i32, vp, vp]
     L.raht_region_assemble_set.argtypes = [vp, i64, i64, vp, i64, i64, i32, vp, C.POINTER(i64), i32, vp]
     L.raht_region_needs.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp, i32, vp, i64, C.POINTER(i64), vp]
+    L.raht_region_needs_bi.argtypes = [vp, i64, i32, i32, i32, vp, i64, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]
     L.raht_predict.argtypes = [vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp]
     L.raht_motion_search.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp]
     L.raht_motion_search_around.argtypes = [vp, i64, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]

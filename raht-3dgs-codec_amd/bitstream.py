@@ -422,16 +422,21 @@ def decode_cells_bytes(blob, depth, ranges, device="cuda", max_voxels=None, keys
     except (TypeError, ValueError):
         raise ValueError(f"{who}: depth is an integer, ranges a list of pairs of integers") from None
     _region_depth(who, h, depth)
-    if not 1 <= len(ranges) <= ops.REGION_MAX_RANGES:
-        raise ValueError(f"{who}: 1 .. {ops.REGION_MAX_RANGES} ranges")
-    if any(not c0 < c1 for c0, c1 in ranges) or any(p[1] > q[0] for p, q in zip(ranges, ranges[1:])) or ranges[0][0] < 0 or ranges[-1][1] > 8 ** depth:
-        raise ValueError(f"{who}: ranges must be ascending, disjoint pairs 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
+    _region_ranges(who, ranges, depth)
     return _decode_cells(who, blob, h, depth, ranges, torch.device(device), max_voxels, keys, ref_keys)[:3]
 
 
 def _region_depth(who, h, depth):
     if not 1 <= depth <= h["J"] - 1:
         raise ValueError(f"{who}: depth must be 1 .. J - 1 = {h['J'] - 1}")
+
+
+def _region_ranges(who, ranges, depth):
+    """the rules of a set of cell ranges (a list of pairs of integers) at ``depth``"""
+    if not 1 <= len(ranges) <= ops.REGION_MAX_RANGES:
+        raise ValueError(f"{who}: 1 .. {ops.REGION_MAX_RANGES} ranges")
+    if any(not c0 < c1 for c0, c1 in ranges) or any(p[1] > q[0] for p, q in zip(ranges, ranges[1:])) or ranges[0][0] < 0 or ranges[-1][1] > 8 ** depth:
+        raise ValueError(f"{who}: ranges must be ascending, disjoint pairs 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
 
 
 def _decode_cells(who, blob, h, depth, ranges, dev, max_voxels, keys, ref_keys=None):
@@ -1175,11 +1180,39 @@ def _merge_cells(cells, group, limit=ops.REGION_MAX_RANGES):
     return list(zip(lo, hi))
 
 
+def _unite_ranges(range_lists, limit=ops.REGION_MAX_RANGES):
+    """ascending lists of disjoint cell ranges -> the ascending list of disjoint ranges that covers them all, overlapping and
+    touching ranges merged; more than ``limit`` ranges are brought down to it as ``_merge_cells`` does, by closing the narrowest
+    gaps. One list is what it is: nothing is merged in it."""
+    lists = [r for r in range_lists if r]
+    if len(lists) <= 1:
+        return list(lists[0]) if lists else []
+    out = []
+    for c0, c1 in sorted(r for rs in lists for r in rs):
+        if out and c0 <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], c1))
+        else:
+            out.append((c0, c1))
+    if len(out) > limit:
+        lo, hi = [r[0] for r in out], [r[1] for r in out]
+        gaps = np.asarray(lo[1:]) - np.asarray(hi[:-1])
+        keep = np.sort(np.argsort(gaps, kind="stable")[len(gaps) - (limit - 1):])      # the limit - 1 widest gaps stay open
+        out = list(zip([lo[0]] + [lo[g + 1] for g in keep], [hi[g] for g in keep] + [hi[-1]]))
+    return out
+
+
 def _region_motion(block_first, mv, rows, dev):
-    """The motion field of a region: ``block_first`` (n_blocks + 1 rows of the whole frame) and ``mv`` of a frame, ``rows`` = [(a,
-    b)] of the region's ranges, ascending -> (block_first, mv) over the rows of the region matrix (the ranges concatenated), as
-    ``ops.predict_mc`` takes them: the blocks that have rows in a range, range by range, each with its first row in the region. A
-    block that two ranges cut is listed once per range."""
+    """The motion field of a region: ``_region_blocks`` for one field -> (block_first, mv) as ``ops.predict_mc`` takes them."""
+    first, (field,) = _region_blocks(block_first, rows, dev, mv)
+    return first, field
+
+
+def _region_blocks(block_first, rows, dev, *per_block):
+    """The blocks of a region: ``block_first`` (n_blocks + 1 rows of the whole frame), ``rows`` = [(a, b)] of the region's ranges,
+    ascending, and any number of ``per_block`` tensors of a frame (a motion field (n_blocks, 3), the block modes (n_blocks,); None
+    stays None) -> (block_first over the rows of the region matrix (the ranges concatenated), [every tensor over the same blocks]),
+    as ``ops.predict_mc`` and ``ops.predict_bi`` take them: the blocks that have rows in a range, range by range, each with its
+    first row in the region. A block that two ranges cut is listed once per range. One selection serves every tensor."""
     import torch
     lo = torch.tensor([a for a, _ in rows], dtype=torch.int64, device=dev)
     hi = torch.tensor([b for _, b in rows], dtype=torch.int64, device=dev)
@@ -1192,7 +1225,8 @@ def _region_motion(block_first, mv, rows, dev):
             first.append(torch.clamp(block_first[b0:b1] - a, min=0) + base)
             base += b - a
     first.append(torch.tensor([base], dtype=torch.int64, device=dev))
-    return torch.cat(first), mv[torch.cat(idx)].contiguous()
+    pick = torch.cat(idx)
+    return torch.cat(first), [None if t is None else t[pick].contiguous() for t in per_block]
 
 
 def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None, max_frames=None, keys=None):
@@ -1220,7 +1254,8 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
     ranges and the bytes of an empty region: its headers, which the walk along the chain reads), bytes_needed (the sum over the
     chain), byte_ranges (the sequence header's bytes, then every chain frame's: everything outside them may be missing), keys.
     ``ValueError`` as ``decode_sequence_bytes`` raises it, a frame named by its index; what the headers show is refused before any
-    device work."""
+    device work. This is the one-range call of ``decode_sequence_cells``' core for I, P and motion-compensated frames; a B frame is
+    refused here and goes through ``decode_sequence_cells``."""
     import torch
     who = "decode_sequence_region"
     off = parse_sequence(blob, max_frames)
@@ -1233,18 +1268,60 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
         raise ValueError(f"{who}: the frame index must be in 0 .. {n - 1}")
     heads = _frame_heads(memoryview(blob), off, [i], max_voxels)
     if heads[i]["kind"] == "B":
-        raise ValueError(f"{who}: frame {i} is a B frame: a region of a frame with two references is not supported, decode it whole")
+        raise ValueError(f"{who}: frame {i} is a B frame: a region of a frame with two references is not supported, decode it whole "
+                         "or through decode_sequence_cells")
     _region_depth(who, heads[i]["h"], depth)                                 # (a chain has one J: _frame_heads)
     if not 0 <= c0 < c1 <= 8 ** depth:
         raise ValueError(f"{who}: cells must satisfy 0 <= c0 < c1 <= 8^depth = {8 ** depth}")
     if keys is not None and not isinstance(keys, dict):
         raise ValueError(f'{who}: keys is the dict an earlier call returned in info["keys"]')
-    dev = torch.device(device)
+    return _decode_sequence_cells(who, blob, off, heads, i, depth, [(c0, c1)], torch.device(device), max_voxels, keys)
+
+
+def decode_sequence_cells(blob, i, depth, ranges, device="cuda", max_voxels=None, max_frames=None, keys=None):
+    """``decode_sequence_region`` for a SET of cell ranges and for a frame of ANY kind, B frames (RAHTB001, RAHTB002) included
+     -> (V_int, C_rec, info): the rows of the ranges of ``decode_sequence_bytes(blob, [i])[0]``, concatenated, bit for
+    bit. ``ranges``: as ``decode_cells_bytes`` takes them, an ascending list of 1 .. 512 disjoint pairs of depth-``depth`` cells.
+
+    The dependencies of a B frame are a small DAG, i -> (a, c), c -> a, a -> ... -> the intra frame: frame i is walked first, then
+    every other frame of the closure in descending index, so that a frame is visited after every frame that needs it. A frame's
+    needed set is the UNION of what its dependants ask of it (each dependant's cells as ranges under its own ``up`` group, the lists
+    united on the host, brought down to 512 ranges by closing the narrowest gaps: a needed set may hold more than it must, never
+    less). A B frame asks both references in one pass over the region's keys (``ops.region_needs_bi``) under the region's blocks, both
+    fields and the block modes: a block in mode 1 asks nothing of reference 1, one in mode 2 nothing of reference 0. A frame nothing
+    is needed of is an empty region: its headers only. The replay runs in ascending order, frame i last, through the one predictor
+    on the region matrices; a reference whose needed rows are empty is taken out through the modes (with reference 1 empty 0 -> 1
+    and 2 -> 3, with reference 0 empty 0 -> 2 and 1 -> 3), which gives the predictor's bits: for a row whose cell is empty in one
+    reference the two-reference prediction is the one-reference prediction of the other.
+
+    info: ``decode_sequence_region``'s, with chain the ascending list of the frames of the closure and frames[f]["ranges"]
+    possibly a union; ``keys`` as there. ``ValueError`` as ``decode_sequence_bytes`` and ``decode_cells_bytes`` raise it."""
+    import torch
+    who = "decode_sequence_cells"
+    off = parse_sequence(blob, max_frames)
+    n = len(off) - 1
+    try:
+        i, depth, ranges = int(i), int(depth), [(int(c0), int(c1)) for c0, c1 in ranges]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: i and depth are integers, ranges a list of pairs of integers") from None
+    if not 0 <= i < n:
+        raise ValueError(f"{who}: the frame index must be in 0 .. {n - 1}")
+    heads = _frame_heads(memoryview(blob), off, [i], max_voxels)
+    _region_depth(who, heads[i]["h"], depth)                                 # (a closure has one J: _frame_heads)
+    _region_ranges(who, ranges, depth)
+    if keys is not None and not isinstance(keys, dict):
+        raise ValueError(f'{who}: keys is the dict an earlier call returned in info["keys"]')
+    return _decode_sequence_cells(who, blob, off, heads, i, depth, ranges, torch.device(device), max_voxels, keys)
+
+
+def _decode_sequence_cells(who, blob, off, heads, i, depth, ranges, dev, max_voxels, keys):
+    """THE region decoder of a sequence, for checked arguments: ``heads`` is ``_frame_heads``' closure of frame ``i``."""
+    import torch
     chain = sorted(heads)
     J = heads[i]["h"]["J"]
     tl = 3 * (J - depth)
-    part, frames, keys_out = {}, {}, {}                                      # part: frame -> (V, C, region keys, region motion)
-    S = [(c0, c1)]
+    part, frames, keys_out = {}, {}, {}                                      # part: frame -> (V, C, region keys, region blocks)
+    asked = {f: [] for f in chain}                                           # frame -> the range lists its dependants ask of it
     given, decoded = keys or {}, set()                                       # decoded: the frames whose geometry this call decodes
 
     def whole_keys(f):
@@ -1267,10 +1344,13 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
         return keys_out[f]
 
     with torch.cuda.device(dev):
-        for f in reversed(chain):                                            # down the chain: what is needed of every frame
+        # frame i, then down the other frames: a B frame is no frame's reference and every other reference points backwards, so
+        # every frame comes after all frames that need it
+        for f in [i] + [g for g in reversed(chain) if g != i]:
             hd = heads[f]
             h, fb = hd["h"], hd["fb"]
             base = off[f + 1] - len(fb)                                      # where the inner frame starts in the sequence blob
+            S = ranges if f == i else _unite_ranges(asked[f])
             if not S:                                                        # nothing but what the walk along the chain reads: as an empty region
                 ao, al = h["attributes"]
                 head = base - off[f] + ao + SegmentedCoder._parse(fb[ao: ao + al], h["N"] * h["D"])[6]
@@ -1283,28 +1363,57 @@ def decode_sequence_region(blob, i, depth, cells, device="cuda", max_voxels=None
                 V, C, info, kr = _decode_cells(who, fb, h, depth, S, dev, max_voxels, kf)
             except ValueError as e:
                 raise ValueError(f"sequence container: frame {f}: {e}") from None
-            ranges = [(base + o, ln) for o, ln in info["byte_ranges"]]
-            ranges[0] = (off[f], ranges[0][1] + base - off[f])               # (the wrapper of a predicted frame lies in front)
+            spans = [(base + o, ln) for o, ln in info["byte_ranges"]]
+            spans[0] = (off[f], spans[0][1] + base - off[f])                 # (the wrapper of a predicted frame lies in front)
             frames[f] = dict(ranges=S, rows=int(kr.shape[0]), n_cells=info["n_cells"], segments_decoded=info["segments_decoded"],
-                             segments_total=info["segments_total"], byte_ranges=ranges, bytes_needed=sum(ln for _, ln in ranges),
+                             segments_total=info["segments_total"], byte_ranges=spans, bytes_needed=sum(ln for _, ln in spans),
                              geometry_decoded=False)
-            motion = None
+            motion, group = None, 8 ** max(hd["up"] - (J - depth), 0)
             if hd["kind"] == "P" and kr.shape[0]:
                 if hd["motion"] is not None:
                     m, mv = hd["motion"]
                     motion = (m,) + _region_motion(ops.motion_blocks(info["keys"], J, m, len(mv)), torch.from_numpy(mv.copy()).to(dev),
                                                    info["rows"], dev)[::-1]
                 need = ops.region_needs(kr, J, tl, hd["up"], *((None, None, 0) if motion is None else (motion[2], motion[1], motion[0])))
-                S = _merge_cells(need, 8 ** max(hd["up"] - (J - depth), 0))
-            else:
-                S = []
+                asked[hd["ref"]].append(_merge_cells(need, group))
+            elif hd["kind"] == "B" and kr.shape[0]:
+                # the region's blocks, once for both fields and the modes: (block_log2, block_first, mv0, mv1, mode), or None
+                blocks = hd["motion"] or hd["modes"]
+                if blocks is not None:
+                    per_block = (*(hd["motion"][1:] if hd["motion"] else (None, None)), hd["modes"][1] if hd["modes"] else None)
+                    per_block = [None if t is None else torch.from_numpy(t.copy()).to(dev) for t in per_block]
+                    bf = ops.motion_blocks(info["keys"], J, blocks[0], len(blocks[1]))
+                    bf, per_block = _region_blocks(bf, info["rows"], dev, *per_block)
+                    motion = (blocks[0], bf, *per_block)
+                need = ops.region_needs_bi(kr, J, tl, hd["up"], *(() if motion is None else (motion[1], *motion[2:], motion[0])))
+                for g, cells in zip((hd["ref"], hd["ref1"]), need):
+                    asked[g].append(_merge_cells(cells, group))
             part[f] = (V, C, kr, motion)
-        for f in chain:                                                      # and up again: a reference is whole before it is used
+        # and up again, frame i last: a reference is whole before it is used
+        for f in [g for g in chain if g != i] + [i]:
             hd = heads[f]
-            g = hd["ref"]
-            if f in part and g in part and part[f][2].shape[0] and part[g][2].shape[0]:
-                _, C, kr, motion = part[f]
-                _Predictor(kr, (part[g][2], part[g][1]), J, hd["up"], motion).restore(C)
+            if f not in part or not part[f][2].shape[0]:
+                continue
+            _, C, kr, motion = part[f]
+            refs = [(part[g][2], part[g][1]) if g in part and part[g][2].shape[0] else None for g in (hd["ref"], hd["ref1"])]
+            if hd["kind"] == "P" and refs[0] is not None:
+                _Predictor(kr, refs[0], J, hd["up"], motion).restore(C)
+            elif hd["kind"] == "B" and (refs[0] is not None or refs[1] is not None):
+                fields = modes = None
+                if motion is not None:
+                    m, bf, mv0, mv1, mode = motion
+                    fields = None if mv0 is None else (m, mv0, mv1, bf)
+                    modes = None if mode is None else (m, mode, bf)
+                if refs[0] is None or refs[1] is None:
+                    # a reference without needed rows goes out through the modes (the ops take no empty reference); the other one
+                    # stands in for it and is never read in its place
+                    if modes is None:
+                        m, bf = (motion[0], motion[1]) if motion is not None else (J, torch.tensor([0, kr.shape[0]], dtype=torch.int64, device=dev))
+                        modes = (m, torch.zeros(bf.shape[0] - 1, dtype=torch.uint8, device=dev), bf)
+                    table = [1, 1, 3, 3] if refs[1] is None else [2, 3, 2, 3]
+                    modes = (modes[0], torch.tensor(table, dtype=torch.uint8, device=dev)[modes[1].long()], modes[2])
+                    refs = [refs[0] or refs[1], refs[1] or refs[0]]
+                _Predictor(kr, refs[0], J, hd["up"], fields, ref1=refs[1], modes=modes).restore(C)
     for f in decoded:
         frames[f]["geometry_decoded"] = True
     byte_ranges = [(0, off[0])] + [r for f in chain for r in frames[f]["byte_ranges"]]

@@ -17,6 +17,9 @@
 //   assemble_set  the run table lies in device memory; a destination row finds its run by binary search over the destinations.
 //   needs         the cells of another frame that a prediction of these rows reaches into: flag / scan / scatter of the rows whose
 //                 (shifted) cell differs from the row before, and under a motion field a sort and a second pass over that list.
+//   needs_bi      the same for the two references of a B frame from ONE pass over the keys: a row's block is found once, both
+//                 candidate cells are formed in registers, reference 1's carry a tag bit above the cell bits, and one sort and one
+//                 flag / scan / pick serve both lists, split at the tag.
 #include "raht_common.h"
 #include "predict_device.h"
 
@@ -265,6 +268,64 @@ __global__ __launch_bounds__(REG_THREADS) void region_needs_pick_kernel(const ui
     }
 }
 
+// ---- the needed sets of a B frame: both references from one pass over the keys (raht_region_needs_bi) ---------------------------
+// the cell of the key a row resolves in one reference, under the vector v of its block (NULL: the key itself)
+__device__ __forceinline__ uint64_t needs_bi_cell(uint64_t key, const int8_t *__restrict__ v, int J, int top_level, int wide)
+{
+    uint64_t k = key;
+    if (v && !pr_shift_key(vox_coords(key), v[0], v[1], v[2], J, k)) return NEEDS_NONE;
+    return (k >> wide) << (wide - top_level);
+}
+
+// One pass: the block of a row is found once, its mode byte and both vectors are read once, and both candidate cells are formed in
+// registers. cand[i] is the row's cell in reference 0, cand[n + i] its cell in reference 1 with the bit `tag` set (the bit above
+// the cell bits), NEEDS_NONE where the mode does not use the reference or the shifted voxel leaves the cube. A candidate is flagged
+// unless the row before it IN THE WAVE has the same one: neighbouring repeats go here, the rest after the sort.
+__global__ __launch_bounds__(REG_THREADS) void region_needs_bi_kernel(const uint64_t *__restrict__ keys, int64_t n, int J, int top_level, int wide,
+                                                                      const int64_t *__restrict__ block_first, int64_t n_blocks,
+                                                                      const int8_t *__restrict__ mv0, const int8_t *__restrict__ mv1,
+                                                                      const uint8_t *__restrict__ mode, uint64_t tag,
+                                                                      uint64_t *__restrict__ cand, uint32_t *__restrict__ flag)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t i0 = (int64_t)blockIdx.x * REG_THREADS; i0 < n; i0 += (int64_t)gridDim.x * REG_THREADS) {
+        const int64_t i = i0 + threadIdx.x;
+        uint64_t c0 = NEEDS_NONE, c1 = NEEDS_NONE;
+        if (i < n) {
+            const uint64_t key = keys[i];
+            const int64_t b = block_first ? pr_block_of(block_first, n_blocks, i) : 0;
+            const uint32_t md = mode ? min((uint32_t)mode[b], 3u) : 0u;      // (a byte above 3 counts as 3: no reference)
+            if (md == 0u || md == 1u) c0 = needs_bi_cell(key, mv0 ? mv0 + 3 * b : nullptr, J, top_level, wide);
+            if (md == 0u || md == 2u) c1 = needs_bi_cell(key, mv1 ? mv1 + 3 * b : nullptr, J, top_level, wide);
+        }
+        const uint64_t p0 = (uint64_t)__shfl_up((unsigned long long)c0, 1), p1 = (uint64_t)__shfl_up((unsigned long long)c1, 1);       // (every lane of the wave is here: i0 is the workgroup's)
+        if (i < n) {
+            flag[i] = (c0 != NEEDS_NONE && (lane == 0 || p0 != c0)) ? 1u : 0u;
+            flag[n + i] = (c1 != NEEDS_NONE && (lane == 0 || p1 != c1)) ? 1u : 0u;
+            cand[i] = c0;
+            cand[n + i] = c1 == NEEDS_NONE ? c1 : (c1 | tag);
+        }
+    }
+}
+
+// region_needs_pick_kernel over the sorted, tagged list: the entries without the tag go to cells0, those with it to cells1 without
+// it. first1: where the tagged entries begin in the list (m: there are none); that entry differs from the one before it, so its
+// position is the number of cells of reference 0. Every store is bounded by cap.
+__global__ __launch_bounds__(REG_THREADS) void region_needs_bi_pick_kernel(const uint64_t *__restrict__ list, int64_t m, const uint32_t *__restrict__ flag,
+                                                                           const uint32_t *__restrict__ pos, const uint32_t *__restrict__ total,
+                                                                           int64_t first1, uint64_t tag, int64_t cap, uint64_t *__restrict__ cells0,
+                                                                           uint64_t *__restrict__ cells1)
+{
+    const int64_t n0 = first1 < m ? (int64_t)pos[first1] : (int64_t)*total;
+    for (int64_t i = (int64_t)blockIdx.x * REG_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * REG_THREADS) {
+        if (!flag[i]) continue;
+        const uint64_t v = list[i];
+        const int64_t j = (int64_t)pos[i];
+        if (!(v & tag)) { if (j < cap) cells0[j] = v; }
+        else if (j >= n0 && j - n0 < cap) cells1[j - n0] = v & ~tag;
+    }
+}
+
 static inline unsigned region_grid(int64_t items, int64_t per_block)
 {
     const int64_t g = ceil_div(items, per_block);
@@ -464,6 +525,85 @@ int raht_region_needs(const uint64_t *keys_sorted, int64_t N, int J, int top_lev
         *n_cells = (int64_t)found;
         if ((int64_t)found > capacity) {
             set_error("raht_region_needs: %u cells, the caller's buffer holds %lld", found, (long long)capacity);
+            return RAHT_ERR_INVALID;
+        }
+        return RAHT_OK;
+    });
+}
+
+int raht_region_needs_bi(const uint64_t *keys_sorted, int64_t N, int J, int top_level, int up, const int64_t *block_first, int64_t n_blocks,
+                         int block_log2, const int8_t *mv0, const int8_t *mv1, const uint8_t *mode, uint64_t *cells0, uint64_t *cells1,
+                         int64_t capacity, int64_t *n_cells, raht_stream_t stream)
+{
+    const char *who = "raht_region_needs_bi";
+    if (J < 1 || J > 21) { set_error("%s: J=%d (1..21)", who, J); return RAHT_ERR_INVALID; }
+    RAHT_RET(region_check_keys(who, keys_sorted, N, 3 * J));
+    if (!cells0 || !cells1 || !n_cells || capacity < 1) { set_error("%s: NULL output or no capacity", who); return RAHT_ERR_INVALID; }
+    if (top_level % 3 || top_level < 3 || top_level > 3 * J - 3) {
+        set_error("%s: top_level=%d must be a multiple of 3 in [3, 3 J - 3]", who, top_level);
+        return RAHT_ERR_INVALID;
+    }
+    if (up < 0 || up > 3) { set_error("%s: up=%d (0..3)", who, up); return RAHT_ERR_INVALID; }
+    const bool blocks = mv0 || mv1 || mode;
+    if (blocks && (!block_first || n_blocks < 1 || n_blocks > N || block_log2 < 1 || block_log2 > J)) {
+        set_error("%s: a motion field or block modes need block_first, 1 <= n_blocks <= N and block_log2 in 1 .. J", who);
+        return RAHT_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int wide = 3 * up > top_level ? 3 * up : top_level;
+    return guarded(who, [&]() -> int {
+        uint32_t found[2] = {0, 0};                      // the cells of reference 0, of reference 1
+        if (!blocks) {
+            // no field, every block in mode 0: the rows' own cells ascend, raht_region_needs' first pass is both answers
+            Scratch ws(sizeof(uint32_t) * (2 * (size_t)N + 2), s);
+            if (!ws.ok()) { set_error("%s: out of device memory", who); return RAHT_ERR_NOMEM; }
+            uint32_t *flag = ws.as<uint32_t>(), *pos = flag + N, *total = pos + N;
+            RAHT_RET(region_needs_first(keys_sorted, N, top_level, wide, SameKey{}, flag, pos, total, cells0, capacity, &found[0], s));
+            found[1] = found[0];
+            const size_t kept = (size_t)((int64_t)found[0] < capacity ? (int64_t)found[0] : capacity);
+            if (kept) RAHT_HIP_CHECK(hipMemcpyAsync(cells1, cells0, sizeof(uint64_t) * kept, hipMemcpyDeviceToDevice, s));
+        } else {
+            // candidates and flags of both references (2 N each) | the flagged candidates | scan | total | the sort's indices
+            const size_t N2 = 2 * (size_t)N;
+            Scratch ws(2 * sizeof(uint64_t) * N2 + sizeof(uint32_t) * (3 * N2 + 2), s);
+            if (!ws.ok()) { set_error("%s: out of device memory", who); return RAHT_ERR_NOMEM; }
+            uint64_t *cand = ws.as<uint64_t>(), *first = cand + N2;
+            uint32_t *flag = (uint32_t *)(first + N2), *pos = flag + N2, *total = pos + N2, *idx = total + 2;
+            const int cell_bits = 3 * J - top_level;     // (<= 60: the tag is bit 60 at most)
+            const uint64_t tag = 1ull << cell_bits;
+            const dim3 blk(REG_THREADS);
+            hipLaunchKernelGGL(region_needs_bi_kernel, dim3(region_grid(N, REG_THREADS * 4)), blk, 0, s, keys_sorted, N, J, top_level, wide,
+                               block_first, n_blocks, mv0, mv1, mode, tag, cand, flag);
+            RAHT_RET(exclusive_scan_u32(flag, pos, (int64_t)N2, total, s));
+            hipLaunchKernelGGL(region_needs_pick_kernel, dim3(region_grid((int64_t)N2, REG_THREADS * 4)), blk, 0, s, (const uint64_t *)cand,
+                               (int64_t)N2, (const uint32_t *)flag, (const uint32_t *)pos, (int64_t)N2, first);
+            RAHT_HIP_CHECK(hipGetLastError());
+            uint32_t m_all = 0, m_0 = 0;                 // the flagged candidates, those of reference 0 (they come first)
+            RAHT_RET(read_back_u32(&m_all, total, 1, &m_0, pos + N, 1, s));
+            if ((int64_t)m_all >= ((int64_t)1 << 31)) {  // (the sort's limit; 2^30 rows at least)
+                set_error("%s: %u candidate cells, 2^31 - 1 at most", who, m_all);
+                return RAHT_ERR_INVALID;
+            }
+            if (m_all) {
+                const int64_t M = (int64_t)m_all, first1 = (int64_t)m_0;
+                uint64_t *sorted = cand;                 // (the candidates are compacted: their buffer is free)
+                RAHT_RET(sort_keys_u32idx(first, M, cell_bits + 1, sorted, idx, s));
+                const dim3 grid(region_grid(M, REG_THREADS * 4));
+                hipLaunchKernelGGL(region_needs_first_kernel, grid, blk, 0, s, (const uint64_t *)sorted, M, flag);
+                RAHT_RET(exclusive_scan_u32(flag, pos, M, total, s));
+                hipLaunchKernelGGL(region_needs_bi_pick_kernel, grid, blk, 0, s, (const uint64_t *)sorted, M, (const uint32_t *)flag,
+                                   (const uint32_t *)pos, (const uint32_t *)total, first1, tag, capacity, cells0, cells1);
+                RAHT_HIP_CHECK(hipGetLastError());
+                uint32_t all = 0, n0 = 0;
+                RAHT_RET(read_back_u32(&all, total, 1, &n0, pos + (first1 < M ? first1 : 0), 1, s));
+                found[0] = first1 < M ? n0 : all;
+                found[1] = all - found[0];
+            }
+        }
+        n_cells[0] = (int64_t)found[0];
+        n_cells[1] = (int64_t)found[1];
+        if ((int64_t)found[0] > capacity || (int64_t)found[1] > capacity) {
+            set_error("%s: %u and %u cells, the caller's buffers hold %lld each", who, found[0], found[1], (long long)capacity);
             return RAHT_ERR_INVALID;
         }
         return RAHT_OK;

@@ -988,6 +988,54 @@ def region_needs(keys, J, top_level, up, block_first=None, mv=None, block_log2=0
     return cells[: n.value]
 
 
+@torch.no_grad()
+def region_needs_bi(keys, J, top_level, up, block_first=None, mv0=None, mv1=None, modes=None, block_log2=0, capacity=None):
+    """``region_needs`` for the two references of a B frame from one pass over the keys (raht_region_needs_bi) ->
+    (cells0, cells1), each (n_r,) int64 on the device, ascending and without repeats: ``region_needs``' entries for reference r
+    under the field ``mv_r``, over the rows whose block's mode uses that reference -- 0: both, 1: reference 0 alone, 2: reference 1
+    alone, 3 (or any byte above it): neither. mv0, mv1: (n_blocks, 3) int8, modes: (n_blocks,) uint8, on the device, each may be None
+    (a zero field; every block in mode 0); block_first ((n_blocks + 1,) int64 rows of ``keys``) and ``block_log2`` are needed as soon
+    as one of them is given. ``capacity``: the entries either list may have (default: as many as there can be); ``RahtError`` for
+    more. Synchronises."""
+    who = "region_needs_bi"
+    J, tl, up = int(J), int(top_level), int(up)
+    given = [t for t in (mv0, mv1, modes) if t is not None]
+    if not given:
+        k = _region_keys(keys, who)
+        bf, n_blocks, m = None, 0, 0
+    else:
+        k, J, m = _motion_frame(who, keys, J, block_log2)
+        if block_first is None:
+            raise ValueError(f"{who}: a motion field or modes need block_first and block_log2")
+        _need_cuda(block_first, "block_first")
+        if block_first.dtype != torch.int64 or block_first.dim() != 1 or not 2 <= block_first.shape[0] <= k.shape[0] + 1:
+            raise ValueError(f"{who}: block_first must hold n_blocks + 1 int64 rows, 1 <= n_blocks <= N")
+        n_blocks = int(block_first.shape[0]) - 1
+        for name, t in (("mv0", mv0), ("mv1", mv1)):
+            if t is not None:
+                _need_cuda(t, name)
+                if t.dtype != torch.int8 or tuple(t.shape) != (n_blocks, 3) or t.device != k.device:
+                    raise ValueError(f"{who}: {name} must be a ({n_blocks}, 3) int8 tensor on the keys' device")
+        if modes is not None:
+            _need_cuda(modes, "modes")
+            if modes.dtype != torch.uint8 or tuple(modes.shape) != (n_blocks,) or modes.device != k.device:
+                raise ValueError(f"{who}: modes must be a ({n_blocks},) uint8 tensor on the keys' device")
+        if block_first.device != k.device:
+            raise ValueError(f"{who}: block_first must lie on the keys' device")
+        bf = block_first.contiguous()
+    f0, f1, md = (None if t is None else t.contiguous() for t in (mv0, mv1, modes))
+    if capacity is None:
+        capacity = min(int(k.shape[0]), 8 ** max(J - tl // 3, 0))
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError(f"{who}: capacity must be at least 1")
+    cells = torch.empty((2, capacity), dtype=torch.int64, device=k.device)
+    n = (C.c_int64 * 2)(0, 0)
+    _call(_lib.lib().raht_region_needs_bi, k.device, _p(k), k.shape[0], J, tl, up, _p(bf), n_blocks, m, _p(f0), _p(f1), _p(md), _p(cells[0]),
+          _p(cells[1]), capacity, n)
+    return cells[0, : n[0]], cells[1, : n[1]]
+
+
 def _predict_rows(M, n_rows, D, name):
     """a float32 CUDA matrix of the predictor, as it is: (n_rows, D), unit column stride, a row stride of at least D"""
     _need_cuda(M, name)
