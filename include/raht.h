@@ -17,6 +17,28 @@
  *     host synchronisation and, after the first call for a given (element type, D) or after
  *     raht_plan_prepare, no allocation: safe to capture in a hipGraph. Plan construction and
  *     raht_voxelize allocate and synchronise `stream` (they size outputs from device counts);
+ *   - every other entry point with a `stream` argument is one of two kinds, and all its device
+ *     work is on `stream`: it reads its device inputs behind whatever the caller has enqueued
+ *     there before the call, on a non-blocking stream too. Where the description of an entry
+ *     point says which kind it is, that holds; for the ones that do not:
+ *       enqueue only, never synchronise:
+ *         raht_voxel_keys, raht_morton, raht_demorton, raht_merge_clusters, raht_rows_gather,
+ *         raht_rows_scatter, raht_transpose_i32, raht_sqdiff_columns, raht_plan_order,
+ *         raht_plan_copy_array, raht_plan_roots, raht_region_layout, raht_region_layout_set,
+ *         raht_region_assemble, raht_region_assemble_set, raht_octree_encode_inter,
+ *         raht_octree_decode_inter, raht_octree_bytes_used;
+ *       synchronise `stream`:
+ *         raht_sort_keys (it reads back the word that says whether the sort must be repeated);
+ *         raht_plan_set_top_level when the new level differs from the plan's and truncates the
+ *         tree (it reads back the number of roots; otherwise it returns without waiting);
+ *         raht_plan_set_row_map with a map (it reads back an error word; with NULL it waits for
+ *         the whole device if a map was set, and for nothing otherwise); raht_region_cells,
+ *         raht_region_needs and raht_region_needs_bi (they return counts); raht_voxelize_all,
+ *         raht_voxelize_plan and raht_voxelize_merge (as raht_voxelize).
+ *     raht_plan_export_level has no stream argument and needs none: what it copies to the host
+ *     was written by plan construction, which has synchronised, and is never rewritten.
+ *     A call that enqueues only may still wait for the device when its host thread's pool of
+ *     temporary blocks has to hand it a block last used on another stream (below);
  *   - the caller owns every data buffer; a plan is an opaque handle owning its own HBM;
  *   - rows of C / T are the points in Morton order, row-major, `ld*` = row stride in ELEMENTS;
  *   - N < 2^31 rows; element offsets are 64-bit;

@@ -524,14 +524,18 @@ static int finish_plan(raht_plan *p, const int64_t *leaf_weights, hipStream_t s,
         // prefix sums of the leaf weights on the host: weighted plans are tiny (<= 512 rows when
         // they stitch the top octree levels of a sharded scene)
         std::vector<int64_t> w((size_t)N), ps((size_t)N + 1);
-        RAHT_HIP_CHECK(hipMemcpy(w.data(), leaf_weights, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToHost));
+        // on `s`, as everything else here: a plain hipMemcpy runs on the null stream, which a non-blocking stream is not
+        // ordered against -- the weights a caller has just produced on `s` would be read before they are written
+        RAHT_HIP_CHECK(hipMemcpyAsync(w.data(), leaf_weights, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToHost, s));
+        RAHT_HIP_CHECK(hipStreamSynchronize(s));
         ps[0] = 0;
         for (int64_t i = 0; i < N; ++i) {
             if (w[(size_t)i] < 1) { set_error("leaf weight < 1 at row %lld", (long long)i); return RAHT_ERR_INVALID; }
             ps[(size_t)i + 1] = ps[(size_t)i] + w[(size_t)i];
         }
         RAHT_HIP_CHECK(p->wsum.alloc((size_t)N + 1));
-        RAHT_HIP_CHECK(hipMemcpy(p->wsum, ps.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice));
+        RAHT_HIP_CHECK(hipMemcpyAsync(p->wsum, ps.data(), sizeof(int64_t) * ((size_t)N + 1), hipMemcpyHostToDevice, s));
+        RAHT_HIP_CHECK(hipStreamSynchronize(s));        // `ps` is a local: the upload has left it before it goes
     }
     RAHT_HIP_CHECK(hipGetLastError());
     // Build the default schedule now so that float32 transforms with D <= 64 never allocate.
@@ -754,6 +758,9 @@ int raht_plan_export_level(const raht_plan *cp, int level, int64_t *list, uint8_
     if (level < 0 || level >= raht_plan_levels(p)) { set_error("raht_plan_export_level: level %d out of range", level); return RAHT_ERR_INVALID; }
     RAHT_RET(check_plan_device(p, "raht_plan_export_level"));
     try {
+    // No stream argument: the plain copies below run on the null stream, which non-blocking streams are not ordered against.
+    // They need no ordering: lvl and wsum are written by plan construction alone, which has synchronised its stream before
+    // it returned the plan, and nothing rewrites them afterwards.
     if (p->lvl_host.empty()) {
         p->lvl_host.resize((size_t)p->N);
         RAHT_HIP_CHECK(hipMemcpy(p->lvl_host.data(), p->lvl, (size_t)p->N, hipMemcpyDeviceToHost));

@@ -1152,7 +1152,8 @@ def motion_search(keys, ref_keys, C_ref, X, J, block_log2, block_first, candidat
     sum_ch w[ch] |X[i, ch] - P_v[i, ch]| in float32 (channels ascending, product rounded before the sum), capped at 2^20 and taken
     to 2^-10 fixed point; a block's cost is the integer sum over its rows; the smallest cost wins, the smallest index among equals.
     -> (mv (n_blocks, 3) int8, best_cost (n_blocks,) int64[, table (n_blocks, K) int64]) on the device; v points from the voxel to
-    its reference voxel. Enqueued only."""
+    its reference voxel. Enqueued only, but for the first call with a given table of candidates or weights on a device, which sends
+    the table up with a blocking copy and so waits for the current stream (``_device_table``)."""
     dev, args, _live, _, _ = _inter_args("motion_search", keys, ref_keys, C_ref, up, X, blocks=(J, block_log2, block_first))
     n_blocks = int(block_first.shape[0]) - 1
     cand_d, w_d, K = _search_host_args("motion_search", candidates, weights, int(C_ref.shape[1]), dev)
@@ -1164,6 +1165,23 @@ def motion_search(keys, ref_keys, C_ref, X, J, block_log2, block_first, candidat
     return (mv, best_cost, table) if want_table else (mv, best_cost)
 
 
+_TABLE_CACHE = {}
+
+
+def _device_table(a, dev):
+    """a small host table (the candidates or the weights of a search) as a device tensor. The upload is a blocking copy, which waits
+    for everything the caller has queued on the current stream; a search is made with the same few tables frame after frame, so the
+    copy is made once per (device, table) -- as ``_vmin_tensor`` keeps a bounding box -- and every later call with that table only
+    enqueues. The tensor handed out is shared and read-only."""
+    key = (str(dev), a.dtype.str, a.shape, a.tobytes())
+    t = _TABLE_CACHE.get(key)
+    if t is None:
+        if len(_TABLE_CACHE) > 64:
+            _TABLE_CACHE.clear()
+        t = _TABLE_CACHE[key] = torch.from_numpy(a).to(dev)
+    return t
+
+
 def _search_host_args(who, candidates, weights, D, dev):
     """the candidates and weights of a search, checked on the host -> (cand (K, 3) int32, weights (D,) float32 on ``dev``, K)"""
     import numpy as np
@@ -1172,16 +1190,17 @@ def _search_host_args(who, candidates, weights, D, dev):
         raise ValueError(f"{who}: candidates must be (K, 3) integers, 1 <= K <= {MOTION_MAX_CANDIDATES}")
     if np.abs(cand.astype(np.int64)).max() > 127:
         raise ValueError(f"{who}: a candidate outside +-127 (a vector is stored as int8)")
-    return torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(dev), _search_weights(who, weights, D, dev), int(cand.shape[0])
+    return _device_table(np.ascontiguousarray(cand, np.int32), dev), _search_weights(who, weights, D, dev), int(cand.shape[0])
 
 
 def _search_weights(who, weights, D, dev):
-    """the weights of a search, checked on the host -> (D,) float32 on ``dev``"""
+    """the weights of a search, checked on the host -> (D,) float32 on ``dev`` (weights given as a device tensor come to the host
+    first, which waits for the stream: pass host numbers to a call that must only enqueue)"""
     import numpy as np
-    w = np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1)
+    w = np.ascontiguousarray(np.asarray(weights.detach().cpu() if isinstance(weights, torch.Tensor) else weights, np.float32).reshape(-1))
     if w.shape[0] != D or not bool(np.all(np.isfinite(w) & (w >= 0))):
         raise ValueError(f"{who}: weights must be D finite numbers >= 0")
-    return torch.from_numpy(w).to(dev)
+    return _device_table(w, dev)
 
 
 # ---- hierarchical motion search (raht_motion_search_around; DESIGN.md 23) -------------------------------------------------------------
@@ -1195,7 +1214,8 @@ def motion_search_around(keys, ref_keys, C_ref, X, J, block_log2, block_first, b
     with a component outside +-127 is invalid: its table entry is -1 (2^64 - 1) and it is never chosen. -> (mv (n_blocks, 3) int8:
     base + the chosen candidate, written by the library; best_cost (n_blocks,) int64; best_k (n_blocks,) int32: the smallest k among
     the valid pairs of the smallest cost[, table (n_blocks, K) int64]). A block with no valid pair has best_k = -1, best_cost = -1
-    and mv = 0. With a zero base the table and the choice are ``motion_search``'s. Enqueued only."""
+    and mv = 0. With a zero base the table and the choice are ``motion_search``'s. Enqueued only, as ``motion_search`` is: but for
+    the first call with a given table."""
     who = "motion_search_around"
     dev, args, _live, _, _ = _inter_args(who, keys, ref_keys, C_ref, up, X, blocks=(J, block_log2, block_first))
     n_blocks = int(block_first.shape[0]) - 1
@@ -1360,7 +1380,8 @@ def mode_search(keys, ref0, ref1, X, J, block_log2, block_first, weights, up=0, 
     0 alone (``predict`` / ``predict_mc`` under mv0; 0 where it has no run), 2: from reference 1 alone, 3: not at all. The cost of a
     row under a mode is ``motion_search``'s row cost against that mode's prediction, a block's cost the integer sum over its rows;
     the smallest cost wins, the smallest mode among equals. -> (mode (n_blocks,) uint8, best_cost (n_blocks,) int64[, table
-    (n_blocks, 4) int64]) on the device. One pass over the frame. Enqueued only."""
+    (n_blocks, 4) int64]) on the device. One pass over the frame. Enqueued only, as ``motion_search`` is: but for the first call
+    with given weights."""
     who = "mode_search"
     (rk0, C0), (rk1, C1) = _ref_pairs(who, ref0, ref1)
     dev, _, live0, _, _ = _inter_args(who, keys, rk0, C0, up, X, blocks=(J, block_log2, block_first, *(() if mv0 is None else (mv0,))))
